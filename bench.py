@@ -3,6 +3,16 @@
 % of MFMA peak at 1/2/4/8 GPUs").
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--mixed bf16x6|bf16x3]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit, higher_is_better,
+dtype, ms_per_step, and what the timed steps themselves recorded: the in-step sketch roofline, collective counts).
+--full adds everything that takes work of its own: the untimed step with phase events, the back-to-back sketch launches
+(roofline.steady_state), the CPU baseline and the accuracy gate against the CPU restatement (C5: the separate
+gradient-stage run, its kernel roofline, the oracle baseline and gradient check).
+--dump-outputs DIR writes what the last timed step returned (C2-C4: u, s, vt; C5: grad_mat, n_regularised, u, s, vt)
+as DIR/<name>.npy in the step's dtype (f32 or f64), at most 64 MB in all: an array over its share is cut to a fixed
+sample of indices along its longest axis (numpy default_rng(0), sorted), the same from run to run.
 
 With --gpus N > 1 and no torch.distributed environment, this process spawns the N ranks itself (one process per
 GPU, 127.0.0.1 rendezvous) BEFORE anything touches the GPU and relays rank 0's JSON line; under
@@ -120,6 +130,30 @@ def spawn_ranks(args):
         time.sleep(0.05)
     kill_all()
     sys.exit(rc)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each of `arrays` (name -> torch tensor or number) as out_dir/<name>.npy, f32 or f64 as computed.
+    Every array gets an equal share of DUMP_BYTES; one larger than its share keeps a seeded sample of indices along its
+    longest axis, selected on the device (nothing larger than the share is copied to the host)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        if not torch.is_tensor(t):
+            t = torch.tensor(t, dtype=torch.float64)
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        if t.numel() * t.element_size() > share:
+            ax = max(range(t.dim()), key=lambda d: t.shape[d])
+            keep = share // (t.numel() // t.shape[ax] * t.element_size())
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[ax], size=keep, replace=False))
+            t = t.index_select(ax, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t.detach().cpu().numpy()))
 
 
 def pmc_traffic(kernel_substrs=("gemm_nn_kernel<float, 2, 9",), summary=r"r\d+_pmc_sketch_gemm_summary\.txt$",
@@ -283,6 +317,21 @@ def run_c5(args):
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     ms_per_step = dt / steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"grad_mat": gm, "n_regularised": nreg, "u": u, "s": s, "vt": vt})
+    result = {
+        "metric": "active-subspace samples/s on 1M x 64 f64 (gradient stage + fit_svd RSVD)",
+        "value": round(n_pts / (ms_per_step * 1e-3), 1), "unit": "samples/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
+        "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"ActiveSsRsvd: create_grad_mat of {n_pts} x {kf} f64 samples (order 1, {n_nbrs} neighbours) + fit_svd "
+                               f"(RSVD of the {kf} x {n_pts} gradient matrix, rank {rank}, q={q}, p={p}); {CONFIGS['C5'][6]}",
+                   "n_samples": n_pts, "n_features": kf, "n_nbrs": n_nbrs, "rank": rank, "parallelism": "single GPU"},
+    }
+    if not args.full:
+        log(f"[bench] C5: step {ms_per_step:.1f} ms, {result['value']:.0f} samples/s")
+        print(json.dumps(result), flush=True)
+        return
     t1 = time.perf_counter()
     ctx.grad_mat(x, y, 1, n_nbrs, scale=1.0 / np.sqrt(n_pts))
     torch.cuda.synchronize(dev)
@@ -316,14 +365,7 @@ def run_c5(args):
         go = aso.create_grad_mat(est, xs[:nq])
         t_cpu = (time.perf_counter() - t0) / nq
     err = float(np.max(np.abs(gm[:, :nq].cpu().numpy() * np.sqrt(n_pts) - go)) / np.abs(go).max())
-    result = {
-        "metric": "active-subspace samples/s on 1M x 64 f64 (gradient stage + fit_svd RSVD)",
-        "value": round(n_pts / (ms_per_step * 1e-3), 1), "unit": "samples/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"ActiveSsRsvd: create_grad_mat of {n_pts} x {kf} f64 samples (order 1, {n_nbrs} neighbours) + fit_svd "
-                               f"(RSVD of the {kf} x {n_pts} gradient matrix, rank {rank}, q={q}, p={p}); {CONFIGS['C5'][6]}",
-                   "n_samples": n_pts, "n_features": kf, "n_nbrs": n_nbrs, "rank": rank, "parallelism": "single GPU"},
+    result.update({
         "roofline": roofline,
         "phases_ms": {"gradient_stage": round(t_grad * 1e3, 2), "knn_scan": round(knn_ms, 2), "local_fits": round(fit_ms, 2),
                       "fit_svd_rsvd": round(ms_per_step - t_grad * 1e3, 2)},
@@ -333,7 +375,7 @@ def run_c5(args):
                                    f"{threads} OpenBLAS threads ({avail} logical CPUs visible)"},
         "accuracy": {"max_rel_dev_of_gradients_vs_oracle_sample": err, "gate": 1e-10, "passed": bool(err <= 1e-10),
                      "n_regularised": int(nreg), "queries_compared": nq},
-    }
+    })
     log(f"[bench] C5: step {ms_per_step:.1f} ms (gradient stage {t_grad * 1e3:.1f} ms: scan {knn_ms:.1f} ms = {achieved:.0f} TF bf16, fits {fit_ms:.1f} ms), "
         f"{result['value']:.0f} samples/s; gradients vs oracle {err:.2e}")
     print(json.dumps(result), flush=True)
@@ -345,7 +387,11 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="C2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the phase step, steady-state sketch launches, CPU baseline and accuracy gate (see the module doc)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and accuracy gate")
     ap.add_argument("--fused", action="store_true",
                     help="CORRLA_POWER_FUSED: one-sweep A^T (A Z) power iteration (SURVEY 8 f4; n <= 512 f32, i.e. --config C4)")
     ap.add_argument("--mixed", choices=["bf16x6", "bf16x3"], default=None,
@@ -457,12 +503,17 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = flops * args.steps / dt / 1e9
+    if args.dump_outputs and rank == 0:
+        u, s, vt = out
+        dump_outputs(args.dump_outputs, {"u": u, "s": s, "vt": vt})
 
-    ctx.set_phase_timings(True)
-    out = step()   # untimed: phase breakdown only
-    fence()
+    tm = ctx.timings()   # call counters (collectives, mixed products) of the last timed step
+    if args.full:
+        ctx.set_phase_timings(True)
+        out = step()   # untimed: phase breakdown only
+        fence()
+        tm = ctx.timings()
     u, s, vt = out
-    tm = ctx.timings()
     sk_ms = sum(sketch_ms_in_steps) / len(sketch_ms_in_steps)
     sk_flops = 2.0 * m_loc * n * l   # algorithmic: unpadded l (the kernel computes 16-column tiles)
     per_rank = [{"rank": rank, "rows": m_loc, "sketch_ms": round(sk_ms, 4),
@@ -474,16 +525,18 @@ def main():
 
     if rank == 0:
         # dominant kernel: the sketch GEMM Y = A * Omega (random_svd.rs:31), hipEvents on the library's stream
-        om = torch.empty((n, l), dtype=tdt, device=dev)
-        ctx.fill_normal(om, seed=SEED_OMEGA)
         # (a) the judged number: average duration of the sketch launch INSIDE the K timed steps
-        # (b) for information: the same launch back-to-back after the chip's clocks have ramped up
-        if args.mixed:
-            os.environ["CORRLA_SKETCH_MIXED"] = args.mixed       # the timing hook takes no opts: environment
-        reps_a, reps_b = (60, 40) if args.config == "C2" else (10, 10)
-        ctx.time_sketch(a, om, reps=reps_a)
-        sk_warm_ms, _ = ctx.time_sketch(a, om, reps=reps_b)
-        os.environ.pop("CORRLA_SKETCH_MIXED", None)
+        # (b) --full, for information: the same launch back-to-back after the chip's clocks have ramped up
+        sk_warm_ms = None
+        if args.full:
+            om = torch.empty((n, l), dtype=tdt, device=dev)
+            ctx.fill_normal(om, seed=SEED_OMEGA)
+            if args.mixed:
+                os.environ["CORRLA_SKETCH_MIXED"] = args.mixed       # the timing hook takes no opts: environment
+            reps_a, reps_b = (60, 40) if args.config == "C2" else (10, 10)
+            ctx.time_sketch(a, om, reps=reps_a)
+            sk_warm_ms, _ = ctx.time_sketch(a, om, reps=reps_b)
+            os.environ.pop("CORRLA_SKETCH_MIXED", None)
         achieved = sk_flops / (sk_ms * 1e-3) / 1e12
         a_gbps = m_loc * n * esz / (sk_ms * 1e-3) / 1e9
         alg_bytes = m_loc * n * esz + n * l * esz + m_loc * l * esz
@@ -513,20 +566,24 @@ def main():
                 # rows once, so the bytes of this launch scale with the rows this rank holds
                 traffic = traffic * (m_loc / 1_250_000.0)
                 traffic_src += f"; measured on a 1,250,000-row shard, scaled by rows to this rank's {m_loc}"
-        steady = {"avg_launch_ms": round(sk_warm_ms, 4), "note": "same launch back-to-back after warm launches (clock ramp)"}
+        steady = None
+        if sk_warm_ms is not None:
+            steady = {"avg_launch_ms": round(sk_warm_ms, 4), "note": "same launch back-to-back after warm launches (clock ramp)"}
         if args.mixed:
             # the split kernels are no longer bound by the matrix pipe: the roof is the stream of A from HBM
             ach_gbps = alg_bytes / (sk_ms * 1e-3) / 1e9
             roofline = {"bound": "hbm", "achieved": round(ach_gbps, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s",
                         "frac": round(ach_gbps / PEAK_HBM_GBPS, 4), "traffic": traffic,
                         "f32_equivalent_TFLOPs": round(achieved, 2)}
-            steady.update({"achieved": round(alg_bytes / (sk_warm_ms * 1e-3) / 1e9, 1),
-                           "frac": round(alg_bytes / (sk_warm_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4)})
+            if steady:
+                steady.update({"achieved": round(alg_bytes / (sk_warm_ms * 1e-3) / 1e9, 1),
+                               "frac": round(alg_bytes / (sk_warm_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4)})
         else:
             roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
                         "frac": round(achieved / peak, 4), "traffic": traffic}
-            steady.update({"achieved": round(sk_flops / (sk_warm_ms * 1e-3) / 1e12, 2),
-                           "frac": round(sk_flops / (sk_warm_ms * 1e-3) / 1e12 / peak, 4)})
+            if steady:
+                steady.update({"achieved": round(sk_flops / (sk_warm_ms * 1e-3) / 1e12, 2),
+                               "frac": round(sk_flops / (sk_warm_ms * 1e-3) / 1e12 / peak, 4)})
             if dtname == "f64":
                 ceil, ceil_src = measured_f64_ceiling()
                 if ceil:
@@ -537,15 +594,15 @@ def main():
             "traffic_source": traffic_src,
             "kernel": f"{kern} (sketch Y = A*Omega, {m_loc}x{n}x{l}, rank 0's shard)",
             "avg_launch_ms": round(sk_ms, 4),
-            "measured": "hipEvents on the library's stream around the sketch launch of each timed step",
-            "steady_state": steady,
+            "measured": "hipEvents on the library's stream around the sketch launch of each timed step"})
+        if steady:
+            roofline["steady_state"] = steady
+        roofline.update({
             "hbm_GBps_on_A_read": round(a_gbps, 1), "hbm_frac_of_8TBps": round(a_gbps / PEAK_HBM_GBPS, 4),
             "per_rank": per_rank})
         log(f"[bench] {args.config} x{world}{' ' + args.mixed if args.mixed else ''}: step {ms_per_step:.3f} ms  value {value:.0f} GFLOP/s  "
-            f"sketch in-step {sk_ms:.3f} ms = {achieved:.1f} TF ({100 * achieved / peak:.1f}% of {dtname} MFMA peak, {a_gbps:.0f} GB/s on A); "
-            f"warmed-up {sk_warm_ms:.3f} ms")
-        phases = {k_: (round(v, 3) if isinstance(v, float) else v) for k_, v in tm.items()}
-        log(f"[bench] last-call device phases (ms): {json.dumps(phases)}")
+            f"sketch in-step {sk_ms:.3f} ms = {achieved:.1f} TF ({100 * achieved / peak:.1f}% of {dtname} MFMA peak, {a_gbps:.0f} GB/s on A)" +
+            (f"; warmed-up {sk_warm_ms:.3f} ms" if sk_warm_ms is not None else ""))
         metric = {"C2": "RSVD GFLOP/s on 16k x 16k f32 rank-128", "C3": "RSVD GFLOP/s on 65536 x 4096 f64 rank-256 (POD schedule q=10)",
                   "C4": "RSVD GFLOP/s on 10M x 512 f32 rank-64 (row-sharded)"}[args.config]
         result = {
@@ -562,22 +619,25 @@ def main():
                        "algorithmic_flops_per_step": flops,
                        f"pct_of_{dtname}_mfma_peak_whole_job": round(100 * value / 1e3 / (peak * world), 2)},
             "roofline": roofline,
-            "phases_ms_extra_untimed_step": phases,
             "schedule": ("one-sweep A^T (A Z) (CORRLA_POWER_FUSED)" if args.fused else "reference (two products per iteration)") +
                         (f"; range finder on the {args.mixed} kernels ({tm['n_mixed_products']} products)" if args.mixed else ""),
             "collectives": {"rccl_nranks": nranks_seen, "allreduces_per_step": tm["n_collectives"],
                             "allreduce_bytes_per_step": tm["collective_bytes"]},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            sample_rows = {"C2": m_loc, "C3": 16384, "C4": 1_250_000}[args.config]
-            result["cpu_baseline"], pack = cpu_baseline(a, k, q, p, l, sample_rows)
-            result["accuracy"] = accuracy_gate(torch, ctx, a, k, q, p, l, pack, mixed=args.mixed)
-            log(f"[bench] accuracy gate (same A, same Omega): {json.dumps(result['accuracy'])}")
-        else:
-            result["cpu_baseline"] = None
-            eye = torch.eye(k, dtype=torch.float64, device=dev)
-            result["accuracy"] = {"VVt_minus_I_max": float((vt.double() @ vt.double().t() - eye).abs().max().item()),
-                                  "note": "rank-local orthonormality only; parity lives in tests/ and in the N = 1 line"}
+        if args.full:
+            phases = {k_: (round(v, 3) if isinstance(v, float) else v) for k_, v in tm.items()}
+            log(f"[bench] last-call device phases (ms): {json.dumps(phases)}")
+            result["phases_ms_extra_untimed_step"] = phases
+            if world == 1 and not args.no_cpu_baseline:
+                sample_rows = {"C2": m_loc, "C3": 16384, "C4": 1_250_000}[args.config]
+                result["cpu_baseline"], pack = cpu_baseline(a, k, q, p, l, sample_rows)
+                result["accuracy"] = accuracy_gate(torch, ctx, a, k, q, p, l, pack, mixed=args.mixed)
+                log(f"[bench] accuracy gate (same A, same Omega): {json.dumps(result['accuracy'])}")
+            else:
+                result["cpu_baseline"] = None
+                eye = torch.eye(k, dtype=torch.float64, device=dev)
+                result["accuracy"] = {"VVt_minus_I_max": float((vt.double() @ vt.double().t() - eye).abs().max().item()),
+                                      "note": "rank-local orthonormality only; parity lives in tests/ and in the N = 1 line"}
         print(json.dumps(result), flush=True)
     if use_dist:
         dist.barrier()

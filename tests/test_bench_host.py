@@ -10,6 +10,30 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_help_and_configs():
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], text=True)
     assert "--gpus" in out and "--steps" in out and "--warmup" in out and "--config" in out
+    assert "--full" in out and "--dump-outputs" in out
+
+
+def test_dump_outputs_keeps_dtype_caps_size_and_samples_the_same_indices(tmp_path, monkeypatch):
+    """--dump-outputs: f32 / f64 kept, numbers as f64, every file within its share of the cap; an array over its share
+    keeps a sorted default_rng(0) sample along its longest axis, so two runs write the same elements."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    u = torch.randn(64, 40000).t()                         # (m, k) column-major view, like the API's U
+    arrays = {"u": u, "s": torch.randn(64, 1), "vt": torch.randn(64, 100, dtype=torch.float64), "n": 3}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    share = bench.DUMP_BYTES // len(arrays)
+    for name, dt in (("u", np.float32), ("s", np.float32), ("vt", np.float64), ("n", np.float64)):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == dt and a.nbytes <= share and np.array_equal(a, b)
+    got = np.load(tmp_path / "a" / "u.npy")
+    idx = np.sort(np.random.default_rng(0).choice(40000, size=got.shape[0], replace=False))
+    assert got.shape[1] == 64 and np.array_equal(got, u.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "vt.npy"), arrays["vt"].numpy())
+    assert np.load(tmp_path / "a" / "n.npy").ravel().tolist() == [3.0]
 
 
 def test_traffic_is_parsed_from_the_tracked_pmc_summary():

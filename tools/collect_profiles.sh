@@ -12,7 +12,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 has() { [[ " $WHAT " == *" $1 "* ]]; }
 if has bench; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 $REPO/bench.py --steps 20 --warmup 3 > $OUT/bench_traced.json 2> $OUT/bench_traced.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 $REPO/bench.py --full --steps 20 --warmup 3 > $OUT/bench_traced.json 2> $OUT/bench_traced.err
   cp $(find $OUT/bench -name '*kernel_stats.csv' | head -1) $OUT/bench_kernel_stats.csv 2>/dev/null
 fi
 if has tl_c2; then
