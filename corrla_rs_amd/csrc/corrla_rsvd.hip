@@ -6,8 +6,6 @@
 
 #include "capi_impl.hpp"
 #include "hip_backend.hpp"
-#include "grad_kernels.hpp"
-#include "knn2_kernels.hpp"
 
 using namespace corrla;
 
@@ -16,19 +14,7 @@ struct corrla_ctx {
   Timings last;
   std::mutex mu;
   bool profile;
-  explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {
-    // function attributes apply to the device that is current when they are set: once per context (HipDev's
-    // constructor has made `ordinal` current), like every other kernel's
-    const hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::knn_kernel, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::knn_mfma_kernel<4, 4>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::knn_mfma_kernel<4, 8>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::knn_mfma_kernel<4, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::knn_mfma_kernel<2, 4>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::knn_mfma_kernel<2, 8>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::knn_mfma_kernel<2, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::grad_fit_kernel, attr, 160 * 1024));
-  }
+  explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
 namespace {

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "core_svd_plan.hpp"
 #include "driver.hpp"
 #include "hip_kernels.hpp"
 #include "tsqr_kernels.hpp"
@@ -22,6 +23,8 @@
 #include "ata_kernels.hpp"
 #include "tall_kernels.hpp"
 #include "mixed_kernels.hpp"
+#include "grad_kernels.hpp"
+#include "knn2_kernels.hpp"
 
 namespace corrla {
 
@@ -80,27 +83,7 @@ class HipDev {
     CORRLA_HIP(hipHostMalloc(&pinned_, kPinnedBytes, hipHostMallocDefault));
     for (auto& e : events_) CORRLA_HIP(hipEventCreate(&e));
     CORRLA_HIP(hipMemsetAsync(zero_page_, 0, 256, stream));
-    set_lds_attrs<float>();
-    set_lds_attrs<double>();
-    set_jacobi_attrs<float>();
-    set_jacobi_attrs<double>();
-    set_ring_attrs<float, 20>();
-    set_ring_attrs<double, 18>();
-    set_tsqr_attrs<float>();
-    set_tsqr_attrs<double>();
-    set_jmc_attrs<float>();
-    set_jmc_attrs<double>();
-    ata_set_attrs<2>();
-    ata_set_attrs<4>();
-    ata_set_attrs<8>();
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_split_kernel<float>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_split_kernel<double>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_block_round_kernel<float>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_block_round_kernel<double>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    set_lds_limits();
     {
       std::random_device rd;
       entropy_ = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
@@ -347,12 +330,7 @@ class HipDev {
   }
   template <int NT, int NP, bool TN>
   void mixed_launch_one(dim3 grid, const k::MxArgs& g) {
-    static bool attr_set = false;  // per instantiation; contexts are created under a process-wide lock
     const int lds = k::mx_lds_bytes(NT, NP);
-    if (!attr_set) {
-      CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_bf16s_kernel<NT, NP, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr_set = true;
-    }
     hipLaunchKernelGGL((k::gemm_bf16s_kernel<NT, NP, TN>), grid, dim3(64 * (k::kMxWaves + k::kMxLoaders)), lds, stream, g);
   }
   template <int NP, bool TN>
@@ -468,15 +446,6 @@ class HipDev {
       case 4: hipLaunchKernelGGL((k::ata_fused_kernel<NK, 4>), grid, block, k::ata_lds_bytes(NK, 4), stream, g); break;
       default: hipLaunchKernelGGL((k::ata_fused_kernel<NK, 5>), grid, block, k::ata_lds_bytes(NK, 5), stream, g); break;
     }
-  }
-  template <int NK>
-  void ata_set_attrs() {
-    const hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::ata_fused_kernel<NK, 1>, attr, k::ata_lds_bytes(NK, 1)));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::ata_fused_kernel<NK, 2>, attr, k::ata_lds_bytes(NK, 2)));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::ata_fused_kernel<NK, 3>, attr, k::ata_lds_bytes(NK, 3)));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::ata_fused_kernel<NK, 4>, attr, k::ata_lds_bytes(NK, 4)));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::ata_fused_kernel<NK, 5>, attr, k::ata_lds_bytes(NK, 5)));
   }
   template <class T>
   void ata_fused(const Big<T>& a, const Skinny<T>& x, Skinny<T>& z) {
@@ -832,19 +801,6 @@ class HipDev {
     CORRLA_HIP(hipGetLastError());
   }
 
-  template <class T>
-  void set_tsqr_attrs() {
-    const hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_leaf_factor_kernel<T, false>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_tree_factor_kernel<T, false>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_tree_apply_kernel<T, false>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_leaf_apply_kernel<T, false>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_leaf_factor_kernel<T, true>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_tree_factor_kernel<T, true>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_tree_apply_kernel<T, true>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::hh_leaf_apply_kernel<T, true>, attr, 160 * 1024));
-  }
-
   // ---- Householder TSQR with explicit thin Q (tsqr_kernels.hpp) -------------------------------------------
   // one 2 l x l panel (plus the 16 x 16 T and Gram blocks of the blocked form) must fit in LDS: l <= 142 (f32) / 99 (f64)
   bool hh_wy_ = env_int("CORRLA_HH_WY", 1) != 0;  // blocked compact-WY panels on the MFMA units (0: the unblocked panels)
@@ -943,20 +899,6 @@ class HipDev {
   }
   int rank() const { return comm_rank; }
 
-  template <class T>
-  void set_jmc_attrs() {
-    const hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 1, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 2, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 3, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 4, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 5, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 6, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 7, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 8, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jmc_step_kernel<T, 9, 16>, attr, 160 * 1024));
-  }
-
   // ---- multi-workgroup block Jacobi (jacobi_mc_kernels.hpp) ------------------------------------------------
   // lanes per Jacobi processor.  (8-lane processors -- half the waves for the same block pair, twice the column per
   // lane -- measured 6 % slower at l = 138 f32: the rounds are bound by the per-lane column traffic, not by the
@@ -965,31 +907,11 @@ class HipDev {
   int jmc_lanes(int64_t) const {
     return 16;
   }
-  // geometry for an l x l core: chunk rows NC, workgroups NP, block width b (even, <= 32); false when it does not fit
+  // geometry for an l x l core (core_svd_plan.hpp); false when it does not fit
   template <class T>
   bool jmc_geometry(int64_t l, int* nc_out, int* np_out, int* b_out) const {
-    if (l < 2 || l > 288) return false;
-    const int lanes = jmc_lanes<T>(l);
-    const int nc = (int)((l + 2 * lanes - 1) / (2 * lanes));
-    // block width: a multiple of four columns (= whole waves of four 16-lane processors, whole sub-blocks of the
-    // wave-local schedule); CORRLA_JMC_LOCAL=0 keeps the round-2 rule (even)
-    const int local = env_int("CORRLA_JMC_LOCAL", 1);
-    auto width = [&](int np_) {
-      int bb = (int)((l + 2 * np_ - 1) / (2 * np_));
-      return local ? (bb + 3) / 4 * 4 : bb + (bb & 1);
-    };
-    int np = env_int("CORRLA_JMC_NP", 0);
-    if (np <= 0) {
-      // fewest workgroups whose block pair fits one CU (<= 32 processors, LDS): fewer, larger steps per sweep
-      np = 2;
-      while (np < 128 && (width(np) > jmc_max_b_ || k::jmc_lds_bytes(nc, width(np), sizeof(T), lanes) > (size_t)160 * 1024)) ++np;
-    }
-    const int b = width(np);
-    if (np < 1 || b < 2 || b > 32 || k::jmc_lds_bytes(nc, b, sizeof(T), lanes) > (size_t)160 * 1024) return false;
-    *nc_out = nc;
-    *np_out = np;
-    *b_out = b;
-    return true;
+    return corrla::jmc_geometry(l, (int)sizeof(T), jmc_lanes<T>(l), jmc_max_b_, env_int("CORRLA_JMC_LOCAL", 1),
+                                env_int("CORRLA_JMC_NP", 0), nc_out, np_out, b_out);
   }
   template <class T, int NC>
   void jmc_launch_step(int lanes, int np, int b, T* w, T* v, int nblocks, int step, int sweep, T tol, T tol_early, T floor2, k::JmcCtl* ctl) {
@@ -1097,67 +1019,52 @@ class HipDev {
     }
   }
 
-  template <class T, int BIG_E>
-  void set_ring_attrs() {
-    const hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_kernel<T, 8>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_kernel<T, 12>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_kernel<T, 16>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_kernel<T, BIG_E>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_w_kernel<T, 8, 8>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_w_kernel<T, 12, 8>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_w_kernel<T, 16, 8>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_w_kernel<T, BIG_E, 8>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_w_kernel<T, 24, 4>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_w_kernel<T, 32, 4>, attr, 160 * 1024));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_ring_w_kernel<T, 36, 4>, attr, 160 * 1024));
-  }
-
-  // SVD of the l x l core (random_svd.rs:89).  Default: single-workgroup LDS-resident Jacobi when W fits
-  // in LDS, block Jacobi over many waves otherwise (any l up to 1024).  CORRLA_SVD=block / host force the
-  // block kernel / the f64 host Jacobi.
+  // SVD of the l x l core (random_svd.rs:89): the kernel family core_svd_plan (core_svd_plan.hpp) picks for l and the
+  // knobs, read on every call.
   template <class T>
   void small_svd(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev, void* conv_status) {
     // conv_status (optional): a device status record; kernels that run a FIXED number of sweeps report there
     // whether they converged, the others (loop to convergence inside one launch) leave it cleared = converged
     if (conv_status) memset_zero(conv_status, sizeof(k::CholStatus));
-    const char* mode = std::getenv("CORRLA_SVD");
-    {
-      int nc_, np_, b_;
-      const bool want_mc = mode && std::strcmp(mode, "mc") == 0;
-      const bool want_other = mode && !want_mc;
-      if (!want_other && !env_int("CORRLA_HOST_SVD", 0) && (want_mc || l >= jmc_min_l_) && jmc_geometry<T>(l, &nc_, &np_, &b_)) {
+    CoreSvdKnobs kn;
+    kn.mode = std::getenv("CORRLA_SVD");
+    kn.host_svd = env_int("CORRLA_HOST_SVD", 0) != 0;
+    kn.jmc_min_l = jmc_min_l_;
+    kn.jmc_max_b = jmc_max_b_;
+    kn.jmc_local = env_int("CORRLA_JMC_LOCAL", 1);
+    kn.jmc_np = env_int("CORRLA_JMC_NP", 0);
+    const CoreSvdPlan plan = core_svd_plan((int)sizeof(T), l, kn);
+    switch (plan.family) {
+      case CoreSvd::kMultiWg:
         small_svd_mc(c, l, k, m1, m2, s_dev, conv_status);
         return;
-      }
+      case CoreSvd::kHost:
+        small_svd_host(*this, c, l, k, m1, m2, s_dev);
+        return;
+      case CoreSvd::kBlock:
+        core_finite_check<T>(c, l, conv_status);
+        small_svd_block(c, l, k, m1, m2, s_dev);
+        return;
+      case CoreSvd::kRing:
+        core_finite_check<T>(c, l, conv_status);
+        small_svd_ring(c, l, k, m1, m2, s_dev, plan.ring_e);
+        return;
     }
-    const bool want_host = (mode && std::strcmp(mode, "host") == 0) || env_int("CORRLA_HOST_SVD", 0);
-    const bool want_lds = mode && std::strcmp(mode, "lds") == 0;
-    if (want_host || l > 1024) {
-      small_svd_host(*this, c, l, k, m1, m2, s_dev);
-      return;
+  }
+  // The ring and block Jacobi kernels carry no status word: a non-finite core would come back as a triplet of zeros.
+  // One small launch scans the core first: optimistic runs find fail = 3 in the status record at the end of the call,
+  // host-controlled ones read the word now.
+  template <class T>
+  void core_finite_check(const Skinny<T>& c, int64_t l, void* conv_status) {
+    int* bad = conv_status ? nullptr : alloc_flags(1);
+    hipLaunchKernelGGL((k::core_finite_check_kernel<T>), dim3(1), dim3(1024), 0, stream, (const T*)c.p, c.ld, (int)l,
+                       (k::CholStatus*)conv_status, bad);
+    CORRLA_HIP(hipGetLastError());
+    if (bad) {
+      int h = 0;
+      read_flags(bad, 1, &h);
+      if (h) throw Error(ST_ENUMERIC, "non-finite core matrix in small SVD");
     }
-    // The single-workgroup and block Jacobi kernels carry no status word: a non-finite core would come back as a
-    // triplet of zeros.  One small launch scans the core first: optimistic runs find fail = 3 in the status record at
-    // the end of the call, host-controlled ones read the word now.
-    {
-      int* bad = conv_status ? nullptr : alloc_flags(1);
-      hipLaunchKernelGGL((k::core_finite_check_kernel<T>), dim3(1), dim3(1024), 0, stream, (const T*)c.p, c.ld, (int)l,
-                         (k::CholStatus*)conv_status, bad);
-      CORRLA_HIP(hipGetLastError());
-      if (bad) {
-        int h = 0;
-        read_flags(bad, 1, &h);
-        if (h) throw Error(ST_ENUMERIC, "non-finite core matrix in small SVD");
-      }
-    }
-    const bool want_block = mode && std::strcmp(mode, "block") == 0;
-    (void)want_lds;
-    if (want_block) {
-      small_svd_block(c, l, k, m1, m2, s_dev);
-      return;
-    }
-    small_svd_lds(c, l, k, m1, m2, s_dev);  // falls through to the block kernel when W does not fit in LDS
   }
 
   template <class T>
@@ -1193,127 +1100,44 @@ class HipDev {
     }
   }
 
+  // single-workgroup ring Jacobi: W in registers, 8 lanes x e rows per column (jacobi_ring_w_kernel), then V from the
+  // recorded rotations (jacobi_replay_v_kernel)
   template <class T>
-  void small_svd_lds(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev) {
-    constexpr size_t kLdsMax = (size_t)160 * 1024;
-    const size_t lds2 = k::jacobi_lds_bytes((int)l, sizeof(T), true);
-    const size_t lds1 = k::jacobi_lds_bytes((int)l, sizeof(T), false);
-    const bool ring_ok = l >= 2 && l <= 144 && !env_int("CORRLA_JACOBI_NORING", 0) &&
-                         k::jacobi_ring_w_lds_bytes((int)l, l <= 96 ? 96 : (l <= 128 ? 128 : 144), sizeof(T)) <= kLdsMax;
-    // the LDS-resident kernels with V in global memory are far slower than the block kernel
-    if (!ring_ok && (lds2 > kLdsMax || l > k::kJacobiMaxL)) {
-      small_svd_block(c, l, k, m1, m2, s_dev);
-      return;
-    }
-    const int64_t ldv = round_up(k::jacobi_pitch((int)l, (int)(16 / sizeof(T))), 16);
-    T* vg = (T*)alloc_bytes((size_t)ldv * l * sizeof(T));
+  void small_svd_ring(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev, int e) {
     int* info = (int*)alloc_bytes(sizeof(int) * 4);
     const double eps = (double)std::numeric_limits<T>::epsilon();
     const T tol = (T)(std::sqrt((double)l) * eps);
     // quadratic convergence: a sweep that starts below sqrt(eps) ends below tol -- except for clustered singular
     // values, whose W / sigma factor the driver re-orthonormalises afterwards (see small_svd_mc)
     const T tol_early = env_int("CORRLA_JACOBI_STRICT", 0) ? tol : (T)std::sqrt(eps);
-    const bool v_lds = lds2 <= kLdsMax;
-    const size_t lds = v_lds ? lds2 : lds1;
-    // ring kernel: columns resident in registers (l <= 144)
-    // ring kernels: rows per column slot = G lanes x E rows.  G = 4 (fewer, longer waves) measured ~12 % slower
-    // than G = 8 at l = 96..144 (latency is hidden by the extra waves); kept behind CORRLA_RING_G4 for experiments
-    const bool ring_replay = !env_int("CORRLA_JACOBI_NOREPLAY", 0);
-    const int ring_g = (ring_replay && l > 64 && env_int("CORRLA_RING_G4", 0)) ? 4 : 8;
-    const int ring_e8 = l <= 64 ? 8 : (l <= 96 ? 12 : (l <= 128 ? 16 : (sizeof(T) == 4 ? 20 : 18)));
-    const int ring_e4 = l <= 96 ? 24 : (l <= 128 ? 32 : 36);
-    const int ring_rs = ring_g == 4 ? 4 * ring_e4 : 8 * ring_e8;
-    const size_t ring_lds = ring_replay ? k::jacobi_ring_w_lds_bytes((int)l, ring_rs, sizeof(T))
-                                        : k::jacobi_ring_lds_bytes((int)l, ring_e8, sizeof(T));
-    if (l >= 2 && l <= 144 && ring_lds <= kLdsMax && !env_int("CORRLA_JACOBI_NORING", 0)) {
-      const int np = (int)((l + 1) / 2);
-      const dim3 block((unsigned)(np * ring_g));  // a partial last wave: no idle processors, no LDS slots for them
-      const int max_sw = env_int("CORRLA_JACOBI_SWEEPS", 40);
-      const bool replay = ring_replay;
-      const int n2 = 2 * np;
-      k::RotEntry<T>* rot = nullptr;
-      int* rank_g = nullptr;
-      if (replay) {
-        rot = (k::RotEntry<T>*)alloc_bytes((size_t)max_sw * n2 * k::kRingProcPad * sizeof(k::RotEntry<T>));
-        rank_g = (int*)alloc_bytes(sizeof(int) * (size_t)n2);
-      }
-#define CORRLA_RING_W(EE, GG)                                                                                       \
-  hipLaunchKernelGGL((k::jacobi_ring_w_kernel<T, EE, GG>), dim3(1), block, ring_lds, stream, (const T*)c.p, c.ld, (int)l, \
+    const size_t ring_lds = k::jacobi_ring_w_lds_bytes((int)l, 8 * e, sizeof(T));
+    const int np = (int)((l + 1) / 2);
+    const dim3 block((unsigned)(np * 8));  // a partial last wave: no idle processors, no LDS slots for them
+    const int max_sw = env_int("CORRLA_JACOBI_SWEEPS", 40);
+    const int n2 = 2 * np;
+    k::RotEntry<T>* rot = (k::RotEntry<T>*)alloc_bytes((size_t)max_sw * n2 * k::kRingProcPad * sizeof(k::RotEntry<T>));
+    int* rank_g = (int*)alloc_bytes(sizeof(int) * (size_t)n2);
+#define CORRLA_RING_W(EE)                                                                                             \
+  hipLaunchKernelGGL((k::jacobi_ring_w_kernel<T, EE, 8>), dim3(1), block, ring_lds, stream, (const T*)c.p, c.ld, (int)l, \
                      m2.p, m2.ld, s_dev, (int)k, tol, tol_early, max_sw, rot, rank_g, info)
-#define CORRLA_RING(EE)                                                                                                  \
-  hipLaunchKernelGGL((k::jacobi_ring_kernel<T, EE>), dim3(1), block, ring_lds, stream, (const T*)c.p, c.ld, (int)l, m1.p, \
-                     m1.ld, m2.p, m2.ld, s_dev, (int)k, tol, tol_early, max_sw, info)
-      constexpr int kBigE = sizeof(T) == 4 ? 20 : 18;
-      if (replay && ring_g == 4) {
-        if (l <= 96) CORRLA_RING_W(24, 4);
-        else if (l <= 128) CORRLA_RING_W(32, 4);
-        else CORRLA_RING_W(36, 4);
-      } else if (replay) {
-        if (l <= 64) CORRLA_RING_W(8, 8);
-        else if (l <= 96) CORRLA_RING_W(12, 8);
-        else if (l <= 128) CORRLA_RING_W(16, 8);
-        else CORRLA_RING_W(kBigE, 8);
-      } else {
-        if (l <= 64) CORRLA_RING(8);
-        else if (l <= 96) CORRLA_RING(12);
-        else if (l <= 128) CORRLA_RING(16);
-        else CORRLA_RING(kBigE);
-      }
+    constexpr int kBigE = sizeof(T) == 4 ? 20 : 18;
+    switch (e) {
+      case 8: CORRLA_RING_W(8); break;
+      case 12: CORRLA_RING_W(12); break;
+      case 16: CORRLA_RING_W(16); break;
+      default: CORRLA_RING_W(kBigE); break;
+    }
 #undef CORRLA_RING_W
-#undef CORRLA_RING
-      CORRLA_HIP(hipGetLastError());
-      if (replay) {
-        hipLaunchKernelGGL((k::jacobi_replay_v_kernel<T>), dim3((unsigned)((l + 256 / k::kReplayLanes - 1) / (256 / k::kReplayLanes))), dim3(256), 0,
-                           stream,
-                           (const k::RotEntry<T>*)rot, (const int*)info, (const int*)rank_g, (int)l, (int)k, m1.p, m1.ld);
-        CORRLA_HIP(hipGetLastError());
-      }
-      if (env_int("CORRLA_DEBUG", 0)) {
-        int h[4] = {0, 0, 0, 0};
-        CORRLA_HIP(hipMemcpyAsync(h, info, sizeof(int), hipMemcpyDeviceToHost, stream));
-        sync();
-        std::fprintf(stderr, "[corrla] jacobi_svd (ring) l=%d sweeps=%d\n", (int)l, h[0]);
-      }
-      return;
-    }
-    // role-split kernel: W updates and V updates on different waves (needs both images in LDS, <= 72 pairs,
-    // <= 36 sixteen-byte chunks per column)
-    const size_t lds_split = k::jacobi_split_lds_bytes((int)l, sizeof(T));
-    const int nchunk_s = k::jacobi_pitch((int)l, (int)(16 / sizeof(T))) / (int)(16 / sizeof(T));
-    if (lds_split <= kLdsMax && (l + 1) / 2 <= 72 && nchunk_s <= 36 && !env_int("CORRLA_JACOBI_NOSPLIT", 0)) {
-      hipLaunchKernelGGL((k::jacobi_svd_split_kernel<T>), dim3(1), dim3(1024), lds_split, stream, (const T*)c.p, c.ld,
-                         (int)l, m1.p, m1.ld, m2.p, m2.ld, s_dev, (int)k, tol, tol_early, 40, info);
-      CORRLA_HIP(hipGetLastError());
-      if (env_int("CORRLA_DEBUG", 0)) {
-        int h[4] = {0, 0, 0, 0};
-        CORRLA_HIP(hipMemcpyAsync(h, info, sizeof(int), hipMemcpyDeviceToHost, stream));
-        sync();
-        std::fprintf(stderr, "[corrla] jacobi_svd (split) l=%d sweeps=%d\n", (int)l, h[0]);
-      }
-      return;
-    }
-#define CORRLA_JACOBI(VL, G, E)                                                                                      \
-  hipLaunchKernelGGL((k::jacobi_svd_kernel<T, VL, G, E>), dim3(1), dim3(1024), lds, stream, (const T*)c.p, c.ld, (int)l, \
-                     vg, ldv, m1.p, m1.ld, m2.p, m2.ld, s_dev, (int)k, tol, tol_early, 40, info)
-    // chunks per column = pitch / VW; G lanes x E chunks per lane must cover them; npairs <= 1024 / G for one round
-    const int nchunk = k::jacobi_pitch((int)l, (int)(16 / sizeof(T))) / (int)(16 / sizeof(T));
-    if (l <= 128 && nchunk <= 32) {
-      if (v_lds) CORRLA_JACOBI(true, 16, 2); else CORRLA_JACOBI(false, 16, 2);
-    } else if (nchunk <= 40) {
-      if (v_lds) CORRLA_JACOBI(true, 8, 5); else CORRLA_JACOBI(false, 8, 5);
-    } else if (nchunk <= 72) {
-      if (v_lds) CORRLA_JACOBI(true, 8, 9); else CORRLA_JACOBI(false, 8, 9);
-    } else {
-      small_svd_block(c, l, k, m1, m2, s_dev);
-      return;
-    }
-#undef CORRLA_JACOBI
+    CORRLA_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k::jacobi_replay_v_kernel<T>), dim3((unsigned)((l + 256 / k::kReplayLanes - 1) / (256 / k::kReplayLanes))), dim3(256), 0,
+                       stream,
+                       (const k::RotEntry<T>*)rot, (const int*)info, (const int*)rank_g, (int)l, (int)k, m1.p, m1.ld);
     CORRLA_HIP(hipGetLastError());
     if (env_int("CORRLA_DEBUG", 0)) {
       int h[4] = {0, 0, 0, 0};
       CORRLA_HIP(hipMemcpyAsync(h, info, sizeof(int), hipMemcpyDeviceToHost, stream));
       sync();
-      std::fprintf(stderr, "[corrla] jacobi_svd l=%d sweeps=%d v_in_lds=%d\n", (int)l, h[0], (int)v_lds);
+      std::fprintf(stderr, "[corrla] jacobi_svd (ring) l=%d sweeps=%d\n", (int)l, h[0]);
     }
   }
   // skinny (rows x ncols) -> column-major destination, optionally transposed (ncols x rows)
@@ -1551,44 +1375,116 @@ class HipDev {
     if (g.y > 65535u || g.z > 65535u) throw Error(ST_EINVAL, "problem too large for the launch grid");
   }
 
+  // ---- dynamic-LDS limits ----
+  // Every kernel launched with more dynamic LDS than the default gets its limit here, once per device: a function
+  // attribute applies to the device that is current when it is set (the constructor has made this one current).
+  static void lds_limit(const void* fn, size_t bytes) {
+    CORRLA_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  }
+  static void set_lds_limits() {
+    constexpr size_t kMax = k::kLdsMaxBytes;
+    set_lds_limits_typed<float>();
+    set_lds_limits_typed<double>();
+    set_ata_limits<2>();
+    set_ata_limits<4>();
+    set_ata_limits<8>();
+    set_mixed_limits<0, false>();
+    set_mixed_limits<0, true>();
+    set_mixed_limits<2, false>();
+    set_mixed_limits<2, true>();
+    set_mixed_limits<3, false>();
+    set_mixed_limits<3, true>();
+    lds_limit((const void*)k::tall_gram_kernel<float, 5>, k::gram_lds_bytes(5, 4));
+    lds_limit((const void*)k::tall_gram_kernel<float, 6>, k::gram_lds_bytes(6, 4));
+    // nearest neighbours and local fits of the gradient stage (corrla_rsvd.hip)
+    lds_limit((const void*)k::knn_kernel, kMax);
+    lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);
+    lds_limit((const void*)k::knn_mfma_kernel<4, 8>, kMax);
+    lds_limit((const void*)k::knn_mfma_kernel<4, 16>, kMax);
+    lds_limit((const void*)k::knn_mfma_kernel<2, 4>, kMax);
+    lds_limit((const void*)k::knn_mfma_kernel<2, 8>, kMax);
+    lds_limit((const void*)k::knn_mfma_kernel<2, 16>, kMax);
+    lds_limit((const void*)k::knn2_kernel<1>, k::k2_lds_bytes(1));
+    lds_limit((const void*)k::knn2_kernel<2>, k::k2_lds_bytes(2));
+    lds_limit((const void*)k::grad_fit_kernel, kMax);
+    lds_limit((const void*)k::grad_fit_lin_kernel<1>, kMax);
+    lds_limit((const void*)k::grad_fit_lin_kernel<2>, kMax);
+    lds_limit((const void*)k::grad_fit_lin_kernel<3>, kMax);
+    lds_limit((const void*)k::grad_fit_lin_kernel<4>, kMax);
+    lds_limit((const void*)k::grad_fit_lin_kernel<5>, kMax);
+  }
+  template <class T>
+  static void set_lds_limits_typed() {
+    constexpr size_t kMax = k::kLdsMaxBytes;
+    set_gemm_limits<T, 1>();
+    set_gemm_limits<T, 2>();
+    set_gemm_limits<T, 3>();
+    set_gemm_limits<T, 4>();
+    set_gemm_limits<T, 5>();
+    set_gemm_limits<T, 6>();
+    set_gemm_limits<T, 7>();
+    set_gemm_limits<T, 8>();
+    set_gemm_limits<T, 9>();
+    lds_limit((const void*)k::tall_gram_kernel<T, 1>, k::gram_lds_bytes(1, (int)sizeof(T)));
+    lds_limit((const void*)k::tall_gram_kernel<T, 2>, k::gram_lds_bytes(2, (int)sizeof(T)));
+    lds_limit((const void*)k::tall_gram_kernel<T, 3>, k::gram_lds_bytes(3, (int)sizeof(T)));
+    lds_limit((const void*)k::tall_gram_kernel<T, 4>, k::gram_lds_bytes(4, (int)sizeof(T)));
+    lds_limit((const void*)k::hh_leaf_factor_kernel<T, false>, kMax);
+    lds_limit((const void*)k::hh_tree_factor_kernel<T, false>, kMax);
+    lds_limit((const void*)k::hh_tree_apply_kernel<T, false>, kMax);
+    lds_limit((const void*)k::hh_leaf_apply_kernel<T, false>, kMax);
+    lds_limit((const void*)k::hh_leaf_factor_kernel<T, true>, kMax);
+    lds_limit((const void*)k::hh_tree_factor_kernel<T, true>, kMax);
+    lds_limit((const void*)k::hh_tree_apply_kernel<T, true>, kMax);
+    lds_limit((const void*)k::hh_leaf_apply_kernel<T, true>, kMax);
+    constexpr int kBigE = sizeof(T) == 4 ? 20 : 18;  // core SVD kernels
+    lds_limit((const void*)k::jacobi_ring_w_kernel<T, 8, 8>, kMax);
+    lds_limit((const void*)k::jacobi_ring_w_kernel<T, 12, 8>, kMax);
+    lds_limit((const void*)k::jacobi_ring_w_kernel<T, 16, 8>, kMax);
+    lds_limit((const void*)k::jacobi_ring_w_kernel<T, kBigE, 8>, kMax);
+    lds_limit((const void*)k::jacobi_block_round_kernel<T>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 1, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 2, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 3, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 4, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 5, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 6, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 7, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 8, 16>, kMax);
+    lds_limit((const void*)k::jmc_step_kernel<T, 9, 16>, kMax);
+  }
   template <class T, int NT>
-  static void set_lds_attr_one() {
-    const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_nn_kernel<T, 1, NT>, attr, k::gemm_lds_bytes(1, NT)));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_tn_kernel<T, 1, NT>, attr, k::gemm_lds_bytes(1, NT)));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_nn_kernel<T, 2, NT>, attr, k::gemm_lds_bytes(2, NT)));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_tn_kernel<T, 2, NT>, attr, k::gemm_lds_bytes(2, NT)));
-    if constexpr (NT <= 8)
-      CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_nn_kernel<T, 2, NT, true>, attr, 3 * k::big_tile_bytes(2)));
+  static void set_gemm_limits() {
+    lds_limit((const void*)k::gemm_nn_kernel<T, 1, NT>, k::gemm_lds_bytes(1, NT));
+    lds_limit((const void*)k::gemm_tn_kernel<T, 1, NT>, k::gemm_lds_bytes(1, NT));
+    lds_limit((const void*)k::gemm_nn_kernel<T, 2, NT>, k::gemm_lds_bytes(2, NT));
+    lds_limit((const void*)k::gemm_tn_kernel<T, 2, NT>, k::gemm_lds_bytes(2, NT));
+    if constexpr (NT <= 8) lds_limit((const void*)k::gemm_nn_kernel<T, 2, NT, true>, 3 * k::big_tile_bytes(2));
     if constexpr (std::is_same<T, double>::value) {  // two MFMA waves per SIMD on the MW = 2 tile (launch_mw)
-      CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_nn_kernel<T, 1, NT, false, 8>, attr, k::gemm_lds_bytes(2, NT)));
-      CORRLA_HIP(hipFuncSetAttribute((const void*)k::gemm_tn_kernel<T, 1, NT, 8>, attr, k::gemm_lds_bytes(2, NT)));
+      lds_limit((const void*)k::gemm_nn_kernel<T, 1, NT, false, 8>, k::gemm_lds_bytes(2, NT));
+      lds_limit((const void*)k::gemm_tn_kernel<T, 1, NT, 8>, k::gemm_lds_bytes(2, NT));
     }
   }
-  template <class T>
-  static void set_jacobi_attrs() {
-    const int lds = 160 * 1024;
-    const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_kernel<T, true, 16, 2>, attr, lds));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_kernel<T, false, 16, 2>, attr, lds));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_kernel<T, true, 8, 5>, attr, lds));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_kernel<T, false, 8, 5>, attr, lds));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_kernel<T, true, 8, 9>, attr, lds));
-    CORRLA_HIP(hipFuncSetAttribute((const void*)k::jacobi_svd_kernel<T, false, 8, 9>, attr, lds));
+  template <int NK>
+  static void set_ata_limits() {
+    lds_limit((const void*)k::ata_fused_kernel<NK, 1>, k::ata_lds_bytes(NK, 1));
+    lds_limit((const void*)k::ata_fused_kernel<NK, 2>, k::ata_lds_bytes(NK, 2));
+    lds_limit((const void*)k::ata_fused_kernel<NK, 3>, k::ata_lds_bytes(NK, 3));
+    lds_limit((const void*)k::ata_fused_kernel<NK, 4>, k::ata_lds_bytes(NK, 4));
+    lds_limit((const void*)k::ata_fused_kernel<NK, 5>, k::ata_lds_bytes(NK, 5));
   }
-  template <class T>
-  static void set_lds_attrs() {
-    set_lds_attr_one<T, 1>();
-    set_lds_attr_one<T, 2>();
-    set_lds_attr_one<T, 3>();
-    set_lds_attr_one<T, 4>();
-    set_lds_attr_one<T, 5>();
-    set_lds_attr_one<T, 6>();
-    set_lds_attr_one<T, 7>();
-    set_lds_attr_one<T, 8>();
-    set_lds_attr_one<T, 9>();
+  template <int NP, bool TN>
+  static void set_mixed_limits() {
+    lds_limit((const void*)k::gemm_bf16s_kernel<1, NP, TN>, k::mx_lds_bytes(1, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<2, NP, TN>, k::mx_lds_bytes(2, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<3, NP, TN>, k::mx_lds_bytes(3, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<4, NP, TN>, k::mx_lds_bytes(4, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<5, NP, TN>, k::mx_lds_bytes(5, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<6, NP, TN>, k::mx_lds_bytes(6, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<7, NP, TN>, k::mx_lds_bytes(7, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<8, NP, TN>, k::mx_lds_bytes(8, NP));
+    lds_limit((const void*)k::gemm_bf16s_kernel<9, NP, TN>, k::mx_lds_bytes(9, NP));
   }
-
   // Launch geometry: MW (16-wide outer tiles per wave), nsplit (split of the reduction into slabs).
   // One workgroup is resident per CU at the large column blockings, so aim for >= num_cus
   // workgroups; prefer the MW = 2 shape (fewer skinny-operand bytes per MFMA) whenever the
@@ -1667,12 +1563,7 @@ class HipDev {
   }
   template <class T, int NCT>
   void launch_tall_gram(dim3 grid, const k::TallGramArgs<T>& g) {
-    static bool attr_set = false;  // per instantiation; contexts are created under a process-wide lock
     const int lds = k::gram_lds_bytes(NCT, (int)sizeof(T));
-    if (!attr_set) {
-      CORRLA_HIP(hipFuncSetAttribute((const void*)k::tall_gram_kernel<T, NCT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr_set = true;
-    }
     hipLaunchKernelGGL((k::tall_gram_kernel<T, NCT>), grid, dim3(256), lds, stream, g);
   }
   template <class T>

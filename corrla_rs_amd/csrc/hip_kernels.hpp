@@ -929,19 +929,13 @@ __global__ void fill_normal_kernel(T* p, int64_t rows, int64_t cols, int64_t rs,
 }
 
 // ---- SVD of the l x l core (random_svd.rs:89) on the device -------------------------------------
-// One-sided (Hestenes) Jacobi in ONE workgroup of 1024 threads: W = C lives in LDS (column-major,
-// odd pitch) and so does the accumulated right-rotation matrix V when both fit (else V sits in
-// global memory, L2-resident, same CU).  A round-robin tournament gives n/2 disjoint column pairs
-// per step; each pair is rotated by a G-lane group (G = 16: 64 pairs in flight; G = 8: 128 pairs, the
-// whole step in ONE round), lane gl owning the 16-byte chunks gl + G*e, e < E, of the four columns
-// involved (ds_read_b128 / ds_write_b128: the scalar version was bound by LDS instruction issue).
-// They are loaded once with independent LDS reads, the three dot products are reduced by xor-
-// shuffles inside the group, and the rotation is applied in registers before the write-back.
-// Convergence is quadratic, so the sweep in which every |w_p.w_q| / (|w_p||w_q|) was already below
-// sqrt(tol) is the last one.  On exit the columns of W are U_c * sigma and V = V_c with
-// C = U_c diag(sigma) V_c^T.  The kernel sorts sigma descending and writes sigma[:k], V_c[:, :k]
-// (-> m1) and U_c[:, :k] (-> m2) directly into the zero-padded skinny operands of the GEMMs that
-// follow (U = Q * m1, V = Qb * m2), so the final stage needs no host round trip.
+// One-sided (Hestenes) Jacobi, in three kernel families: the single-workgroup ring kernel below (l <= 144), the
+// multi-workgroup block Jacobi (jacobi_mc_kernels.hpp) and the block Jacobi with one launch per round (any l);
+// core_svd_plan.hpp chooses between them.  Convergence is quadratic, so the sweep in which every
+// |w_p.w_q| / (|w_p||w_q|) was already below sqrt(tol) is the last one.  On exit the columns of W are U_c * sigma
+// and V = V_c with C = U_c diag(sigma) V_c^T.  sigma[:k], V_c[:, :k] (-> m1) and U_c[:, :k] (-> m2), sorted by
+// sigma descending, go directly into the zero-padded skinny operands of the GEMMs that follow (U = Q * m1,
+// V = Qb * m2), so the final stage needs no host round trip.
 // Sum over a G-lane group (G = 8 or 16, groups aligned to G lanes), result in every lane.  f32 uses DPP
 // (quad_perm xor-1 / xor-2, row_half_mirror, row_mirror) on the VALU; __shfl_xor would go through the LDS
 // crossbar (ds_bpermute), which the Jacobi kernels cannot afford.  f64 keeps the shuffles.
@@ -1041,344 +1035,38 @@ __device__ __forceinline__ void tournament_pair(int n, int step, int pr, int& p,
     q = t_;
   }
 }
-// column pitch of the LDS-resident Jacobi images: multiple of the 16-byte vector width, and an odd number
-// of 16-byte slots so consecutive columns start on different bank groups
-__host__ __device__ inline int jacobi_pitch(int l, int vw) {
-  int slots = (l + vw - 1) / vw;
-  slots |= 1;
-  return slots * vw;
-}
-// W + V images, sigma, order, flags
-__host__ __device__ inline size_t jacobi_lds_bytes_fwd(int l, size_t esz) {
-  const int vw = (int)(16 / esz);
-  return (size_t)l * jacobi_pitch(l, vw) * esz * 2 + (size_t)(l + 2) * esz + (size_t)(l + 2) * sizeof(int) + 64;
-}
-template <class T, bool V_IN_LDS, int G, int E>
-__global__ __launch_bounds__(1024) void jacobi_svd_kernel(const T* __restrict__ c, int64_t ldc, int l, T* vg, int64_t ldv,
-                                                          T* m1, int64_t ld1, T* m2, int64_t ld2, T* s_out, int k, T tol,
-                                                          T tol_early, int max_sweeps, int* info) {
-  typedef typename MT<T>::vec_t vec_t;
-  constexpr int VW = MT<T>::VEC;  // elements per 16-byte LDS access
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NG = 1024 / G;  // groups = pairs in flight
-  // Column pitch: a multiple of the vector width (16-byte aligned columns); the pad rows stay zero, so
-  // whole 16-byte chunks are loaded, rotated and stored without per-element masks.
-  const int LP = jacobi_pitch(l, VW);
-  const int nchunk = LP / VW;
-  T* w = (T*)smem;
-  T* sigma = w + (size_t)l * LP * (V_IN_LDS ? 2 : 1);
-  int* order = (int*)(sigma + l + 2);
-  int* flag = order + l + 2;  // flag[0]: rotated this sweep, flag[1]: some pair above tol_early
-  if (V_IN_LDS) {
-    vg = w + (size_t)l * LP;
-    ldv = LP;
-  }
-  const int tid = threadIdx.x;
-  for (int idx = tid; idx < l * LP; idx += 1024) {
-    const int j = idx / LP, i = idx - j * LP;
-    w[j * LP + i] = (i < l) ? c[(int64_t)j * ldc + i] : (T)0;
-    vg[(int64_t)j * ldv + i] = (i == j) ? (T)1 : (T)0;
-  }
-  __syncthreads();
-  const int n = (l + 1) & ~1;  // players in the tournament (one dummy when l is odd)
-  const int npairs = n / 2;
-  const int group = tid / G, gl = tid % G;
-  int sweep = 0;
-  for (; sweep < max_sweeps; ++sweep) {
-    if (tid < 2) flag[tid] = 0;
-    __syncthreads();
-    for (int step = 0; step < n - 1; ++step) {
-      for (int pr = group; pr < npairs; pr += NG) {
-        int p, q;
-        tournament_pair(n, step, pr, p, q);
-        if (q >= l) continue;  // the dummy player (uniform within the group)
-        vec_t* wp = (vec_t*)(w + p * LP);
-        vec_t* wq = (vec_t*)(w + q * LP);
-        vec_t* vp = (vec_t*)(vg + (int64_t)p * ldv);
-        vec_t* vq = (vec_t*)(vg + (int64_t)q * ldv);
-        vec_t x[E], y[E], vx[E], vy[E];
-        vec_t zero;
-#pragma unroll
-        for (int z = 0; z < VW; ++z) zero[z] = (T)0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const int ch = gl + G * e;
-          const bool in = ch < nchunk;
-          x[e] = in ? wp[ch] : zero;
-          y[e] = in ? wq[ch] : zero;
-          vx[e] = in ? vp[ch] : zero;
-          vy[e] = in ? vq[ch] : zero;
-        }
-        T a = 0, b = 0, g = 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-#pragma unroll
-          for (int z = 0; z < VW; ++z) {
-            a += x[e][z] * x[e][z];
-            b += y[e][z] * y[e][z];
-            g += x[e][z] * y[e][z];
-          }
-        a = group_sum<G>(a);
-        b = group_sum<G>(b);
-        g = group_sum<G>(g);
-        T cs, sn, rel;
-        if (jacobi_rotation(a, b, g, tol, cs, sn, rel)) {
-#pragma unroll
-          for (int e = 0; e < E; ++e) {
-            const int ch = gl + G * e;
-            if (ch < nchunk) {
-              wp[ch] = cs * x[e] - sn * y[e];
-              wq[ch] = sn * x[e] + cs * y[e];
-              vp[ch] = cs * vx[e] - sn * vy[e];
-              vq[ch] = sn * vx[e] + cs * vy[e];
-            }
-          }
-          if (gl == 0) {
-            flag[0] = 1;
-            if (rel > tol_early) flag[1] = 1;
-          }
-        }
-      }
-      __syncthreads();
-    }
-    const int rotated = flag[0], big = flag[1];
-    __syncthreads();
-    if (!rotated || !big) {
-      if (rotated) ++sweep;  // this sweep did (small, final) rotations
-      break;
-    }
-  }
-  // singular values and descending order
-  for (int j = group; j < l; j += NG) {
-    T a = 0;
-    for (int i = gl; i < l; i += G) {
-      const T xx = w[j * LP + i];
-      a += xx * xx;
-    }
-#pragma unroll
-    for (int msk = 1; msk < G; msk <<= 1) a += __shfl_xor(a, msk, G);
-    if (gl == 0) sigma[j] = jacobi_safe_sigma(a);  // NaN-safe: the ranking below must stay a permutation
-  }
-  __syncthreads();
-  for (int j = tid; j < l; j += 1024) {
-    const T sj = sigma[j];
-    int r = 0;
-    for (int i = 0; i < l; ++i) {
-      const T si = sigma[i];
-      r += (si > sj || (si == sj && i < j)) ? 1 : 0;
-    }
-    order[r] = j;
-  }
-  __syncthreads();
-  for (int r = group; r < k; r += NG) {
-    const int j = order[r];
-    const T sj = sigma[j];
-    const T inv = sj > (T)0 ? (T)1 / sj : (T)0;
-    for (int i = gl; i < l; i += G) {
-      m2[(int64_t)r * ld2 + i] = w[j * LP + i] * inv;
-      m1[(int64_t)r * ld1 + i] = vg[(int64_t)j * ldv + i];
-    }
-    if (gl == 0) s_out[r] = sj;
-  }
-  if (tid == 0) info[0] = sweep;
-}
-// Role-split variant of jacobi_svd_kernel for l <= 144 with W and V both in LDS: V never feeds back into
-// the iteration, so waves 0..8 (72 eight-lane groups) compute the rotations and update W only, publishing
-// (cos, sin) per pair in a double-buffered LDS table, while waves 9..15 (112 four-lane groups) apply the
-// PREVIOUS step's rotations to V.  The per-step critical path is the W half; the V half runs beside it.
-template <class T>
-__global__ __launch_bounds__(1024) void jacobi_svd_split_kernel(const T* __restrict__ c, int64_t ldc, int l, T* m1,
-                                                                int64_t ld1, T* m2, int64_t ld2, T* s_out, int k, T tol,
-                                                                T tol_early, int max_sweeps, int* info) {
-  typedef typename MT<T>::vec_t vec_t;
-  constexpr int VW = MT<T>::VEC;
-  constexpr int GW = 8, EW = 5;   // W groups: 8 lanes x 5 chunks  (>= 36 chunks of 16 bytes)
-  constexpr int GV = 4, EV = 9;   // V groups: 4 lanes x 9 chunks
-  constexpr int NWG = 72;         // W groups (waves 0..8)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int LP = jacobi_pitch(l, VW);
-  const int nchunk = LP / VW;
-  T* w = (T*)smem;
-  T* v = w + (size_t)l * LP;
-  T* sigma = v + (size_t)l * LP;
-  int* order = (int*)(sigma + l + 2);
-  int* flag = order + l + 2;
-  T* rot = (T*)(((uintptr_t)(flag + 4) + 15) & ~(uintptr_t)15);  // [2][NWG][2]
-  const int tid = threadIdx.x;
-  for (int idx = tid; idx < l * LP; idx += 1024) {
-    const int j = idx / LP, i = idx - j * LP;
-    w[idx] = (i < l) ? c[(int64_t)j * ldc + i] : (T)0;
-    v[idx] = (i == j) ? (T)1 : (T)0;
-  }
-  __syncthreads();
-  const int n = (l + 1) & ~1;
-  const int npairs = n / 2;  // <= NWG
-  const bool is_w = tid < NWG * GW;
-  const int wgroup = tid / GW, wl = tid % GW;
-  const int vgroup = (tid - NWG * GW) / GV, vl = (tid - NWG * GW) % GV;
-  auto pair_of = [&](int step, int pr, int& p, int& q) { tournament_pair(n, step, pr, p, q); };
-  vec_t zero;
-#pragma unroll
-  for (int z = 0; z < VW; ++z) zero[z] = (T)0;
-  // V worker: apply the rotations published for (pstep) from table buffer tb
-  auto v_pass = [&](int pstep, int tb) {
-    if (is_w || vgroup >= npairs) return;
-    int p, q;
-    pair_of(pstep, vgroup, p, q);
-    if (q >= l) return;
-    const T cs = rot[(tb * NWG + vgroup) * 2], sn = rot[(tb * NWG + vgroup) * 2 + 1];
-    if (sn == (T)0) return;
-    vec_t* vp = (vec_t*)(v + p * LP);
-    vec_t* vq = (vec_t*)(v + q * LP);
-    vec_t vx[EV], vy[EV];
-#pragma unroll
-    for (int e = 0; e < EV; ++e) {
-      const int ch = vl + GV * e;
-      const bool in = ch < nchunk;
-      vx[e] = in ? vp[ch] : zero;
-      vy[e] = in ? vq[ch] : zero;
-    }
-#pragma unroll
-    for (int e = 0; e < EV; ++e) {
-      const int ch = vl + GV * e;
-      if (ch < nchunk) {
-        vp[ch] = cs * vx[e] - sn * vy[e];
-        vq[ch] = sn * vx[e] + cs * vy[e];
-      }
-    }
-  };
-  int sweep = 0;
-  int gs = 0;  // global step counter (table parity)
-  int last_step = -1;
-  for (; sweep < max_sweeps; ++sweep) {
-    if (tid < 2) flag[tid] = 0;
-    __syncthreads();
-    for (int step = 0; step < n - 1; ++step, ++gs) {
-      if (is_w) {
-        if (wgroup < npairs) {
-          int p, q;
-          pair_of(step, wgroup, p, q);
-          T cs = (T)1, sn = (T)0;
-          if (q < l) {
-            vec_t* wp = (vec_t*)(w + p * LP);
-            vec_t* wq = (vec_t*)(w + q * LP);
-            vec_t x[EW], y[EW];
-#pragma unroll
-            for (int e = 0; e < EW; ++e) {
-              const int ch = wl + GW * e;
-              const bool in = ch < nchunk;
-              x[e] = in ? wp[ch] : zero;
-              y[e] = in ? wq[ch] : zero;
-            }
-            T a = 0, b = 0, g = 0;
-#pragma unroll
-            for (int e = 0; e < EW; ++e)
-#pragma unroll
-              for (int z = 0; z < VW; ++z) {
-                a += x[e][z] * x[e][z];
-                b += y[e][z] * y[e][z];
-                g += x[e][z] * y[e][z];
-              }
-            a = group_sum<GW>(a);
-            b = group_sum<GW>(b);
-            g = group_sum<GW>(g);
-            T rel;
-            if (jacobi_rotation(a, b, g, tol, cs, sn, rel)) {
-#pragma unroll
-              for (int e = 0; e < EW; ++e) {
-                const int ch = wl + GW * e;
-                if (ch < nchunk) {
-                  wp[ch] = cs * x[e] - sn * y[e];
-                  wq[ch] = sn * x[e] + cs * y[e];
-                }
-              }
-              if (wl == 0) {
-                flag[0] = 1;
-                if (rel > tol_early) flag[1] = 1;
-              }
-            } else {
-              cs = (T)1;
-              sn = (T)0;
-            }
-          }
-          if (wl == 0) {
-            rot[((gs & 1) * NWG + wgroup) * 2] = cs;
-            rot[((gs & 1) * NWG + wgroup) * 2 + 1] = sn;
-          }
-        }
-      } else if (last_step >= 0) {
-        v_pass(last_step, (gs - 1) & 1);
-      }
-      last_step = step;
-      __syncthreads();
-    }
-    const int rotated = flag[0], big = flag[1];
-    __syncthreads();
-    if (!rotated || !big) {
-      if (rotated) ++sweep;
-      break;
-    }
-  }
-  // drain: the rotations of the last step have not reached V yet
-  if (last_step >= 0) v_pass(last_step, (gs - 1) & 1);
-  __syncthreads();
-  // singular values, order, outputs
-  const int group = tid >> 4, gl = tid & 15;
-  for (int j = group; j < l; j += 64) {
-    T a = 0;
-    for (int i = gl; i < l; i += 16) {
-      const T xx = w[j * LP + i];
-      a += xx * xx;
-    }
-#pragma unroll
-    for (int msk = 1; msk < 16; msk <<= 1) a += __shfl_xor(a, msk, 16);
-    if (gl == 0) sigma[j] = jacobi_safe_sigma(a);  // NaN-safe: the ranking below must stay a permutation
-  }
-  __syncthreads();
-  for (int j = tid; j < l; j += 1024) {
-    const T sj = sigma[j];
-    int r = 0;
-    for (int i = 0; i < l; ++i) {
-      const T si = sigma[i];
-      r += (si > sj || (si == sj && i < j)) ? 1 : 0;
-    }
-    order[r] = j;
-  }
-  __syncthreads();
-  for (int r = group; r < k; r += 64) {
-    const int j = order[r];
-    const T sj = sigma[j];
-    const T inv = sj > (T)0 ? (T)1 / sj : (T)0;
-    for (int i = gl; i < l; i += 16) {
-      m2[(int64_t)r * ld2 + i] = w[j * LP + i] * inv;
-      m1[(int64_t)r * ld1 + i] = v[j * LP + i];
-    }
-    if (gl == 0) s_out[r] = sj;
-  }
-  if (tid == 0) info[0] = sweep;
-}
-__host__ __device__ inline size_t jacobi_split_lds_bytes(int l, size_t esz) {
-  return jacobi_lds_bytes_fwd(l, esz) + 16 + 2 * 72 * 2 * esz;
-}
-
-__host__ __device__ inline size_t jacobi_lds_bytes(int l, size_t esz, bool v_in_lds) {
-  const int vw = (int)(16 / esz);
-  return (size_t)l * jacobi_pitch(l, vw) * esz * (v_in_lds ? 2 : 1) + (size_t)(l + 2) * esz +
-         (size_t)(l + 2) * sizeof(int) + 64;
-}
 // ---- ring Jacobi: columns resident in registers --------------------------------------------------
-// Same one-sided Jacobi, but the two columns a processor (8 lanes) works on stay in REGISTERS (W and V,
-// lane g owning the 16-byte row chunks g, g + 8, ...), and the pairs follow the odd-even transposition
-// ordering: processor i holds the columns at line positions (2i, 2i + 1); after every rotation the two
-// columns swap positions, and the window of every processor slides by one position back and forth, so
-// only ONE column per processor crosses LDS per round (half the traffic of the LDS-resident kernels, no
-// address arithmetic or predication in the loop).  n rounds make every pair of columns meet exactly once.
-// Even round: rotate (P, Q), send Q to processor i - 1, receive Q from i + 1.  Odd round: rotate (P, Q),
-// send P to i + 1, receive P from i - 1; the last processor then holds (position n - 1, wrapped position 0),
-// which are not a pair of the line ordering: it applies (cs, sn) = (0, 1), i.e. P <- -Q, Q <- P, a swap that
-// flips the sign of one singular-vector pair.  V lags W by half a round so its update overlaps the exchange.
-__device__ __forceinline__ float ring_sum8(float x) { return group_sum<8>(x); }
-__device__ __forceinline__ double ring_sum8(double x) {
+// One-sided Jacobi on one workgroup.  The column a processor (8 lanes) works on stays in REGISTERS (lane g
+// owning the 16-byte row chunks g, g + 8, ...), and the pairs follow the odd-even transposition ordering:
+// processor i holds the columns at line positions (2i, 2i + 1); after every rotation the two columns swap
+// positions, and the window of every processor slides by one position back and forth, so only ONE column per
+// processor crosses LDS per round (no address arithmetic or predication in the loop).  n rounds make every pair
+// of columns meet exactly once.  Even round: rotate (P, Q), send Q to processor i - 1, receive Q from i + 1.  Odd
+// round: rotate (P, Q), send P to i + 1, receive P from i - 1; the last processor then holds (position n - 1,
+// wrapped position 0), which are not a pair of the line ordering: it applies (cs, sn) = (0, 1), i.e. P <- -Q,
+// Q <- P, a swap that flips the sign of one singular-vector pair.
+// The rows of V are independent and need nothing but the (cs, sn) of every round, so V is not accumulated here
+// (that was ~45 % of the instructions of a ring kernel that did): jacobi_ring_w_kernel keeps only W in
+// registers, records every round's rotations in a global stream (rot[round][processor] = (cs, sn), identity for
+// skipped pairs) and double-buffers the W exchange: ONE barrier per round.  jacobi_replay_v_kernel then applies
+// the recorded stream to V = I with 8 lanes per ROW of V (18 positions per lane in registers), 32 rows per
+// workgroup, on as many CUs as there are row groups.  Line positions after S sweeps are known in closed form
+// (always-swap odd-even transposition reverses the order every sweep), so the W kernel only has to publish
+// rank[position] for the replay to scatter V_c[:, :k].
+template <int G>
+__device__ __forceinline__ float ring_sum(float x) {
+  static_assert(G == 8, "lanes per processor");
+  auto dpp = [](float v, auto ctrl) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value, 0xf, 0xf, true));
+  };
+  x += dpp(x, std::integral_constant<int, 0xB1>{});  // quad_perm [1,0,3,2]
+  x += dpp(x, std::integral_constant<int, 0x4E>{});  // quad_perm [2,3,0,1]
+  x += dpp(x, std::integral_constant<int, 0x141>{});  // row_half_mirror
+  return x;
+}
+template <int G>
+__device__ __forceinline__ double ring_sum(double x) {
+  static_assert(G == 8, "lanes per processor");
   auto dpp = [](double v, auto ctrl) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_update_dpp(0, lo, decltype(ctrl)::value, 0xf, 0xf, true);
@@ -1390,261 +1078,6 @@ __device__ __forceinline__ double ring_sum8(double x) {
   x += dpp(x, std::integral_constant<int, 0x141>{});
   return x;
 }
-template <int G>
-__device__ __forceinline__ float ring_sum(float x) {
-  static_assert(G == 4 || G == 8, "lanes per processor");
-  auto dpp = [](float v, auto ctrl) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value, 0xf, 0xf, true));
-  };
-  x += dpp(x, std::integral_constant<int, 0xB1>{});  // quad_perm [1,0,3,2]
-  x += dpp(x, std::integral_constant<int, 0x4E>{});  // quad_perm [2,3,0,1]
-  if constexpr (G == 8) x += dpp(x, std::integral_constant<int, 0x141>{});  // row_half_mirror
-  return x;
-}
-template <int G>
-__device__ __forceinline__ double ring_sum(double x) {
-  static_assert(G == 4 || G == 8, "lanes per processor");
-  auto dpp = [](double v, auto ctrl) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, decltype(ctrl)::value, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, decltype(ctrl)::value, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-  };
-  x += dpp(x, std::integral_constant<int, 0xB1>{});
-  x += dpp(x, std::integral_constant<int, 0x4E>{});
-  if constexpr (G == 8) x += dpp(x, std::integral_constant<int, 0x141>{});
-  return x;
-}
-constexpr int kRingMaxThreads = 576;  // 72 processors x 8 lanes
-template <class T, int E>
-__global__ __launch_bounds__(kRingMaxThreads) void jacobi_ring_kernel(const T* __restrict__ c, int64_t ldc, int l, T* m1,
-                                                                      int64_t ld1, T* m2, int64_t ld2, T* s_out, int k,
-                                                                      T tol, T tol_early, int max_sweeps, int* info) {
-  typedef typename MT<T>::vec_t vec_t;
-  constexpr int VW = MT<T>::VEC;
-  static_assert(E % VW == 0, "whole 16-byte chunks per lane");
-  constexpr int NC = E / VW;
-  constexpr int RS = 8 * E;  // padded column length
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int n2 = (l + 1) & ~1, np = n2 >> 1;
-  T* xw = (T*)smem;                  // [np][RS] W column in flight
-  T* xv = xw + (size_t)np * RS;      // [np][RS] V column in flight
-  T* sigma = xv + (size_t)np * RS;   // [n2]
-  T* xn = sigma + n2;                // [np] squared norm of the W column in flight
-  int* rank = (int*)(xn + np);       // [n2]
-  int* flag = rank + n2;             // [4]
-  const int tid = threadIdx.x, proc = tid >> 3, g = tid & 7;
-  const bool act = proc < np;
-  const bool last = proc == np - 1;
-  vec_t pw[NC], qw[NC], pv[NC], qv[NC];
-  {
-    const int colp = 2 * proc, colq = 2 * proc + 1;
-#pragma unroll
-    for (int cc = 0; cc < NC; ++cc)
-#pragma unroll
-      for (int z = 0; z < VW; ++z) {
-        const int row = (cc * 8 + g) * VW + z;
-        const bool ok = act && row < l;
-        pw[cc][z] = (ok && colp < l) ? c[(int64_t)colp * ldc + row] : (T)0;
-        qw[cc][z] = (ok && colq < l) ? c[(int64_t)colq * ldc + row] : (T)0;
-        pv[cc][z] = (ok && row == colp) ? (T)1 : (T)0;
-        qv[cc][z] = (ok && row == colq) ? (T)1 : (T)0;
-      }
-  }
-  const int my_off = proc * RS + g * VW;
-  const int up_off = (proc + 1 >= np ? 0 : proc + 1) * RS + g * VW;
-  const int dn_off = (proc == 0 ? np - 1 : proc - 1) * RS + g * VW;
-  auto store = [&](T* buf, const vec_t (&x)[NC]) {
-    if (act) {
-#pragma unroll
-      for (int cc = 0; cc < NC; ++cc) *(vec_t*)(buf + my_off + cc * 8 * VW) = x[cc];
-    }
-  };
-  auto load = [&](const T* buf, int off, vec_t (&x)[NC]) {
-    if (act) {
-#pragma unroll
-      for (int cc = 0; cc < NC; ++cc) x[cc] = *(const vec_t*)(buf + off + cc * 8 * VW);
-    }
-  };
-  // squared norms of the two resident W columns: recomputed from the registers at the start of every sweep,
-  // updated analytically by each rotation in between (a' = a - t g, b' = b + t g), and travelling with their
-  // column through xn, so a round needs ONE dot product instead of three
-  T na = (T)0, nb = (T)0;
-  auto recompute_norms = [&]() {
-    vec_t va, vb;
-#pragma unroll
-    for (int z = 0; z < VW; ++z) va[z] = vb[z] = (T)0;
-#pragma unroll
-    for (int cc = 0; cc < NC; ++cc) {
-      va += pw[cc] * pw[cc];
-      vb += qw[cc] * qw[cc];
-    }
-    T a = va[0], b = vb[0];
-#pragma unroll
-    for (int z = 1; z < VW; ++z) {
-      a += va[z];
-      b += vb[z];
-    }
-    na = ring_sum8(a);
-    nb = ring_sum8(b);
-  };
-  // rotation of the W pair in registers; forced: the wrap-around pseudo pair of the last processor
-  auto rotate_w = [&](bool forced, T& cs, T& sn) {
-    vec_t vg;
-#pragma unroll
-    for (int z = 0; z < VW; ++z) vg[z] = (T)0;
-#pragma unroll
-    for (int cc = 0; cc < NC; ++cc) vg += pw[cc] * qw[cc];
-    T gg = vg[0];
-#pragma unroll
-    for (int z = 1; z < VW; ++z) gg += vg[z];
-    gg = ring_sum8(gg);
-    T rel = (T)0, t = (T)0;
-    cs = (T)1;
-    sn = (T)0;
-    const bool rot = !forced && jacobi_rotation(na, nb, gg, tol, cs, sn, rel, t);
-    if (rot) {
-      if (g == 0) {
-        flag[0] = 1;
-        if (rel > tol_early) flag[1] = 1;
-      }
-      na -= t * gg;
-      nb += t * gg;
-    } else {
-      cs = forced ? (T)0 : (T)1;
-      sn = forced ? (T)1 : (T)0;
-      if (forced) {
-        const T tmp = na;
-        na = nb;
-        nb = tmp;
-      }
-    }
-    if (sn != (T)0) {
-#pragma unroll
-      for (int cc = 0; cc < NC; ++cc) {
-        const vec_t x = pw[cc], y = qw[cc];
-        pw[cc] = cs * x - sn * y;
-        qw[cc] = sn * x + cs * y;
-      }
-    }
-  };
-  auto apply_v = [&](T cs, T sn) {
-    if (sn != (T)0) {
-#pragma unroll
-      for (int cc = 0; cc < NC; ++cc) {
-        const vec_t x = pv[cc], y = qv[cc];
-        pv[cc] = cs * x - sn * y;
-        qv[cc] = sn * x + cs * y;
-      }
-    }
-  };
-  const int up_proc = proc + 1 >= np ? 0 : proc + 1, dn_proc = proc == 0 ? np - 1 : proc - 1;
-  int sweep = 0;
-  for (; sweep < max_sweeps; ++sweep) {
-    if (tid < 2) flag[tid] = 0;
-    recompute_norms();
-    __syncthreads();
-    for (int r2 = 0; r2 < np; ++r2) {
-      T cs, sn;
-      // even round
-      rotate_w(false, cs, sn);
-      store(xw, qw);
-      if (act && g == 0) xn[proc] = nb;
-      __syncthreads();
-      apply_v(cs, sn);
-      store(xv, qv);
-      load(xw, up_off, qw);
-      if (act) nb = xn[up_proc];
-      __syncthreads();
-      load(xv, up_off, qv);
-      // odd round
-      rotate_w(last, cs, sn);
-      store(xw, pw);
-      if (act && g == 0) xn[proc] = na;
-      __syncthreads();
-      apply_v(cs, sn);
-      store(xv, pv);
-      load(xw, dn_off, pw);
-      if (act) na = xn[dn_proc];
-      __syncthreads();
-      load(xv, dn_off, pv);
-    }
-    __syncthreads();
-    const int rotated = flag[0], big = flag[1];
-    __syncthreads();
-    if (!rotated || !big) {
-      if (rotated) ++sweep;
-      break;
-    }
-  }
-  // singular values; the zero padding column of an odd l (its V column is zero too) sorts last
-  {
-    T a = 0, b = 0, va = 0, vb = 0;
-#pragma unroll
-    for (int cc = 0; cc < NC; ++cc)
-#pragma unroll
-      for (int z = 0; z < VW; ++z) {
-        a += pw[cc][z] * pw[cc][z];
-        b += qw[cc][z] * qw[cc][z];
-        va += pv[cc][z] * pv[cc][z];
-        vb += qv[cc][z] * qv[cc][z];
-      }
-    a = ring_sum8(a);
-    b = ring_sum8(b);
-    va = ring_sum8(va);
-    vb = ring_sum8(vb);
-    if (act && g == 0) {
-      sigma[2 * proc] = va > (T)0 ? jacobi_safe_sigma(a) : (T)-1;
-      sigma[2 * proc + 1] = vb > (T)0 ? jacobi_safe_sigma(b) : (T)-1;
-    }
-  }
-  __syncthreads();
-  for (int j = tid; j < n2; j += blockDim.x) {
-    const T sj = sigma[j];
-    int r = 0;
-    for (int i = 0; i < n2; ++i) {
-      const T si = sigma[i];
-      r += (si > sj || (si == sj && i < j)) ? 1 : 0;
-    }
-    rank[j] = r;
-  }
-  __syncthreads();
-  if (act) {
-    const int rp = rank[2 * proc], rq = rank[2 * proc + 1];
-    const T sp = sigma[2 * proc], sq = sigma[2 * proc + 1];
-    const T ip = sp > (T)0 ? (T)1 / sp : (T)0, iq = sq > (T)0 ? (T)1 / sq : (T)0;
-#pragma unroll
-    for (int cc = 0; cc < NC; ++cc)
-#pragma unroll
-      for (int z = 0; z < VW; ++z) {
-        const int row = (cc * 8 + g) * VW + z;
-        if (row < l) {
-          if (rp < k) {
-            m2[(int64_t)rp * ld2 + row] = pw[cc][z] * ip;
-            m1[(int64_t)rp * ld1 + row] = pv[cc][z];
-          }
-          if (rq < k) {
-            m2[(int64_t)rq * ld2 + row] = qw[cc][z] * iq;
-            m1[(int64_t)rq * ld1 + row] = qv[cc][z];
-          }
-        }
-      }
-    if (g == 0) {
-      if (rp < k) s_out[rp] = sp > (T)0 ? sp : (T)0;
-      if (rq < k) s_out[rq] = sq > (T)0 ? sq : (T)0;
-    }
-  }
-  if (tid == 0) info[0] = sweep;
-}
-// ---- ring Jacobi, W only + replay of the rotation stream onto V ------------------------------------
-// The ring kernel above is VALU-issue bound and ~45 % of its instructions accumulate V.  The rows of V are
-// independent and need nothing but the (cs, sn) of every round, so: jacobi_ring_w_kernel keeps only W in
-// registers, records every round's rotations in a global stream (rot[round][processor] = (cs, sn), identity for
-// skipped pairs) and -- with the V buffer gone from LDS -- double-buffers the W exchange: ONE barrier per
-// round.  jacobi_replay_v_kernel then applies the recorded stream to V = I with 8 lanes per ROW of V (18
-// positions per lane in registers), 32 rows per workgroup, on as many CUs as there are row groups.  Line
-// positions after S sweeps are known in closed form (always-swap odd-even transposition reverses the order
-// every sweep), so the W kernel only has to publish rank[position] for the replay to scatter V_c[:, :k].
 constexpr int kRingProcPad = 72;  // processors per stream row (padded)
 template <class T>
 struct RotEntry {
@@ -1860,15 +1293,9 @@ __global__ __launch_bounds__(kRingProcPad * G) void jacobi_ring_w_kernel(const T
     info[1] = rounds;
   }
 }
-// rs = G * E: rows per column slot
-__host__ __device__ inline size_t jacobi_ring_w_lds_bytes(int l, int rs, size_t esz) {
-  const int n2 = (l + 1) & ~1;
-  const int nproc = n2 / 2;  // launched with exactly G * np threads
-  return (size_t)2 * nproc * rs * esz + (size_t)n2 * (esz + sizeof(int)) + (size_t)2 * nproc * esz + 64;
-}
 
 // V_c[:, :k] from the recorded rotation stream: 8 lanes per row of V, 18 line positions per lane, 32 rows per
-// workgroup.  Round semantics (identical to the ring kernels): pair (first, second) = positions (2i, 2i + 1) in
+// workgroup.  Round semantics (identical to the ring kernel): pair (first, second) = positions (2i, 2i + 1) in
 // even rounds, (2i + 1, 2i + 2) in odd rounds; first <- sn x + cs y, second <- cs x - sn y (rotation, then the two
 // columns swap positions); in odd rounds positions n - 1 and 0 are idle and position 0 changes sign (the pseudo
 // pair of the last processor).
@@ -2010,13 +1437,6 @@ __global__ __launch_bounds__(256) void jacobi_replay_v_kernel(const RotEntry<T>*
     }
   }
 }
-
-__host__ __device__ inline size_t jacobi_ring_lds_bytes(int l, int e, size_t esz) {
-  const int n2 = (l + 1) & ~1;
-  return (size_t)2 * (n2 / 2) * 8 * e * esz + (size_t)n2 * (esz + sizeof(int)) + (size_t)(n2 / 2) * esz + 64;
-}
-
-constexpr int kJacobiMaxL = 256;  // 8-lane groups x 8 chunks x 4 elements
 
 // ---- block Jacobi SVD of the l x l core for any l (random_svd.rs:89) -----------------------------
 // W (= C on entry) and V (= I) live in global memory (L2-resident, a few hundred KiB).  The columns are
@@ -2198,7 +1618,7 @@ __global__ void jacobi_init_kernel(const T* c, int64_t ldc, int l, T* w, int64_t
   }
 }
 
-// sigma_j = ||w_j||, descending order, outputs (see jacobi_svd_kernel)
+// sigma_j = ||w_j||, descending order, outputs (see the top of the core-SVD section)
 template <class T>
 __global__ __launch_bounds__(1024) void jacobi_finish_kernel(const T* w, int64_t ldw, const T* v, int64_t ldv, int l, T* m1,
                                                              int64_t ld1, T* m2, int64_t ld2, T* s_out, int k) {
@@ -2664,7 +2084,7 @@ __global__ void series_combine_kernel(const T* e1, const T* e2, const T* e3, int
 
 // ---- non-finite cores -------------------------------------------------------------------------------
 // One workgroup scans the l x l core of the small SVD (random_svd.rs:89) before a kernel family that has no status
-// word of its own (ring / LDS / split / block Jacobi): *bad <- 1 and, when a status record is given, st->fail <- 3,
+// word of its own (ring / block Jacobi): *bad <- 1 and, when a status record is given, st->fail <- 3,
 // so that a non-finite core ends the call with CORRLA_ENUMERIC instead of a triplet of zeros.  (The multi-workgroup
 // Jacobi reports the same through jmc_init_kernel / jmc_finish_kernel.)
 template <class T>

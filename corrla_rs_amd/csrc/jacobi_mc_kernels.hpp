@@ -33,6 +33,7 @@
 // The host enqueues a fixed number of sweeps and never synchronises; jmc_finish_kernel reports whether the
 // iteration had converged (checked together with the Cholesky status records at the end of the call).
 #pragma once
+#include "core_svd_plan.hpp"
 #include "hip_kernels.hpp"
 
 namespace corrla {
@@ -88,20 +89,7 @@ __device__ __forceinline__ double jmc_sum(double x) {
   return x;
 }
 
-// rows per column image: NC chunk rows of `lanes` lanes x 2 elements
-__host__ __device__ constexpr int jmc_rows(int nc, int lanes) { return nc * 2 * lanes; }
-// LDS column pitch (elements).  16 lanes per processor: b64 reads (f32) are serviced per 32-lane half = two
-// processors, whose 128-byte segments must fall in different halves of the 256-byte bank row -> pitch = 32 (mod 64);
-// b128 reads (f64) are serviced in interleaved 16-lane groups that mix two processors -> their columns must be
-// bank-aligned, pitch = 0 (mod 32).  8 lanes per processor (f32 only): a 32-lane half is four processors reading 64
-// bytes each from four (mostly consecutive) columns -> pitch = 16 or 48 (mod 64).
-__host__ __device__ constexpr int jmc_pitch(int nc, int esz, int lanes) {
-  return lanes == 8 ? (jmc_rows(nc, 8) + ((nc % 2 == 0) ? 16 : 0))
-                    : (esz == 4 ? (jmc_rows(nc, 16) + ((nc % 2 == 0) ? 32 : 0)) : jmc_rows(nc, 16));
-}
-__host__ __device__ constexpr size_t jmc_lds_bytes(int nc, int b, int esz, int lanes) {
-  return (size_t)2 * (2 * b) * jmc_pitch(nc, esz, lanes) * esz + (size_t)2 * b * esz + 64;
-}
+// jmc_rows / jmc_pitch / jmc_lds_bytes: core_svd_plan.hpp (the geometry choice needs them on the host)
 
 // W <- 2^sexp * C (zero padded to rp x ncols_pad, rp = the LDS column pitch so that a block of columns is ONE
 // contiguous byte range in global memory and in LDS), V <- I, ctl cleared.  One workgroup.

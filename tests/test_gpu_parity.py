@@ -314,7 +314,7 @@ def test_c4_like_tall_f32(ctx, torch):
 
 
 # ---- alternate SVD-of-the-core paths and error handling ------------------------------------------
-@pytest.mark.parametrize("mode", ["block", "host", "nosplit"])
+@pytest.mark.parametrize("mode", ["block", "host", "mc"])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_small_svd_paths_agree(ctx, mode, dtype, monkeypatch):
     """The l x l SVD (random_svd.rs:89) has three device kernels and a host routine; all must give the same
@@ -324,13 +324,9 @@ def test_small_svd_paths_agree(ctx, mode, dtype, monkeypatch):
         a = g["A"].astype(dtype)
         om = g["omega"].astype(dtype)
         u0, s0, vt0 = ctx.rsvd(a, g["k"], g["q"], g["p"], omega=om)
-        if mode == "nosplit":
-            monkeypatch.setenv("CORRLA_JACOBI_NOSPLIT", "1")
-        else:
-            monkeypatch.setenv("CORRLA_SVD", mode)
+        monkeypatch.setenv("CORRLA_SVD", mode)
         u1, s1, vt1 = ctx.rsvd(a, g["k"], g["q"], g["p"], omega=om)
-        monkeypatch.delenv("CORRLA_SVD", raising=False)
-        monkeypatch.delenv("CORRLA_JACOBI_NOSPLIT", raising=False)
+        monkeypatch.delenv("CORRLA_SVD")
         tol = 1e-10 if dtype == np.float64 else 5e-5
         assert np.max(np.abs(s1 - s0)) <= tol * s0[0, 0]
         rec0 = (u0.astype(np.float64) * s0.ravel()) @ vt0.astype(np.float64)
@@ -355,8 +351,8 @@ def test_f64_core_sizes_cross_kernel_boundaries(ctx, l_total):
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_core_widths_across_every_kernel_boundary(ctx, dtype):
-    """l = k + p swept over the selection boundaries of the device kernels: ring Jacobi register variants (64 / 96 /
-    128 / 144, odd widths carry a zero padding column through the ring), LDS-resident and block Jacobi beyond,
+    """l = k + p swept over the selection boundaries of the device kernels: block Jacobi at l = 1, ring Jacobi register
+    variants (64 / 96, odd widths carry a zero padding column through the ring), multi-workgroup and block Jacobi beyond,
     device Cholesky + inverse (l <= 176) vs the host-controlled path.  Same Omega as the oracle."""
     rng = np.random.default_rng(7)
     m, n = 420, 230
@@ -379,18 +375,19 @@ def test_core_widths_across_every_kernel_boundary(ctx, dtype):
         assert np.all(np.diff(s.ravel()) <= 0) and np.all(s >= 0), l
 
 
-@pytest.mark.parametrize("env", ["CORRLA_JACOBI_NOREPLAY", "CORRLA_JACOBI_NORING", "CORRLA_RING_G4", "CORRLA_HOST_CHOL"])
+@pytest.mark.parametrize("env", ["CORRLA_SVD=block", "CORRLA_SVD=mc", "CORRLA_HOST_CHOL"])
 def test_alternative_device_paths_agree(ctx, env, monkeypatch):
-    """The full ring kernel (V accumulated in the kernel), the LDS-resident kernels, the 4-lane ring variant and the
-    host-controlled Cholesky-QR must reproduce the default path (W-only ring + replay, device Cholesky)."""
+    """The block Jacobi, the multi-workgroup Jacobi and the host-controlled Cholesky-QR must reproduce the default
+    path (W-only ring + replay at l = 75, multi-workgroup Jacobi at 138; device Cholesky)."""
+    name, _, val = env.partition("=")
     rng = np.random.default_rng(11)
     a = (rng.standard_normal((600, 150)) * (0.98 ** np.arange(150))).astype(np.float32)
     for l in (75, 138):   # odd pair count / the C2 width
         om = rng.standard_normal((150, l)).astype(np.float32)
         u0, s0, vt0 = ctx.rsvd(a, l - 10, 2, 10, omega=om)
-        monkeypatch.setenv(env, "1")
+        monkeypatch.setenv(name, val or "1")
         u1, s1, vt1 = ctx.rsvd(a, l - 10, 2, 10, omega=om)
-        monkeypatch.delenv(env)
+        monkeypatch.delenv(name)
         assert np.max(np.abs(s1 - s0)) <= 3e-5 * s0[0, 0]
         rec0 = (u0.astype(np.float64) * s0.ravel()) @ vt0.astype(np.float64)
         rec1 = (u1.astype(np.float64) * s1.ravel()) @ vt1.astype(np.float64)

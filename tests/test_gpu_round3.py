@@ -29,18 +29,18 @@ def torch():
 #  formed at random_svd.rs:89 with NaN (1) / +inf (2), AFTER both thin-Qs, so nothing upstream can catch it.)
 _POISON_CASES = [
     # (l, environment that selects the kernel family)
+    (1, {}),                                             # l = 1: block kernel (the ring needs a column pair)
     (24, {}),                                            # ring (W only) + replay, one wave
     (75, {}),                                            # ring (W only) + replay, odd pair count
-    (75, {"CORRLA_JACOBI_NOREPLAY": "1"}),               # ring with V accumulated in the kernel
-    (75, {"CORRLA_JACOBI_NORING": "1"}),                 # role-split LDS kernel
-    (75, {"CORRLA_JACOBI_NORING": "1", "CORRLA_JACOBI_NOSPLIT": "1"}),  # LDS-resident kernel
+    (95, {}),                                            # ring at the widest width the default gives it (E = 12)
     (96, {}),                                            # multi-workgroup block Jacobi, smallest
     (138, {}),                                           # ... the C2 width
     (138, {"CORRLA_JMC_FORCE_V": "1"}),                  # ... with V accumulated in the sweeps
     (266, {}),                                           # ... the C3 width (2 x 2 blocked Cholesky around it)
+    (288, {}),                                           # ... the widest geometry
     (138, {"CORRLA_SVD": "lds"}),                        # ring kernel at a width the default gives to the block Jacobi
-    (138, {"CORRLA_SVD": "lds", "CORRLA_JACOBI_NORING": "1"}),   # split kernel, widest
-    (170, {"CORRLA_SVD": "lds"}),                        # LDS-resident kernel beyond the ring / split widths
+    (144, {"CORRLA_SVD": "lds"}),                        # ring at its widest (f32, E = 20); f64: W does not fit, block kernel
+    (170, {"CORRLA_SVD": "lds"}),                        # single-workgroup request beyond the ring's widths: block kernel
     (138, {"CORRLA_SVD": "block"}),                      # one launch per round (MFMA block kernel)
     (300, {}),                                           # beyond the multi-workgroup geometry: block kernel
     (138, {"CORRLA_SVD": "host"}),                       # host Jacobi
@@ -58,7 +58,8 @@ def test_non_finite_core_is_an_error_in_every_svd_kernel_family(ctx, monkeypatch
     rng = np.random.default_rng(100 + case)
     m, n = max(3 * l, 200), l + 25
     a = rng.standard_normal((m, n)).astype(dtype)
-    k, p = l - 8, 8
+    p = min(8, l - 1)
+    k = l - p
     om = rng.standard_normal((n, l)).astype(dtype)
     for name, val in env.items():
         monkeypatch.setenv(name, val)

@@ -15,8 +15,7 @@ def orth(x):
 for m in (200_000, 1_250_000):
     a = torch.empty((m, 512), dtype=torch.float32, device="cuda")
     ctx.fill_normal(a, seed=11)
-    for env in ({}, {"CORRLA_NO_GRAM_ALIAS": "1"}, {"CORRLA_SVD": "host"}, {"CORRLA_SVD": "host", "CORRLA_NO_GRAM_ALIAS": "1"},
-                {"CORRLA_JACOBI_NOREPLAY": "1"}):
+    for env in ({}, {"CORRLA_NO_GRAM_ALIAS": "1"}, {"CORRLA_SVD": "host"}, {"CORRLA_SVD": "host", "CORRLA_NO_GRAM_ALIAS": "1"}):
         for k_, v_ in env.items():
             os.environ[k_] = v_
         u, s, vt = ctx.rsvd(a, 64, 2, 10, seed=3)
