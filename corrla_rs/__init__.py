@@ -17,7 +17,7 @@ __all__ = ["rsvd", "rpca", "random_svd", "power_iter", "PcaRsvd", "PyDMDc", "PyP
 def active_ss(a_mat, y, order, n_nbr, n_comps):
     """pyo3 ``active_ss(a_mat, y, order, n_nbr, n_comps)`` (src/lib_math_utils_py.rs:57-86): local polynomial gradients
     (GPU), eigendecomposition of G G^T / N (``ActiveSsRsvd::fit``); returns (components, singular values as a diagonal
-    matrix, diagonal sensitivity)."""
+    matrix, diagonal sensitivity).  Any number of input parameters and neighbours (above 64 / 512 on the wide kernels)."""
     from corrla_rs_amd.callers import ActiveSsRsvd, PolyGradientEstimator
     x = _np.asarray(a_mat, dtype=_np.float64)
     fit = ActiveSsRsvd(PolyGradientEstimator(x, _np.asarray(y, dtype=_np.float64), int(order), int(n_nbr)), int(n_comps)).fit(x)

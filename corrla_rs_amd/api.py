@@ -313,7 +313,8 @@ class Context:
         """``ActiveSsRsvd::create_grad_mat`` with a ``PolyGradientEstimator(x_mat, y, est_order, n_nbrs)``
         (active_subspaces.rs:66-141, 215-229): returns (G, n_regularised) with G the k x n_q gradient matrix (column i =
         gradient at query i; queries default to the support points), scaled by `scale`.  numpy in -> numpy out;
-        torch CUDA tensors in -> torch CUDA tensor out (no host copies)."""
+        torch CUDA tensors in -> torch CUDA tensor out (no host copies).  Any number of features and neighbours: calls
+        beyond k <= 64 / n_nbrs <= 512 take the wide kernels (see include/corrla_rsvd.h for the remaining limits)."""
         est_order, n_nbrs = int(est_order), int(n_nbrs)
         nreg = C.c_int(0)
         if _is_torch(x_mat) and x_mat.is_cuda:

@@ -45,7 +45,8 @@ def active_ss_fit_svd(grad_mat, n_comps, n_iter=8, n_oversamples=10, *, seed=Non
 class PolyGradientEstimator:
     """Mirror of ``PolyGradientEstimator`` (active_subspaces.rs:21-141): local polynomial gradient estimates over a
     point cloud.  The nearest-neighbour search and the per-point least-squares fits run on the GPU
-    (``corrla_grad_mat_f64``); ``grad_at`` returns the reference's 1 x k row."""
+    (``corrla_grad_mat_f64``) for any number of features and neighbours, like the reference; ``grad_at`` returns the
+    reference's 1 x k row."""
 
     def __init__(self, x_mat, y, est_order, n_nbrs, *, ctx=None):
         self.x_mat = np.ascontiguousarray(np.asarray(x_mat, dtype=np.float64))

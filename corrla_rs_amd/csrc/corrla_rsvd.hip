@@ -246,17 +246,11 @@ static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x
     corrla_ctx* c = need(ctx);
     if (!x || !y || !xq || !g) throw Error(ST_EINVAL, "NULL argument");
     if (n_pts < 1 || n_q < 1 || kf < 1) throw Error(ST_EINVAL, "empty point set");
-    if (est_order != 1 && est_order != 2) throw Error(ST_EINVAL, "est_order must be 1 or 2 (the reference panics otherwise)");
-    if (kf > k::kGradMaxDim) throw Error(ST_EINVAL, "more than 64 features are not supported");
-    const int64_t need_pts = est_order == 1 ? kf + 1 : kf * (kf + 3) / 2;  // active_subspaces.rs:118-119, 129-130
-    if (!(n_pts > need_pts && n_nbrs > need_pts))
-      throw Error(ST_EINVAL, "n_pts and n_nbrs must exceed k + 1 (order 1) / k (k + 3) / 2 (order 2)");
-    if (n_nbrs > n_pts) throw Error(ST_EINVAL, "n_nbrs exceeds the number of support points");
-    if (n_nbrs > k::kGradMaxNbr) throw Error(ST_EINVAL, "more than 512 neighbours are not supported");
-    if (k::grad_fit_lds_bytes((int)kf, (int)n_nbrs, est_order, /*m_in_lds=*/false) > (size_t)160 * 1024)
-      throw Error(ST_EINVAL, "the neighbours of one query do not fit in 160 KiB of LDS");
     if (ldg < kf) throw Error(ST_EINVAL, "ldg < k");
-    if (n_pts > 0x7fffffff || n_q * n_nbrs > ((int64_t)1 << 40)) throw Error(ST_EINVAL, "point set too large");
+    // which scan and which fit (grad_plan.hpp); a call the limited kernels cannot take goes to the wide ones
+    const GradPlan plan = grad_plan(n_pts, kf, n_q, est_order, n_nbrs, env_int("CORRLA_KNN", 0), env_int("CORRLA_FIT", 0),
+                                    c->dev.num_cus, kGradWideBudgetBytes);
+    if (plan.error) throw Error(ST_EINVAL, plan.error);
     locked_call(c, [&] {
     HipDev& dev = c->dev;
     dev.begin_call();
@@ -278,25 +272,38 @@ static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x
       gd = (double*)dev.alloc_bytes(sizeof(double) * (size_t)n_q * kf);
     }
     const int64_t ldt = round_up(n_pts, 64);
-    double* xt = (double*)dev.alloc_bytes(sizeof(double) * (size_t)ldt * kf);
+    const bool wide_scan = plan.scan == GradScan::kWide;
+    double* xt = wide_scan ? nullptr : (double*)dev.alloc_bytes(sizeof(double) * (size_t)ldt * kf);
     int* nbr = (int*)dev.alloc_bytes(sizeof(int) * (size_t)n_q * nn);
     int* status = (int*)dev.alloc_bytes(sizeof(int) * (size_t)n_q);
-    hipLaunchKernelGGL(k::grad_transpose_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, dev.stream, xd, n_pts, kk, xt,
-                       ldt);
-    // normal equations in LDS when they fit next to the neighbours, else in a per-workgroup slice of global memory
-    const bool m_in_lds = k::grad_fit_lds_bytes(kk, nn, est_order, true) <= (size_t)160 * 1024;
-    const size_t lds_fit = k::grad_fit_lds_bytes(kk, nn, est_order, m_in_lds);
-    if (lds_fit > (size_t)160 * 1024) throw Error(ST_EINVAL, "problem does not fit in LDS");
-    if (n_q > 0x7fffffff) throw Error(ST_EINVAL, "too many query points for one launch");
+    // the wide kernels' workspaces, before the first launch
+    k::WideScanArgs wsa{};
+    if (wide_scan) {
+      wsa.list_d = (double*)dev.alloc_bytes((size_t)plan.scan_wgs * k::kWsQ * (size_t)n_nbrs * sizeof(double));
+      wsa.cand_d = (double*)dev.alloc_bytes((size_t)plan.scan_wgs * k::kWsQ * k::kWsCap * sizeof(double));
+      wsa.cand_i = (int*)dev.alloc_bytes((size_t)plan.scan_wgs * k::kWsQ * k::kWsCap * sizeof(int));
+    }
+    double* wf_ws = plan.fit == GradFit::kWide ? (double*)dev.alloc_bytes(plan.fit_ws) : nullptr;
+    if (!wide_scan)
+      hipLaunchKernelGGL(k::grad_transpose_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, dev.stream, xd, n_pts, kk, xt,
+                         ldt);
     // Both kernels spend ~n_nbrs ln(n_pts / n_nbrs) list insertions per query; the MFMA distance tile only pays off
     // once the scan itself dominates (measured: 5e4 points 0.10 s VALU / 0.14 s MFMA, 1e5 0.28 / 0.30, 2e5 0.93 / 0.45)
     dev.event_mark(0);  // corrla_timings.knn_ms / fit_ms: events 0-1 around the scan, 1-2 around the fits
-    const int knn_mode = env_int("CORRLA_KNN", 0);  // 1: VALU kernel, 2: f32-MFMA kernel, 3: bf16-filter kernel, 0: by size
     // knn2_kernels.hpp (round 3): bf16x3 MFMA filter + batched bitonic list merges; n_nbrs <= 128.  Small clouds keep the
     // VALU scan (its per-query lists live in LDS and there is too little work to amortise the split of the cloud).
-    const bool knn2 = (knn_mode == 3 || (knn_mode == 0 && n_pts >= 8192)) && nn <= k::kK2List;
-    if (knn2) {
-      const int S = kk <= 32 ? 1 : 2;
+    if (wide_scan) {
+      wsa.x = xd;
+      wsa.xq = qd;
+      wsa.n_pts = n_pts;
+      wsa.n_q = n_q;
+      wsa.n_nbrs = n_nbrs;
+      wsa.ntiles = (n_q + k::kWsQ - 1) / k::kWsQ;
+      wsa.k = kk;
+      wsa.nbr = nbr;
+      hipLaunchKernelGGL(k::knn_wide_kernel, dim3((unsigned)plan.scan_wgs), dim3(64 * k::kWsWaves), plan.scan_lds, dev.stream, wsa);
+    } else if (plan.scan == GradScan::kKnn2) {
+      const int S = plan.scan_s;
       const int64_t nchunks = (n_pts + k::kK2Chunk - 1) / k::kK2Chunk;
       __bf16* pb = (__bf16*)dev.alloc_bytes((size_t)nchunks * (size_t)k::k2_chunk_bytes(S));
       float* pnf = (float*)dev.alloc_bytes((size_t)nchunks * k::kK2Chunk * 4 * sizeof(float));  // -c_p, four copies per point
@@ -343,12 +350,10 @@ static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x
         std::fprintf(stderr, "knn2 prof (wave 0 of %lld workgroups, 100 MHz ticks): total %llu, flushes %llu (%.1f %%), chunk waits %llu (%.1f %%), "
                      "%llu merge batches\n", (long long)wgs, h[2], h[0], 100.0 * h[0] / (double)h[2], h[1], 100.0 * h[1] / (double)h[2], h[3]);
       }
-    } else if (knn_mode == 1 || (knn_mode == 0 && n_pts < 131072) ||
-               k::knn_mfma_lds_bytes(kk, nn, 2) > (size_t)160 * 1024) {
+    } else if (plan.scan == GradScan::kValu) {
       // (also when the MFMA scan's per-query lists outgrow LDS: n_nbrs > ~400 at k = 64 -- the VALU scan's fit up to the
       //  interface's 512)
-      const size_t lds_knn = k::knn_lds_bytes(kk, nn);
-      if (lds_knn > (size_t)160 * 1024) throw Error(ST_EINVAL, "problem does not fit in LDS");
+      const size_t lds_knn = plan.scan_lds;
       const int64_t knn_blocks = (n_q + k::kKnnQueries - 1) / k::kKnnQueries;
       hipLaunchKernelGGL(k::knn_kernel, dim3((unsigned)knn_blocks), dim3(64 * k::kKnnWaves), lds_knn, dev.stream, (const double*)xt,
                          ldt, n_pts, kk, qd, n_q, nn, nbr);
@@ -356,11 +361,10 @@ static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x
       double* pnorm = (double*)dev.alloc_bytes(sizeof(double) * (size_t)n_pts);
       hipLaunchKernelGGL(k::point_norms_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, dev.stream, (const double*)xt, ldt,
                          n_pts, kk, pnorm);
-      const int waves = k::knn_mfma_lds_bytes(kk, nn, 4) <= (size_t)160 * 1024 ? 4 : 2;
-      const size_t lds_knn = k::knn_mfma_lds_bytes(kk, nn, waves);
-      if (lds_knn > (size_t)160 * 1024) throw Error(ST_EINVAL, "problem does not fit in LDS");
+      const int waves = plan.scan_w;
+      const size_t lds_knn = plan.scan_lds;
       const int64_t knn_blocks = (n_q + 16 * waves - 1) / (16 * waves);
-      const int nks = k::knn_mfma_slices(kk);
+      const int nks = plan.scan_nks;
 #define CORRLA_KNN_LAUNCH(W_, S_)                                                                                              \
   hipLaunchKernelGGL((k::knn_mfma_kernel<W_, S_>), dim3((unsigned)knn_blocks), dim3(64 * W_), lds_knn, dev.stream, (const double*)xt, \
                      ldt, (const double*)pnorm, n_pts, kk, qd, n_q, nn, nbr)
@@ -378,9 +382,26 @@ static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x
     const int64_t ldgd = host_ptrs ? kf : ldg;
     dev.event_mark(1);
     // order 1: the MFMA-built normal equations (round 3; CORRLA_FIT=1 keeps the general kernel)
-    if (est_order == 1 && env_int("CORRLA_FIT", 0) != 1) {
-      const size_t lds_lin = k::grad_fit_lin_lds_bytes(kk, nn);
-      const int ntt = (kk + 2 + 15) / 16;
+    if (plan.fit == GradFit::kWide) {
+      k::WideFitArgs wfa;
+      wfa.x = xd;
+      wfa.y = yd;
+      wfa.xq = qd;
+      wfa.nbr = nbr;
+      wfa.n_q = n_q;
+      wfa.n_nbrs = n_nbrs;
+      wfa.P = k::grad_design_cols(kf, est_order);
+      wfa.k = kk;
+      wfa.order = est_order;
+      wfa.out_scale = out_scale;
+      wfa.g = gd;
+      wfa.ldg = ldgd;
+      wfa.status = status;
+      wfa.ws = wf_ws;
+      hipLaunchKernelGGL(k::grad_fit_wide_kernel, dim3((unsigned)plan.fit_wgs), dim3(256), plan.fit_lds, dev.stream, wfa);
+    } else if (plan.fit == GradFit::kLin) {
+      const size_t lds_lin = plan.fit_lds;
+      const int ntt = plan.fit_ntt;
       const k::FitRowTab rtab = k::grad_fit_lin_row_table(kk + 1);
       unsigned long long* fprof = nullptr;
       if (env_int("CORRLA_KNN2_PROF", 0)) {
@@ -407,14 +428,14 @@ static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x
                      "solves %.0f (%.0f %%)\n", h[3], h[0] / (double)h[3], 100.0 * h[0] / tot, h[1] / (double)h[3], 100.0 * h[1] / tot,
                      h[2] / (double)h[3], 100.0 * h[2] / tot);
       }
-    } else if (m_in_lds) {
-      hipLaunchKernelGGL(k::grad_fit_kernel, dim3((unsigned)n_q), dim3(64), lds_fit, dev.stream, xd, yd, kk, qd, n_q, (const int*)nbr,
+    } else if (plan.fit == GradFit::kLds) {
+      hipLaunchKernelGGL(k::grad_fit_kernel, dim3((unsigned)n_q), dim3(64), plan.fit_lds, dev.stream, xd, yd, kk, qd, n_q, (const int*)nbr,
                          nn, est_order, out_scale, gd, ldgd, status, (double*)nullptr, (int64_t)0);
     } else {
-      const int64_t wgs = std::min<int64_t>(n_q, 2 * (int64_t)dev.num_cus);
+      const int64_t wgs = plan.fit_wgs;
       const size_t melems = k::grad_fit_m_elems(kk, est_order);
       double* mg = (double*)dev.alloc_bytes((size_t)wgs * melems * sizeof(double));
-      hipLaunchKernelGGL(k::grad_fit_kernel, dim3((unsigned)wgs), dim3(64), lds_fit, dev.stream, xd, yd, kk, qd, n_q, (const int*)nbr,
+      hipLaunchKernelGGL(k::grad_fit_kernel, dim3((unsigned)wgs), dim3(64), plan.fit_lds, dev.stream, xd, yd, kk, qd, n_q, (const int*)nbr,
                          nn, est_order, out_scale, gd, ldgd, status, mg, (int64_t)melems);
     }
     CORRLA_HIP(hipGetLastError());

@@ -22,15 +22,11 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "grad_plan.hpp"
+
 namespace corrla {
 namespace k {
 
-constexpr int kGradMaxDim = 64;    // features k
-constexpr int kGradMaxNbr = 512;   // neighbours per query (register arrays of the list insertion; LDS is checked per call)
-// design-matrix columns: k + 1 (order 1), k + k (k + 1) / 2 + 1 (order 2); no fixed cap: the neighbours of a query live in
-// LDS (grad_fit_lds_bytes(k, n_nbrs, order, false) <= 160 KiB), its normal equations next to them when they fit (order 2
-// up to k = 14) and in a per-workgroup slice of global memory otherwise (order 2 up to k = 30, where n_nbrs <= 512 binds)
-constexpr int kKnnQueriesPerWave = 4, kKnnWaves = 4, kKnnQueries = kKnnQueriesPerWave * kKnnWaves;
 
 // xt (k x ldt, dimension-major) <- x (n x k, row-major)
 __global__ void grad_transpose_kernel(const double* __restrict__ x, int64_t n, int k, double* xt, int64_t ldt) {
@@ -128,9 +124,6 @@ __global__ __launch_bounds__(64 * kKnnWaves) void knn_kernel(const double* __res
     if (q0 + qq < n_q) nbr[(q0 + qq) * n_nbrs + (idx - qq * n_nbrs)] = li[idx];
   }
 }
-inline size_t knn_lds_bytes(int k, int n_nbrs) {
-  return (size_t)k * 64 * 8 + (size_t)kKnnQueries * k * 8 + (size_t)kKnnQueries * n_nbrs * 12 + 64;
-}
 
 // ---- k-NN with the distance tile on the f64 MFMA ---------------------------------------------------------
 // d^2(q, p) = |q|^2 + |p|^2 - 2 q.p: each wave owns 16 queries whose MFMA A-fragments (16 x 4 slices of the query
@@ -141,7 +134,6 @@ inline size_t knn_lds_bytes(int k, int n_nbrs) {
 // distance sum_d (p_d - q_d)^2 recomputed across the lanes before it may enter the sorted list, so the neighbour sets
 // and their order are those of the exact search.
 typedef float knn_f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kKnnPitch = 80;
 __device__ __forceinline__ double wave_max_f64(double x) {
   auto dpp = [](double v, auto ctrl) {
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -363,12 +355,6 @@ __global__ __launch_bounds__(64 * W) void knn_mfma_kernel(const double* __restri
     for (int f = 0; f < n_nbrs; ++f) rank += (qd[f] < v || (qd[f] == v && qix[f] < ix)) ? 1 : 0;
     nbr[(q0 + qq) * n_nbrs + rank] = ix;
   }
-}
-inline int knn_mfma_slices(int k) { return k <= 16 ? 4 : (k <= 32 ? 8 : 16); }
-inline size_t knn_mfma_lds_bytes(int k, int n_nbrs, int waves) {
-  const int k4 = (k + 3) & ~3, qt = 16 * waves, kd = 4 * knn_mfma_slices(k);
-  return ((size_t)qt * k4 + qt + (size_t)kd * kKnnPitch + 64 + (size_t)qt * n_nbrs + qt) * 8 +
-         ((size_t)kd * kKnnPitch + (size_t)qt * n_nbrs + 1 + qt) * 4 + 64;
 }
 // |p|^2 of every support point (from the dimension-major copy)
 __global__ void point_norms_kernel(const double* __restrict__ xt, int64_t ldt, int64_t n, int k, double* pn) {
@@ -612,39 +598,6 @@ __global__ __launch_bounds__(64) void grad_fit_kernel(const double* __restrict__
 //  * LDS holds the packed lower triangle of the (k + 1) x (k + 1) system and its right-hand side only (17 KB at k = 64:
 //    eight queries per CU), factorised left-looking with eight products in flight per lane, solved column-oriented.
 // NTT = 16-column tiles of the design including the constant and y: ceil((k + 2) / 16).
-// Rows of the packed lower triangle of grad_fit_lin_kernel (rows 0 .. P; row P = the right-hand side): row i holds columns
-// 0 .. i in an even number of doubles, so every row starts on a 16-byte LDS slot; the rows are stored in a PERMUTED order
-// chosen so that row i starts at a slot congruent to i modulo 16.  Lane r owns row r, and the 16 lanes a ds_read_b128 is
-// serviced for together have distinct lane numbers modulo 16, so their reads of one column fall into 16 different slots of
-// the 256-byte bank line: conflict-free (in index order the starts are m (m + 1) or (m + 1)^2 slots, which take 4 - 8
-// residues: 4-way conflicts on every read, 12 % of the kernel's LDS cycles).  The greedy below always finds a row of the
-// residue it needs while rows of every residue are left (no padding at P = 65; 2 % at P = 50).
-struct FitRowTab {
-  unsigned short off[68];  // start of row i in doubles
-  unsigned short total;    // doubles in all
-};
-inline FitRowTab grad_fit_lin_row_table(int P) {
-  FitRowTab t{};
-  bool placed[68] = {};
-  int end = 0;  // in 16-byte slots
-  for (int n = 0; n <= P; ++n) {
-    int pick = -1, pad = 0;
-    for (pad = 0; pad < 16 && pick < 0; ++pad) {
-      const int res = (end + pad) & 15;
-      for (int r = P; r >= 0; --r)  // the longest unplaced row of that residue
-        if (!placed[r] && (r & 15) == res) {
-          pick = r;
-          break;
-        }
-      if (pick >= 0) break;
-    }
-    placed[pick] = true;
-    t.off[pick] = (unsigned short)(2 * (end + pad));
-    end += pad + ((pick + 2) >> 1);
-  }
-  t.total = (unsigned short)(2 * end);
-  return t;
-}
 template <int NTT>
 __global__ __launch_bounds__(64, 2) void grad_fit_lin_kernel(const double* __restrict__ x, const double* __restrict__ y, int k,
                                                           const double* __restrict__ xq, int64_t n_q,
@@ -889,21 +842,6 @@ __global__ __launch_bounds__(64, 2) void grad_fit_lin_kernel(const double* __res
     atomicAdd(prof + 2, tp3 - tp2);
     atomicAdd(prof + 3, 1ull);
   }
-}
-inline size_t grad_fit_lin_lds_bytes(int k, int n_nbrs) {
-  const int P = k + 1;
-  return ((size_t)grad_fit_lin_row_table(P).total + 2 * P) * 8 + (size_t)(((n_nbrs + 15) & ~15) + 16) * 4 + 128 * 2 + 64;
-}
-
-// m_in_lds = false: the normal equations live in global memory (grad_fit_kernel's m_glob)
-inline size_t grad_fit_lds_bytes(int k, int n_nbrs, int order, bool m_in_lds = true) {
-  const int P = order == 1 ? k + 1 : k + k * (k + 1) / 2 + 1;
-  const int LM = (P + 1) | 1;
-  return ((size_t)n_nbrs * k + n_nbrs + (m_in_lds ? (size_t)P * LM : (size_t)0) + k + 2 * P) * 8 + (size_t)(2 * P + 4 + n_nbrs) * 4 + 64;
-}
-inline size_t grad_fit_m_elems(int k, int order) {
-  const int P = order == 1 ? k + 1 : k + k * (k + 1) / 2 + 1;
-  return (size_t)P * (size_t)((P + 1) | 1);
 }
 
 }  // namespace k

@@ -25,6 +25,7 @@
 #include "mixed_kernels.hpp"
 #include "grad_kernels.hpp"
 #include "knn2_kernels.hpp"
+#include "grad_wide_kernels.hpp"
 
 namespace corrla {
 
@@ -1412,6 +1413,8 @@ class HipDev {
     lds_limit((const void*)k::grad_fit_lin_kernel<3>, kMax);
     lds_limit((const void*)k::grad_fit_lin_kernel<4>, kMax);
     lds_limit((const void*)k::grad_fit_lin_kernel<5>, kMax);
+    lds_limit((const void*)k::knn_wide_kernel, k::ws_lds_bytes());
+    lds_limit((const void*)k::grad_fit_wide_kernel, k::wf_lds_bytes());
   }
   template <class T>
   static void set_lds_limits_typed() {

@@ -32,30 +32,13 @@
 
 #include <cstdint>
 
+#include "grad_plan.hpp"
 #include "mixed_kernels.hpp"
 
 namespace corrla {
 namespace k {
 
-constexpr int kK2Waves = 12;            // scanning waves per workgroup = 3 per SIMD (168 VGPRs: at 4 per SIMD the query fragments spill;
-                                        // 8 waves x 4 row tiles at 256 VGPRs measured 446 vs 436 ms at 1e6 points; two chunks
-                                        // per ring slot and barrier 455 ms: the longer live ranges put scratch into the loop)
-constexpr int kK2RowTiles = 2;          // 16-query MFMA row tiles per wave: every B fragment read from LDS serves both
-                                        // (with one, the 16 waves' fragment reads -- 256 KiB per chunk and CU at 128 B/clk
-                                        // -- outweighed the MFMAs)
-constexpr int kK2WQ = 16 * kK2RowTiles; // queries per wave
-constexpr int kK2Q = kK2WQ * kK2Waves;  // queries per workgroup tile
-constexpr int kK2Cap = 256;             // candidate slots per query between flushes
-constexpr int kK2List = 128;            // list entries per query (n_nbrs <= 128)
-constexpr int kK2Chunk = 64;            // support points per chunk
 constexpr float kK2Margin = 2.0e-4f;    // bound on |d^2_filter - d^2| / (|q|^2 + |p|^2), see the header
-
-__host__ __device__ constexpr int k2_chunk_bytes(int s) { return s * 8192; }            // s = 32-dimension MFMA steps
-__host__ __device__ constexpr int k2_stage_bytes(int s) { return k2_chunk_bytes(s) + 1024; }  // + 64 x 4 f32: -c_p, replicated
-// two stages + one 64-coordinate f64 row per wave (the query whose candidates are being re-checked)
-constexpr int kK2Stages = 4;            // ring of staged chunks: three in flight behind the one being scanned (with one, every
-                                        // chunk waited for its own DMA: 29 % of the scan at 1e6 points, CORRLA_KNN2_PROF)
-__host__ __device__ constexpr int k2_lds_bytes(int s) { return kK2Stages * k2_stage_bytes(s) + kK2Waves * 512 + 1024; }
 
 struct Knn2Args {
   const __bf16* pb;   // [chunk][s][plane (hi, lo)][tile t of 16 points][lane][8]: B fragments of the centred points

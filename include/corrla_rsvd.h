@@ -274,9 +274,12 @@ CORRLA_API corrla_status corrla_fill_normal_dev_f64(corrla_ctx* ctx, double* p, 
  * xq : n_q x k query points (the reference uses the support points themselves);
  * est_order 1: least-squares hyper-plane through the n_nbrs nearest support points of each query (needs n_pts,
  *              n_nbrs > k + 1); 2: full quadratic [x, x_a x_b (a <= b), 1], build_vandermonde (stats_corr.rs:198-207;
- *              needs n_pts, n_nbrs > k (k + 3) / 2).  Limits: k <= 64, n_nbrs <= 512 (hence order 2 for k <= 30), and one
- *              query's neighbours must fit in 160 KiB of LDS; normal equations that do not fit next to them (order 2
- *              beyond k = 14) live in global memory.
+ *              needs n_pts, n_nbrs > k (k + 3) / 2).  Any k and any n_nbrs <= n_pts: calls with k <= 64,
+ *              n_nbrs <= 512 whose neighbours fit in 160 KiB of LDS take the limited kernels, all others the wide
+ *              kernels (features streamed, lists and normal equations in global memory).  Still rejected: n_pts >
+ *              2^31 - 1, n_q * n_nbrs > 2^40, and normal equations of one query ((P + 1)^2 doubles, P = k + 1 or
+ *              k + k (k + 1) / 2 + 1 design columns) above a 4 GiB workspace budget (order 1 to k ~ 23000, order 2 to
+ *              k = 213).  Order 2 at large k is expensive by nature: ~P^2 n_nbrs + P^3 / 3 flops per query.
  * g  : out_scale * gradients in the reference's k x n_q column-major layout: n_q rows of k contiguous values, row
  *      stride ldg >= k.  fit_svd (active_subspaces.rs:233-250) passes out_scale = 1 / sqrt(n_q) and hands g to
  *      corrla_rsvd_dev_f64 as the k x n_q matrix (row_stride 1, col_stride ldg).
