@@ -16,6 +16,7 @@
 #include <functional>
 #include <vector>
 
+#include "gemm_plan.hpp"
 #include "small_linalg.hpp"
 
 namespace corrla {
@@ -30,22 +31,9 @@ inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 // Skinny matrices (Omega, Y, Z, Q, B^T, small l x l operands) are column-major device
 // buffers with a leading dimension padded to 64 elements and a column count padded to the
-// kernel's column blocking; ALL padding is kept zero so the GEMM kernels never bounds-check them.
-constexpr int kMaxColTiles = 9;  // 16-column MFMA tiles per workgroup column block (144 columns)
+// kernel's column blocking (col_blocking, gemm_plan.hpp); ALL padding is kept zero so the GEMM
+// kernels never bounds-check them.
 constexpr int kLdPad = 64;
-
-struct ColBlocking {
-  int tiles, nblk, nt;
-  int64_t cols_alloc;
-};
-inline ColBlocking col_blocking(int64_t cols) {
-  ColBlocking b;
-  b.tiles = (int)std::max<int64_t>(1, (cols + 15) / 16);
-  b.nblk = (b.tiles + kMaxColTiles - 1) / kMaxColTiles;
-  b.nt = (b.tiles + b.nblk - 1) / b.nblk;
-  b.cols_alloc = (int64_t)b.nblk * b.nt * 16;
-  return b;
-}
 
 template <class T>
 struct Skinny {

@@ -13,6 +13,7 @@
 #include <limits>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "core_svd_plan.hpp"
@@ -89,22 +90,25 @@ class HipDev {
       std::random_device rd;
       entropy_ = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
     }
-    split_nn_override_ = env_int("CORRLA_SPLIT_NN", 0);
-    split_tn_override_ = env_int("CORRLA_SPLIT_TN", 0);
-    mw_override_ = env_int("CORRLA_MW", 0);
     no_device_chol_ = env_int("CORRLA_HOST_CHOL", 0) != 0;
     jmc_min_l_ = env_int("CORRLA_JMC_MIN_L", 96);  // below: the single-workgroup ring kernel + replay is as fast (one launch)
     jmc_max_b_ = std::min(32, std::max(2, env_int("CORRLA_JMC_MAX_B", 24)));
-    gemm_xcd_remap_ = env_int("CORRLA_GEMM_XCD", 1);
-    tall_min_rows_ = env_int("CORRLA_TALL_MIN_ROWS", 65536);  // 0: the general kernels everywhere
     robust_passes_ = std::max(2, env_int("CORRLA_ROBUST_PASSES", 2));
     robust_qr_ = env_int("CORRLA_DEVICE_ROBUST_QR", 1) != 0;  // 0: the round-1 optimistic CholeskyQR2 + host-controlled repeat
-    persist_max_tiles_ = env_int("CORRLA_GEMM_PERSIST_TILES", 16);  // 0: one workgroup per outer tile everywhere
     gemm_debug_flags_ = env_int("CORRLA_GEMM_DEBUG", 0);  // timing-only ablations, results are wrong
-    if (const char* e = std::getenv("CORRLA_MIXED_MIN_WORK")) mixed_min_work_ = std::atof(e);
-    gemm_wide_mode_ = env_int("CORRLA_GEMM_WIDE", gemm_wide_mode_);
-    f64_mfma_waves_ = env_int("CORRLA_F64_WAVES", f64_mfma_waves_);
-    gemm_wide_max_red_ = env_int("CORRLA_GEMM_WIDE_MAX_RED", (int)gemm_wide_max_red_);
+    // the tall products' geometry knobs (gemm_plan.hpp)
+    gemm_knobs_.split_nn = env_int("CORRLA_SPLIT_NN", 0);
+    gemm_knobs_.split_tn = env_int("CORRLA_SPLIT_TN", 0);
+    gemm_knobs_.mw = env_int("CORRLA_MW", 0);
+    gemm_knobs_.xcd_remap = env_int("CORRLA_GEMM_XCD", 1);
+    gemm_knobs_.tall_min_rows = env_int("CORRLA_TALL_MIN_ROWS", 65536);  // 0: the general kernels everywhere
+    gemm_knobs_.persist_max_tiles = env_int("CORRLA_GEMM_PERSIST_TILES", 16);  // 0: one workgroup per outer tile everywhere
+    gemm_knobs_.f64_waves = env_int("CORRLA_F64_WAVES", 8);
+    if (const char* e = std::getenv("CORRLA_MIXED_MIN_WORK")) gemm_knobs_.mixed_min_work = std::atof(e);
+    gemm_knobs_.even_blocks = env_int("CORRLA_EVEN_BLOCKS", 0) != 0;
+    gemm_knobs_.no_gram_alias = env_int("CORRLA_NO_GRAM_ALIAS", 0) != 0;
+    gemm_knobs_.no_rotate = env_int("CORRLA_GEMM_NO_ROTATE", 0) != 0;
+    gemm_knobs_.mixed_split = env_int("CORRLA_MIXED_SPLIT", 0);
   }
   ~HipDev() {
     (void)hipSetDevice(device);
@@ -283,70 +287,24 @@ class HipDev {
     h2d_2d((void*)dst, dpitch_e, (const void*)src, spitch_e, width_e, rows, sizeof(T));
   }
 
-  // ---- GEMMs -----------------------------------------------------------------------------
+  // ---- tall products: gemm_plan (gemm_plan.hpp) decides, the functions below launch what it says ----------------
   template <class T>
   void gemm_nn(const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev) {
     if (x.rows != r.cols) throw Error(ST_EINVAL, "gemm_nn: inner dimensions differ");
-    if (wide_exact_wanted<T>(false, r, x, out)) return gemm_mixed<T>(false, r, x, out, scale_dev, 0);
-    launch_gemm<T>(false, r, x, out, scale_dev, r.rows, r.cols);
+    launch_gemm<T>(false, r, x, out, scale_dev);
   }
   template <class T>
   void gemm_tn(const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev) {
     if (x.rows != r.rows) throw Error(ST_EINVAL, "gemm_tn: inner dimensions differ");
-    if (wide_exact_wanted<T>(true, r, x, out)) return gemm_mixed<T>(true, r, x, out, scale_dev, 0);
-    launch_gemm<T>(true, r, x, out, scale_dev, r.cols, r.rows);
+    launch_gemm<T>(true, r, x, out, scale_dev);
   }
 
-  // ---- bf16-split tall products (mixed_kernels.hpp): f32 operands, bf16 MFMA, f32 accumulate ----------
-  // np = 2 ("bf16x3": hi hi + hi lo + lo hi) or 3 ("bf16x6").  Serves row-major f32 big operands against one column
-  // block (<= 144 columns) when the product is large enough to be worth the extra launches; everything else keeps the
-  // exact f32 kernels (the caller asks mixed_fits first).
+  // bf16-split tall products (mixed_kernels.hpp): f32 operands, bf16 MFMA, f32 accumulate.  np = 2
+  // ("bf16x3": hi hi + hi lo + lo hi) or 3 ("bf16x6").  The caller asks mixed_fits first and keeps the exact kernels
+  // for everything outside the split kernels' domain (gemm_mixed_domain).
   template <class T>
   bool mixed_fits(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out) const {
-    if constexpr (!std::is_same<T, float>::value) {
-      return false;
-    } else {
-      const int64_t outer_n = tn ? r.cols : r.rows, red_n = tn ? r.rows : r.cols;
-      if (x.external || col_blocking(x.cols).nblk != 1) return false;
-      if (((uintptr_t)r.p % 16) || (r.ld % 4) || (r.cols_readable % 4) || ((uintptr_t)x.p % 16) || (x.ld % 64)) return false;
-      if (x.ld < round_up(red_n, k::kMxKT) || out.ld < outer_n || out.rows != outer_n) return false;
-      if ((const void*)r.p == (const void*)x.p) return false;  // Gram products stay exact
-      // (CORRLA_MIXED_MIN_WORK: tests drive small shapes through the kernels)
-      return outer_n >= 1 && red_n >= 1 && (double)outer_n * (double)red_n >= (double)mixed_min_work_;
-    }
-  }
-  // np = 0 runs the same 8-wave / 256-outer-index skeleton with EXACT f32 MFMAs (mixed_kernels.hpp): the skinny operand is
-  // restaged half as often as in the 4-wave kernels of gemm_kernels.hpp, which is what bounds the short-reduction
-  // products (CORRLA_GEMM_WIDE: 0 = never, 1 = whenever the operands fit, 2 = by shape; see wide_exact_wanted).
-  template <class T>
-  bool wide_exact_wanted(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out) const {
-    if constexpr (!std::is_same<T, float>::value) {
-      return false;
-    } else {
-      if (gemm_wide_mode_ == 0 || !mixed_fits<float>(tn, r, x, out)) return false;
-      if (gemm_wide_mode_ == 1) return true;
-      const int64_t red_n = tn ? r.rows : r.cols;
-      return red_n <= gemm_wide_max_red_;
-    }
-  }
-  template <int NT, int NP, bool TN>
-  void mixed_launch_one(dim3 grid, const k::MxArgs& g) {
-    const int lds = k::mx_lds_bytes(NT, NP);
-    hipLaunchKernelGGL((k::gemm_bf16s_kernel<NT, NP, TN>), grid, dim3(64 * (k::kMxWaves + k::kMxLoaders)), lds, stream, g);
-  }
-  template <int NP, bool TN>
-  void mixed_launch_nt(int nt, dim3 grid, const k::MxArgs& g) {
-    switch (nt) {
-      case 1: mixed_launch_one<1, NP, TN>(grid, g); break;
-      case 2: mixed_launch_one<2, NP, TN>(grid, g); break;
-      case 3: mixed_launch_one<3, NP, TN>(grid, g); break;
-      case 4: mixed_launch_one<4, NP, TN>(grid, g); break;
-      case 5: mixed_launch_one<5, NP, TN>(grid, g); break;
-      case 6: mixed_launch_one<6, NP, TN>(grid, g); break;
-      case 7: mixed_launch_one<7, NP, TN>(grid, g); break;
-      case 8: mixed_launch_one<8, NP, TN>(grid, g); break;
-      default: mixed_launch_one<9, NP, TN>(grid, g); break;
-    }
+    return gemm_mixed_domain(gemm_shape(tn, r, x, out, 2), gemm_knobs_);
   }
   template <class T>
   void gemm_mixed(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev, int np) {
@@ -356,97 +314,39 @@ class HipDev {
       throw Error(ST_EINVAL, "internal: the bf16-split products are f32 only");
   }
   void gemm_mixed_f32(bool tn, const Big<float>& r, const Skinny<float>& x, Skinny<float>& out, const float* scale_dev, int np) {
-    if (np != 0 && np != 2 && np != 3) throw Error(ST_EINVAL, "internal: bf16 split takes 2 or 3 planes (0 = exact f32)");
-    if (!mixed_fits<float>(tn, r, x, out)) throw Error(ST_EINVAL, "internal: operands outside the bf16-split kernels' domain");
-    const int64_t outer_n = tn ? r.cols : r.rows, red_n = tn ? r.rows : r.cols;
-    const ColBlocking cb = col_blocking(x.cols);
-    if (cb.cols_alloc > x.cols_alloc || (!out.external && cb.cols_alloc > out.cols_alloc) || (out.external && out.cols < x.cols))
-      throw Error(ST_EINVAL, "internal: skinny column padding too small for the column blocking");
+    const GemmPlan p = plan_gemm(tn, r, x, out, np);
     // the skinny operand in np bf16 planes, reduction index in MFMA fragment order
-    const int64_t plane_stride = x.ld * cb.cols_alloc;
-    __bf16* planes = np ? (__bf16*)alloc_bytes((size_t)np * (size_t)plane_stride * 2) : (__bf16*)x.p;  // exact: X as it is
-    if (np) {
-      const int64_t slots = plane_stride / 8;
-      const dim3 sg((unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (slots + 255) / 256)));
-      if (np == 3)
-        hipLaunchKernelGGL((k::split_planes_kernel<3>), sg, dim3(256), 0, stream, (const float*)x.p, x.ld, cb.cols_alloc, planes, plane_stride, run_if_);
-      else
-        hipLaunchKernelGGL((k::split_planes_kernel<2>), sg, dim3(256), 0, stream, (const float*)x.p, x.ld, cb.cols_alloc, planes, plane_stride, run_if_);
-      CORRLA_HIP(hipGetLastError());
-    }
-    const int64_t tiles64 = (red_n + k::kMxKT - 1) / k::kMxKT;
-    if (tiles64 > 0x7fffffff) throw Error(ST_EINVAL, "reduction dimension too large");
-    const int tiles_total = (int)tiles64;
-    const int64_t outer_tiles = (outer_n + k::kMxOuter - 1) / k::kMxOuter;
-    if (outer_tiles > 0x7fffffff) throw Error(ST_EINVAL, "outer dimension too large");
-    // one workgroup per CU (120-155 KB of LDS): split the reduction until the grid fills the chip
-    int nsplit = 1;
-    if (outer_tiles < num_cus) nsplit = (int)std::min<int64_t>((num_cus + outer_tiles / 2) / outer_tiles, std::max(1, tiles_total / 16));
-    if (const int ov = env_int("CORRLA_MIXED_SPLIT", 0)) nsplit = ov;
-    nsplit = std::max(1, std::min(std::min(nsplit, tiles_total), 65535));
-    k::MxArgs a;
-    a.r = r.p;
-    a.r_rows = r.rows;
-    a.r_cols = r.cols;
-    a.r_ld = r.ld;
-    a.r_cols_readable = r.cols_readable;
-    a.planes = planes;
-    a.x_ld = x.ld;
-    a.plane_stride = plane_stride;
-    a.out = out.p;
-    a.out_ld = out.ld;
-    a.out_cols = out.external ? out.cols : cb.cols_alloc;
-    a.slab = nullptr;
-    a.slab_stride = (int64_t)out.ld * cb.cols_alloc;
-    if (nsplit > 1) a.slab = (float*)alloc_bytes((size_t)nsplit * (size_t)a.slab_stride * sizeof(float));
-    a.scale = scale_dev;
-    a.zero = (const float*)zero_page_;
-    a.tiles_total = tiles_total;
-    a.tiles_per_split = (tiles_total + nsplit - 1) / nsplit;
-    a.nsplit = nsplit;
-    a.run_if = run_if_;
-    a.vec_store = ((out.ld % 4) == 0 && ((uintptr_t)out.p % 16) == 0) ? 1 : 0;
-    a.debug_flags = gemm_debug_flags_;
-    const dim3 grid((unsigned)outer_tiles, 1, (unsigned)nsplit);
-    check_grid(grid);
-    if (np == 0) {
-      if (tn) mixed_launch_nt<0, true>(cb.nt, grid, a); else mixed_launch_nt<0, false>(cb.nt, grid, a);
-    } else if (np == 3) {
-      if (tn) mixed_launch_nt<3, true>(cb.nt, grid, a); else mixed_launch_nt<3, false>(cb.nt, grid, a);
-    } else {
-      if (tn) mixed_launch_nt<2, true>(cb.nt, grid, a); else mixed_launch_nt<2, false>(cb.nt, grid, a);
-    }
+    __bf16* planes = (__bf16*)alloc_bytes(p.plane_bytes);
+    with_nt<3, 2>(p.np, [&](auto np_c) {
+      hipLaunchKernelGGL((k::split_planes_kernel<decltype(np_c)::value>), dim3(p.split_grid), dim3(256), 0, stream, (const float*)x.p,
+                         x.ld, p.plane_cols, planes, p.plane_stride, run_if_);
+    });
     CORRLA_HIP(hipGetLastError());
-    if (nsplit >= 8) {
-      dim3 rg((unsigned)((outer_n + 63) / 64), (unsigned)cb.cols_alloc);
-      check_grid(rg);
-      hipLaunchKernelGGL((k::slab_reduce_deep_kernel<float>), rg, dim3(256), 0, stream, (const float*)a.slab, a.slab_stride, nsplit,
-                         out.p, out.ld, outer_n, a.out_cols, scale_dev, run_if_);
-      CORRLA_HIP(hipGetLastError());
-    } else if (nsplit > 1) {
-      dim3 rg((unsigned)((outer_n + 255) / 256), (unsigned)cb.cols_alloc);
-      check_grid(rg);
-      hipLaunchKernelGGL((k::slab_reduce_kernel<float>), rg, dim3(256), 0, stream, (const float*)a.slab, a.slab_stride, nsplit,
-                         out.p, out.ld, outer_n, a.out_cols, scale_dev, run_if_);
-      CORRLA_HIP(hipGetLastError());
-    }
+    float* slab = p.reduce.kind != SlabReduce::none ? (float*)alloc_bytes(p.slab_bytes) : nullptr;
+    const k::MxArgs a{r.p, r.rows, r.cols, r.ld, r.cols_readable,  // big operand
+                      planes, x.ld, p.plane_stride,                // skinny operand
+                      out.p, out.ld, p.out_cols,                   // output
+                      slab, p.slab_stride, scale_dev, (const float*)zero_page_,
+                      p.tiles_total, p.tiles_per_split, p.nsplit, run_if_, p.vec_store, gemm_debug_flags_};
+    const GemmLaunch& L = p.launch[0];
+    with_nt<kMaxColTiles>(L.nt, [&](auto nt) {
+      with_nt<3, 2>(p.np, [&](auto np_c) {
+        constexpr int NT = decltype(nt)::value, NP = decltype(np_c)::value;
+        const dim3 grid(L.grid[0], L.grid[1], L.grid[2]), block(p.block);
+        if (tn)
+          hipLaunchKernelGGL((k::gemm_bf16s_kernel<NT, NP, true>), grid, block, L.lds, stream, a);
+        else
+          hipLaunchKernelGGL((k::gemm_bf16s_kernel<NT, NP, false>), grid, block, L.lds, stream, a);
+      });
+    });
+    CORRLA_HIP(hipGetLastError());
+    slab_reduce<float>(p.reduce, slab, p.slab_stride, out.p, out.ld, scale_dev, run_if_);
   }
 
   // ---- one-sweep Z' = A^T (A Z) (ata_kernels.hpp): row-major f32 A with n <= 512, l <= 80 -----------
   template <class T>
   bool ata_fused_fits(const Big<T>& a, int64_t l) const {
     return std::is_same<T, float>::value && a.cols <= 512 && a.cols >= 16 && l <= 80 && a.rows >= 4096;
-  }
-  template <int NK>
-  void ata_launch_nct(int nct, dim3 grid, const k::AtaArgs& g) {
-    const dim3 block(256);
-    switch (nct) {
-      case 1: hipLaunchKernelGGL((k::ata_fused_kernel<NK, 1>), grid, block, k::ata_lds_bytes(NK, 1), stream, g); break;
-      case 2: hipLaunchKernelGGL((k::ata_fused_kernel<NK, 2>), grid, block, k::ata_lds_bytes(NK, 2), stream, g); break;
-      case 3: hipLaunchKernelGGL((k::ata_fused_kernel<NK, 3>), grid, block, k::ata_lds_bytes(NK, 3), stream, g); break;
-      case 4: hipLaunchKernelGGL((k::ata_fused_kernel<NK, 4>), grid, block, k::ata_lds_bytes(NK, 4), stream, g); break;
-      default: hipLaunchKernelGGL((k::ata_fused_kernel<NK, 5>), grid, block, k::ata_lds_bytes(NK, 5), stream, g); break;
-    }
   }
   template <class T>
   void ata_fused(const Big<T>& a, const Skinny<T>& x, Skinny<T>& z) {
@@ -479,16 +379,17 @@ class HipDev {
       g.rows_per_group = rows_per_group;
       g.nrowgroups = nrg;
       g.zero = (const float*)zero_page_;
-      const dim3 grid((unsigned)nrg);
-      if (nk == 2) ata_launch_nct<2>(nct, grid, g);
-      else if (nk == 4) ata_launch_nct<4>(nct, grid, g);
-      else ata_launch_nct<8>(nct, grid, g);
+      with_nt<8, 2>(nk, [&](auto nk_c) {  // nk is 2, 4 or 8
+        with_nt<5>(nct, [&](auto nct_c) {
+          constexpr int NK = decltype(nk_c)::value, NCT = decltype(nct_c)::value;
+          if constexpr (NK == 2 || NK == 4 || NK == 8)
+            hipLaunchKernelGGL((k::ata_fused_kernel<NK, NCT>), dim3((unsigned)nrg), dim3(256), k::ata_lds_bytes(NK, NCT), stream, g);
+        });
+      });
       CORRLA_HIP(hipGetLastError());
-      dim3 rgd((unsigned)((a.cols + 63) / 64), (unsigned)cb.cols_alloc);
-      check_grid(rgd);
-      hipLaunchKernelGGL((k::slab_reduce_deep_kernel<float>), rgd, dim3(256), 0, stream, (const float*)g.slab, g.slab_stride, nrg,
-                         z.p, z.ld, a.cols, cb.cols_alloc, (const float*)nullptr, (const int*)nullptr);
-      CORRLA_HIP(hipGetLastError());
+      const SlabReducePlan rp{SlabReduce::deep, {(unsigned)((a.cols + 63) / 64), (unsigned)cb.cols_alloc}, nrg, a.cols, cb.cols_alloc};
+      check_grid(dim3(rp.grid[0], rp.grid[1]));
+      slab_reduce<float>(rp, g.slab, g.slab_stride, z.p, z.ld, nullptr, nullptr);
     }
   }
 
@@ -752,7 +653,7 @@ class HipDev {
     Skinny<T> out = y.view_cols(l);
     Skinny<T> mv = m.view_cols(l);
     mv.rows = l;
-    launch_gemm<T>(true, as_rowmajor_transposed(y, l), mv, out, (const T*)nullptr, y.rows, l);
+    launch_gemm<T>(true, as_rowmajor_transposed(y, l), mv, out, (const T*)nullptr);
   }
   template <class T>
   void refill_null(Skinny<T>& y, int64_t l, const int* null_mask, uint64_t seed) {
@@ -1354,23 +1255,17 @@ class HipDev {
   size_t ev_used_ = 0;
   std::vector<PhaseMark> marks_;
   static constexpr size_t kPinnedBytes = (size_t)8 << 20;
-  int split_nn_override_ = 0, split_tn_override_ = 0, mw_override_ = 0, gemm_debug_flags_ = 0;
+  int gemm_debug_flags_ = 0;
+  GemmKnobs gemm_knobs_;
   uint64_t entropy_ = 0, calls_ = 0, calls_sharded_ = 0;
   bool no_device_chol_ = false;
   int jmc_min_l_ = 96, jmc_max_b_ = 24, jmc_local_ = 1;
-  int gemm_xcd_remap_ = 1;  // CORRLA_GEMM_XCD=0: plain block mapping in gemm_tn (see GemmArgs::xcd_remap)
-  int persist_max_tiles_ = 16;
   const int* run_if_ = nullptr;
   bool phase_events_ = true;
   bool robust_qr_ = true;
   int robust_passes_ = 2;
   int jmc_extra_sweeps_ = 0, jmc_sweeps_hint_ = 0;
   bool jmc_force_v_ = false;
-  int64_t tall_min_rows_ = 65536;
-  int f64_mfma_waves_ = 8;
-  int gemm_wide_mode_ = 0;
-  int64_t gemm_wide_max_red_ = 2048;
-  double mixed_min_work_ = 16777216.0;  // outer x reduction elements below which a product keeps the exact kernels
 
   static void check_grid(const dim3& g) {
     if (g.y > 65535u || g.z > 65535u) throw Error(ST_EINVAL, "problem too large for the launch grid");
@@ -1389,14 +1284,10 @@ class HipDev {
     set_ata_limits<2>();
     set_ata_limits<4>();
     set_ata_limits<8>();
-    set_mixed_limits<0, false>();
-    set_mixed_limits<0, true>();
     set_mixed_limits<2, false>();
     set_mixed_limits<2, true>();
     set_mixed_limits<3, false>();
     set_mixed_limits<3, true>();
-    lds_limit((const void*)k::tall_gram_kernel<float, 5>, k::gram_lds_bytes(5, 4));
-    lds_limit((const void*)k::tall_gram_kernel<float, 6>, k::gram_lds_bytes(6, 4));
     // nearest neighbours and local fits of the gradient stage (corrla_rsvd.hip)
     lds_limit((const void*)k::knn_kernel, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);
@@ -1419,19 +1310,10 @@ class HipDev {
   template <class T>
   static void set_lds_limits_typed() {
     constexpr size_t kMax = k::kLdsMaxBytes;
-    set_gemm_limits<T, 1>();
-    set_gemm_limits<T, 2>();
-    set_gemm_limits<T, 3>();
-    set_gemm_limits<T, 4>();
-    set_gemm_limits<T, 5>();
-    set_gemm_limits<T, 6>();
-    set_gemm_limits<T, 7>();
-    set_gemm_limits<T, 8>();
-    set_gemm_limits<T, 9>();
-    lds_limit((const void*)k::tall_gram_kernel<T, 1>, k::gram_lds_bytes(1, (int)sizeof(T)));
-    lds_limit((const void*)k::tall_gram_kernel<T, 2>, k::gram_lds_bytes(2, (int)sizeof(T)));
-    lds_limit((const void*)k::tall_gram_kernel<T, 3>, k::gram_lds_bytes(3, (int)sizeof(T)));
-    lds_limit((const void*)k::tall_gram_kernel<T, 4>, k::gram_lds_bytes(4, (int)sizeof(T)));
+    for_each_nt<kMaxColTiles>([](auto nt) { set_gemm_limits<T, decltype(nt)::value>(); });
+    for_each_nt<sizeof(T) == 4 ? 6 : 4>([](auto nct) {
+      lds_limit((const void*)k::tall_gram_kernel<T, decltype(nct)::value>, k::gram_lds_bytes(nct, (int)sizeof(T)));
+    });
     lds_limit((const void*)k::hh_leaf_factor_kernel<T, false>, kMax);
     lds_limit((const void*)k::hh_tree_factor_kernel<T, false>, kMax);
     lds_limit((const void*)k::hh_tree_apply_kernel<T, false>, kMax);
@@ -1446,15 +1328,7 @@ class HipDev {
     lds_limit((const void*)k::jacobi_ring_w_kernel<T, 16, 8>, kMax);
     lds_limit((const void*)k::jacobi_ring_w_kernel<T, kBigE, 8>, kMax);
     lds_limit((const void*)k::jacobi_block_round_kernel<T>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 1, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 2, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 3, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 4, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 5, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 6, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 7, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 8, 16>, kMax);
-    lds_limit((const void*)k::jmc_step_kernel<T, 9, 16>, kMax);
+    for_each_nt<9>([](auto nc) { lds_limit((const void*)k::jmc_step_kernel<T, decltype(nc)::value, 16>, k::kLdsMaxBytes); });
   }
   template <class T, int NT>
   static void set_gemm_limits() {
@@ -1463,329 +1337,128 @@ class HipDev {
     lds_limit((const void*)k::gemm_nn_kernel<T, 2, NT>, k::gemm_lds_bytes(2, NT));
     lds_limit((const void*)k::gemm_tn_kernel<T, 2, NT>, k::gemm_lds_bytes(2, NT));
     if constexpr (NT <= 8) lds_limit((const void*)k::gemm_nn_kernel<T, 2, NT, true>, 3 * k::big_tile_bytes(2));
-    if constexpr (std::is_same<T, double>::value) {  // two MFMA waves per SIMD on the MW = 2 tile (launch_mw)
+    if constexpr (std::is_same<T, double>::value) {  // two MFMA waves per SIMD on the MW = 2 tile (launch_general)
       lds_limit((const void*)k::gemm_nn_kernel<T, 1, NT, false, 8>, k::gemm_lds_bytes(2, NT));
       lds_limit((const void*)k::gemm_tn_kernel<T, 1, NT, 8>, k::gemm_lds_bytes(2, NT));
     }
   }
   template <int NK>
   static void set_ata_limits() {
-    lds_limit((const void*)k::ata_fused_kernel<NK, 1>, k::ata_lds_bytes(NK, 1));
-    lds_limit((const void*)k::ata_fused_kernel<NK, 2>, k::ata_lds_bytes(NK, 2));
-    lds_limit((const void*)k::ata_fused_kernel<NK, 3>, k::ata_lds_bytes(NK, 3));
-    lds_limit((const void*)k::ata_fused_kernel<NK, 4>, k::ata_lds_bytes(NK, 4));
-    lds_limit((const void*)k::ata_fused_kernel<NK, 5>, k::ata_lds_bytes(NK, 5));
+    for_each_nt<5>([](auto nct) { lds_limit((const void*)k::ata_fused_kernel<NK, decltype(nct)::value>, k::ata_lds_bytes(NK, nct)); });
   }
   template <int NP, bool TN>
   static void set_mixed_limits() {
-    lds_limit((const void*)k::gemm_bf16s_kernel<1, NP, TN>, k::mx_lds_bytes(1, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<2, NP, TN>, k::mx_lds_bytes(2, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<3, NP, TN>, k::mx_lds_bytes(3, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<4, NP, TN>, k::mx_lds_bytes(4, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<5, NP, TN>, k::mx_lds_bytes(5, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<6, NP, TN>, k::mx_lds_bytes(6, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<7, NP, TN>, k::mx_lds_bytes(7, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<8, NP, TN>, k::mx_lds_bytes(8, NP));
-    lds_limit((const void*)k::gemm_bf16s_kernel<9, NP, TN>, k::mx_lds_bytes(9, NP));
+    for_each_nt<kMaxColTiles>([](auto nt) {
+      lds_limit((const void*)k::gemm_bf16s_kernel<decltype(nt)::value, NP, TN>, k::mx_lds_bytes(nt, NP));
+    });
   }
-  // Launch geometry: MW (16-wide outer tiles per wave), nsplit (split of the reduction into slabs).
-  // One workgroup is resident per CU at the large column blockings, so aim for >= num_cus
-  // workgroups; prefer the MW = 2 shape (fewer skinny-operand bytes per MFMA) whenever the
-  // reduction is long enough to make up the workgroup count by splitting it.
-  void choose_geometry(bool tn, int64_t outer_n, int nblk, int tiles_total, int* mw_out, int* nsplit_out) const {
-    const int ov = tn ? split_tn_override_ : split_nn_override_;
-    int mw = (outer_n >= 256 && tiles_total >= 8) ? 2 : 1;  // small outputs (Gram, core) use the MW = 1 instantiation
-    if (mw_override_ > 0) mw = mw_override_;
-    const int64_t outer_tiles = (outer_n + 64 * mw - 1) / (64 * mw);
-    const int64_t wgs = outer_tiles * nblk;
-    int ns = 1;
-    if (ov > 0) {
-      ns = ov;
-    } else if (wgs < num_cus) {
-      ns = (int)((num_cus + wgs - 1) / wgs);
-      if (wgs * ns < 2 * (int64_t)num_cus && wgs < num_cus / 4) ns *= 2;  // small grids: two waves of WGs
-      ns = std::min(ns, std::max(1, tiles_total / 4));
+  // ---- launchers of the tall products (gemm_plan.hpp) ----
+  template <class T>
+  GemmShape gemm_shape(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out, int np) const {
+    auto aligned = [](const void* p) { return (uintptr_t)p % 16 == 0; };
+    GemmShape s;
+    s.tn = tn;
+    s.esz = (int)sizeof(T);
+    s.r = {r.rows, r.cols, r.ld, r.cols_readable, 0, false, aligned(r.p)};
+    s.x = {x.rows, x.cols, x.ld, 0, x.cols_alloc, x.external, aligned(x.p)};
+    s.out = {out.rows, out.cols, out.ld, 0, out.cols_alloc, out.external, aligned(out.p)};
+    s.same = (const void*)r.p == (const void*)x.p;
+    s.np = np;
+    s.num_cus = num_cus;
+    return s;
+  }
+  template <class T>
+  GemmPlan plan_gemm(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out, int np) const {
+    const GemmPlan p = gemm_plan(gemm_shape(tn, r, x, out, np), gemm_knobs_);
+    if (p.error) throw Error(ST_EINVAL, p.error);
+    return p;
+  }
+  // the instantiations of a kernel over its column tiles (or planes): with_nt calls f(std::integral_constant<int, n>)
+  // for one n in [N, MAX], for_each_nt for every one
+  template <int MAX, int N = 1, class F>
+  static void with_nt(int n, const F& f) {
+    if constexpr (N < MAX) {
+      if (n > N) return with_nt<MAX, N + 1>(n, f);
     }
-    ns = std::max(1, std::min(ns, tiles_total));
-    *mw_out = mw;
-    *nsplit_out = std::min(ns, 65535);
+    if (n != N) throw Error(ST_EINVAL, "internal: no kernel instantiation for " + std::to_string(n));
+    f(std::integral_constant<int, N>{});
   }
-
-  template <class T, int MW, int NT, int NW = 4>
-  void launch_one(bool tn, dim3 grid, const k::GemmArgs<T>& a) {
-    constexpr int GW = MW * NW / 4;  // row tiles per SIMD: the tile geometry (hip_kernels.hpp: gemm_nn_kernel)
-    // the kernels only touch ring buffers [0, min(tiles per workgroup, stages)): a short reduction (the l-deep
-    // products Y * R^-1 and U = Q * U~ have 2-3 tiles) asks for less LDS, so several workgroups share a CU and one's
-    // load latency hides behind another's MFMAs and stores
-    const int64_t per_wg = (int64_t)std::max(1, a.tiles_per_split) * ((a.outer_blocks + (int64_t)grid.x - 1) / grid.x);
-    const int lds = (int)std::min<int64_t>(k::gemm_stages(GW, NT), per_wg) * k::stage_bytes(GW, NT);
-    const dim3 block(64 * (NW + k::kLoaders));  // MFMA waves + loader waves
-    if (tn)
-      hipLaunchKernelGGL((k::gemm_tn_kernel<T, MW, NT, NW>), grid, block, lds, stream, a);
+  template <int MAX, int N = 1, class F>
+  static void for_each_nt(const F& f) {
+    f(std::integral_constant<int, N>{});
+    if constexpr (N < MAX) for_each_nt<MAX, N + 1>(f);
+  }
+  // sum of the partial results of a split reduction (slab_reduce_kernel / slab_reduce_deep_kernel)
+  template <class T>
+  void slab_reduce(const SlabReducePlan& rp, const T* slab, int64_t stride, T* out, int64_t ld, const T* scale, const int* run_if) {
+    if (rp.kind == SlabReduce::none) return;
+    const dim3 grid(rp.grid[0], rp.grid[1]);
+    if (rp.kind == SlabReduce::deep)
+      hipLaunchKernelGGL((k::slab_reduce_deep_kernel<T>), grid, dim3(256), 0, stream, slab, stride, rp.slabs, out, ld, rp.rows,
+                         rp.cols, scale, run_if);
     else
-      hipLaunchKernelGGL((k::gemm_nn_kernel<T, MW, NT, false, NW>), grid, block, lds, stream, a);
-  }
-  template <class T>
-  void launch_nt(bool tn, int mw, int nt, dim3 grid, const k::GemmArgs<T>& a) {
-    switch (nt) {
-      case 1: launch_mw<T, 1>(tn, mw, grid, a); break;
-      case 2: launch_mw<T, 2>(tn, mw, grid, a); break;
-      case 3: launch_mw<T, 3>(tn, mw, grid, a); break;
-      case 4: launch_mw<T, 4>(tn, mw, grid, a); break;
-      case 5: launch_mw<T, 5>(tn, mw, grid, a); break;
-      case 6: launch_mw<T, 6>(tn, mw, grid, a); break;
-      case 7: launch_mw<T, 7>(tn, mw, grid, a); break;
-      case 8: launch_mw<T, 8>(tn, mw, grid, a); break;
-      case 9: launch_mw<T, 9>(tn, mw, grid, a); break;
-      default: throw Error(ST_EINVAL, "internal: bad column blocking");
-    }
-  }
-  template <class T, int NT>
-  void launch_alias(dim3 grid, const k::GemmArgs<T>& a) {
-    const dim3 block(64 * (4 + k::kLoaders));
-    hipLaunchKernelGGL((k::gemm_nn_kernel<T, 2, NT, true>), grid, block, 3 * k::big_tile_bytes(2), stream, a);
-  }
-  template <class T, int NT>
-  void launch_mw(bool tn, int mw, dim3 grid, const k::GemmArgs<T>& a) {
-    if (mw == 2) {
-      // f64: the same 128-index tile with EIGHT MFMA waves of one row tile each -- two waves per SIMD keep the f64 matrix
-      // pipe busier than one can (77.8 vs 60.5 TF register-only); CORRLA_F64_WAVES=4 keeps round 2's shape
-      if constexpr (std::is_same<T, double>::value) {
-        if (f64_mfma_waves_ == 8) return launch_one<T, 1, NT, 8>(tn, grid, a);
-      }
-      launch_one<T, 2, NT>(tn, grid, a);
-    } else {
-      launch_one<T, 1, NT>(tn, grid, a);
-    }
+      hipLaunchKernelGGL((k::slab_reduce_kernel<T>), grid, dim3(256), 0, stream, slab, stride, rp.slabs, out, ld, rp.rows, rp.cols,
+                         scale, run_if);
+    CORRLA_HIP(hipGetLastError());
   }
 
-  // ---- tall_kernels.hpp: Y M and Y^T Y of a very tall sketch with l <= 96 (f32) / 64 (f64) ----
-  template <class T, int K>
-  void launch_tall_apply(dim3 grid, const k::TallApplyArgs<T>& g) {
-    hipLaunchKernelGGL((k::tall_apply_kernel<T, K, K>), grid, dim3(256), 0, stream, g);
-  }
-  template <class T, int NCT>
-  void launch_tall_gram(dim3 grid, const k::TallGramArgs<T>& g) {
-    const int lds = k::gram_lds_bytes(NCT, (int)sizeof(T));
-    hipLaunchKernelGGL((k::tall_gram_kernel<T, NCT>), grid, dim3(256), lds, stream, g);
-  }
-  template <class T>
-  bool launch_tall(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev, int64_t outer_n,
-                   int64_t red_n, const ColBlocking& cb) {
-    constexpr int kMaxL = sizeof(T) == 4 ? 96 : 64;  // register budget of the B fragments
-    constexpr int kVecElems = 16 / (int)sizeof(T);
-    if (tall_min_rows_ <= 0) return false;
-    if (tn) {
-      // out (m x n2) = R^T X with R = Y^T stored row-major kdim x m: the columns of Y are contiguous
-      const int64_t m = outer_n, kdim = red_n, n2 = x.cols;
-      if (kdim > kMaxL || n2 > kMaxL || m < tall_min_rows_ || r.rows != kdim) return false;
-      if (r.ld < round_up(m, 64) || (r.ld % kVecElems) || ((uintptr_t)r.p % 16)) return false;
-      if (x.external || x.ld < kdim) return false;
-      if (out.rows != m || out.ld < m || out.cols < n2) throw Error(ST_EINVAL, "internal: gemm output shape mismatch");
-      const int kt = (int)std::max((kdim + 15) / 16, (n2 + 15) / 16);
-      k::TallApplyArgs<T> g;
-      g.y = r.p;
-      g.m = m;
-      g.ld_y = r.ld;
-      g.kdim = (int)kdim;
-      g.mat = x.p;
-      g.ld_m = x.ld;
-      g.n2 = (int)n2;
-      g.out = out.p;
-      g.ld_o = out.ld;
-      g.out_cols = (int)(out.external ? out.cols : std::min<int64_t>(out.cols_alloc, 16 * kt));
-      g.scale = scale_dev;
-      g.vec_store = ((out.ld % kVecElems) == 0 && ((uintptr_t)out.p % 16) == 0) ? 1 : 0;
-      g.run_if = run_if_;
-      const int64_t nblocks = (m + 16 * kVecElems - 1) / (16 * kVecElems);
-      dim3 grid((unsigned)std::min<int64_t>((nblocks + 3) / 4, num_cus));
-      switch (kt) {
-        case 1: launch_tall_apply<T, 1>(grid, g); break;
-        case 2: launch_tall_apply<T, 2>(grid, g); break;
-        case 3: launch_tall_apply<T, 3>(grid, g); break;
-        case 4: launch_tall_apply<T, 4>(grid, g); break;
-        default:
-          if constexpr (sizeof(T) == 4) {
-            if (kt == 5)
-              launch_tall_apply<T, 5>(grid, g);
-            else
-              launch_tall_apply<T, 6>(grid, g);
-          }
-          break;
-      }
-      CORRLA_HIP(hipGetLastError());
-      return true;
-    }
-    // G (l x l) = Y^T Y: both operands are the same column-major m x l memory
-    const int64_t l = outer_n, m = red_n;
-    if ((const void*)r.p != (const void*)x.p || r.ld != x.ld || l != x.cols || l > kMaxL || m < tall_min_rows_) return false;
-    if ((r.ld % kVecElems) || ((uintptr_t)r.p % 16) || x.external || out.external) return false;
-    const int nct = (int)((l + 15) / 16);
-    if (out.ld < 16 * nct || out.cols_alloc < 16 * nct || cb.cols_alloc < 16 * nct) return false;
-    if (out.rows != l) throw Error(ST_EINVAL, "internal: gemm output shape mismatch");
-    constexpr int kRows = k::gram_rows<T>();
-    const int64_t rows = x.ld;  // the padding rows are zero and may be read
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(num_cus, rows / (4 * kRows)));
-    const int64_t rpg = round_up((rows + want - 1) / want, kRows);
-    const int64_t ngroups = (rows + rpg - 1) / rpg;
-    k::TallGramArgs<T> g;
-    g.y = x.p;
-    g.m = m;
-    g.ld = x.ld;
-    g.l = (int)l;
-    g.slab_stride = (int64_t)out.ld * out.cols_alloc;
-    g.slab = (T*)alloc_bytes((size_t)ngroups * (size_t)g.slab_stride * sizeof(T));
-    g.out_ld = out.ld;
-    g.rows_per_group = rpg;
-    g.zero = (const T*)zero_page_;
-    g.run_if = run_if_;
-    dim3 grid((unsigned)ngroups);
-    switch (nct) {
-      case 1: launch_tall_gram<T, 1>(grid, g); break;
-      case 2: launch_tall_gram<T, 2>(grid, g); break;
-      case 3: launch_tall_gram<T, 3>(grid, g); break;
-      case 4: launch_tall_gram<T, 4>(grid, g); break;
-      default:
-        if constexpr (sizeof(T) == 4) {
-          if (nct == 5)
-            launch_tall_gram<T, 5>(grid, g);
+  // gemm_nn_kernel / gemm_tn_kernel<T, MW, NT, NW> with the plan's MW and NW (NW = 8: the f64 MW = 2 tile on eight waves)
+  template <class T, int NT>
+  void launch_general(bool tn, const GemmPlan& p, dim3 grid, dim3 block, int lds, const k::GemmArgs<T>& a) {
+    with_nt<2>(p.mw, [&](auto mw) {
+      with_nt<8, 4>(p.nw, [&](auto nw) {
+        constexpr int MW = decltype(mw)::value, NW = decltype(nw)::value;
+        if constexpr (NW == 4 || (NW == 8 && MW == 1 && std::is_same<T, double>::value)) {
+          if (tn)
+            hipLaunchKernelGGL((k::gemm_tn_kernel<T, MW, NT, NW>), grid, block, lds, stream, a);
           else
-            launch_tall_gram<T, 6>(grid, g);
+            hipLaunchKernelGGL((k::gemm_nn_kernel<T, MW, NT, false, NW>), grid, block, lds, stream, a);
         }
-        break;
-    }
-    CORRLA_HIP(hipGetLastError());
-    dim3 rg((unsigned)((l + 63) / 64), (unsigned)(16 * nct));
-    hipLaunchKernelGGL((k::slab_reduce_deep_kernel<T>), rg, dim3(256), 0, stream, (const T*)g.slab, g.slab_stride, (int)ngroups,
-                       out.p, out.ld, l, (int64_t)(16 * nct), scale_dev, run_if_);
-    CORRLA_HIP(hipGetLastError());
-    return true;
+      });
+    });
   }
 
-  // out (outer_n x L) = scale * op(R) * X; `outer_n` = surviving dimension of R, `red_n` = reduced one
+  // out (outer_n x L) = scale * op(R) * X: op(R) = R (tn false, outer_n = R's rows) or R^T (outer_n = R's columns)
   template <class T>
-  void launch_gemm(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev, int64_t outer_n,
-                   int64_t red_n) {
-    constexpr int KT = k::MT<T>::KT;
-    constexpr int VEC = k::MT<T>::VEC;
-    const ColBlocking cb = col_blocking(x.cols);
-    if (x.external) throw Error(ST_EINVAL, "internal: an external buffer cannot be a padded operand");
-    if (cb.cols_alloc > x.cols_alloc || (!out.external && cb.cols_alloc > out.cols_alloc) || (out.external && out.cols < x.cols))
-      throw Error(ST_EINVAL, "internal: skinny column padding too small for the column blocking");
-    if (out.rows != outer_n || out.ld < outer_n) throw Error(ST_EINVAL, "internal: gemm output shape mismatch");
-    if (((uintptr_t)r.p % 16) || (r.ld % VEC) || (r.cols_readable % VEC) || ((uintptr_t)x.p % 16))
-      throw Error(ST_EINVAL, "internal: operand not 16-byte vector aligned");
-    if (launch_tall<T>(tn, r, x, out, scale_dev, outer_n, red_n, cb)) return;
-    const int64_t tiles64 = (red_n + KT - 1) / KT;
-    if (tiles64 > 0x7fffffff) throw Error(ST_EINVAL, "reduction dimension too large");
-    const int tiles_total = (int)tiles64;
-    if (x.ld < (int64_t)tiles_total * KT) throw Error(ST_EINVAL, "internal: skinny leading dimension too small");
-    int mw = 1, nsplit = 1;
-    // an uneven column blocking (see below) runs its wide and its narrow blocks as two launches: each must fill the
-    // chip by itself, so the reduction split is sized for the blocks of ONE launch
-    const int n_wide0 = cb.tiles - cb.nblk * (cb.nt - 1);
-    // (only where it pays: the second launch costs ~10 us, the skipped tile 1/18 of a product's time)
-    const bool uneven0 = cb.nblk > 1 && n_wide0 < cb.nblk && cb.nt >= 2 && !env_int("CORRLA_EVEN_BLOCKS", 0) &&
-                         (double)outer_n * (double)red_n * (double)cb.cols_alloc >= 1.0e10;
-    choose_geometry(tn, outer_n, uneven0 ? std::max(1, std::min(n_wide0, cb.nblk - n_wide0)) : cb.nblk, tiles_total, &mw, &nsplit);
-    // Gram matrix G = Y^T Y: both operands are the same memory and one outer tile (MW = 2: 128 indices) holds every
-    // column -> the aliased instantiation stages Y once per tile
-    const bool alias = !tn && (const void*)r.p == (const void*)x.p && r.ld == x.ld && cb.nblk == 1 && outer_n <= 128 &&
-                       cb.nt <= 8 && outer_n == x.cols && !env_int("CORRLA_NO_GRAM_ALIAS", 0);
-    if (alias) {
-      mw = 2;
-      const int64_t wgs1 = 1;
-      nsplit = (int)std::min<int64_t>(std::max<int64_t>(1, tiles_total / 4), 2 * (int64_t)num_cus / wgs1);
-      if (split_nn_override_ > 0) nsplit = std::min(split_nn_override_, tiles_total);
-    }
-    const int64_t outer_tiles = (outer_n + 64 * mw - 1) / (64 * mw);
-    if (outer_tiles > 0x7fffffff) throw Error(ST_EINVAL, "outer dimension too large");
-    k::GemmArgs<T> a;
-    a.r = r.p;
-    a.r_rows = r.rows;
-    a.r_cols = r.cols;
-    a.r_ld = r.ld;
-    a.r_cols_readable = r.cols_readable;
-    a.x = x.p;
-    a.x_ld = x.ld;
-    a.out = out.p;
-    a.out_ld = out.ld;
-    // columns this product may write: a caller's buffer has exactly `cols`; an uneven column blocking (below) never
-    // computes the all-zero tail tile, which therefore stays as allocated (zero)
-    const int n_wide = cb.tiles - cb.nblk * (cb.nt - 1);  // column blocks that really have cb.nt tiles
-    const bool uneven = !alias && uneven0;
-    a.out_cols = out.external ? out.cols : (uneven ? (int64_t)cb.tiles * 16 : cb.cols_alloc);
-    a.scale = scale_dev;
-    a.zero = (const T*)zero_page_;
-    a.tiles_total = tiles_total;
-    a.tiles_per_split = (tiles_total + nsplit - 1) / nsplit;
-    a.nsplit = nsplit;
-    a.debug_flags = gemm_debug_flags_;
-    a.slab = nullptr;
-    a.slab_stride = (int64_t)out.ld * cb.cols_alloc;
-    if (nsplit > 1) a.slab = (T*)alloc_bytes((size_t)nsplit * (size_t)a.slab_stride * sizeof(T));
-    a.outer_blocks = (int)outer_tiles;
-    a.run_if = run_if_;
-    a.vec_store = ((out.ld % 4) == 0 && ((uintptr_t)out.p % 16) == 0) ? 1 : 0;
-    a.rotate = (!tn && !alias && a.tiles_per_split <= 32 && a.tiles_per_split > 1 && !env_int("CORRLA_GEMM_NO_ROTATE", 0)) ? 1 : 0;
-    // Short reductions (A Z with n = 512: 8 tiles; Y R^-1: 2): a workgroup per outer tile spends a fifth of its life
-    // waiting for its first tile.  A persistent launch -- as many workgroups as fit the chip at once, each walking its
-    // outer tiles with the DMA ring running on across the boundaries -- pays that latency once.
-    int64_t gx = outer_tiles;
-    if (!alias && a.tiles_per_split <= persist_max_tiles_) {
-      const int64_t lds_full = (int64_t)k::gemm_stages(mw, cb.nt) * k::stage_bytes(mw, cb.nt);
-      const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / lds_full));
-      const int64_t slots = per_cu * num_cus / ((int64_t)cb.nblk * nsplit);
-      if (slots >= 1 && outer_tiles >= 3 * slots) gx = slots;
-    }
-    dim3 grid((unsigned)gx, (unsigned)cb.nblk, (unsigned)nsplit);
-    check_grid(grid);
-    // gemm_tn with a few outer tiles and a long, split reduction (A^T Y at n = 512): the outer tiles of one slab on one XCD
-    // (per launch: the kernel's remap assumes gridDim.y == 1 -- the two launches of an uneven blocking qualify one by one)
-    auto xcd_ok = [&](unsigned gy) {
-      return (tn && gemm_xcd_remap_ && gy == 1 && gx == outer_tiles && outer_tiles >= 2 && outer_tiles <= 32 && nsplit >= 8) ? 1 : 0;
-    };
-    a.xcd_remap = xcd_ok((unsigned)cb.nblk);
-    a.col_base = 0;
-    // Uneven column blocking: `tiles` 16-column tiles over nblk blocks need not all be cb.nt wide -- 17 tiles (l = 266)
-    // are 9 + 8, not 9 + 9: the narrower blocks run the next-smaller instantiation in a second launch and skip the
-    // all-zero padding tile (5.5 % of the MFMA work of every tall product at l = 266).
-    if (uneven) {
-      dim3 g1((unsigned)gx, (unsigned)n_wide, (unsigned)nsplit);
-      dim3 g2((unsigned)gx, (unsigned)(cb.nblk - n_wide), (unsigned)nsplit);
-      a.xcd_remap = xcd_ok(g1.y);
-      launch_nt<T>(tn, mw, cb.nt, g1, a);
-      a.col_base = (int64_t)n_wide * cb.nt * 16;
-      a.xcd_remap = xcd_ok(g2.y);
-      launch_nt<T>(tn, mw, cb.nt - 1, g2, a);
-    } else if (alias) {
-      switch (cb.nt) {
-        case 1: launch_alias<T, 1>(grid, a); break;
-        case 2: launch_alias<T, 2>(grid, a); break;
-        case 3: launch_alias<T, 3>(grid, a); break;
-        case 4: launch_alias<T, 4>(grid, a); break;
-        case 5: launch_alias<T, 5>(grid, a); break;
-        case 6: launch_alias<T, 6>(grid, a); break;
-        case 7: launch_alias<T, 7>(grid, a); break;
-        default: launch_alias<T, 8>(grid, a); break;
-      }
+  void launch_gemm(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev) {
+    const GemmPlan p = plan_gemm(tn, r, x, out, 0);
+    const GemmLaunch& L0 = p.launch[0];
+    T* slab = p.reduce.kind != SlabReduce::none ? (T*)alloc_bytes(p.slab_bytes) : nullptr;
+    if (p.family == GemmFamily::tall_apply) {  // tall_kernels.hpp: out (m x n2) = Y M with Y^T stored row-major kdim x m
+      const k::TallApplyArgs<T> g{r.p, r.cols, r.ld, (int)r.rows, x.p, x.ld, (int)x.cols, out.p, out.ld, (int)p.out_cols,
+                                  scale_dev, p.vec_store, run_if_};
+      with_nt<sizeof(T) == 4 ? 6 : 4>(L0.nt, [&](auto kt) {
+        constexpr int K = decltype(kt)::value;
+        hipLaunchKernelGGL((k::tall_apply_kernel<T, K, K>), dim3(L0.grid[0]), dim3(p.block), L0.lds, stream, g);
+      });
+    } else if (p.family == GemmFamily::tall_gram) {  // G (l x l) = Y^T Y: both operands are the same m x l memory
+      const k::TallGramArgs<T> g{x.p, r.cols, x.ld, (int)out.rows, slab, p.slab_stride, out.ld, p.rows_per_group,
+                                 (const T*)zero_page_, run_if_};
+      with_nt<sizeof(T) == 4 ? 6 : 4>(L0.nt, [&](auto nct) {
+        hipLaunchKernelGGL((k::tall_gram_kernel<T, decltype(nct)::value>), dim3(L0.grid[0]), dim3(p.block), L0.lds, stream, g);
+      });
     } else {
-      launch_nt<T>(tn, mw, cb.nt, grid, a);
+      k::GemmArgs<T> a{r.p, r.rows, r.cols, r.ld, r.cols_readable,  // big operand
+                       x.p, x.ld,                                     // skinny operand
+                       out.p, out.ld, p.out_cols, 0,                  // output; col_base per launch
+                       slab, p.slab_stride, scale_dev, (const T*)zero_page_,
+                       p.tiles_total, p.tiles_per_split, p.nsplit, gemm_debug_flags_, run_if_,
+                       p.vec_store, p.rotate, p.outer_blocks, 0};     // xcd_remap per launch
+      for (int i = 0; i < p.nlaunch; ++i) {
+        const GemmLaunch& L = p.launch[i];
+        const dim3 grid(L.grid[0], L.grid[1], L.grid[2]), block(p.block);
+        a.col_base = L.col_base;
+        a.xcd_remap = L.xcd_remap;
+        if (p.family == GemmFamily::gram_alias)
+          with_nt<8>(L.nt, [&](auto nt) {
+            hipLaunchKernelGGL((k::gemm_nn_kernel<T, 2, decltype(nt)::value, true>), grid, block, L.lds, stream, a);
+          });
+        else
+          with_nt<kMaxColTiles>(L.nt, [&](auto nt) { launch_general<T, decltype(nt)::value>(tn, p, grid, block, L.lds, a); });
+      }
     }
     CORRLA_HIP(hipGetLastError());
-    if (nsplit >= 8) {
-      dim3 rg((unsigned)((outer_n + 63) / 64), (unsigned)cb.cols_alloc);
-      check_grid(rg);
-      hipLaunchKernelGGL((k::slab_reduce_deep_kernel<T>), rg, dim3(256), 0, stream, (const T*)a.slab, a.slab_stride,
-                         nsplit, out.p, out.ld, outer_n, a.out_cols, scale_dev, run_if_);
-      CORRLA_HIP(hipGetLastError());
-    } else if (nsplit > 1) {
-      dim3 rg((unsigned)((outer_n + 255) / 256), (unsigned)cb.cols_alloc);
-      check_grid(rg);
-      hipLaunchKernelGGL((k::slab_reduce_kernel<T>), rg, dim3(256), 0, stream, (const T*)a.slab, a.slab_stride, nsplit,
-                         out.p, out.ld, outer_n, a.out_cols, scale_dev, run_if_);
-      CORRLA_HIP(hipGetLastError());
-    }
+    slab_reduce<T>(p.reduce, slab, p.slab_stride, out.p, out.ld, scale_dev, run_if_);
   }
 
   template <class T>

@@ -35,6 +35,8 @@
 
 #include <type_traits>
 
+#include "gemm_plan.hpp"  // kLoaders, kRowBytes, the tile and LDS sizes
+
 namespace corrla {
 namespace k {
 
@@ -51,8 +53,8 @@ template <>
 struct MT<float> {
   typedef f32x4 acc_t;
   typedef f32x4 vec_t;
-  static constexpr int VEC = 4;  // elements per 16 bytes
-  static constexpr int KT = 64;  // reduction elements per 256-byte LDS row
+  static constexpr int VEC = gemm_vec(4);  // elements per 16 bytes
+  static constexpr int KT = gemm_kt(4);    // reduction elements per 256-byte LDS row
   // The tall GEMMs feed the BIG operand as MFMA A and the skinny one as B: a lane's four D registers are then four
   // consecutive OUTER indices of one result column, i.e. one 16-byte store (a quarter of the store instructions of
   // the other order; 10^7 x 80 results made the stores 10 % of the product's time).
@@ -70,8 +72,8 @@ template <>
 struct MT<double> {
   typedef f64x4 acc_t;
   typedef f64x2 vec_t;
-  static constexpr int VEC = 2;
-  static constexpr int KT = 32;
+  static constexpr int VEC = gemm_vec(8);
+  static constexpr int KT = gemm_kt(8);
   // f64 D registers are 4 rows apart: the skinny operand stays MFMA A, so that 16 lanes store 128 contiguous bytes
   static constexpr bool kBigIsA = false;
   static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) {
@@ -84,7 +86,6 @@ struct MT<double> {
   static __device__ __forceinline__ int tswz(int row) { return ((row >> 1) & 1) << 3; }
 };
 
-constexpr int kRowBytes = 256;  // LDS row of the k-contiguous images
 #ifndef CORRLA_PD
 #define CORRLA_PD 4
 #endif
@@ -92,18 +93,6 @@ constexpr int kRowBytes = 256;  // LDS row of the k-contiguous images
 #define CORRLA_GEMM_DEFER 2  // pipeline steps whose MFMAs are issued after the next tile's barrier (0 = off)
 #endif
 constexpr int kPrefetchSteps = CORRLA_PD;  // LDS fragment reads run this many MFMA steps ahead
-constexpr int kLoaders = 4;      // LDS-DMA loader waves per workgroup (besides the 4 MFMA waves); must divide 4
-// A workgroup owns 64*MW outer indices (4 waves x MW 16-wide MFMA tiles each).  MW = 2 halves the
-// skinny-operand bytes staged per MFMA (the per-CU global->LDS fill rate, ~11 B/clk, is what bounds
-// the MW = 1 shape at 144 columns: 52 KiB per 4608 MFMA cycles); MW = 1 keeps small problems spread
-// over more workgroups.
-__host__ __device__ constexpr int outer_tile(int mw) { return 64 * mw; }
-__host__ __device__ constexpr int big_tile_bytes(int mw) { return 64 * 256 * mw; }
-__host__ __device__ constexpr int stage_bytes(int mw, int nt) { return big_tile_bytes(mw) + nt * 16 * kRowBytes; }
-// LDS ring depth: 3 stages (the loaders run two tiles ahead, which hides the higher memory latency of the
-// chip's low-clock state between bursts) whenever they fit in 160 KiB, else 2.
-__host__ __device__ constexpr int gemm_stages(int mw, int nt) { return 3 * stage_bytes(mw, nt) <= 160 * 1024 ? 3 : 2; }
-__host__ __device__ constexpr int gemm_lds_bytes(int mw, int nt) { return gemm_stages(mw, nt) * stage_bytes(mw, nt); }
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");

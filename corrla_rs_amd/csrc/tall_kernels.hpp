@@ -144,20 +144,7 @@ struct TallGramArgs {
   const int* run_if;       // optional device word: nothing happens when it is 0
 };
 
-// rows per LDS tile: 512 bytes per column
-template <class T>
-__host__ __device__ constexpr int gram_rows() { return 512 / (int)sizeof(T); }
-__host__ __device__ constexpr int gram_tile_bytes(int nct) { return 16 * nct * 512; }
-__host__ __device__ constexpr int gram_stages(int nct) {
-  const int s = (160 * 1024 - 4096) / gram_tile_bytes(nct);
-  return s > 4 ? 4 : s;
-}
-__host__ __device__ constexpr int gram_lds_bytes(int nct, int esz) {
-  const int ring = gram_stages(nct) * gram_tile_bytes(nct);
-  const int red = 3 * (nct * (nct + 1) / 2) * 256 * esz;  // cross-wave sum of the partial tiles (waves 1..3)
-  return ring > red ? ring : red;
-}
-
+// rows per LDS tile and the LDS size: gram_rows, gram_lds_bytes (gemm_plan.hpp)
 template <class T, int NCT>
 __global__ __launch_bounds__(256) void tall_gram_kernel(TallGramArgs<T> g) {
   typedef typename MT<T>::vec_t vec_t;
