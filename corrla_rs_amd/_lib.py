@@ -62,6 +62,14 @@ def _sigs():
         s["corrla_power_iter_" + suf] = (C.c_int, pw)
         s["corrla_power_iter_dev_" + suf] = (C.c_int, pw)
         s["corrla_matmul_dev_" + suf] = (C.c_int, [vp, C.c_int, vp, i64, i64, i64, i64, vp, i64, i64, sc, vp, i64])
+        # CSR input: values, int32 col_idx, int64 row_ptr, m, n, nnz in place of (a, m, n, rs, cs)
+        rsvd_csr = [vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
+        s["corrla_rsvd_csr_" + suf] = (C.c_int, rsvd_csr)
+        s["corrla_rsvd_csr_dev_" + suf] = (C.c_int, rsvd_csr)
+        pca_csr = [vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, vp, vp, i64]
+        s["corrla_pca_csr_" + suf] = (C.c_int, pca_csr)
+        s["corrla_pca_csr_dev_" + suf] = (C.c_int, pca_csr)
+        s["corrla_spmm_csr_dev_" + suf] = (C.c_int, [vp, C.c_int, vp, vp, vp, i64, i64, i64, vp, i64, i64, sc, vp, i64])
         s["corrla_fill_normal_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])

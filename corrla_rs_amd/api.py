@@ -29,6 +29,92 @@ def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
 
 
+def _is_torch_csr(x):
+    return _is_torch(x) and str(getattr(x, "layout", "")) == "torch.sparse_csr"
+
+
+def _is_sparse(x):
+    """True for what _as_csr takes: a scipy sparse matrix / array (duck-typed), a torch.sparse_csr tensor, or an explicit
+    (data, indices, indptr, shape) tuple."""
+    if isinstance(x, tuple):
+        # (data, indices, indptr, shape): three 1-D arrays and a length-2 shape.  Anything else that happens to be a
+        # 4-tuple (a dense matrix given as four rows) stays a dense input.
+        def nd(v):
+            return v.ndim if hasattr(v, "ndim") else np.ndim(v)
+        if len(x) != 4 or not all(nd(v) == 1 for v in x[:3]):
+            return False
+        shp = x[3]
+        if not (isinstance(shp, (tuple, list)) and len(shp) == 2 and all(nd(d) == 0 for d in shp)):
+            return False
+        try:  # ... consistent with each other (a 4 x 2 dense matrix has the same outline but not these lengths)
+            return len(x[0]) == len(x[1]) and len(x[2]) == int(shp[0]) + 1
+        except (TypeError, ValueError):
+            return False
+    if _is_torch(x):
+        return _is_torch_csr(x)
+    return hasattr(x, "tocsr") and hasattr(x, "nnz") and not isinstance(x, np.ndarray)
+
+
+def _as_csr(x):
+    """The one normaliser of sparse inputs -> (values, int32 col_idx, int64 row_ptr, (m, n), on_device).
+
+    scipy sparse matrices / arrays of any format (through ``.tocsr()``; scipy itself is never imported), CPU
+    ``torch.sparse_csr`` tensors and ``(data, indices, indptr, shape)`` tuples give C-contiguous numpy arrays
+    (on_device False); a CUDA ``torch.sparse_csr`` tensor gives torch tensors on its device (on_device True) and the
+    matrix is never copied to the host.  float32 values stay float32, everything else becomes float64 -- as for dense
+    inputs.  Column indices within a row may be unsorted; duplicates add."""
+    if _is_torch_csr(x):
+        if x.dim() != 2:
+            raise ValueError("sparse input must be 2-D")
+        shape = tuple(int(d) for d in x.shape)
+        vals, ci, rp = x.values(), x.col_indices(), x.crow_indices()
+        if x.is_cuda:
+            import torch
+            if vals.dtype != torch.float32:
+                vals = vals.to(torch.float64)
+            m, n = shape
+            if rp.numel() != m + 1 or ci.numel() != vals.numel():
+                raise ValueError("inconsistent CSR arrays")
+            if ci.dtype != torch.int32:
+                # as on the host: an index that does not fit int32 must stay out of range, not wrap into it
+                ci = torch.where((ci < 0) | (ci >= 2 ** 31), torch.full_like(ci, -1), ci).to(torch.int32)
+            return vals.contiguous(), ci.contiguous(), rp.to(torch.int64).contiguous(), shape, True
+        data, indices, indptr = vals.detach().numpy(), ci.numpy(), rp.numpy()
+    elif isinstance(x, tuple):
+        if len(x) != 4:
+            raise ValueError("a CSR tuple is (data, indices, indptr, shape)")
+        data, indices, indptr, shape = x
+        shape = tuple(shape) if np.ndim(shape) == 1 else (shape,)
+    elif hasattr(x, "tocsr"):
+        if getattr(x, "ndim", 2) != 2:
+            raise ValueError("sparse input must be 2-D")
+        c = x.tocsr()
+        data, indices, indptr, shape = c.data, c.indices, c.indptr, tuple(c.shape)
+    else:
+        raise TypeError("not a sparse matrix: expected scipy sparse, torch.sparse_csr or (data, indices, indptr, shape)")
+    if len(shape) != 2:
+        raise ValueError("sparse input must be 2-D")
+    m, n = int(shape[0]), int(shape[1])
+    data = np.asarray(data)
+    if data.dtype != np.float32:
+        data = data.astype(np.float64, copy=False)
+    indices, indptr = np.asarray(indices), np.asarray(indptr)
+    if data.ndim != 1 or indices.ndim != 1 or indptr.ndim != 1:
+        raise ValueError("data, indices and indptr must be 1-D")
+    if indptr.shape[0] != m + 1:
+        raise ValueError(f"indptr has {indptr.shape[0]} entries, shape {(m, n)} needs {m + 1}")
+    if indices.shape[0] != data.shape[0]:
+        raise ValueError("data and indices differ in length")
+    if m < 0 or n < 0 or n >= 2 ** 31 or m >= 2 ** 31:
+        raise ValueError("shape out of range")
+    if indices.dtype != np.int32:
+        # a value that does not fit int32 cannot be a column index below 2^31: keep it out of range instead of wrapping
+        wide = indices.astype(np.int64, copy=False)
+        indices = np.where((wide < 0) | (wide >= 2 ** 31), -1, wide).astype(np.int32)
+    indptr = indptr.astype(np.int64, copy=False)
+    return np.ascontiguousarray(data), np.ascontiguousarray(indices), np.ascontiguousarray(indptr), (m, n), False
+
+
 # Contexts own HIP streams / allocations / RCCL communicators: destroy them before the interpreter (and
 # the HIP runtime's own static destructors) tear down, never from a late __del__.
 _live = weakref.WeakSet()
@@ -153,6 +239,8 @@ class Context:
         """fused=True: CORRLA_POWER_FUSED (one-sweep A^T (A Z) power iteration; f32 row-major inputs with <= 512 columns).
         mixed="bf16x6" | "bf16x3": see _mixed_flag."""
         n_rank, n_iters, n_oversamples = int(n_rank), int(n_iters), int(n_oversamples)
+        if _is_sparse(a_mat):  # fused / mixed have no sparse kernels: ignored, as for every operand outside their domain
+            return self._rsvd_csr(a_mat, n_rank, n_iters, n_oversamples, seed, omega, qr)
         if _is_torch(a_mat) and a_mat.is_cuda:
             return self._rsvd_torch(a_mat, n_rank, n_iters, n_oversamples, seed, omega, qr=qr, fused=fused, mixed=mixed)
         a = np.asarray(a_mat.detach().cpu().numpy() if _is_torch(a_mat) else a_mat)
@@ -180,6 +268,98 @@ class Context:
                    C.byref(o) if o is not None else None, u.ctypes.data, m, s.ctypes.data, vt.ctypes.data, kk))
         del keep
         return u, s, vt
+
+    # ---- CSR sparse input (corrla_*_csr_*; see _as_csr) ---------------------------------------
+    @staticmethod
+    def _ptr(t):
+        return t.data_ptr() if _is_torch(t) else t.ctypes.data
+
+    def _csr_args(self, a):
+        vals, ci, rp, (m, n), on_dev = _as_csr(a)
+        if m == 0 or n == 0:
+            raise ValueError("a_mat must be non-empty")
+        if on_dev:
+            import torch
+            if vals.device.index != self.device:
+                raise ValueError(f"tensor is on {vals.device}, context is on cuda:{self.device}")
+            torch.cuda.current_stream(vals.device).synchronize()
+            suf = "f32" if vals.dtype == torch.float32 else "f64"
+        else:
+            suf = "f32" if vals.dtype == np.float32 else "f64"
+        return vals, ci, rp, m, n, int(vals.shape[0]), on_dev, suf
+
+    def _rsvd_csr(self, a, k, q, p, seed, omega, qr):
+        vals, ci, rp, m, n, nnz, on_dev, suf = self._csr_args(a)
+        nt = min(m, n)
+        l = min(k + max(p, 0), nt)
+        o, keep = self._opts(seed, omega, nt, l, vals.dtype, on_dev, self._qr_flag(qr))
+        kk = max(k, 1)
+        if on_dev:
+            import torch
+            dev = vals.device
+            u = torch.empty((kk, m), dtype=vals.dtype, device=dev).t()     # (m, k) column-major
+            s = torch.empty((kk, 1), dtype=vals.dtype, device=dev)
+            vt = torch.empty((n, kk), dtype=vals.dtype, device=dev).t()    # (k, n) column-major
+        else:
+            u = np.empty((m, kk), dtype=vals.dtype, order="F")
+            s = np.empty((kk, 1), dtype=vals.dtype, order="F")
+            vt = np.empty((kk, n), dtype=vals.dtype, order="F")
+        fn = getattr(self._lib, ("corrla_rsvd_csr_dev_" if on_dev else "corrla_rsvd_csr_") + suf)
+        P = self._ptr
+        L.check(fn(self._h, P(vals), P(ci), P(rp), m, n, nnz, k, q, p, C.byref(o) if o is not None else None,
+                   P(u), m, P(s), P(vt), kk))
+        del keep
+        return u, s, vt
+
+    def _pca_csr(self, x, rank, n_iter, n_oversamples, seed, omega, center):
+        if center == "copy":
+            raise ValueError("center='copy' on sparse input: a centred copy would densify the matrix")
+        vals, ci, rp, m, n, nnz, on_dev, suf = self._csr_args(x)
+        q = 20 if n_iter is None else int(n_iter)
+        p = min(n, 10) if n_oversamples is None else int(n_oversamples)
+        nt = min(m, n)
+        l = min(rank + max(p, 0), nt)
+        o, keep = self._opts(seed, omega, nt, l, vals.dtype, on_dev, L.PCA_CENTER_FUSED)
+        kk = max(rank, 1)
+        if on_dev:
+            import torch
+            dev = vals.device
+            means = torch.empty((1, n), dtype=vals.dtype, device=dev)
+            s = torch.empty((kk, 1), dtype=vals.dtype, device=dev)
+            comps = torch.empty((n, kk), dtype=vals.dtype, device=dev).t()
+        else:
+            means = np.empty((1, n), dtype=vals.dtype)
+            s = np.empty((kk, 1), dtype=vals.dtype)
+            comps = np.empty((kk, n), dtype=vals.dtype, order="F")
+        fn = getattr(self._lib, ("corrla_pca_csr_dev_" if on_dev else "corrla_pca_csr_") + suf)
+        P = self._ptr
+        L.check(fn(self._h, P(vals), P(ci), P(rp), m, n, nnz, rank, q, p, C.byref(o) if o is not None else None,
+                   P(means), P(s), P(comps), kk))
+        del keep
+        return means, s, comps
+
+    def spmm(self, a_csr, x, trans=False, beta=1.0):
+        """res = beta * op(a_csr) @ x for a sparse a_csr (any form _as_csr takes) and a dense x (n x l, or m x l with
+        trans); the sparse twin of matmul.  Runs on the device; returns a torch CUDA tensor."""
+        import torch
+        vals, ci, rp, (m, n), on_dev = _as_csr(a_csr)
+        dev = torch.device(f"cuda:{self.device}")
+        if not on_dev:
+            vals, ci, rp = (torch.from_numpy(v).to(dev) for v in (vals, ci, rp))
+        xin, xout = (m, n) if trans else (n, m)
+        xt = x if _is_torch(x) else torch.as_tensor(np.asarray(x))
+        xt = xt.to(device=dev, dtype=vals.dtype)
+        if xt.dim() != 2 or xt.shape[0] != xin:
+            raise ValueError(f"x must have {xin} rows")
+        l = xt.shape[1]
+        xc = xt.t().contiguous()  # column-major (xin, l)
+        res = torch.empty((l, xout), dtype=vals.dtype, device=dev)
+        suf = "f32" if vals.dtype == torch.float32 else "f64"
+        torch.cuda.current_stream(dev).synchronize()
+        fn = getattr(self._lib, "corrla_spmm_csr_dev_" + suf)
+        L.check(fn(self._h, 1 if trans else 0, vals.data_ptr(), ci.data_ptr(), rp.data_ptr(), m, n, int(vals.shape[0]),
+                   xc.data_ptr(), xin, l, float(beta), res.data_ptr(), xout))
+        return res.t()
 
     def _rsvd_torch(self, a, k, q, p, seed, omega, sharded=False, qr=None, fused=False, shard_cols=False, mixed=None):
         import torch
@@ -258,11 +438,13 @@ class Context:
         """PcaRsvd::new(x, rank): returns (means (1, n), singular values (k, 1), components (k, n)).
         n_iter / n_oversamples default to the reference's hard-coded 20 / min(n_dim, 10) (pca_rsvd.rs:65-66).
         center: None (library default: implicit rank-1 corrections for f64, a centred copy for f32), "fused" or
-        "copy" (CORRLA_PCA_CENTER_* in include/corrla_rsvd.h)."""
+        "copy" (CORRLA_PCA_CENTER_* in include/corrla_rsvd.h).  Sparse x_mat (see _as_csr): always "fused"; "copy" raises."""
         rank = int(rank)
         if center not in (None, "fused", "copy"):
             raise ValueError("center must be None, 'fused' or 'copy'")
         cflags = {None: 0, "fused": L.PCA_CENTER_FUSED, "copy": L.PCA_CENTER_COPY}[center]
+        if _is_sparse(x_mat):  # always the fused centring: the matrix stays sparse
+            return self._pca_csr(x_mat, rank, n_iter, n_oversamples, seed, omega, center)
         if _is_torch(x_mat) and x_mat.is_cuda:
             import torch
             x = x_mat if x_mat.dtype in (torch.float32, torch.float64) else x_mat.to(torch.float64)
@@ -452,8 +634,8 @@ class PcaRsvd:
 
     def __init__(self, x_mat, rank, *, seed=None, omega=None, ctx=None):
         self.pca_rank = int(rank)
-        x = np.asarray(x_mat)
-        self.n_samples = x.shape[0]
+        x = x_mat if _is_sparse(x_mat) else np.asarray(x_mat)
+        self.n_samples = int(x[3][0] if isinstance(x, tuple) else x.shape[0])
         self.means, self.pca_s, self.components_ = (ctx or default_context()).pca(x, rank, seed=seed, omega=omega)
 
     def fit(self, x_mat, rank, **kw):  # pca_rsvd.rs:85-88

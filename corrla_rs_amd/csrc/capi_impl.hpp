@@ -430,4 +430,215 @@ inline void matmul_entry(Dev& dev, int trans, const T* a, int64_t m, int64_t n, 
   if (tm_out) tm_out->n_mixed_products = drv.tm.n_mixed_products;
 }
 
+// ---- CSR sparse input ------------------------------------------------------------------------------------------------
+// The sparse counterparts of rsvd_entry / pca_entry / matmul_entry (unsharded): A arrives as CSR (values, int32 column
+// indices, int64 row_ptr).  Host arrays are uploaded and take the device path, so there is one validation and one
+// transposition path.  Only instantiated for backends that carry the SpMM kernels (dev_has_spmm).
+inline void validate_csr_args(const void* values, const void* ci, const void* rp, int64_t m, int64_t n, int64_t nnz) {
+  if (!values || !ci || !rp) throw Error(ST_EINVAL, "values, col_idx or row_ptr is NULL");
+  if (m < 1 || n < 1) throw Error(ST_EINVAL, "matrix must have at least one row and one column");
+  if (m > 0x7fffffff || n > 0x7fffffff) throw Error(ST_EINVAL, "CSR input: m and n must be below 2^31");
+  // an all-zero matrix has no range to find (every sketch is zero); rejected rather than run
+  if (nnz < 1) throw Error(ST_EINVAL, "CSR input: nnz must be >= 1");
+  if (nnz > 0x7fffffff) throw Error(ST_EINVAL, "CSR input: nnz must be below 2^31");
+}
+
+// Uploads (host pointers), validates on the device, transposes once, and describes the result as the TALL operand:
+// the caller's CSR is the tall view for m >= n and its transpose for a fat input (m < n, strict) -- the two simply swap.
+template <class Dev, class T>
+inline TallA<T> stage_csr(Dev& dev, bool host_ptrs, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
+                          int64_t nnz, bool keep_orientation) {
+  CsrView<T> a;
+  a.rows = m;
+  a.cols = n;
+  a.nnz = nnz;
+  if (host_ptrs) {
+    // row_ptr[m] decides how much of the two nnz-sized arrays exists: check it on the host before the copies read them
+    if (rp[m] != nnz) throw Error(ST_EINVAL, "invalid CSR matrix: row_ptr[m] != nnz");
+    T* dv = (T*)dev.alloc_bytes(sizeof(T) * (size_t)nnz);
+    int32_t* dc = (int32_t*)dev.alloc_bytes(sizeof(int32_t) * (size_t)nnz);
+    int64_t* dr = (int64_t*)dev.alloc_bytes(sizeof(int64_t) * (size_t)(m + 1));
+    dev.h2d_bytes(dv, values, sizeof(T) * (size_t)nnz);
+    dev.h2d_bytes(dc, ci, sizeof(int32_t) * (size_t)nnz);
+    dev.h2d_bytes(dr, rp, sizeof(int64_t) * (size_t)(m + 1));
+    a.val = dv;
+    a.ci = dc;
+    a.rp = dr;
+  } else {
+    a.val = values;
+    a.ci = ci;
+    a.rp = rp;
+  }
+  dev.csr_plan(a, /*check_idx=*/true);  // throws ST_EINVAL before any gather
+  CsrView<T> at = dev.csr_transpose(a);
+  dev.csr_plan(at, /*check_idx=*/false);
+  TallA<T> ta;
+  ta.sparse = true;
+  const bool fat = !keep_orientation && m < n;
+  ta.mt = fat ? n : m;
+  ta.nt = fat ? m : n;
+  ta.csr = fat ? at : a;
+  ta.csr_t = fat ? a : at;
+  return ta;
+}
+
+// CORRLA_POWER_FUSED and CORRLA_SKETCH_BF16X3 / X6 have no sparse kernels: ignored, as documented for every operand
+// outside their domain.
+inline RunOpts parse_opts_sparse(const corrla_opts* o, bool dev_ptrs) {
+  RunOpts r = parse_opts(o, dev_ptrs);
+  r.power_fused = false;
+  r.mixed_planes = 0;
+  return r;
+}
+
+template <class Dev, class T>
+inline void rsvd_csr_entry(Dev& dev, bool host_ptrs, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
+                           int64_t nnz, int64_t rank, int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, T* u,
+                           int64_t ldu, T* s, T* vt, int64_t ldvt, Timings* tm_out, bool profile) {
+  static_assert(dev_has_spmm<Dev>::value, "CSR entries need a backend with SpMM kernels");
+  if (!u || !s || !vt) throw Error(ST_EINVAL, "output pointer is NULL");
+  validate_csr_args(values, ci, rp, m, n, nnz);
+  validate_rank(m, n, rank, n_iter, n_oversamples);
+  if (ldu < m) throw Error(ST_EINVAL, "ldu < m");
+  if (ldvt < rank) throw Error(ST_EINVAL, "ldvt < rank");
+  RunOpts ro = parse_opts_sparse(opts, !host_ptrs);
+  if (!ro.seed_explicit && !ro.omega) ro.seed = dev.fresh_seed(false);
+  dev.begin_call();
+  TallA<T> ta = stage_csr<Dev, T>(dev, host_ptrs, values, ci, rp, m, n, nnz, false);
+  const bool fat = m < n;
+  const int64_t k = rank;
+  const int64_t l = std::min<int64_t>(rank + n_oversamples, ta.nt);  // random_svd.rs:77
+  if (ro.omega && ro.omega_ld < ta.nt) throw Error(ST_EINVAL, "omega_ld < min(m, n)");
+  const bool u_in_place = !fat && !host_ptrs;  // as rsvd_entry: U straight into the caller's buffer
+  Skinny<T> ut;
+  if (u_in_place) {
+    ut.p = u;
+    ut.rows = ta.mt;
+    ut.cols = k;
+    ut.ld = ldu;
+    ut.cols_alloc = k;
+    ut.external = true;
+  } else {
+    ut = dev.template alloc_skinny<T>(ta.mt, k);
+  }
+  Skinny<T> vtall = dev.template alloc_skinny<T>(ta.nt, k);
+  T* s_dev = dev.template alloc_scalar<T>((int)k);
+  RsvdDriver<Dev, T> drv(dev, profile);
+  drv.random_svd_tall(ta, k, l, n_iter, ro, ut, s_dev, vtall, [&] {
+    // random_svd.rs:96-109: tall -> (U, S, V^T); fat -> (V, S, U^T) of the transposed problem
+    if (!fat) {
+      if (!u_in_place) dev.copy_out(ut, k, u, ldu, /*transpose=*/false, host_ptrs);
+      dev.copy_out(vtall, k, vt, ldvt, /*transpose=*/true, host_ptrs);
+    } else {
+      dev.copy_out(vtall, k, u, ldu, false, host_ptrs);
+      dev.copy_out(ut, k, vt, ldvt, true, host_ptrs);
+    }
+    dev.copy_values_out(s_dev, k, s, host_ptrs);
+  });
+  PhaseTimer fin;
+  drv.phase(drv.tm.finalize_ms, fin);
+  dev.phase_end();
+  dev.end_call();
+  dev.phase_resolve(&drv.tm.total_ms);
+  drv.tm.n_collectives = dev.n_collectives;
+  drv.tm.collective_bytes = dev.collective_bytes;
+  drv.tm.sketch_kernel_ms = dev.event_elapsed_ms(0, 1);
+  if (tm_out) *tm_out = drv.tm;
+}
+
+// PcaRsvd::new (pca_rsvd.rs:56-82) on CSR data: always the fused centring -- the centred operator
+// is A X - 1 (mu^T X), A itself is never rewritten, so the matrix stays sparse.  The means are A^T 1 / m through the
+// same SpMM as every other product.
+template <class Dev, class T>
+inline void pca_csr_entry(Dev& dev, bool host_ptrs, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
+                          int64_t nnz, int64_t rank, int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, T* means,
+                          T* s, T* comps, int64_t ldc, Timings* tm_out, bool profile) {
+  static_assert(dev_has_spmm<Dev>::value, "CSR entries need a backend with SpMM kernels");
+  if (!means || !s || !comps) throw Error(ST_EINVAL, "output pointer is NULL");
+  validate_csr_args(values, ci, rp, m, n, nnz);
+  validate_rank(m, n, rank, n_iter, n_oversamples);
+  if (ldc < rank) throw Error(ST_EINVAL, "ldc < rank");
+  if (m < 2) throw Error(ST_EINVAL, "PCA needs at least two samples");
+  RunOpts ro = parse_opts_sparse(opts, !host_ptrs);
+  if (ro.pca_center == 2)
+    throw Error(ST_EINVAL, "CORRLA_PCA_CENTER_COPY on CSR input: a centred copy would densify the matrix (use the fused centring)");
+  if (!ro.seed_explicit && !ro.omega) ro.seed = dev.fresh_seed(false);
+  dev.begin_call();
+  TallA<T> ta = stage_csr<Dev, T>(dev, host_ptrs, values, ci, rp, m, n, nnz, false);
+  const bool fat = m < n;  // the tall view is x^T: its ROWS are the data columns
+  RsvdDriver<Dev, T> drv(dev, profile);
+  const int64_t samples_dim_tall = fat ? ta.nt : ta.mt;
+  Skinny<T> ones = dev.template alloc_skinny<T>(samples_dim_tall, 1);
+  dev.fill_const(ones.p, samples_dim_tall, (T)1);
+  Skinny<T> mu = dev.template alloc_skinny<T>(fat ? ta.mt : ta.nt, 1);
+  T* inv_m = dev.template alloc_scalar<T>(1);
+  const T inv_m_host = (T)(1.0 / (double)m);
+  dev.store_values(&inv_m_host, (int64_t)1, inv_m, /*dst_is_host=*/false);
+  if (!fat)
+    drv.at_times(ta, ones, mu, inv_m, false);  // mu (n) = x^T 1 / m
+  else
+    drv.a_times(ta, ones, mu, inv_m);          // tall view = x^T (n x m)
+  TallA<T> tc = ta;
+  if (!fat)
+    tc.mu_short = mu.p;
+  else
+    tc.mu_tall = mu.p;
+  const int64_t k = rank;
+  const int64_t l = std::min<int64_t>(rank + n_oversamples, tc.nt);
+  if (ro.omega && ro.omega_ld < tc.nt) throw Error(ST_EINVAL, "omega_ld < min(m, n)");
+  Skinny<T> ut = dev.template alloc_skinny<T>(tc.mt, k);
+  Skinny<T> vtall = dev.template alloc_skinny<T>(tc.nt, k);
+  T* s_dev = dev.template alloc_scalar<T>((int)k);
+  drv.random_svd_tall(tc, k, l, n_iter, ro, ut, s_dev, vtall, [&] {
+    // components_ = vr = V^T (k x n_dim)   pca_rsvd.rs:70-71
+    if (!fat)
+      dev.copy_out(vtall, k, comps, ldc, /*transpose=*/true, host_ptrs);
+    else
+      dev.copy_out(ut, k, comps, ldc, true, host_ptrs);
+    dev.copy_values_out(s_dev, k, s, host_ptrs);
+    dev.copy_values_out(mu.p, n, means, host_ptrs);
+  });
+  PhaseTimer fin;
+  drv.phase(drv.tm.finalize_ms, fin);
+  dev.phase_end();
+  dev.end_call();
+  dev.phase_resolve(&drv.tm.total_ms);
+  drv.tm.n_collectives = dev.n_collectives;
+  drv.tm.collective_bytes = dev.collective_bytes;
+  if (tm_out) *tm_out = drv.tm;
+}
+
+// res = beta * op(S) * X for a device CSR matrix S (test hook, the sparse twin of matmul_entry)
+template <class Dev, class T>
+inline void spmm_entry(Dev& dev, int trans, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n, int64_t nnz,
+                       const T* x, int64_t ldx, int64_t l, T beta, T* res, int64_t ldres) {
+  static_assert(dev_has_spmm<Dev>::value, "CSR entries need a backend with SpMM kernels");
+  if (!x || !res) throw Error(ST_EINVAL, "x or res is NULL");
+  validate_csr_args(values, ci, rp, m, n, nnz);
+  if (l < 1) throw Error(ST_EINVAL, "l must be >= 1");
+  const int64_t xin = trans ? m : n, xout = trans ? n : m;
+  if (ldx < xin || ldres < xout) throw Error(ST_EINVAL, "leading dimension too small");
+  dev.begin_call();
+  TallA<T> ta = stage_csr<Dev, T>(dev, false, values, ci, rp, m, n, nnz, /*keep_orientation=*/true);
+  RsvdDriver<Dev, T> drv(dev, false);
+  Skinny<T> xs = dev.template alloc_skinny<T>(xin, l);
+  dev.copy_in_skinny(x, ldx, xs);
+  // the caller's buffer is the destination itself (an `external` Skinny: ld = ldres, exactly l columns): the hook shows
+  // what the SpMM kernels store, and a caller who pads res can see that nothing else is touched
+  Skinny<T> out;
+  out.p = res;
+  out.rows = xout;
+  out.cols = l;
+  out.ld = ldres;
+  out.cols_alloc = l;
+  out.external = true;
+  T* beta_dev = dev.template alloc_scalar<T>(1);
+  dev.store_values(&beta, (int64_t)1, beta_dev, /*dst_is_host=*/false);
+  if (trans)
+    drv.at_times(ta, xs, out, beta_dev, false);
+  else
+    drv.a_times(ta, xs, out, beta_dev);
+  dev.end_call();
+}
+
 }  // namespace corrla

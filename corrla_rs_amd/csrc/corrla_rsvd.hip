@@ -82,6 +82,38 @@ corrla_status matmul_c(corrla_ctx* ctx, int trans, const T* a, int64_t m, int64_
   });
 }
 template <class T>
+corrla_status rsvd_csr_c(corrla_ctx* ctx, bool host, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
+                         int64_t nnz, int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* u, int64_t ldu, T* s,
+                         T* vt, int64_t ldvt) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    locked_call(c, [&] {
+      rsvd_csr_entry<HipDev, T>(c->dev, host, values, ci, rp, m, n, nnz, rank, n_iter, p, o, u, ldu, s, vt, ldvt, &c->last,
+                                c->profile);
+    });
+  });
+}
+template <class T>
+corrla_status pca_csr_c(corrla_ctx* ctx, bool host, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
+                        int64_t nnz, int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* means, T* s, T* comps,
+                        int64_t ldc) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    locked_call(c, [&] {
+      pca_csr_entry<HipDev, T>(c->dev, host, values, ci, rp, m, n, nnz, rank, n_iter, p, o, means, s, comps, ldc, &c->last,
+                               c->profile);
+    });
+  });
+}
+template <class T>
+corrla_status spmm_csr_c(corrla_ctx* ctx, int trans, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
+                         int64_t nnz, const T* x, int64_t ldx, int64_t l, T beta, T* res, int64_t ldres) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    locked_call(c, [&] { spmm_entry<HipDev, T>(c->dev, trans, values, ci, rp, m, n, nnz, x, ldx, l, beta, res, ldres); });
+  });
+}
+template <class T>
 corrla_status fill_c(corrla_ctx* ctx, T* p, int64_t rows, int64_t cols, int64_t rs, int64_t cs, uint64_t seed,
                      int64_t row0, int64_t global_cols) {
   return guarded([&] {
@@ -237,6 +269,42 @@ CORRLA_API corrla_status corrla_ctx_get_timings(corrla_ctx* ctx, corrla_timings*
 
 CORRLA_DEFINE(f32, float)
 CORRLA_DEFINE(f64, double)
+
+// ---- CSR sparse input (values, int32 column indices, int64 row_ptr) ----------------------------------------------
+#define CORRLA_DEFINE_CSR(SUF, T)                                                                                      \
+  CORRLA_API corrla_status corrla_rsvd_csr_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,             \
+                                                 const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,            \
+                                                 int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* u,  \
+                                                 int64_t ldu, T* s, T* vt, int64_t ldvt) {                             \
+    return rsvd_csr_c<T>(ctx, true, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, u, ldu, s, vt, ldvt);     \
+  }                                                                                                                    \
+  CORRLA_API corrla_status corrla_rsvd_csr_dev_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,         \
+                                                     const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,        \
+                                                     int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o,    \
+                                                     T* u, int64_t ldu, T* s, T* vt, int64_t ldvt) {                   \
+    return rsvd_csr_c<T>(ctx, false, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, u, ldu, s, vt, ldvt);    \
+  }                                                                                                                    \
+  CORRLA_API corrla_status corrla_pca_csr_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,              \
+                                                const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,             \
+                                                int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o,         \
+                                                T* means, T* s, T* comps, int64_t ldc) {                               \
+    return pca_csr_c<T>(ctx, true, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, means, s, comps, ldc);     \
+  }                                                                                                                    \
+  CORRLA_API corrla_status corrla_pca_csr_dev_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,          \
+                                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,         \
+                                                    int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o,     \
+                                                    T* means, T* s, T* comps, int64_t ldc) {                           \
+    return pca_csr_c<T>(ctx, false, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, means, s, comps, ldc);    \
+  }                                                                                                                    \
+  CORRLA_API corrla_status corrla_spmm_csr_dev_##SUF(corrla_ctx* ctx, int trans, const T* values,                      \
+                                                     const int32_t* col_idx, const int64_t* row_ptr, int64_t m,        \
+                                                     int64_t n, int64_t nnz, const T* x, int64_t ldx, int64_t l,       \
+                                                     T beta, T* res, int64_t ldres) {                                  \
+    return spmm_csr_c<T>(ctx, trans, values, col_idx, row_ptr, m, n, nnz, x, ldx, l, beta, res, ldres);                \
+  }
+
+CORRLA_DEFINE_CSR(f32, float)
+CORRLA_DEFINE_CSR(f64, double)
 
 // ---- active-subspace gradient stage ------------------------------------------------------
 static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,

@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 #include <functional>
+#include <type_traits>
 #include <vector>
 
 #include "gemm_plan.hpp"
@@ -69,6 +70,26 @@ inline Big<T> as_rowmajor_transposed(const Skinny<T>& y, int64_t ncols) {
   return b;
 }
 
+// A CSR matrix on the device (values, int32 column indices, int64 row_ptr with rows + 1 entries) together with the
+// split of its long rows into chunks that the backend's plan step built (spmm_kernels.hpp); validated before use.
+template <class T>
+struct CsrView {
+  const T* val = nullptr;
+  const int32_t* ci = nullptr;
+  const int64_t* rp = nullptr;
+  int64_t rows = 0, cols = 0, nnz = 0;
+  int64_t n_long = 0, n_chunks = 0;  // rows split into chunks / chunks in all
+  const int64_t* long_row = nullptr;
+  const int64_t* long_base = nullptr;
+  const int32_t* chunk_long = nullptr;
+};
+
+// Backends that carry the SpMM kernels say so with a static member kHasSpmm (the emulation backend has none).
+template <class D, class = void>
+struct dev_has_spmm : std::false_type {};
+template <class D>
+struct dev_has_spmm<D, std::void_t<decltype(D::kHasSpmm)>> : std::true_type {};
+
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).
 template <class T>
@@ -80,6 +101,10 @@ struct TallA {
   // A - mu_tall 1^T (mu_tall: mt values); A itself is never rewritten.  At most one of them is set.
   const T* mu_short = nullptr;
   const T* mu_tall = nullptr;
+  // Sparse operand: `mem` is unused; csr is the tall view (mt x nt) and csr_t its transpose (nt x mt), so both
+  // products of the range finder are row gathers.  For a fat input the caller's CSR is csr_t (no copy).
+  bool sparse = false;
+  CsrView<T> csr, csr_t;
 };
 
 struct RunOpts {
@@ -143,8 +168,16 @@ struct RsvdDriver {
   // ---- op(A) * skinny ---------------------------------------------------------------
   // Y (mt x L) = scale * A * X (nt x L)                         random_svd.rs:31,47-51
   int mixed_planes_ = 0;  // set from RunOpts while the range finder runs (power_iter), see RunOpts::mixed_planes
+  void sparse_times(const CsrView<T>& s, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev) {
+    if constexpr (dev_has_spmm<Dev>::value)
+      dev.spmm(s, x, y, scale_dev);
+    else
+      throw Error(ST_EINVAL, "this backend has no SpMM kernels: sparse operands are not supported");
+  }
   void a_times(const TallA<T>& a, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev) {
-    if (mixed_planes_ && dev.template mixed_fits<T>(!a.row_major, a.mem, x, y))
+    if (a.sparse)
+      sparse_times(a.csr, x, y, scale_dev);
+    else if (mixed_planes_ && dev.template mixed_fits<T>(!a.row_major, a.mem, x, y))
       dev.gemm_mixed(!a.row_major, a.mem, x, y, scale_dev, mixed_planes_), ++tm.n_mixed_products;
     else if (a.row_major)
       dev.gemm_nn(a.mem, x, y, scale_dev);
@@ -159,7 +192,9 @@ struct RsvdDriver {
   }
   // Z (nt x L) = scale * A^T * Y (mt x L); all-reduced when rows are sharded   random_svd.rs:42-46,80
   void at_times(const TallA<T>& a, const Skinny<T>& y, Skinny<T>& z, const T* scale_dev, bool sharded) {
-    if (mixed_planes_ && dev.template mixed_fits<T>(a.row_major, a.mem, y, z))
+    if (a.sparse)
+      sparse_times(a.csr_t, y, z, scale_dev);
+    else if (mixed_planes_ && dev.template mixed_fits<T>(a.row_major, a.mem, y, z))
       dev.gemm_mixed(a.row_major, a.mem, y, z, scale_dev, mixed_planes_), ++tm.n_mixed_products;
     else if (a.row_major)
       dev.gemm_tn(a.mem, y, z, scale_dev);
@@ -719,7 +754,7 @@ struct RsvdDriver {
     //   Z(0) = A^T (A Omega), Z(i) = A^T (A Z^(i-1)), i < nf = min(q, 3);  then Y = A Z^(nf-1) and the loop continues
     // with the reference's own steps.  A is read nf + 1 times instead of 2 nf + 1 and no m x l matrix is written.
     int64_t i0 = 0;
-    const bool fused = o.power_fused && n_iter > 0 && a.row_major && !a.mu_short && !a.mu_tall &&
+    const bool fused = o.power_fused && n_iter > 0 && !a.sparse && a.row_major && !a.mu_short && !a.mu_tall &&
                        dev.template ata_fused_fits<T>(a.mem, l);
     if (fused) {
       const int64_t nf = std::min<int64_t>(n_iter, 3);

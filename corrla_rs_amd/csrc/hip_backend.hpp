@@ -27,6 +27,7 @@
 #include "grad_kernels.hpp"
 #include "knn2_kernels.hpp"
 #include "grad_wide_kernels.hpp"
+#include "spmm_kernels.hpp"
 
 namespace corrla {
 
@@ -174,6 +175,8 @@ class HipDev {
     ev_used_ = 0;
     phase_mark(nullptr);  // start of the call
     for (auto& c : chunks_) c.used = 0;
+    sp_scratch_ = nullptr;
+    sp_scratch_bytes_ = 0;
     // zero pool: the part the previous call used is cleared by ONE memset per chunk (capped), instead of one
     // small memset per workspace allocation
     for (auto& c : zchunks_) {
@@ -297,6 +300,117 @@ class HipDev {
   void gemm_tn(const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev) {
     if (x.rows != r.rows) throw Error(ST_EINVAL, "gemm_tn: inner dimensions differ");
     launch_gemm<T>(true, r, x, out, scale_dev);
+  }
+
+  // ---- CSR sparse operand (spmm_kernels.hpp) ---------------------------------------------------------------------
+  static constexpr bool kHasSpmm = true;  // driver.hpp: dev_has_spmm
+  // Validates row_ptr (and, check_idx, every column index) of `v` on the device, ends the call with ST_EINVAL on a
+  // violation -- before anything is gathered through these arrays -- and builds the lists of long rows and their chunks.
+  // One host synchronisation (the verdict and the two list sizes come back in one 40-byte copy).
+  template <class T>
+  void csr_plan(CsrView<T>& v, bool check_idx) {
+    k::CsrCounts* cnt = (k::CsrCounts*)alloc_zeroed(sizeof(k::CsrCounts));
+    const int64_t top = std::max(v.rows, v.nnz);
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((top + 255) / 256, (int64_t)num_cus * 16));
+    hipLaunchKernelGGL(k::csr_validate_kernel, dim3(blocks), dim3(256), 0, stream, v.rp, v.ci, v.rows, v.cols, v.nnz, check_idx ? 1 : 0, cnt);
+    CORRLA_HIP(hipGetLastError());
+    k::CsrCounts h;
+    read_bytes(cnt, sizeof(h), &h);
+    if (h.bad) {
+      std::string why;
+      if (h.bad & 1) why += " row_ptr[0] != 0;";
+      if (h.bad & 2) why += " row_ptr is not monotone within [0, nnz];";
+      if (h.bad & 4) why += " row_ptr[m] != nnz;";
+      if (h.bad & 8) why += " a column index lies outside [0, n);";
+      throw Error(ST_EINVAL, "invalid CSR matrix:" + why);
+    }
+    v.n_long = (int64_t)h.n_long;
+    v.n_chunks = (int64_t)h.n_chunks;
+    if (v.n_long == 0) return;
+    if (v.n_chunks > 0x7fffffff) throw Error(ST_EINVAL, "problem too large for the launch grid");
+    int64_t* lr = (int64_t*)alloc_bytes(sizeof(int64_t) * (size_t)v.n_long);
+    int64_t* lb = (int64_t*)alloc_bytes(sizeof(int64_t) * (size_t)v.n_long);
+    int32_t* cl = (int32_t*)alloc_bytes(sizeof(int32_t) * (size_t)v.n_chunks);
+    const unsigned b2 = (unsigned)std::max<int64_t>(1, std::min<int64_t>((v.rows + 255) / 256, (int64_t)num_cus * 16));
+    hipLaunchKernelGGL(k::csr_long_build_kernel, dim3(b2), dim3(256), 0, stream, v.rp, v.rows, cnt, lr, lb, cl);
+    CORRLA_HIP(hipGetLastError());
+    v.long_row = lr;
+    v.long_base = lb;
+    v.chunk_long = cl;
+  }
+  // CSR of the transpose of a VALIDATED matrix, in arena memory (released with the call).  Entries of a row of the
+  // transpose keep the order (original row, original position): a stable radix sort by column index.
+  template <class T>
+  CsrView<T> csr_transpose(const CsrView<T>& a) {
+    const int64_t nnz = a.nnz;
+    if (nnz < 1 || nnz > 0x7fffffff) throw Error(ST_EINVAL, "csr_transpose: nnz must be in [1, 2^31)");
+    const int64_t nb = (nnz + k::kSortTile - 1) / k::kSortTile;
+    uint32_t* key[2] = {(uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz), (uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz)};
+    uint32_t* pay[2] = {(uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz), (uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz)};
+    uint32_t* hist = (uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nb * 256);
+    int bits = 1;
+    while (((int64_t)1 << bits) < a.cols) ++bits;
+    const int passes = (bits + 7) / 8;
+    const uint32_t* kin = (const uint32_t*)a.ci;  // validated: every index is in [0, cols), so the bit patterns agree
+    const uint32_t* pin = nullptr;
+    for (int ps = 0; ps < passes; ++ps) {
+      uint32_t* kout = key[ps & 1];
+      uint32_t* pout = pay[ps & 1];
+      hipLaunchKernelGGL(k::csr_radix_hist_kernel, dim3((unsigned)nb), dim3(64), 0, stream, kin, nnz, 8 * ps, hist, nb);
+      hipLaunchKernelGGL(k::csr_scan_kernel, dim3(1), dim3(1024), 0, stream, hist, nb * 256);
+      hipLaunchKernelGGL(k::csr_radix_scatter_kernel, dim3((unsigned)nb), dim3(64), 0, stream, kin, pin, nnz, 8 * ps, (const uint32_t*)hist, nb,
+                         kout, pout);
+      CORRLA_HIP(hipGetLastError());
+      kin = kout;
+      pin = pout;
+    }
+    CsrView<T> t;
+    t.rows = a.cols;
+    t.cols = a.rows;
+    t.nnz = nnz;
+    int64_t* trp = (int64_t*)alloc_bytes(sizeof(int64_t) * (size_t)(a.cols + 1));
+    int32_t* tci = (int32_t*)alloc_bytes(sizeof(int32_t) * (size_t)nnz);
+    T* tval = (T*)alloc_bytes(sizeof(T) * (size_t)nnz);
+    hipLaunchKernelGGL((k::csr_transpose_finish_kernel<T>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, kin, pin, a.rp, a.rows,
+                       a.val, nnz, a.cols, trp, tci, tval);
+    CORRLA_HIP(hipGetLastError());
+    t.rp = trp;
+    t.ci = tci;
+    t.val = tval;
+    return t;
+  }
+  // y (s.rows x L) = scale * S * x (s.cols x L); writes rows [0, s.rows) x columns [0, x.cols) of y and nothing else
+  template <class T>
+  void spmm(const CsrView<T>& s, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev) {
+    if (x.rows != s.cols || y.rows != s.rows) throw Error(ST_EINVAL, "spmm: dimensions differ");
+    const int64_t L = x.cols;
+    if (L < 1 || y.cols < L) throw Error(ST_EINVAL, "spmm: destination has fewer columns than the operand");
+    const int64_t Lp = round_up(L, 16), jt = (L + k::kSpTile - 1) / k::kSpTile, Lpart = jt * 64;
+    const size_t xt_bytes = ((size_t)s.cols * (size_t)Lp * sizeof(T) + 255) / 256 * 256;
+    const size_t need = xt_bytes + (size_t)s.n_chunks * (size_t)Lpart * sizeof(T);
+    if (need > sp_scratch_bytes_) {  // one scratch per call, grown on demand (the arena is released at end_call)
+      sp_scratch_ = alloc_bytes(need);
+      sp_scratch_bytes_ = need;
+    }
+    T* xt = (T*)sp_scratch_;
+    T* part = (T*)((char*)sp_scratch_ + xt_bytes);
+    dim3 gx((unsigned)((s.cols + k::kSpTile - 1) / k::kSpTile), (unsigned)((Lp + k::kSpTile - 1) / k::kSpTile));
+    dim3 gr((unsigned)((s.rows + k::kSpTile - 1) / k::kSpTile), (unsigned)jt);
+    check_grid(gx);
+    check_grid(gr);
+    hipLaunchKernelGGL((k::spmm_xt_kernel<T>), gx, dim3(256), 0, stream, (const T*)x.p, x.ld, s.cols, L, xt, Lp);
+    hipLaunchKernelGGL((k::spmm_rows_kernel<T>), gr, dim3(256), 0, stream, s.rp, s.ci, s.val, (const T*)xt, Lp, s.rows, L, y.p, y.ld, scale_dev);
+    if (s.n_long > 0) {
+      hipLaunchKernelGGL((k::spmm_long_partial_kernel<T>), dim3((unsigned)s.n_chunks, (unsigned)jt), dim3(256), 0, stream, s.rp, s.ci, s.val,
+                         (const T*)xt, Lp, L, s.long_row, s.long_base, s.chunk_long, part, Lpart);
+      hipLaunchKernelGGL((k::spmm_long_reduce_kernel<T>), dim3((unsigned)s.n_long, (unsigned)jt), dim3(64), 0, stream, s.rp, s.long_row,
+                         s.long_base, (const T*)part, Lpart, L, y.p, y.ld, scale_dev);
+    }
+    CORRLA_HIP(hipGetLastError());
+  }
+  void h2d_bytes(void* dst, const void* src, size_t bytes) {
+    CORRLA_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
+    sync();
   }
 
   // bf16-split tall products (mixed_kernels.hpp): f32 operands, bf16 MFMA, f32 accumulate.  np = 2
@@ -575,6 +689,8 @@ class HipDev {
     return mk;
   }
   void arena_rewind(const ArenaMark& mk) {
+    sp_scratch_ = nullptr;  // may lie behind the mark
+    sp_scratch_bytes_ = 0;
     for (size_t i = 0; i < chunks_.size(); ++i) chunks_[i].used = i < mk.used.size() ? mk.used[i] : 0;
     for (size_t i = 0; i < zchunks_.size(); ++i) {
       Chunk& c = zchunks_[i];
@@ -1243,6 +1359,8 @@ class HipDev {
   };
   std::vector<Chunk> chunks_;
   std::vector<Chunk> zchunks_;  // zero pool (alloc_zeroed)
+  void* sp_scratch_ = nullptr;  // XT + long-row partial sums of the SpMM (spmm), valid within one call
+  size_t sp_scratch_bytes_ = 0;
   void* zero_page_ = nullptr;
   void* pinned_ = nullptr;  // staging for the small l x l transfers
   hipEvent_t events_[3] = {nullptr, nullptr, nullptr};

@@ -256,6 +256,73 @@ CORRLA_API corrla_status corrla_matmul_dev_f64(corrla_ctx* ctx, int trans, const
                                     int64_t row_stride, int64_t col_stride, const double* x, int64_t ldx, int64_t l,
                                     double beta, double* res, int64_t ldres);
 
+/* ---- CSR sparse input ----------------------------------------------------------------
+ * random_svd (random_svd.rs:63-110) and PcaRsvd::new (pca_rsvd.rs:56-82) for a matrix that is not dense: the
+ * reference takes a dense faer Mat only; its own comparator in examples/benchmark_rsvd.py
+ * (sklearn.utils.extmath.randomized_svd) accepts sparse input, and this is that surface.  A (m x n) is given in CSR:
+ *   values  : nnz entries
+ *   col_idx : nnz column indices, int32, each in [0, n)
+ *   row_ptr : m + 1 offsets, int64, row_ptr[0] == 0, non-decreasing, row_ptr[m] == nnz
+ * Column indices need not be sorted within a row; duplicate entries add.  The two products of the range finder
+ * (random_svd.rs:31, 42-51, 80) are row gathers over A and over a CSR of A^T that the call builds once on the
+ * device; A is never densified.  The arrays are validated ON THE DEVICE before anything is gathered through them: a
+ * violation returns CORRLA_EINVAL (message in corrla_last_error()).  Outputs, l = min(rank + n_oversamples, min(m, n)),
+ * the fat (m < n) handling, the sign convention and the status codes are those of corrla_rsvd_* / corrla_pca_*.
+ * opts: seed, omega, CORRLA_OMEGA_ON_DEVICE, CORRLA_SEED_EXPLICIT and CORRLA_QR_HOUSEHOLDER work unchanged;
+ * CORRLA_POWER_FUSED and CORRLA_SKETCH_BF16X3 / X6 are ignored.  Results are bitwise reproducible for a fixed seed (no
+ * floating-point atomics; sums run in stored order within a row).
+ * Limits: m, n < 2^31; 1 <= nnz < 2^31 -- an all-zero matrix (nnz == 0) returns CORRLA_EINVAL.  No sharded variant.
+ * The *_dev variants take HIP device pointers for the three arrays and every output. */
+CORRLA_API corrla_status corrla_rsvd_csr_f32(corrla_ctx* ctx, const float* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, float* u, int64_t ldu,
+                                    float* s, float* vt, int64_t ldvt);
+CORRLA_API corrla_status corrla_rsvd_csr_dev_f32(corrla_ctx* ctx, const float* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, float* u, int64_t ldu,
+                                    float* s, float* vt, int64_t ldvt);
+CORRLA_API corrla_status corrla_rsvd_csr_f64(corrla_ctx* ctx, const double* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, double* u, int64_t ldu,
+                                    double* s, double* vt, int64_t ldvt);
+CORRLA_API corrla_status corrla_rsvd_csr_dev_f64(corrla_ctx* ctx, const double* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, double* u, int64_t ldu,
+                                    double* s, double* vt, int64_t ldvt);
+
+/* PCA of CSR data (pca_rsvd.rs:56-82): the centring of center_mat_col (mat_utils.rs:482-502) is ALWAYS applied as
+ * implicit rank-1 corrections (CORRLA_PCA_CENTER_FUSED; the means are A^T 1 / n_samples through the same gather), so
+ * the matrix stays sparse.  CORRLA_PCA_CENTER_COPY returns CORRLA_EINVAL: a centred copy would densify the matrix. */
+CORRLA_API corrla_status corrla_pca_csr_f32(corrla_ctx* ctx, const float* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t n_samples, int64_t n_dim, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, float* means,
+                                    float* s, float* components, int64_t ldc);
+CORRLA_API corrla_status corrla_pca_csr_dev_f32(corrla_ctx* ctx, const float* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t n_samples, int64_t n_dim, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, float* means,
+                                    float* s, float* components, int64_t ldc);
+CORRLA_API corrla_status corrla_pca_csr_f64(corrla_ctx* ctx, const double* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t n_samples, int64_t n_dim, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, double* means,
+                                    double* s, double* components, int64_t ldc);
+CORRLA_API corrla_status corrla_pca_csr_dev_f64(corrla_ctx* ctx, const double* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t n_samples, int64_t n_dim, int64_t nnz, int64_t rank,
+                                    int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, double* means,
+                                    double* s, double* components, int64_t ldc);
+
+/* The sparse twin of corrla_matmul_dev_* (par_matmul_helper, mat_utils.rs:20-33), a test hook:
+ *   trans == 0 : res (m x l) = beta * A   * X (n x l)
+ *   trans == 1 : res (n x l) = beta * A^T * X (m x l)
+ * A in CSR as above; X and res column-major with leading dimensions ldx / ldres.  DEVICE pointers.  res is the
+ * destination of the SpMM kernels themselves: only rows [0, m or n) of its l columns are written, whatever else the
+ * caller's buffer holds (rows up to ldres, further columns) is left as it was. */
+CORRLA_API corrla_status corrla_spmm_csr_dev_f32(corrla_ctx* ctx, int trans, const float* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, const float* x,
+                                    int64_t ldx, int64_t l, float beta, float* res, int64_t ldres);
+CORRLA_API corrla_status corrla_spmm_csr_dev_f64(corrla_ctx* ctx, int trans, const double* values, const int32_t* col_idx,
+                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, const double* x,
+                                    int64_t ldx, int64_t l, double beta, double* res, int64_t ldres);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller

@@ -54,6 +54,37 @@ extern "C" {
     fn corrla_grad_mat_f64(ctx: *mut c_void, x: *const f64, n_pts: i64, k: i64, y: *const f64, xq: *const f64,
                            n_q: i64, est_order: c_int, n_nbrs: i64, out_scale: f64, g: *mut f64, ldg: i64,
                            n_regularised: *mut c_int) -> c_int;
+    // CSR sparse input (include/corrla_rsvd.h, "CSR sparse input"): values, int32 col_idx, int64 row_ptr (m + 1 entries)
+    pub fn corrla_rsvd_csr_f32(ctx: *mut c_void, values: *const f32, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                               n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                               u: *mut f32, ldu: i64, s: *mut f32, vt: *mut f32, ldvt: i64) -> c_int;
+    pub fn corrla_pca_csr_f32(ctx: *mut c_void, values: *const f32, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                              n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                              means: *mut f32, s: *mut f32, comps: *mut f32, ldc: i64) -> c_int;
+    pub fn corrla_rsvd_csr_dev_f32(ctx: *mut c_void, values: *const f32, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                               n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                               u: *mut f32, ldu: i64, s: *mut f32, vt: *mut f32, ldvt: i64) -> c_int;
+    pub fn corrla_pca_csr_dev_f32(ctx: *mut c_void, values: *const f32, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                              n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                              means: *mut f32, s: *mut f32, comps: *mut f32, ldc: i64) -> c_int;
+    pub fn corrla_spmm_csr_dev_f32(ctx: *mut c_void, trans: c_int, values: *const f32, col_idx: *const i32,
+                                   row_ptr: *const i64, m: i64, n: i64, nnz: i64, x: *const f32, ldx: i64, l: i64,
+                                   beta: f32, res: *mut f32, ldres: i64) -> c_int;
+    pub fn corrla_rsvd_csr_f64(ctx: *mut c_void, values: *const f64, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                               n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                               u: *mut f64, ldu: i64, s: *mut f64, vt: *mut f64, ldvt: i64) -> c_int;
+    pub fn corrla_pca_csr_f64(ctx: *mut c_void, values: *const f64, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                              n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                              means: *mut f64, s: *mut f64, comps: *mut f64, ldc: i64) -> c_int;
+    pub fn corrla_rsvd_csr_dev_f64(ctx: *mut c_void, values: *const f64, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                               n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                               u: *mut f64, ldu: i64, s: *mut f64, vt: *mut f64, ldvt: i64) -> c_int;
+    pub fn corrla_pca_csr_dev_f64(ctx: *mut c_void, values: *const f64, col_idx: *const i32, row_ptr: *const i64, m: i64,
+                              n: i64, nnz: i64, rank: i64, n_iter: i64, n_over: i64, opts: *const CorrlaOpts,
+                              means: *mut f64, s: *mut f64, comps: *mut f64, ldc: i64) -> c_int;
+    pub fn corrla_spmm_csr_dev_f64(ctx: *mut c_void, trans: c_int, values: *const f64, col_idx: *const i32,
+                                   row_ptr: *const i64, m: i64, n: i64, nnz: i64, x: *const f64, ldx: i64, l: i64,
+                                   beta: f64, res: *mut f64, ldres: i64) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
