@@ -115,6 +115,60 @@ def _as_csr(x):
     return np.ascontiguousarray(data), np.ascontiguousarray(indices), np.ascontiguousarray(indptr), (m, n), False
 
 
+def _suffix(dtype):
+    """Symbol suffix of a numpy or torch dtype (inputs are float32 or float64 by the time they get here)."""
+    return "f32" if str(dtype).endswith("float32") else "f64"
+
+
+def _ptr(t):
+    return t.data_ptr() if _is_torch(t) else t.ctypes.data
+
+
+def _c_args(operand):
+    """The C arguments of an operand description: its arrays as pointers, its integers as they are.  The description
+    itself holds the arrays, so they outlive the call."""
+    return [v if isinstance(v, int) else _ptr(v) for v in operand]
+
+
+def _as_dense(x, what):
+    """The one normaliser of dense inputs -> (array, on_device): a torch CUDA tensor stays on its device, everything else
+    becomes a numpy array without negative strides (torch has none).  float32 stays float32, the rest becomes float64."""
+    if _is_torch(x) and x.is_cuda:
+        import torch
+        if x.dim() != 2:
+            raise ValueError(f"{what} must be 2-D")
+        return (x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float64)), True
+    a = np.asarray(x.detach().cpu().numpy() if _is_torch(x) else x)
+    if a.ndim != 2:
+        raise ValueError(f"{what} must be 2-D")
+    if a.dtype != np.float32:
+        a = a.astype(np.float64, copy=False)
+    if any(st < 0 for st in a.strides):
+        a = np.ascontiguousarray(a)
+    return a, False
+
+
+def _strides(a):
+    """(row, column) strides in elements."""
+    return tuple(a.stride()) if _is_torch(a) else (a.strides[0] // a.itemsize, a.strides[1] // a.itemsize)
+
+
+def _empty_colmajor(like, rows, cols):
+    """Uninitialised (rows, cols) output, column-major like the reference's owned faer `Mat`s, of the array kind, dtype
+    and device of `like`: a numpy F-ordered array, or the transpose of a (cols, rows) torch tensor."""
+    if _is_torch(like):
+        import torch
+        return torch.empty((cols, rows), dtype=like.dtype, device=like.device).t()
+    return np.empty((rows, cols), dtype=like.dtype, order="F")
+
+
+def _sync_stream(t):
+    """Inputs produced on torch's current stream are complete before the library's own (non-blocking) stream reads them:
+    called last before a library call, after every torch operation that prepares an argument."""
+    import torch
+    torch.cuda.current_stream(t.device).synchronize()
+
+
 # Contexts own HIP streams / allocations / RCCL communicators: destroy them before the interpreter (and
 # the HIP runtime's own static destructors) tear down, never from a late __del__.
 _live = weakref.WeakSet()
@@ -234,167 +288,80 @@ class Context:
             o.omega_ld = nt
         return o, keep
 
-    # ---- random_svd ----------------------------------------------------------------------
-    def rsvd(self, a_mat, n_rank, n_iters, n_oversamples, *, seed=None, omega=None, qr=None, fused=False, mixed=None):
-        """fused=True: CORRLA_POWER_FUSED (one-sweep A^T (A Z) power iteration; f32 row-major inputs with <= 512 columns).
-        mixed="bf16x6" | "bf16x3": see _mixed_flag."""
-        n_rank, n_iters, n_oversamples = int(n_rank), int(n_iters), int(n_oversamples)
-        if _is_sparse(a_mat):  # fused / mixed have no sparse kernels: ignored, as for every operand outside their domain
-            return self._rsvd_csr(a_mat, n_rank, n_iters, n_oversamples, seed, omega, qr)
-        if _is_torch(a_mat) and a_mat.is_cuda:
-            return self._rsvd_torch(a_mat, n_rank, n_iters, n_oversamples, seed, omega, qr=qr, fused=fused, mixed=mixed)
-        a = np.asarray(a_mat.detach().cpu().numpy() if _is_torch(a_mat) else a_mat)
-        if a.ndim != 2:
-            raise ValueError("a_mat must be 2-D")
-        if a.dtype != np.float32:
-            a = a.astype(np.float64, copy=False)
-        m, n = a.shape
-        if m == 0 or n == 0:
-            raise ValueError("a_mat must be non-empty")
-        suf = "f32" if a.dtype == np.float32 else "f64"
-        if any(s < 0 for s in a.strides):
-            a = np.ascontiguousarray(a)
-        rs, cs = a.strides[0] // a.itemsize, a.strides[1] // a.itemsize
-        k = n_rank
-        nt = min(m, n)
-        l = min(k + max(n_oversamples, 0), nt)
-        o, keep = self._opts(seed, omega, nt, l, a.dtype, False, self._qr_flag(qr) | (L.POWER_FUSED if fused else 0) | self._mixed_flag(mixed))
-        kk = max(k, 1)
-        u = np.empty((m, kk), dtype=a.dtype, order="F")
-        s = np.empty((kk, 1), dtype=a.dtype, order="F")
-        vt = np.empty((kk, n), dtype=a.dtype, order="F")
-        fn = getattr(self._lib, "corrla_rsvd_" + suf)
-        L.check(fn(self._h, a.ctypes.data, m, n, rs, cs, k, n_iters, n_oversamples,
-                   C.byref(o) if o is not None else None, u.ctypes.data, m, s.ctypes.data, vt.ctypes.data, kk))
-        del keep
-        return u, s, vt
+    def _on_my_device(self, t):
+        if t.device.index != self.device:
+            raise ValueError(f"tensor is on {t.device}, context is on cuda:{self.device}")
 
-    # ---- CSR sparse input (corrla_*_csr_*; see _as_csr) ---------------------------------------
-    @staticmethod
-    def _ptr(t):
-        return t.data_ptr() if _is_torch(t) else t.ctypes.data
-
-    def _csr_args(self, a):
+    def _csr_operand(self, a):
+        """Sparse input -> (operand description of the corrla_*_csr_* entries, m, n, an array of its kind, on_device)."""
         vals, ci, rp, (m, n), on_dev = _as_csr(a)
         if m == 0 or n == 0:
             raise ValueError("a_mat must be non-empty")
         if on_dev:
-            import torch
-            if vals.device.index != self.device:
-                raise ValueError(f"tensor is on {vals.device}, context is on cuda:{self.device}")
-            torch.cuda.current_stream(vals.device).synchronize()
-            suf = "f32" if vals.dtype == torch.float32 else "f64"
-        else:
-            suf = "f32" if vals.dtype == np.float32 else "f64"
-        return vals, ci, rp, m, n, int(vals.shape[0]), on_dev, suf
+            self._on_my_device(vals)
+        return (vals, ci, rp, m, n, int(vals.shape[0])), m, n, vals, on_dev
 
-    def _rsvd_csr(self, a, k, q, p, seed, omega, qr):
-        vals, ci, rp, m, n, nnz, on_dev, suf = self._csr_args(a)
-        nt = min(m, n)
+    def _entry(self, stem, on_device, dtype):
+        return getattr(self._lib, stem + ("dev_" if on_device else "") + _suffix(dtype))
+
+    def _run_rsvd(self, stem, operand, m, n, nt, like, on_device, k, q, p, seed, omega, flags):
+        """The one caller of the rsvd entries `stem`[dev_]{f32,f64}: `operand` describes the m x n matrix (its arrays and
+        integer arguments, see _c_args), `like` an array of the kind, dtype and device the outputs take.
+        -> (U (m, k), S (k, 1), Vt (k, n))"""
         l = min(k + max(p, 0), nt)
-        o, keep = self._opts(seed, omega, nt, l, vals.dtype, on_dev, self._qr_flag(qr))
+        o, keep = self._opts(seed, omega, nt, l, like.dtype, on_device, flags)
         kk = max(k, 1)
-        if on_dev:
-            import torch
-            dev = vals.device
-            u = torch.empty((kk, m), dtype=vals.dtype, device=dev).t()     # (m, k) column-major
-            s = torch.empty((kk, 1), dtype=vals.dtype, device=dev)
-            vt = torch.empty((n, kk), dtype=vals.dtype, device=dev).t()    # (k, n) column-major
-        else:
-            u = np.empty((m, kk), dtype=vals.dtype, order="F")
-            s = np.empty((kk, 1), dtype=vals.dtype, order="F")
-            vt = np.empty((kk, n), dtype=vals.dtype, order="F")
-        fn = getattr(self._lib, ("corrla_rsvd_csr_dev_" if on_dev else "corrla_rsvd_csr_") + suf)
-        P = self._ptr
-        L.check(fn(self._h, P(vals), P(ci), P(rp), m, n, nnz, k, q, p, C.byref(o) if o is not None else None,
-                   P(u), m, P(s), P(vt), kk))
+        u, s, vt = (_empty_colmajor(like, *shape) for shape in ((m, kk), (kk, 1), (kk, n)))
+        if on_device:
+            _sync_stream(like)  # after _opts: the device copy of omega is made on torch's stream too
+        L.check(self._entry(stem, on_device, like.dtype)(self._h, *_c_args(operand), k, q, p, C.byref(o) if o is not None else None,
+                                                         _ptr(u), m, _ptr(s), _ptr(vt), kk))
         del keep
         return u, s, vt
 
-    def _pca_csr(self, x, rank, n_iter, n_oversamples, seed, omega, center):
-        if center == "copy":
-            raise ValueError("center='copy' on sparse input: a centred copy would densify the matrix")
-        vals, ci, rp, m, n, nnz, on_dev, suf = self._csr_args(x)
+    def _run_pca(self, stem, operand, m, n, nt, like, on_device, rank, n_iter, n_oversamples, seed, omega, flags):
+        """The same for the PCA entries.  -> (means (1, n), S (k, 1), components (k, n)); n_iter / n_oversamples default as
+        in pca_rsvd.rs:65-66."""
         q = 20 if n_iter is None else int(n_iter)
         p = min(n, 10) if n_oversamples is None else int(n_oversamples)
-        nt = min(m, n)
         l = min(rank + max(p, 0), nt)
-        o, keep = self._opts(seed, omega, nt, l, vals.dtype, on_dev, L.PCA_CENTER_FUSED)
+        o, keep = self._opts(seed, omega, nt, l, like.dtype, on_device, flags)
         kk = max(rank, 1)
-        if on_dev:
-            import torch
-            dev = vals.device
-            means = torch.empty((1, n), dtype=vals.dtype, device=dev)
-            s = torch.empty((kk, 1), dtype=vals.dtype, device=dev)
-            comps = torch.empty((n, kk), dtype=vals.dtype, device=dev).t()
-        else:
-            means = np.empty((1, n), dtype=vals.dtype)
-            s = np.empty((kk, 1), dtype=vals.dtype)
-            comps = np.empty((kk, n), dtype=vals.dtype, order="F")
-        fn = getattr(self._lib, ("corrla_pca_csr_dev_" if on_dev else "corrla_pca_csr_") + suf)
-        P = self._ptr
-        L.check(fn(self._h, P(vals), P(ci), P(rp), m, n, nnz, rank, q, p, C.byref(o) if o is not None else None,
-                   P(means), P(s), P(comps), kk))
+        means, s, comps = (_empty_colmajor(like, *shape) for shape in ((1, n), (kk, 1), (kk, n)))
+        if on_device:
+            _sync_stream(like)  # after _opts, as in _run_rsvd
+        L.check(self._entry(stem, on_device, like.dtype)(self._h, *_c_args(operand), rank, q, p, C.byref(o) if o is not None else None,
+                                                         _ptr(means), _ptr(s), _ptr(comps), kk))
         del keep
         return means, s, comps
 
-    def spmm(self, a_csr, x, trans=False, beta=1.0):
-        """res = beta * op(a_csr) @ x for a sparse a_csr (any form _as_csr takes) and a dense x (n x l, or m x l with
-        trans); the sparse twin of matmul.  Runs on the device; returns a torch CUDA tensor."""
-        import torch
-        vals, ci, rp, (m, n), on_dev = _as_csr(a_csr)
-        dev = torch.device(f"cuda:{self.device}")
-        if not on_dev:
-            vals, ci, rp = (torch.from_numpy(v).to(dev) for v in (vals, ci, rp))
-        xin, xout = (m, n) if trans else (n, m)
-        xt = x if _is_torch(x) else torch.as_tensor(np.asarray(x))
-        xt = xt.to(device=dev, dtype=vals.dtype)
-        if xt.dim() != 2 or xt.shape[0] != xin:
-            raise ValueError(f"x must have {xin} rows")
-        l = xt.shape[1]
-        xc = xt.t().contiguous()  # column-major (xin, l)
-        res = torch.empty((l, xout), dtype=vals.dtype, device=dev)
-        suf = "f32" if vals.dtype == torch.float32 else "f64"
-        torch.cuda.current_stream(dev).synchronize()
-        fn = getattr(self._lib, "corrla_spmm_csr_dev_" + suf)
-        L.check(fn(self._h, 1 if trans else 0, vals.data_ptr(), ci.data_ptr(), rp.data_ptr(), m, n, int(vals.shape[0]),
-                   xc.data_ptr(), xin, l, float(beta), res.data_ptr(), xout))
-        return res.t()
+    # ---- random_svd ----------------------------------------------------------------------
+    def rsvd(self, a_mat, n_rank, n_iters, n_oversamples, *, seed=None, omega=None, qr=None, fused=False, mixed=None):
+        """fused=True: CORRLA_POWER_FUSED (one-sweep A^T (A Z) power iteration; f32 row-major inputs with <= 512 columns).
+        mixed="bf16x6" | "bf16x3": see _mixed_flag."""
+        k, q, p = int(n_rank), int(n_iters), int(n_oversamples)
+        if _is_sparse(a_mat):  # fused / mixed have no sparse kernels: ignored, as for every operand outside their domain
+            operand, m, n, like, on_dev = self._csr_operand(a_mat)
+            return self._run_rsvd("corrla_rsvd_csr_", operand, m, n, min(m, n), like, on_dev, k, q, p, seed, omega, self._qr_flag(qr))
+        return self._rsvd_dense(a_mat, k, q, p, seed, omega, qr=qr, fused=fused, mixed=mixed)
 
-    def _rsvd_torch(self, a, k, q, p, seed, omega, sharded=False, qr=None, fused=False, shard_cols=False, mixed=None):
-        import torch
-        if a.dim() != 2:
-            raise ValueError("a_mat must be 2-D")
-        if a.dtype not in (torch.float32, torch.float64):
-            a = a.to(torch.float64)
-        if a.device.index != self.device:
-            raise ValueError(f"tensor is on {a.device}, context is on cuda:{self.device}")
+    def _rsvd_dense(self, a_mat, k, q, p, seed, omega, sharded=False, qr=None, fused=False, shard_cols=False, mixed=None):
+        a, on_dev = _as_dense(a_mat, "a_mat")
+        if on_dev:
+            self._on_my_device(a)
+        elif sharded:
+            raise ValueError("rsvd_sharded takes torch CUDA tensors")
         m, n = a.shape
         # an EMPTY shard (no rows; no columns with shard="cols") is legal on the sharded entry point: the rank takes part
         # in the collectives with zero contributions and gets a 0-row (0-column) block of the sharded factor
         empty_shard = sharded and ((n == 0 and m > 0) if shard_cols else (m == 0 and n > 0))
         if (m == 0 or n == 0) and not empty_shard:
             raise ValueError("a_mat must be non-empty")
-        if any(s < 0 for s in a.stride()):
-            a = a.contiguous()
-        rs, cs = (max(n, 1), 1) if empty_shard else a.stride()
-        suf = "f32" if a.dtype == torch.float32 else "f64"
+        rs, cs = (max(n, 1), 1) if empty_shard else _strides(a)
         nt = (m if shard_cols else n) if sharded else min(m, n)
-        l = min(k + max(p, 0), nt)
-        o, keep = self._opts(seed, omega, nt, l, a.dtype, True, self._qr_flag(qr) | (L.POWER_FUSED if fused else 0) |
-                             (L.SHARD_COLS if shard_cols else 0) | self._mixed_flag(mixed))
-        kk = max(k, 1)
-        dev = a.device
-        u = torch.empty((kk, m), dtype=a.dtype, device=dev).t()     # (m, k) column-major
-        s = torch.empty((kk, 1), dtype=a.dtype, device=dev)
-        vt = torch.empty((n, kk), dtype=a.dtype, device=dev).t()    # (k, n) column-major
-        torch.cuda.current_stream(dev).synchronize()  # inputs produced on torch's stream are complete
-        name = ("corrla_rsvd_sharded_dev_" if sharded else "corrla_rsvd_dev_") + suf
-        fn = getattr(self._lib, name)
-        L.check(fn(self._h, a.data_ptr(), m, n, rs, cs, k, q, p, C.byref(o) if o is not None else None,
-                   u.data_ptr(), m, s.data_ptr(), vt.data_ptr(), kk))
-        del keep
-        return u, s, vt
+        flags = self._qr_flag(qr) | (L.POWER_FUSED if fused else 0) | (L.SHARD_COLS if shard_cols else 0) | self._mixed_flag(mixed)
+        return self._run_rsvd("corrla_rsvd_sharded_" if sharded else "corrla_rsvd_", (a, m, n, rs, cs), m, n, nt, a, on_dev,
+                              k, q, p, seed, omega, flags)
 
     def rsvd_sharded(self, a_local, n_rank, n_iters, n_oversamples, *, seed=None, omega=None, fused=False, shard="rows", qr=None,
                      mixed=None):
@@ -404,35 +371,23 @@ class Context:
         (CORRLA_SHARD_COLS: the long side is what gets sharded, after the reference's fat -> tall transpose)."""
         if shard not in ("rows", "cols"):
             raise ValueError("shard must be 'rows' or 'cols'")
-        return self._rsvd_torch(a_local, int(n_rank), int(n_iters), int(n_oversamples), seed, omega, sharded=True, fused=fused,
+        return self._rsvd_dense(a_local, int(n_rank), int(n_iters), int(n_oversamples), seed, omega, sharded=True, fused=fused,
                                 shard_cols=(shard == "cols"), qr=qr, mixed=mixed)
 
     # ---- PCA caller (pca_rsvd.rs:56-82) ---------------------------------------------------
+    def _pca_dense(self, x_mat, rank, n_iter, n_oversamples, seed, omega, center, sharded):
+        cflags = {None: 0, "fused": L.PCA_CENTER_FUSED, "copy": L.PCA_CENTER_COPY}[center]
+        x, on_dev = _as_dense(x_mat, "x_mat")
+        m, n = x.shape
+        return self._run_pca("corrla_pca_sharded_" if sharded else "corrla_pca_", (x, m, n, *_strides(x)), m, n,
+                             n if sharded else min(m, n), x, on_dev, int(rank), n_iter, n_oversamples, seed, omega, cflags)
+
     def pca_sharded(self, x_local, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None):
         """PcaRsvd::new on SAMPLE-sharded data (one process per GPU, `comm_init` done): `x_local` = this rank's samples
         (CUDA tensor m_local x n_dim).  Returns (means, S, components), replicated on every rank."""
-        import torch
         if not (_is_torch(x_local) and x_local.is_cuda):
             raise ValueError("pca_sharded takes torch CUDA tensors")
-        cflags = {None: 0, "fused": L.PCA_CENTER_FUSED, "copy": L.PCA_CENTER_COPY}[center]
-        x = x_local if x_local.dtype in (torch.float32, torch.float64) else x_local.to(torch.float64)
-        m, n = x.shape
-        rank = int(rank)
-        q = 20 if n_iter is None else int(n_iter)
-        p = min(n, 10) if n_oversamples is None else int(n_oversamples)
-        rs, cs = x.stride()
-        l = min(rank + max(p, 0), n)
-        o, keep = self._opts(seed, omega, n, l, x.dtype, True, cflags)
-        kk = max(rank, 1)
-        means = torch.empty((1, n), dtype=x.dtype, device=x.device)
-        s = torch.empty((kk, 1), dtype=x.dtype, device=x.device)
-        comps = torch.empty((n, kk), dtype=x.dtype, device=x.device).t()
-        torch.cuda.current_stream(x.device).synchronize()
-        fn = getattr(self._lib, "corrla_pca_sharded_dev_" + ("f32" if x.dtype == torch.float32 else "f64"))
-        L.check(fn(self._h, x.data_ptr(), m, n, rs, cs, rank, q, p, C.byref(o) if o is not None else None,
-                   means.data_ptr(), s.data_ptr(), comps.data_ptr(), kk))
-        del keep
-        return means, s, comps
+        return self._pca_dense(x_local, rank, n_iter, n_oversamples, seed, omega, center, sharded=True)
 
     def pca(self, x_mat, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None):
         """PcaRsvd::new(x, rank): returns (means (1, n), singular values (k, 1), components (k, n)).
@@ -442,53 +397,48 @@ class Context:
         rank = int(rank)
         if center not in (None, "fused", "copy"):
             raise ValueError("center must be None, 'fused' or 'copy'")
-        cflags = {None: 0, "fused": L.PCA_CENTER_FUSED, "copy": L.PCA_CENTER_COPY}[center]
-        if _is_sparse(x_mat):  # always the fused centring: the matrix stays sparse
-            return self._pca_csr(x_mat, rank, n_iter, n_oversamples, seed, omega, center)
-        if _is_torch(x_mat) and x_mat.is_cuda:
-            import torch
-            x = x_mat if x_mat.dtype in (torch.float32, torch.float64) else x_mat.to(torch.float64)
-            if x.dim() != 2:
-                raise ValueError("x_mat must be 2-D")
-            m, n = x.shape
-            q = 20 if n_iter is None else int(n_iter)
-            p = min(n, 10) if n_oversamples is None else int(n_oversamples)
-            rs, cs = x.stride()
-            nt = min(m, n)
-            l = min(rank + max(p, 0), nt)
-            o, keep = self._opts(seed, omega, nt, l, x.dtype, True, cflags)
-            kk = max(rank, 1)
-            means = torch.empty((1, n), dtype=x.dtype, device=x.device)
-            s = torch.empty((kk, 1), dtype=x.dtype, device=x.device)
-            comps = torch.empty((n, kk), dtype=x.dtype, device=x.device).t()
-            torch.cuda.current_stream(x.device).synchronize()
-            fn = getattr(self._lib, "corrla_pca_dev_" + ("f32" if x.dtype == torch.float32 else "f64"))
-            L.check(fn(self._h, x.data_ptr(), m, n, rs, cs, rank, q, p, C.byref(o) if o is not None else None,
-                       means.data_ptr(), s.data_ptr(), comps.data_ptr(), kk))
-            del keep
-            return means, s, comps
-        x = np.asarray(x_mat.detach().cpu().numpy() if _is_torch(x_mat) else x_mat)
-        if x.ndim != 2:
-            raise ValueError("x_mat must be 2-D")
-        if x.dtype != np.float32:
-            x = x.astype(np.float64, copy=False)
-        if any(st < 0 for st in x.strides):
-            x = np.ascontiguousarray(x)
-        m, n = x.shape
-        q = 20 if n_iter is None else int(n_iter)
-        p = min(n, 10) if n_oversamples is None else int(n_oversamples)
-        nt = min(m, n)
-        l = min(rank + max(p, 0), nt)
-        o, keep = self._opts(seed, omega, nt, l, x.dtype, False, cflags)
-        kk = max(rank, 1)
-        means = np.empty((1, n), dtype=x.dtype)
-        s = np.empty((kk, 1), dtype=x.dtype)
-        comps = np.empty((kk, n), dtype=x.dtype, order="F")
-        fn = getattr(self._lib, "corrla_pca_" + ("f32" if x.dtype == np.float32 else "f64"))
-        L.check(fn(self._h, x.ctypes.data, m, n, x.strides[0] // x.itemsize, x.strides[1] // x.itemsize, rank, q, p,
-                   C.byref(o) if o is not None else None, means.ctypes.data, s.ctypes.data, comps.ctypes.data, kk))
-        del keep
-        return means, s, comps
+        if not _is_sparse(x_mat):
+            return self._pca_dense(x_mat, rank, n_iter, n_oversamples, seed, omega, center, sharded=False)
+        if center == "copy":  # always the fused centring: the matrix stays sparse
+            raise ValueError("center='copy' on sparse input: a centred copy would densify the matrix")
+        operand, m, n, like, on_dev = self._csr_operand(x_mat)
+        return self._run_pca("corrla_pca_csr_", operand, m, n, min(m, n), like, on_dev, rank, n_iter, n_oversamples, seed, omega,
+                             L.PCA_CENTER_FUSED)
+
+    # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
+    def _run_product(self, name, operand, m, n, xt, trans, beta):
+        """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that
+        describe A); xt a device tensor with as many rows as op(A) has columns."""
+        import torch
+        xin, xout = (m, n) if trans else (n, m)
+        l = xt.shape[1]
+        xc = xt.t().contiguous()  # column-major (xin, l)
+        res = torch.empty((l, xout), dtype=xt.dtype, device=xt.device)
+        _sync_stream(xt)
+        L.check(self._entry(name, True, xt.dtype)(self._h, 1 if trans else 0, *_c_args(operand), xc.data_ptr(), xin, l, float(beta),
+                                                  res.data_ptr(), xout))
+        return res.t()
+
+    def spmm(self, a_csr, x, trans=False, beta=1.0):
+        """res = beta * op(a_csr) @ x for a sparse a_csr (any form _as_csr takes) and a dense x (n x l, or m x l with
+        trans); the sparse twin of matmul.  Runs on the device; returns a torch CUDA tensor."""
+        import torch
+        vals, ci, rp, (m, n), on_dev = _as_csr(a_csr)
+        dev = torch.device(f"cuda:{self.device}")
+        if not on_dev:
+            vals, ci, rp = (torch.from_numpy(v).to(dev) for v in (vals, ci, rp))
+        xt = x if _is_torch(x) else torch.as_tensor(np.asarray(x))
+        xt = xt.to(device=dev, dtype=vals.dtype)
+        if xt.dim() != 2 or xt.shape[0] != (m if trans else n):
+            raise ValueError(f"x must have {m if trans else n} rows")
+        return self._run_product("corrla_spmm_csr_", (vals, ci, rp, m, n, int(vals.shape[0])),
+                                 m, n, xt, trans, beta)
+
+    def matmul(self, a, x, trans=False, beta=1.0):
+        """res = beta * op(a) @ x on device tensors (par_matmul_helper, mat_utils.rs:20-33)."""
+        m, n = a.shape
+        assert x.shape[0] == (m if trans else n) and x.dtype == a.dtype
+        return self._run_product("corrla_matmul_", (a, m, n, *a.stride()), m, n, x, trans, beta)
 
     # ---- active-subspace gradient stage (SURVEY 8 f2) ---------------------------------------
     def grad_mat(self, x_mat, y, est_order, n_nbrs, x_query=None, *, scale=1.0):
@@ -507,7 +457,7 @@ class Context:
             if x.dim() != 2 or xq.dim() != 2 or xq.shape[1] != x.shape[1] or yv.numel() != x.shape[0]:
                 raise ValueError("x_mat (n, k), y (n,), x_query (n_q, k) expected")
             g = torch.empty((xq.shape[0], x.shape[1]), dtype=torch.float64, device=x.device)
-            torch.cuda.current_stream(x.device).synchronize()
+            _sync_stream(x)
             L.check(self._lib.corrla_grad_mat_dev_f64(self._h, x.data_ptr(), x.shape[0], x.shape[1], yv.data_ptr(), xq.data_ptr(),
                                                       xq.shape[0], est_order, n_nbrs, float(scale), g.data_ptr(), x.shape[1],
                                                       C.byref(nreg)))
@@ -532,42 +482,22 @@ class Context:
             a = a.astype(np.float64, copy=False)
         m, n = a.shape
         w = int(omega_rank)
-        suf = "f32" if a.dtype == np.float32 else "f64"
-        rs, cs = a.strides[0] // a.itemsize, a.strides[1] // a.itemsize
+        rs, cs = _strides(a)
         o, keep = self._opts(seed, omega, n, w, a.dtype, False, self._qr_flag(qr))
-        q = np.empty((m, max(w, 1)), dtype=a.dtype, order="F")
-        fn = getattr(self._lib, "corrla_power_iter_" + suf)
+        q = _empty_colmajor(a, m, max(w, 1))
+        fn = self._entry("corrla_power_iter_", False, a.dtype)
         L.check(fn(self._h, a.ctypes.data, m, n, rs, cs, w, int(n_iter), C.byref(o) if o is not None else None,
                    q.ctypes.data, m))
         del keep
         return q
 
     # ---- low-level hooks used by tests / bench ---------------------------------------------
-    def matmul(self, a, x, trans=False, beta=1.0):
-        """res = beta * op(a) @ x on device tensors (par_matmul_helper, mat_utils.rs:20-33)."""
-        import torch
-        m, n = a.shape
-        rs, cs = a.stride()
-        xin, xout = (m, n) if trans else (n, m)
-        assert x.shape[0] == xin and x.dtype == a.dtype
-        l = x.shape[1]
-        xc = x.t().contiguous()  # column-major (xin, l)
-        res = torch.empty((l, xout), dtype=a.dtype, device=a.device)
-        suf = "f32" if a.dtype == torch.float32 else "f64"
-        torch.cuda.current_stream(a.device).synchronize()
-        fn = getattr(self._lib, "corrla_matmul_dev_" + suf)
-        L.check(fn(self._h, 1 if trans else 0, a.data_ptr(), m, n, rs, cs, xc.data_ptr(), xin, l, beta,
-                   res.data_ptr(), xout))
-        return res.t()
-
     def fill_normal(self, t, seed, row0=0, global_cols=None):
         """In-place N(0,1) fill of a 2-D device tensor (random_mat_normal, mat_utils.rs:161-175)."""
-        import torch
         rows, cols = t.shape
         rs, cs = t.stride()
-        suf = "f32" if t.dtype == torch.float32 else "f64"
-        torch.cuda.current_stream(t.device).synchronize()
-        fn = getattr(self._lib, "corrla_fill_normal_dev_" + suf)
+        _sync_stream(t)
+        fn = self._entry("corrla_fill_normal_", True, t.dtype)
         L.check(fn(self._h, t.data_ptr(), rows, cols, rs, cs, int(seed), int(row0),
                    int(global_cols if global_cols is not None else cols)))
         return t
@@ -582,9 +512,8 @@ class Context:
         xc = x.t().contiguous()
         y = torch.empty((l, m), dtype=a.dtype, device=a.device)
         ms = C.c_double()
-        suf = "f32" if a.dtype == torch.float32 else "f64"
-        torch.cuda.current_stream(a.device).synchronize()
-        fn = getattr(self._lib, "corrla_time_sketch_dev_" + suf)
+        _sync_stream(a)
+        fn = self._entry("corrla_time_sketch_", True, a.dtype)
         L.check(fn(self._h, a.data_ptr(), m, n, rs, cs, xc.data_ptr(), n, l, y.data_ptr(), m, int(reps), C.byref(ms)))
         return ms.value, y.t()
 

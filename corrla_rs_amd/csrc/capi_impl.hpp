@@ -66,39 +66,55 @@ inline RunOpts parse_opts(const corrla_opts* o, bool dev_ptrs) {
   return r;
 }
 
+// A caller's column-major buffer (exactly `cols` columns, leading dimension ld) as the destination of a product: an
+// `external` Skinny, see driver.hpp.
+template <class T>
+inline Skinny<T> caller_skinny(T* p, int64_t rows, int64_t cols, int64_t ld) {
+  Skinny<T> s;
+  s.p = p;
+  s.rows = rows;
+  s.cols = cols;
+  s.ld = ld;
+  s.cols_alloc = cols;
+  s.external = true;
+  return s;
+}
+
+// `rows` x `cols` row-major at p: cols_readable says how far a row may be read (the zero padding included).
+template <class T>
+inline TallA<T> tall_over(const T* p, bool row_major, int64_t mt, int64_t nt, int64_t rows, int64_t cols, int64_t ld,
+                          int64_t cols_readable) {
+  TallA<T> ta;
+  ta.mt = mt;
+  ta.nt = nt;
+  ta.row_major = row_major;
+  ta.mem.p = p;
+  ta.mem.rows = rows;
+  ta.mem.cols = cols;
+  ta.mem.ld = ld;
+  ta.mem.cols_readable = cols_readable;
+  return ta;
+}
+
+// The stand-in for an EMPTY shard: ONE zero row of the tall view, which adds nothing to any sum.
+template <class Dev, class T>
+inline TallA<T> zero_row_tall(Dev& dev, int64_t nt) {
+  const int64_t ldp = round_up(nt, kLdPad);
+  T* zrow = (T*)dev.alloc_bytes((size_t)ldp * sizeof(T));
+  dev.memset_zero(zrow, (size_t)ldp * sizeof(T));
+  return tall_over<T>(zrow, true, 1, nt, 1, nt, ldp, ldp);
+}
+
 // Bring the strided input into one of the two layouts the kernels take and describe it as the
 // TALL matrix.  Host pointers are always staged (H2D) into a padded row-major device buffer;
 // device pointers are used in place when 16-byte vector loads are legal, else repacked.
+// force_tall (sharded / power_iter / product hooks): never transpose, see classify.
 template <class Dev, class T>
 inline TallA<T> stage_input(Dev& dev, bool host_ptrs, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs,
                             bool force_tall) {
   validate_matrix(a, m, n, rs, cs);
-  Layout L = classify(m, n, rs, cs);
-  if (force_tall && L.fat) {
-    // sharded / power_iter: never transpose (random_svd.rs:15-59 takes the matrix as given)
-    L = classify(m, n, rs, cs);
-    L.fat = false;
-    L.mt = m;
-    L.nt = n;
-    if ((cs == 1 || n == 1) && (rs >= n || m == 1)) {
-      L.row_major = true;
-      L.needs_pack = false;
-      L.ld = m == 1 ? n : rs;
-    } else if ((rs == 1 || m == 1) && (cs >= m || n == 1)) {
-      L.row_major = false;
-      L.needs_pack = false;
-      L.ld = n == 1 ? m : cs;
-    } else {
-      L.row_major = true;
-      L.needs_pack = true;
-      L.ld = n;
-    }
-  }
+  const Layout L = classify(m, n, rs, cs, force_tall);
   constexpr int64_t VEC = 16 / (int64_t)sizeof(T);
-  TallA<T> ta;
-  ta.mt = L.mt;
-  ta.nt = L.nt;
-  ta.row_major = L.row_major;
   const int64_t mem_rows = L.row_major ? L.mt : L.nt;
   const int64_t mem_cols = L.row_major ? L.nt : L.mt;
   // strides of the memory-row-major view in the ORIGINAL array
@@ -109,14 +125,7 @@ inline TallA<T> stage_input(Dev& dev, bool host_ptrs, const T* a, int64_t m, int
     vcs = L.row_major ? tcs : trs;
   }
   const bool aligned = !L.needs_pack && (((uintptr_t)a) % 16 == 0) && (L.ld % VEC == 0) && (mem_cols % VEC == 0);
-  if (!host_ptrs && aligned) {
-    ta.mem.p = a;
-    ta.mem.rows = mem_rows;
-    ta.mem.cols = mem_cols;
-    ta.mem.ld = L.ld;
-    ta.mem.cols_readable = mem_cols;
-    return ta;
-  }
+  if (!host_ptrs && aligned) return tall_over<T>(a, L.row_major, L.mt, L.nt, mem_rows, mem_cols, L.ld, mem_cols);
   const int64_t ldp = round_up(mem_cols, kLdPad);
   T* buf = (T*)dev.alloc_bytes((size_t)mem_rows * (size_t)ldp * sizeof(T));
   dev.memset_zero(buf, (size_t)mem_rows * (size_t)ldp * sizeof(T));
@@ -132,12 +141,144 @@ inline TallA<T> stage_input(Dev& dev, bool host_ptrs, const T* a, int64_t m, int
   } else {
     dev.pack_strided(a, mem_rows, mem_cols, vrs, vcs, buf, ldp);
   }
-  ta.mem.p = buf;
-  ta.mem.rows = mem_rows;
-  ta.mem.cols = mem_cols;
-  ta.mem.ld = ldp;
-  ta.mem.cols_readable = ldp;
-  return ta;
+  return tall_over<T>(buf, L.row_major, L.mt, L.nt, mem_rows, mem_cols, ldp, ldp);
+}
+
+// The options of one rsvd / PCA call.  Sparse operands: CORRLA_POWER_FUSED and CORRLA_SKETCH_BF16X3 / X6 have no sparse
+// kernels and are ignored, as documented for every operand outside their domain.
+inline RunOpts call_opts(const corrla_opts* o, bool host_ptrs, bool sharded, bool sparse) {
+  RunOpts ro = parse_opts(o, !host_ptrs);
+  if (sparse) {
+    ro.power_fused = false;
+    ro.mixed_planes = 0;
+  }
+  ro.sharded = sharded;
+  return ro;
+}
+template <class Dev>
+inline void draw_seed(Dev& dev, RunOpts& ro) {
+  if (!ro.seed_explicit && !ro.omega) ro.seed = dev.fresh_seed(/*rank_invariant=*/ro.sharded);
+}
+
+// Everything that can fail on ONE rank only (arguments in `check`; staging and workspace in `stage`, inside the call
+// that this helper begins) happens before the first collective; on the sharded entry points its outcome is then agreed
+// by one small all-reduce, so that a rank-local failure ends the call on every rank instead of stranding the peers in
+// a collective (Dev::sharded_handshake).
+template <class Dev, class Check, class Stage>
+inline void prepare_call(Dev& dev, bool sharded, Check&& check, Stage&& stage) {
+  bool begun = false;
+  auto prepare = [&] {
+    check();
+    dev.begin_call();
+    begun = true;
+    stage();
+  };
+  if (!sharded) {
+    prepare();
+    return;
+  }
+  if (dev.nranks() < 1) throw Error(ST_ECOMM, "communicator not initialised");
+  int local = ST_OK;
+  std::string local_msg;
+  try {
+    prepare();
+  } catch (const Error& e) {
+    local = e.code;
+    local_msg = e.what();
+  } catch (const std::bad_alloc&) {
+    local = ST_ENOMEM;
+    local_msg = "host allocation failed";
+  }
+  if (!begun) dev.begin_call();
+  const int agreed = dev.sharded_handshake(local);
+  if (local != ST_OK) throw Error(local, local_msg);
+  if (agreed != ST_OK)
+    throw Error(agreed, "sharded call abandoned: another rank failed before the first collective (status " + std::to_string(agreed) +
+                            "); this rank's arguments were valid");
+}
+
+// The end of an rsvd / PCA call: the output copies that emit() enqueued, the call's timings and counters.
+template <class Dev, class T>
+inline void finish_call(RsvdDriver<Dev, T>& drv, Dev& dev, Timings* tm_out, bool with_sketch_kernel_ms) {
+  PhaseTimer fin;
+  drv.phase(drv.tm.finalize_ms, fin);  // output copies enqueued by emit()
+  dev.phase_end();
+  dev.end_call();
+  dev.phase_resolve(&drv.tm.total_ms);
+  drv.tm.n_collectives = dev.n_collectives;
+  drv.tm.collective_bytes = dev.collective_bytes;
+  if (with_sketch_kernel_ms) drv.tm.sketch_kernel_ms = dev.event_elapsed_ms(0, 1);
+  if (tm_out) *tm_out = drv.tm;
+}
+
+// ---- random_svd ------------------------------------------------------------------------------------------------------
+// What an rsvd call is, apart from its operand.  First the arguments every rsvd entry has, in the order of its
+// prototype (m is the caller's row count, of U); then the kind of call, which the entries set BY NAME: `fat` = the tall
+// view is the transpose of what the caller passed, `empty_shard` = the operand is the zero-row stand-in.
+template <class T>
+struct RsvdCall {
+  bool host_ptrs;
+  int64_t m, rank, n_iter, n_oversamples;
+  const corrla_opts* opts;
+  T* u;
+  int64_t ldu;
+  T* s;
+  T* vt;
+  int64_t ldvt;
+  Timings* tm_out;
+  bool profile;
+  bool sharded = false, sparse = false, fat = false, empty_shard = false;
+};
+
+// The one body of random_svd (random_svd.rs:63-110) for every operand.  `validate` checks the operand and the rank;
+// `stage` returns the staged tall operand.
+template <class Dev, class T, class Validate, class Stage>
+inline void rsvd_body(Dev& dev, const RsvdCall<T>& c, Validate&& validate, Stage&& stage) {
+  const bool shard_cols = c.sharded && c.fat;
+  const int64_t k = c.rank;
+  RunOpts ro;
+  TallA<T> ta;
+  bool u_in_place = false;
+  int64_t l = 0;
+  Skinny<T> ut, vtall;
+  T* s_dev = nullptr;
+  prepare_call(
+      dev, c.sharded,
+      [&] {
+        // (an empty shard has no rows of its sharded output factor: that pointer may be NULL)
+        if ((!c.u && !(c.empty_shard && !shard_cols)) || !c.s || (!c.vt && !(c.empty_shard && shard_cols)))
+          throw Error(ST_EINVAL, "output pointer is NULL");
+        validate();
+        if (c.ldu < c.m) throw Error(ST_EINVAL, "ldu < m");
+        if (c.ldvt < c.rank) throw Error(ST_EINVAL, "ldvt < rank");
+        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse);
+        draw_seed(dev, ro);
+      },
+      [&] {
+        ta = stage();
+        l = std::min<int64_t>(c.rank + c.n_oversamples, ta.nt);  // random_svd.rs:77
+        if (ro.omega && ro.omega_ld < ta.nt) throw Error(ST_EINVAL, "omega_ld < min(m, n)");
+        // Tall input, device pointers: the m x k factor U is produced directly in the caller's buffer (column-major,
+        // ldu) -- no staging copy of the largest output.
+        u_in_place = !c.fat && !c.host_ptrs && !c.empty_shard;
+        ut = u_in_place ? caller_skinny(c.u, ta.mt, k, c.ldu) : dev.template alloc_skinny<T>(ta.mt, k);
+        vtall = dev.template alloc_skinny<T>(ta.nt, k);
+        s_dev = dev.template alloc_scalar<T>((int)k);
+      });
+  RsvdDriver<Dev, T> drv(dev, c.profile);
+  if (c.empty_shard) drv.m_local_override_ = 0;  // the stand-in zero row is not a row of the matrix
+  drv.random_svd_tall(ta, k, l, c.n_iter, ro, ut, s_dev, vtall, [&] {
+    // random_svd.rs:96-109: tall -> (U, S, V^T); fat -> (V, S, U^T) of the transposed problem
+    if (!c.fat) {
+      if (!u_in_place && !c.empty_shard) dev.copy_out(ut, k, c.u, c.ldu, /*transpose=*/false, c.host_ptrs);
+      dev.copy_out(vtall, k, c.vt, c.ldvt, /*transpose=*/true, c.host_ptrs);
+    } else {
+      dev.copy_out(vtall, k, c.u, c.ldu, false, c.host_ptrs);
+      if (!c.empty_shard) dev.copy_out(ut, k, c.vt, c.ldvt, true, c.host_ptrs);
+    }
+    dev.copy_values_out(s_dev, k, c.s, c.host_ptrs);
+  });
+  finish_call(drv, dev, c.tm_out, /*with_sketch_kernel_ms=*/true);
 }
 
 template <class Dev, class T>
@@ -150,179 +291,82 @@ inline void rsvd_entry(Dev& dev, bool host_ptrs, bool sharded, const T* a, int64
   const bool shard_cols = sharded && opts && (opts->flags & CORRLA_SHARD_COLS) != 0;
   // An EMPTY shard (m_local == 0 rows, or n_local == 0 columns with CORRLA_SHARD_COLS) is legal on the sharded entry
   // points -- more ranks than row blocks, ragged partitions: the rank takes part in every collective with zero
-  // contributions (its block is replaced by ONE zero row of the tall view, which adds nothing to any sum) and writes
-  // no row of the sharded output factor.
+  // contributions (zero_row_tall) and writes no row of the sharded output factor.
   const bool empty_shard = sharded && m >= 0 && n >= 0 && (shard_cols ? (n == 0 && m >= 1) : (m == 0 && n >= 1));
-  const int64_t k = rank;
-  RunOpts ro;
-  TallA<T> ta;
-  bool fat = false, u_in_place = false;
-  int64_t l = 0;
-  Skinny<T> ut, vtall;
-  T* s_dev = nullptr;
-  bool begun = false;
-  // Everything that can fail on ONE rank only (arguments, staging, workspace) happens before the first collective;
-  // on the sharded entry points its outcome is then agreed by one small all-reduce, so that a rank-local failure ends
-  // the call on every rank instead of stranding the peers in a collective (Dev::sharded_handshake).
-  auto prepare = [&] {
-    // (an empty shard has no rows of its sharded output factor: that pointer may be NULL)
-    if ((!u && !(empty_shard && !shard_cols)) || !s || (!vt && !(empty_shard && shard_cols)))
-      throw Error(ST_EINVAL, "output pointer is NULL");
-    if (!empty_shard) validate_matrix(a, m, n, rs, cs);
-    if (!sharded && opts && (opts->flags & CORRLA_SHARD_COLS)) throw Error(ST_EINVAL, "CORRLA_SHARD_COLS is only valid for sharded entry points");
-    const int64_t short_side = shard_cols ? m : n;
-    if (sharded) {
-      if (rank < 1 || rank > short_side) throw Error(ST_EINVAL, "rank must be in [1, short side] for the sharded path");
-      if (n_iter < 0 || n_oversamples < 0) throw Error(ST_EINVAL, "n_iter and n_oversamples must be >= 0");
-    } else {
-      validate_rank(m, n, rank, n_iter, n_oversamples);
-    }
-    if (ldu < m) throw Error(ST_EINVAL, "ldu < m");
-    if (ldvt < rank) throw Error(ST_EINVAL, "ldvt < rank");
-    ro = parse_opts(opts, !host_ptrs);
-    ro.sharded = sharded;
-    if (!ro.seed_explicit && !ro.omega) ro.seed = dev.fresh_seed(/*rank_invariant=*/sharded);
-    dev.begin_call();
-    begun = true;
-    if (empty_shard) {
-      const int64_t nt = short_side, ldp = round_up(nt, kLdPad);
-      T* zrow = (T*)dev.alloc_bytes((size_t)ldp * sizeof(T));
-      dev.memset_zero(zrow, (size_t)ldp * sizeof(T));
-      ta.mt = 1;
-      ta.nt = nt;
-      ta.row_major = true;
-      ta.mem.p = zrow;
-      ta.mem.rows = 1;
-      ta.mem.cols = nt;
-      ta.mem.ld = ldp;
-      ta.mem.cols_readable = ldp;
-    } else {
-      ta = shard_cols ? stage_input<Dev, T>(dev, host_ptrs, a, n, m, cs, rs, true)
-                      : stage_input<Dev, T>(dev, host_ptrs, a, m, n, rs, cs, sharded);
-    }
-    fat = sharded ? shard_cols : m < n;
-    l = std::min<int64_t>(rank + n_oversamples, ta.nt);  // random_svd.rs:77
-    if (ro.omega && ro.omega_ld < ta.nt) throw Error(ST_EINVAL, "omega_ld < min(m, n)");
-    // Tall input, device pointers: the m x k factor U is produced directly in the caller's buffer (column-major, ldu)
-    // -- no staging copy of the largest output.
-    u_in_place = !fat && !host_ptrs && !empty_shard;
-    if (u_in_place) {
-      ut.p = u;
-      ut.rows = ta.mt;
-      ut.cols = k;
-      ut.ld = ldu;
-      ut.cols_alloc = k;
-      ut.external = true;
-    } else {
-      ut = dev.template alloc_skinny<T>(ta.mt, k);
-    }
-    vtall = dev.template alloc_skinny<T>(ta.nt, k);
-    s_dev = dev.template alloc_scalar<T>((int)k);
-  };
-  if (!sharded) {
-    prepare();
-  } else {
-    if (dev.nranks() < 1) throw Error(ST_ECOMM, "communicator not initialised");
-    int local = ST_OK;
-    std::string local_msg;
-    try {
-      prepare();
-    } catch (const Error& e) {
-      local = e.code;
-      local_msg = e.what();
-    } catch (const std::bad_alloc&) {
-      local = ST_ENOMEM;
-      local_msg = "host allocation failed";
-    }
-    if (!begun) dev.begin_call();
-    const int agreed = dev.sharded_handshake(local);
-    if (local != ST_OK) throw Error(local, local_msg);
-    if (agreed != ST_OK)
-      throw Error(agreed, "sharded call abandoned: another rank failed before the first collective (status " + std::to_string(agreed) +
-                              "); this rank's arguments were valid");
-  }
-  RsvdDriver<Dev, T> drv(dev, profile);
-  if (empty_shard) drv.m_local_override_ = 0;  // the stand-in zero row is not a row of the matrix
-  drv.random_svd_tall(ta, k, l, n_iter, ro, ut, s_dev, vtall, [&] {
-    // random_svd.rs:96-109: tall -> (U, S, V^T); fat -> (V, S, U^T) of the transposed problem
-    if (!fat) {
-      if (!u_in_place && !empty_shard) dev.copy_out(ut, k, u, ldu, /*transpose=*/false, host_ptrs);
-      dev.copy_out(vtall, k, vt, ldvt, /*transpose=*/true, host_ptrs);
-    } else {
-      dev.copy_out(vtall, k, u, ldu, false, host_ptrs);
-      if (!empty_shard) dev.copy_out(ut, k, vt, ldvt, true, host_ptrs);
-    }
-    dev.copy_values_out(s_dev, k, s, host_ptrs);
-  });
-  PhaseTimer fin;
-  drv.phase(drv.tm.finalize_ms, fin);  // output copies enqueued by emit()
-  dev.phase_end();
-  dev.end_call();
-  dev.phase_resolve(&drv.tm.total_ms);
-  drv.tm.n_collectives = dev.n_collectives;
-  drv.tm.collective_bytes = dev.collective_bytes;
-  drv.tm.sketch_kernel_ms = dev.event_elapsed_ms(0, 1);
-  if (tm_out) *tm_out = drv.tm;
+  const int64_t short_side = shard_cols ? m : n;
+  RsvdCall<T> c{host_ptrs, m, rank, n_iter, n_oversamples, opts, u, ldu, s, vt, ldvt, tm_out, profile};
+  c.sharded = sharded;
+  c.fat = sharded ? shard_cols : m < n;
+  c.empty_shard = empty_shard;
+  rsvd_body(
+      dev, c,
+      [&] {
+        if (!empty_shard) validate_matrix(a, m, n, rs, cs);
+        if (!sharded && opts && (opts->flags & CORRLA_SHARD_COLS)) throw Error(ST_EINVAL, "CORRLA_SHARD_COLS is only valid for sharded entry points");
+        if (sharded) {
+          if (rank < 1 || rank > short_side) throw Error(ST_EINVAL, "rank must be in [1, short side] for the sharded path");
+          if (n_iter < 0 || n_oversamples < 0) throw Error(ST_EINVAL, "n_iter and n_oversamples must be >= 0");
+        } else {
+          validate_rank(m, n, rank, n_iter, n_oversamples);
+        }
+      },
+      [&] {
+        if (empty_shard) return zero_row_tall<Dev, T>(dev, short_side);
+        return shard_cols ? stage_input<Dev, T>(dev, host_ptrs, a, n, m, cs, rs, true)
+                          : stage_input<Dev, T>(dev, host_ptrs, a, m, n, rs, cs, sharded);
+      });
 }
 
-// PcaRsvd::new (pca_rsvd.rs:56-82): means, centring (implicit rank-1 corrections or a centred copy, see
-// CORRLA_PCA_CENTER_*), random_svd of the centred matrix; keeps S and V^T.
+// ---- PCA -------------------------------------------------------------------------------------------------------------
+inline void need_two_samples(int64_t m) {
+  if (m < 2) throw Error(ST_EINVAL, "PCA needs at least two samples");
+}
+
+// as RsvdCall: the entries' arguments in prototype order, then the kind of call, set by name
+template <class T>
+struct PcaCall {
+  bool host_ptrs;
+  int64_t m, n, rank, n_iter, n_oversamples;
+  const corrla_opts* opts;
+  T* means;
+  T* s;
+  T* comps;
+  int64_t ldc;
+  Timings* tm_out;
+  bool profile;
+  bool sharded = false, sparse = false;
+};
+
+// The one body of PcaRsvd::new (pca_rsvd.rs:56-82) for every operand: means, centring (implicit rank-1 corrections or
+// a centred copy, see CORRLA_PCA_CENTER_*), random_svd of the centred matrix; keeps S and V^T.
 // sharded: the SAMPLES (rows of x) are sharded over the ranks; means, S and the components come out replicated.  The
 // column means and every product with the centred matrix are linear in the rows, so they are all-reduced partial sums.
-template <class Dev, class T>
-inline void pca_entry(Dev& dev, bool host_ptrs, const T* x, int64_t m, int64_t n, int64_t rs, int64_t cs, int64_t rank,
-                      int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, T* means, T* s, T* comps,
-                      int64_t ldc, Timings* tm_out, bool profile, bool sharded = false) {
+// An empty shard is not supported here (the centring has no zero-contribution stand-in): it fails validation, on every
+// rank alike.
+// sparse: always the fused centring -- the centred operator is A X - 1 (mu^T X), A itself is never
+// rewritten, so the matrix stays sparse; the means are A^T 1 / m through the same SpMM as every other product.
+template <class Dev, class T, class Validate, class Stage>
+inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&& stage) {
   RunOpts ro;
   TallA<T> ta;
-  bool begun = false;
-  // what can fail on one rank only comes before the first collective and is agreed by the handshake (see rsvd_entry);
-  // an empty shard is not supported here (the centring has no zero-contribution stand-in): it fails validation, on
-  // every rank alike
-  auto prepare = [&] {
-    if (!means || !s || !comps) throw Error(ST_EINVAL, "output pointer is NULL");
-    validate_matrix(x, m, n, rs, cs);
-    if (sharded) {
-      if (rank < 1 || rank > n) throw Error(ST_EINVAL, "rank must be in [1, n_dim] for the sample-sharded PCA");
-      if (n_iter < 0 || n_oversamples < 0) throw Error(ST_EINVAL, "n_iter and n_oversamples must be >= 0");
-    } else {
-      validate_rank(m, n, rank, n_iter, n_oversamples);
-    }
-    if (ldc < rank) throw Error(ST_EINVAL, "ldc < rank");
-    ro = parse_opts(opts, !host_ptrs);
-    ro.sharded = sharded;
-    if (!ro.seed_explicit && !ro.omega) ro.seed = dev.fresh_seed(sharded);
-    dev.begin_call();
-    begun = true;
-    ta = stage_input<Dev, T>(dev, host_ptrs, x, m, n, rs, cs, sharded);
-  };
-  if (!sharded) {
-    prepare();
-  } else {
-    if (dev.nranks() < 1) throw Error(ST_ECOMM, "communicator not initialised");
-    int local = ST_OK;
-    std::string local_msg;
-    try {
-      prepare();
-    } catch (const Error& e) {
-      local = e.code;
-      local_msg = e.what();
-    } catch (const std::bad_alloc&) {
-      local = ST_ENOMEM;
-      local_msg = "host allocation failed";
-    }
-    if (!begun) dev.begin_call();
-    const int agreed = dev.sharded_handshake(local);
-    if (local != ST_OK) throw Error(local, local_msg);
-    if (agreed != ST_OK)
-      throw Error(agreed, "sharded call abandoned: another rank failed before the first collective (status " + std::to_string(agreed) +
-                              "); this rank's arguments were valid");
-  }
-  const int64_t m_global = sharded ? dev.allreduce_sum_host(m) : m;  // every rank makes this call (rank-invariant)
-  if (m_global < 2) throw Error(ST_EINVAL, "PCA needs at least two samples");
-  const bool fat = !sharded && m < n;  // the tall view is x^T: its ROWS are the data columns
-  // column means of x = (1/m) x^T 1: one pass of the transposed-GEMM kernel against a ones vector
-  RsvdDriver<Dev, T> drv(dev, profile);
+  prepare_call(
+      dev, c.sharded,
+      [&] {
+        if (!c.means || !c.s || !c.comps) throw Error(ST_EINVAL, "output pointer is NULL");
+        validate();
+        if (c.ldc < c.rank) throw Error(ST_EINVAL, "ldc < rank");
+        if (c.sparse) need_two_samples(c.m);  // never sharded: the sample count is known before anything is staged
+        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse);
+        if (c.sparse && ro.pca_center == 2)
+          throw Error(ST_EINVAL, "CORRLA_PCA_CENTER_COPY on CSR input: a centred copy would densify the matrix (use the fused centring)");
+        draw_seed(dev, ro);
+      },
+      [&] { ta = stage(); });
+  const int64_t m_global = c.sharded ? dev.allreduce_sum_host(c.m) : c.m;  // every rank makes this call (rank-invariant)
+  need_two_samples(m_global);
+  const bool fat = !c.sharded && c.m < c.n;  // the tall view is x^T: its ROWS are the data columns
+  // column means of x = (1/m) x^T 1: one pass of the transposed product against a ones vector
+  RsvdDriver<Dev, T> drv(dev, c.profile);
   const int64_t samples_dim_tall = fat ? ta.nt : ta.mt;  // n_samples as a dimension of the tall view
   Skinny<T> ones = dev.template alloc_skinny<T>(samples_dim_tall, 1);
   dev.fill_const(ones.p, samples_dim_tall, (T)1);
@@ -331,11 +375,11 @@ inline void pca_entry(Dev& dev, bool host_ptrs, const T* x, int64_t m, int64_t n
   const T inv_m_host = (T)(1.0 / (double)m_global);
   dev.store_values(&inv_m_host, (int64_t)1, inv_m, /*dst_is_host=*/false);
   if (!fat)
-    drv.at_times(ta, ones, mu, inv_m, sharded);  // mu (n) = x^T 1 / m (all-reduced partial sums when sharded)
+    drv.at_times(ta, ones, mu, inv_m, c.sharded);  // mu (n) = x^T 1 / m (all-reduced partial sums when sharded)
   else
-    drv.a_times(ta, ones, mu, inv_m);          // tall view = x^T (n x m): mu (n) = x^T 1 / m
+    drv.a_times(ta, ones, mu, inv_m);            // tall view = x^T (n x m): mu (n) = x^T 1 / m
   TallA<T> tc = ta;
-  const bool fused = ro.pca_center == 1 || (ro.pca_center == 0 && sizeof(T) == 8);
+  const bool fused = c.sparse || ro.pca_center == 1 || (ro.pca_center == 0 && sizeof(T) == 8);
   if (fused) {
     // the centred matrix is never formed.  Tall view (i, j) = x(i, j) for tall inputs (means run
     // along the SHORT side), = x(j, i) for fat inputs (means run along the TALL side).
@@ -357,29 +401,39 @@ inline void pca_entry(Dev& dev, bool host_ptrs, const T* x, int64_t m, int64_t n
     tc.mem.ld = ldp;
     tc.mem.cols_readable = ldp;
   }
-  const int64_t k = rank;
-  const int64_t l = std::min<int64_t>(rank + n_oversamples, tc.nt);
+  const int64_t k = c.rank;
+  const int64_t l = std::min<int64_t>(c.rank + c.n_oversamples, tc.nt);
   if (ro.omega && ro.omega_ld < tc.nt) throw Error(ST_EINVAL, "omega_ld < min(m, n)");
   Skinny<T> ut = dev.template alloc_skinny<T>(tc.mt, k);
   Skinny<T> vtall = dev.template alloc_skinny<T>(tc.nt, k);
   T* s_dev = dev.template alloc_scalar<T>((int)k);
-  drv.random_svd_tall(tc, k, l, n_iter, ro, ut, s_dev, vtall, [&] {
+  drv.random_svd_tall(tc, k, l, c.n_iter, ro, ut, s_dev, vtall, [&] {
     // components_ = vr = V^T (k x n_dim)   pca_rsvd.rs:70-71
-    if (!fat)
-      dev.copy_out(vtall, k, comps, ldc, /*transpose=*/true, host_ptrs);
-    else
-      dev.copy_out(ut, k, comps, ldc, true, host_ptrs);
-    dev.copy_values_out(s_dev, k, s, host_ptrs);
-    dev.copy_values_out(mu.p, n, means, host_ptrs);
+    dev.copy_out(fat ? ut : vtall, k, c.comps, c.ldc, /*transpose=*/true, c.host_ptrs);
+    dev.copy_values_out(s_dev, k, c.s, c.host_ptrs);
+    dev.copy_values_out(mu.p, c.n, c.means, c.host_ptrs);
   });
-  PhaseTimer fin;
-  drv.phase(drv.tm.finalize_ms, fin);
-  dev.phase_end();
-  dev.end_call();
-  dev.phase_resolve(&drv.tm.total_ms);
-  drv.tm.n_collectives = dev.n_collectives;
-  drv.tm.collective_bytes = dev.collective_bytes;
-  if (tm_out) *tm_out = drv.tm;
+  finish_call(drv, dev, c.tm_out, /*with_sketch_kernel_ms=*/false);
+}
+
+template <class Dev, class T>
+inline void pca_entry(Dev& dev, bool host_ptrs, const T* x, int64_t m, int64_t n, int64_t rs, int64_t cs, int64_t rank,
+                      int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, T* means, T* s, T* comps,
+                      int64_t ldc, Timings* tm_out, bool profile, bool sharded = false) {
+  PcaCall<T> c{host_ptrs, m, n, rank, n_iter, n_oversamples, opts, means, s, comps, ldc, tm_out, profile};
+  c.sharded = sharded;
+  pca_body(
+      dev, c,
+      [&] {
+        validate_matrix(x, m, n, rs, cs);
+        if (sharded) {
+          if (rank < 1 || rank > n) throw Error(ST_EINVAL, "rank must be in [1, n_dim] for the sample-sharded PCA");
+          if (n_iter < 0 || n_oversamples < 0) throw Error(ST_EINVAL, "n_iter and n_oversamples must be >= 0");
+        } else {
+          validate_rank(m, n, rank, n_iter, n_oversamples);
+        }
+      },
+      [&] { return stage_input<Dev, T>(dev, host_ptrs, x, m, n, rs, cs, sharded); });
 }
 
 template <class Dev, class T>
@@ -403,37 +457,50 @@ inline void power_iter_entry(Dev& dev, bool host_ptrs, const T* a, int64_t m, in
   dev.end_call();
 }
 
-// res = beta * op(A) * X   (mat_utils.rs:20-33 for the two hot-path shapes)
-template <class Dev, class T>
-inline void matmul_entry(Dev& dev, int trans, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs, const T* x,
-                         int64_t ldx, int64_t l, T beta, T* res, int64_t ldres, Timings* tm_out = nullptr) {
+// ---- product hooks ---------------------------------------------------------------------------------------------------
+// res = beta * op(A) * X on device pointers, A as given (m x n, never transposed); `validate` checks the operand,
+// `stage` returns it as the tall operand.  A dense product lands in a padded Skinny and is copied out; a sparse one is
+// written straight into the caller's buffer (an `external` Skinny: ld = ldres, exactly l columns): the hook shows what
+// the SpMM kernels store, and a caller who pads res can see that nothing else is touched.
+template <class Dev, class T, class Validate, class Stage>
+inline void product_body(Dev& dev, int trans, int64_t m, int64_t n, const T* x, int64_t ldx, int64_t l, T beta, T* res,
+                         int64_t ldres, Timings* tm_out, Validate&& validate, Stage&& stage) {
   if (!x || !res) throw Error(ST_EINVAL, "x or res is NULL");
-  validate_matrix(a, m, n, rs, cs);
+  validate();
   if (l < 1) throw Error(ST_EINVAL, "l must be >= 1");
   const int64_t xin = trans ? m : n, xout = trans ? n : m;
   if (ldx < xin || ldres < xout) throw Error(ST_EINVAL, "leading dimension too small");
   dev.begin_call();
-  TallA<T> ta = stage_input<Dev, T>(dev, false, a, m, n, rs, cs, true);
+  TallA<T> ta = stage();
   RsvdDriver<Dev, T> drv(dev, false);
-  drv.mixed_planes_ = parse_opts(nullptr, true).mixed_planes;  // CORRLA_SKETCH_MIXED (this hook takes no opts)
+  if (!ta.sparse) drv.mixed_planes_ = parse_opts(nullptr, true).mixed_planes;  // CORRLA_SKETCH_MIXED (the hooks take no opts)
   Skinny<T> xs = dev.template alloc_skinny<T>(xin, l);
   dev.copy_in_skinny(x, ldx, xs);
-  Skinny<T> out = dev.template alloc_skinny<T>(xout, l);
+  Skinny<T> out = ta.sparse ? caller_skinny(res, xout, l, ldres) : dev.template alloc_skinny<T>(xout, l);
   T* beta_dev = dev.template alloc_scalar<T>(1);
   dev.store_values(&beta, (int64_t)1, beta_dev, /*dst_is_host=*/false);
   if (trans)
     drv.at_times(ta, xs, out, beta_dev, false);
   else
     drv.a_times(ta, xs, out, beta_dev);
-  dev.copy_out(out, l, res, ldres, false, false);
+  if (!out.external) dev.copy_out(out, l, res, ldres, false, false);
   dev.end_call();
   if (tm_out) tm_out->n_mixed_products = drv.tm.n_mixed_products;
 }
 
+// mat_utils.rs:20-33 for the two hot-path shapes
+template <class Dev, class T>
+inline void matmul_entry(Dev& dev, int trans, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs, const T* x,
+                         int64_t ldx, int64_t l, T beta, T* res, int64_t ldres, Timings* tm_out = nullptr) {
+  product_body(
+      dev, trans, m, n, x, ldx, l, beta, res, ldres, tm_out, [&] { validate_matrix(a, m, n, rs, cs); },
+      [&] { return stage_input<Dev, T>(dev, false, a, m, n, rs, cs, true); });
+}
+
 // ---- CSR sparse input ------------------------------------------------------------------------------------------------
-// The sparse counterparts of rsvd_entry / pca_entry / matmul_entry (unsharded): A arrives as CSR (values, int32 column
-// indices, int64 row_ptr).  Host arrays are uploaded and take the device path, so there is one validation and one
-// transposition path.  Only instantiated for backends that carry the SpMM kernels (dev_has_spmm).
+// A arrives as CSR (values, int32 column indices, int64 row_ptr), unsharded.  Host arrays are uploaded and take the
+// device path, so there is one validation and one transposition path.  Only instantiated for backends that carry the
+// SpMM kernels (dev_has_spmm).
 inline void validate_csr_args(const void* values, const void* ci, const void* rp, int64_t m, int64_t n, int64_t nnz) {
   if (!values || !ci || !rp) throw Error(ST_EINVAL, "values, col_idx or row_ptr is NULL");
   if (m < 1 || n < 1) throw Error(ST_EINVAL, "matrix must have at least one row and one column");
@@ -482,130 +549,37 @@ inline TallA<T> stage_csr(Dev& dev, bool host_ptrs, const T* values, const int32
   return ta;
 }
 
-// CORRLA_POWER_FUSED and CORRLA_SKETCH_BF16X3 / X6 have no sparse kernels: ignored, as documented for every operand
-// outside their domain.
-inline RunOpts parse_opts_sparse(const corrla_opts* o, bool dev_ptrs) {
-  RunOpts r = parse_opts(o, dev_ptrs);
-  r.power_fused = false;
-  r.mixed_planes = 0;
-  return r;
-}
-
 template <class Dev, class T>
 inline void rsvd_csr_entry(Dev& dev, bool host_ptrs, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
                            int64_t nnz, int64_t rank, int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, T* u,
                            int64_t ldu, T* s, T* vt, int64_t ldvt, Timings* tm_out, bool profile) {
   static_assert(dev_has_spmm<Dev>::value, "CSR entries need a backend with SpMM kernels");
-  if (!u || !s || !vt) throw Error(ST_EINVAL, "output pointer is NULL");
-  validate_csr_args(values, ci, rp, m, n, nnz);
-  validate_rank(m, n, rank, n_iter, n_oversamples);
-  if (ldu < m) throw Error(ST_EINVAL, "ldu < m");
-  if (ldvt < rank) throw Error(ST_EINVAL, "ldvt < rank");
-  RunOpts ro = parse_opts_sparse(opts, !host_ptrs);
-  if (!ro.seed_explicit && !ro.omega) ro.seed = dev.fresh_seed(false);
-  dev.begin_call();
-  TallA<T> ta = stage_csr<Dev, T>(dev, host_ptrs, values, ci, rp, m, n, nnz, false);
-  const bool fat = m < n;
-  const int64_t k = rank;
-  const int64_t l = std::min<int64_t>(rank + n_oversamples, ta.nt);  // random_svd.rs:77
-  if (ro.omega && ro.omega_ld < ta.nt) throw Error(ST_EINVAL, "omega_ld < min(m, n)");
-  const bool u_in_place = !fat && !host_ptrs;  // as rsvd_entry: U straight into the caller's buffer
-  Skinny<T> ut;
-  if (u_in_place) {
-    ut.p = u;
-    ut.rows = ta.mt;
-    ut.cols = k;
-    ut.ld = ldu;
-    ut.cols_alloc = k;
-    ut.external = true;
-  } else {
-    ut = dev.template alloc_skinny<T>(ta.mt, k);
-  }
-  Skinny<T> vtall = dev.template alloc_skinny<T>(ta.nt, k);
-  T* s_dev = dev.template alloc_scalar<T>((int)k);
-  RsvdDriver<Dev, T> drv(dev, profile);
-  drv.random_svd_tall(ta, k, l, n_iter, ro, ut, s_dev, vtall, [&] {
-    // random_svd.rs:96-109: tall -> (U, S, V^T); fat -> (V, S, U^T) of the transposed problem
-    if (!fat) {
-      if (!u_in_place) dev.copy_out(ut, k, u, ldu, /*transpose=*/false, host_ptrs);
-      dev.copy_out(vtall, k, vt, ldvt, /*transpose=*/true, host_ptrs);
-    } else {
-      dev.copy_out(vtall, k, u, ldu, false, host_ptrs);
-      dev.copy_out(ut, k, vt, ldvt, true, host_ptrs);
-    }
-    dev.copy_values_out(s_dev, k, s, host_ptrs);
-  });
-  PhaseTimer fin;
-  drv.phase(drv.tm.finalize_ms, fin);
-  dev.phase_end();
-  dev.end_call();
-  dev.phase_resolve(&drv.tm.total_ms);
-  drv.tm.n_collectives = dev.n_collectives;
-  drv.tm.collective_bytes = dev.collective_bytes;
-  drv.tm.sketch_kernel_ms = dev.event_elapsed_ms(0, 1);
-  if (tm_out) *tm_out = drv.tm;
+  RsvdCall<T> c{host_ptrs, m, rank, n_iter, n_oversamples, opts, u, ldu, s, vt, ldvt, tm_out, profile};
+  c.sparse = true;
+  c.fat = m < n;
+  rsvd_body(
+      dev, c,
+      [&] {
+        validate_csr_args(values, ci, rp, m, n, nnz);
+        validate_rank(m, n, rank, n_iter, n_oversamples);
+      },
+      [&] { return stage_csr<Dev, T>(dev, host_ptrs, values, ci, rp, m, n, nnz, false); });
 }
 
-// PcaRsvd::new (pca_rsvd.rs:56-82) on CSR data: always the fused centring -- the centred operator
-// is A X - 1 (mu^T X), A itself is never rewritten, so the matrix stays sparse.  The means are A^T 1 / m through the
-// same SpMM as every other product.
 template <class Dev, class T>
 inline void pca_csr_entry(Dev& dev, bool host_ptrs, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
                           int64_t nnz, int64_t rank, int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, T* means,
                           T* s, T* comps, int64_t ldc, Timings* tm_out, bool profile) {
   static_assert(dev_has_spmm<Dev>::value, "CSR entries need a backend with SpMM kernels");
-  if (!means || !s || !comps) throw Error(ST_EINVAL, "output pointer is NULL");
-  validate_csr_args(values, ci, rp, m, n, nnz);
-  validate_rank(m, n, rank, n_iter, n_oversamples);
-  if (ldc < rank) throw Error(ST_EINVAL, "ldc < rank");
-  if (m < 2) throw Error(ST_EINVAL, "PCA needs at least two samples");
-  RunOpts ro = parse_opts_sparse(opts, !host_ptrs);
-  if (ro.pca_center == 2)
-    throw Error(ST_EINVAL, "CORRLA_PCA_CENTER_COPY on CSR input: a centred copy would densify the matrix (use the fused centring)");
-  if (!ro.seed_explicit && !ro.omega) ro.seed = dev.fresh_seed(false);
-  dev.begin_call();
-  TallA<T> ta = stage_csr<Dev, T>(dev, host_ptrs, values, ci, rp, m, n, nnz, false);
-  const bool fat = m < n;  // the tall view is x^T: its ROWS are the data columns
-  RsvdDriver<Dev, T> drv(dev, profile);
-  const int64_t samples_dim_tall = fat ? ta.nt : ta.mt;
-  Skinny<T> ones = dev.template alloc_skinny<T>(samples_dim_tall, 1);
-  dev.fill_const(ones.p, samples_dim_tall, (T)1);
-  Skinny<T> mu = dev.template alloc_skinny<T>(fat ? ta.mt : ta.nt, 1);
-  T* inv_m = dev.template alloc_scalar<T>(1);
-  const T inv_m_host = (T)(1.0 / (double)m);
-  dev.store_values(&inv_m_host, (int64_t)1, inv_m, /*dst_is_host=*/false);
-  if (!fat)
-    drv.at_times(ta, ones, mu, inv_m, false);  // mu (n) = x^T 1 / m
-  else
-    drv.a_times(ta, ones, mu, inv_m);          // tall view = x^T (n x m)
-  TallA<T> tc = ta;
-  if (!fat)
-    tc.mu_short = mu.p;
-  else
-    tc.mu_tall = mu.p;
-  const int64_t k = rank;
-  const int64_t l = std::min<int64_t>(rank + n_oversamples, tc.nt);
-  if (ro.omega && ro.omega_ld < tc.nt) throw Error(ST_EINVAL, "omega_ld < min(m, n)");
-  Skinny<T> ut = dev.template alloc_skinny<T>(tc.mt, k);
-  Skinny<T> vtall = dev.template alloc_skinny<T>(tc.nt, k);
-  T* s_dev = dev.template alloc_scalar<T>((int)k);
-  drv.random_svd_tall(tc, k, l, n_iter, ro, ut, s_dev, vtall, [&] {
-    // components_ = vr = V^T (k x n_dim)   pca_rsvd.rs:70-71
-    if (!fat)
-      dev.copy_out(vtall, k, comps, ldc, /*transpose=*/true, host_ptrs);
-    else
-      dev.copy_out(ut, k, comps, ldc, true, host_ptrs);
-    dev.copy_values_out(s_dev, k, s, host_ptrs);
-    dev.copy_values_out(mu.p, n, means, host_ptrs);
-  });
-  PhaseTimer fin;
-  drv.phase(drv.tm.finalize_ms, fin);
-  dev.phase_end();
-  dev.end_call();
-  dev.phase_resolve(&drv.tm.total_ms);
-  drv.tm.n_collectives = dev.n_collectives;
-  drv.tm.collective_bytes = dev.collective_bytes;
-  if (tm_out) *tm_out = drv.tm;
+  PcaCall<T> c{host_ptrs, m, n, rank, n_iter, n_oversamples, opts, means, s, comps, ldc, tm_out, profile};
+  c.sparse = true;
+  pca_body(
+      dev, c,
+      [&] {
+        validate_csr_args(values, ci, rp, m, n, nnz);
+        validate_rank(m, n, rank, n_iter, n_oversamples);
+      },
+      [&] { return stage_csr<Dev, T>(dev, host_ptrs, values, ci, rp, m, n, nnz, false); });
 }
 
 // res = beta * op(S) * X for a device CSR matrix S (test hook, the sparse twin of matmul_entry)
@@ -613,32 +587,9 @@ template <class Dev, class T>
 inline void spmm_entry(Dev& dev, int trans, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n, int64_t nnz,
                        const T* x, int64_t ldx, int64_t l, T beta, T* res, int64_t ldres) {
   static_assert(dev_has_spmm<Dev>::value, "CSR entries need a backend with SpMM kernels");
-  if (!x || !res) throw Error(ST_EINVAL, "x or res is NULL");
-  validate_csr_args(values, ci, rp, m, n, nnz);
-  if (l < 1) throw Error(ST_EINVAL, "l must be >= 1");
-  const int64_t xin = trans ? m : n, xout = trans ? n : m;
-  if (ldx < xin || ldres < xout) throw Error(ST_EINVAL, "leading dimension too small");
-  dev.begin_call();
-  TallA<T> ta = stage_csr<Dev, T>(dev, false, values, ci, rp, m, n, nnz, /*keep_orientation=*/true);
-  RsvdDriver<Dev, T> drv(dev, false);
-  Skinny<T> xs = dev.template alloc_skinny<T>(xin, l);
-  dev.copy_in_skinny(x, ldx, xs);
-  // the caller's buffer is the destination itself (an `external` Skinny: ld = ldres, exactly l columns): the hook shows
-  // what the SpMM kernels store, and a caller who pads res can see that nothing else is touched
-  Skinny<T> out;
-  out.p = res;
-  out.rows = xout;
-  out.cols = l;
-  out.ld = ldres;
-  out.cols_alloc = l;
-  out.external = true;
-  T* beta_dev = dev.template alloc_scalar<T>(1);
-  dev.store_values(&beta, (int64_t)1, beta_dev, /*dst_is_host=*/false);
-  if (trans)
-    drv.at_times(ta, xs, out, beta_dev, false);
-  else
-    drv.a_times(ta, xs, out, beta_dev);
-  dev.end_call();
+  product_body(
+      dev, trans, m, n, x, ldx, l, beta, res, ldres, (Timings*)nullptr, [&] { validate_csr_args(values, ci, rp, m, n, nnz); },
+      [&] { return stage_csr<Dev, T>(dev, false, values, ci, rp, m, n, nnz, /*keep_orientation=*/true); });
 }
 
 }  // namespace corrla

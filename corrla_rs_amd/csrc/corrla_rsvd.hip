@@ -38,80 +38,24 @@ inline void locked_call(corrla_ctx* c, F&& f) {
   }
 }
 
-template <class T>
-corrla_status rsvd_c(corrla_ctx* ctx, bool host, bool sharded, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs,
-                     int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* u, int64_t ldu, T* s, T* vt,
-                     int64_t ldvt) {
+// One entry point: status and message from what `f` throws (guarded), a context (need), the lock (locked_call); `after`
+// runs once the lock is released.
+template <class F, class After>
+inline corrla_status ctx_call(corrla_ctx* ctx, F&& f, After&& after) {
   return guarded([&] {
     corrla_ctx* c = need(ctx);
-    locked_call(c, [&] {
-      rsvd_entry<HipDev, T>(c->dev, host, sharded, a, m, n, rs, cs, rank, n_iter, p, o, u, ldu, s, vt, ldvt, &c->last,
-                            c->profile);
-    });
-    if (c->profile && env_int("CORRLA_DEBUG", 0))
-      std::fprintf(stderr, "[corrla] qr breakdown (ms): gram %.3f  download+check %.3f  host chol/inv %.3f  upload+apply %.3f  (%d passes)\n",
-                   c->last.qr_gram_ms, c->last.qr_down_ms, c->last.qr_host_ms, c->last.qr_apply_ms, c->last.qr_passes);
+    locked_call(c, [&] { f(*c); });
+    after(*c);
   });
 }
-template <class T>
-corrla_status pca_c(corrla_ctx* ctx, bool host, const T* x, int64_t m, int64_t n, int64_t rs, int64_t cs, int64_t rank,
-                    int64_t n_iter, int64_t p, const corrla_opts* o, T* means, T* s, T* comps, int64_t ldc,
-                    bool sharded = false) {
-  return guarded([&] {
-    corrla_ctx* c = need(ctx);
-    locked_call(c, [&] {
-      pca_entry<HipDev, T>(c->dev, host, x, m, n, rs, cs, rank, n_iter, p, o, means, s, comps, ldc, &c->last, c->profile,
-                           sharded);
-    });
-  });
+template <class F>
+inline corrla_status ctx_call(corrla_ctx* ctx, F&& f) {
+  return ctx_call(ctx, f, [](corrla_ctx&) {});
 }
-template <class T>
-corrla_status power_c(corrla_ctx* ctx, bool host, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs, int64_t width,
-                      int64_t n_iter, const corrla_opts* o, T* q, int64_t ldq) {
-  return guarded([&] {
-    corrla_ctx* c = need(ctx);
-    locked_call(c, [&] { power_iter_entry<HipDev, T>(c->dev, host, a, m, n, rs, cs, width, n_iter, o, q, ldq); });
-  });
-}
-template <class T>
-corrla_status matmul_c(corrla_ctx* ctx, int trans, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs, const T* x,
-                       int64_t ldx, int64_t l, T beta, T* res, int64_t ldres) {
-  return guarded([&] {
-    corrla_ctx* c = need(ctx);
-    locked_call(c, [&] { matmul_entry<HipDev, T>(c->dev, trans, a, m, n, rs, cs, x, ldx, l, beta, res, ldres, &c->last); });
-  });
-}
-template <class T>
-corrla_status rsvd_csr_c(corrla_ctx* ctx, bool host, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
-                         int64_t nnz, int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* u, int64_t ldu, T* s,
-                         T* vt, int64_t ldvt) {
-  return guarded([&] {
-    corrla_ctx* c = need(ctx);
-    locked_call(c, [&] {
-      rsvd_csr_entry<HipDev, T>(c->dev, host, values, ci, rp, m, n, nnz, rank, n_iter, p, o, u, ldu, s, vt, ldvt, &c->last,
-                                c->profile);
-    });
-  });
-}
-template <class T>
-corrla_status pca_csr_c(corrla_ctx* ctx, bool host, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
-                        int64_t nnz, int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* means, T* s, T* comps,
-                        int64_t ldc) {
-  return guarded([&] {
-    corrla_ctx* c = need(ctx);
-    locked_call(c, [&] {
-      pca_csr_entry<HipDev, T>(c->dev, host, values, ci, rp, m, n, nnz, rank, n_iter, p, o, means, s, comps, ldc, &c->last,
-                               c->profile);
-    });
-  });
-}
-template <class T>
-corrla_status spmm_csr_c(corrla_ctx* ctx, int trans, const T* values, const int32_t* ci, const int64_t* rp, int64_t m, int64_t n,
-                         int64_t nnz, const T* x, int64_t ldx, int64_t l, T beta, T* res, int64_t ldres) {
-  return guarded([&] {
-    corrla_ctx* c = need(ctx);
-    locked_call(c, [&] { spmm_entry<HipDev, T>(c->dev, trans, values, ci, rp, m, n, nnz, x, ldx, l, beta, res, ldres); });
-  });
+inline void debug_qr_breakdown(const corrla_ctx& c) {
+  if (c.profile && env_int("CORRLA_DEBUG", 0))
+    std::fprintf(stderr, "[corrla] qr breakdown (ms): gram %.3f  download+check %.3f  host chol/inv %.3f  upload+apply %.3f  (%d passes)\n",
+                 c.last.qr_gram_ms, c.last.qr_down_ms, c.last.qr_host_ms, c.last.qr_apply_ms, c.last.qr_passes);
 }
 template <class T>
 corrla_status fill_c(corrla_ctx* ctx, T* p, int64_t rows, int64_t cols, int64_t rs, int64_t cs, uint64_t seed,
@@ -212,50 +156,48 @@ CORRLA_API corrla_status corrla_ctx_get_timings(corrla_ctx* ctx, corrla_timings*
   });
 }
 
+// parameter lists of include/corrla_rsvd.h, after the context
+#define CORRLA_DENSE(T, A) const T *A, int64_t m, int64_t n, int64_t rs, int64_t cs
+#define CORRLA_CSR_A(T) const T *values, const int32_t *col_idx, const int64_t *row_ptr, int64_t m, int64_t n, int64_t nnz
+#define CORRLA_RSVD_REST(T) int64_t rank, int64_t n_iter, int64_t p, const corrla_opts *o, T *u, int64_t ldu, T *s, T *vt, int64_t ldvt
+#define CORRLA_PCA_REST(T) int64_t rank, int64_t n_iter, int64_t p, const corrla_opts *o, T *means, T *s, T *comps, int64_t ldc
+#define CORRLA_PRODUCT_REST(T) const T *x, int64_t ldx, int64_t l, T beta, T *res, int64_t ldres
+
+#define CORRLA_DEFINE_RSVD(NAME, T, HOST, SHARDED)                                                                      \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(T, a), CORRLA_RSVD_REST(T)) {                              \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                           \
+      rsvd_entry<HipDev, T>(c.dev, HOST, SHARDED, a, m, n, rs, cs, rank, n_iter, p, o, u, ldu, s, vt, ldvt, &c.last,     \
+                            c.profile);                                                                                 \
+    }, debug_qr_breakdown);                                                                                             \
+  }
+#define CORRLA_DEFINE_PCA(NAME, T, HOST, SHARDED)                                                                       \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(T, x), CORRLA_PCA_REST(T)) {                             \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                           \
+      pca_entry<HipDev, T>(c.dev, HOST, x, m, n, rs, cs, rank, n_iter, p, o, means, s, comps, ldc, &c.last, c.profile,   \
+                           SHARDED);                                                                                    \
+    });                                                                                                                 \
+  }
+#define CORRLA_DEFINE_POWER(NAME, T, HOST)                                                                              \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(T, a), int64_t width, int64_t n_iter, const corrla_opts* o, \
+                                T* q, int64_t ldq) {                                                                    \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                           \
+      power_iter_entry<HipDev, T>(c.dev, HOST, a, m, n, rs, cs, width, n_iter, o, q, ldq);                              \
+    });                                                                                                                 \
+  }
+
 #define CORRLA_DEFINE(SUF, T)                                                                                          \
-  CORRLA_API corrla_status corrla_rsvd_##SUF(corrla_ctx* ctx, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs,           \
-                                  int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* u, int64_t ldu,    \
-                                  T* s, T* vt, int64_t ldvt) {                                                         \
-    return rsvd_c<T>(ctx, true, false, a, m, n, rs, cs, rank, n_iter, p, o, u, ldu, s, vt, ldvt);                      \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_rsvd_dev_##SUF(corrla_ctx* ctx, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs,       \
-                                      int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* u,             \
-                                      int64_t ldu, T* s, T* vt, int64_t ldvt) {                                        \
-    return rsvd_c<T>(ctx, false, false, a, m, n, rs, cs, rank, n_iter, p, o, u, ldu, s, vt, ldvt);                     \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_rsvd_sharded_dev_##SUF(corrla_ctx* ctx, const T* a, int64_t m, int64_t n, int64_t rs,           \
-                                              int64_t cs, int64_t rank, int64_t n_iter, int64_t p,                     \
-                                              const corrla_opts* o, T* u, int64_t ldu, T* s, T* vt, int64_t ldvt) {    \
-    return rsvd_c<T>(ctx, false, true, a, m, n, rs, cs, rank, n_iter, p, o, u, ldu, s, vt, ldvt);                      \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_pca_##SUF(corrla_ctx* ctx, const T* x, int64_t m, int64_t n, int64_t rs, int64_t cs, \
-                                            int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* means,   \
-                                            T* s, T* comps, int64_t ldc) {                                             \
-    return pca_c<T>(ctx, true, x, m, n, rs, cs, rank, n_iter, p, o, means, s, comps, ldc);                             \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_pca_dev_##SUF(corrla_ctx* ctx, const T* x, int64_t m, int64_t n, int64_t rs,         \
-                                                int64_t cs, int64_t rank, int64_t n_iter, int64_t p,                   \
-                                                const corrla_opts* o, T* means, T* s, T* comps, int64_t ldc) {         \
-    return pca_c<T>(ctx, false, x, m, n, rs, cs, rank, n_iter, p, o, means, s, comps, ldc);                            \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_pca_sharded_dev_##SUF(corrla_ctx* ctx, const T* x, int64_t m, int64_t n, int64_t rs,  \
-                                                        int64_t cs, int64_t rank, int64_t n_iter, int64_t p,           \
-                                                        const corrla_opts* o, T* means, T* s, T* comps, int64_t ldc) { \
-    return pca_c<T>(ctx, false, x, m, n, rs, cs, rank, n_iter, p, o, means, s, comps, ldc, true);                      \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_power_iter_##SUF(corrla_ctx* ctx, const T* a, int64_t m, int64_t n, int64_t rs, int64_t cs,     \
-                                        int64_t width, int64_t n_iter, const corrla_opts* o, T* q, int64_t ldq) {      \
-    return power_c<T>(ctx, true, a, m, n, rs, cs, width, n_iter, o, q, ldq);                                           \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_power_iter_dev_##SUF(corrla_ctx* ctx, const T* a, int64_t m, int64_t n, int64_t rs,             \
-                                            int64_t cs, int64_t width, int64_t n_iter, const corrla_opts* o, T* q,     \
-                                            int64_t ldq) {                                                             \
-    return power_c<T>(ctx, false, a, m, n, rs, cs, width, n_iter, o, q, ldq);                                          \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_matmul_dev_##SUF(corrla_ctx* ctx, int trans, const T* a, int64_t m, int64_t n, int64_t rs,      \
-                                        int64_t cs, const T* x, int64_t ldx, int64_t l, T beta, T* res,                \
-                                        int64_t ldres) {                                                               \
-    return matmul_c<T>(ctx, trans, a, m, n, rs, cs, x, ldx, l, beta, res, ldres);                                      \
+  CORRLA_DEFINE_RSVD(corrla_rsvd_##SUF, T, true, false)                                                                \
+  CORRLA_DEFINE_RSVD(corrla_rsvd_dev_##SUF, T, false, false)                                                           \
+  CORRLA_DEFINE_RSVD(corrla_rsvd_sharded_dev_##SUF, T, false, true)                                                    \
+  CORRLA_DEFINE_PCA(corrla_pca_##SUF, T, true, false)                                                                  \
+  CORRLA_DEFINE_PCA(corrla_pca_dev_##SUF, T, false, false)                                                             \
+  CORRLA_DEFINE_PCA(corrla_pca_sharded_dev_##SUF, T, false, true)                                                      \
+  CORRLA_DEFINE_POWER(corrla_power_iter_##SUF, T, true)                                                                \
+  CORRLA_DEFINE_POWER(corrla_power_iter_dev_##SUF, T, false)                                                           \
+  CORRLA_API corrla_status corrla_matmul_dev_##SUF(corrla_ctx* ctx, int trans, CORRLA_DENSE(T, a), CORRLA_PRODUCT_REST(T)) { \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                          \
+      matmul_entry<HipDev, T>(c.dev, trans, a, m, n, rs, cs, x, ldx, l, beta, res, ldres, &c.last);                    \
+    });                                                                                                                \
   }                                                                                                                    \
   CORRLA_API corrla_status corrla_fill_normal_dev_##SUF(corrla_ctx* ctx, T* p, int64_t rows, int64_t cols, int64_t rs,            \
                                              int64_t cs, uint64_t seed, int64_t row0, int64_t global_cols) {           \
@@ -271,36 +213,30 @@ CORRLA_DEFINE(f32, float)
 CORRLA_DEFINE(f64, double)
 
 // ---- CSR sparse input (values, int32 column indices, int64 row_ptr) ----------------------------------------------
+#define CORRLA_DEFINE_RSVD_CSR(NAME, T, HOST)                                                                           \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_CSR_A(T), CORRLA_RSVD_REST(T)) {                                \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                           \
+      rsvd_csr_entry<HipDev, T>(c.dev, HOST, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, u, ldu, s, vt,     \
+                                ldvt, &c.last, c.profile);                                                              \
+    });                                                                                                                 \
+  }
+#define CORRLA_DEFINE_PCA_CSR(NAME, T, HOST)                                                                            \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_CSR_A(T), CORRLA_PCA_REST(T)) {                                 \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                           \
+      pca_csr_entry<HipDev, T>(c.dev, HOST, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, means, s, comps,    \
+                               ldc, &c.last, c.profile);                                                                \
+    });                                                                                                                 \
+  }
+
 #define CORRLA_DEFINE_CSR(SUF, T)                                                                                      \
-  CORRLA_API corrla_status corrla_rsvd_csr_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,             \
-                                                 const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,            \
-                                                 int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o, T* u,  \
-                                                 int64_t ldu, T* s, T* vt, int64_t ldvt) {                             \
-    return rsvd_csr_c<T>(ctx, true, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, u, ldu, s, vt, ldvt);     \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_rsvd_csr_dev_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,         \
-                                                     const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,        \
-                                                     int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o,    \
-                                                     T* u, int64_t ldu, T* s, T* vt, int64_t ldvt) {                   \
-    return rsvd_csr_c<T>(ctx, false, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, u, ldu, s, vt, ldvt);    \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_pca_csr_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,              \
-                                                const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,             \
-                                                int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o,         \
-                                                T* means, T* s, T* comps, int64_t ldc) {                               \
-    return pca_csr_c<T>(ctx, true, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, means, s, comps, ldc);     \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_pca_csr_dev_##SUF(corrla_ctx* ctx, const T* values, const int32_t* col_idx,          \
-                                                    const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz,         \
-                                                    int64_t rank, int64_t n_iter, int64_t p, const corrla_opts* o,     \
-                                                    T* means, T* s, T* comps, int64_t ldc) {                           \
-    return pca_csr_c<T>(ctx, false, values, col_idx, row_ptr, m, n, nnz, rank, n_iter, p, o, means, s, comps, ldc);    \
-  }                                                                                                                    \
-  CORRLA_API corrla_status corrla_spmm_csr_dev_##SUF(corrla_ctx* ctx, int trans, const T* values,                      \
-                                                     const int32_t* col_idx, const int64_t* row_ptr, int64_t m,        \
-                                                     int64_t n, int64_t nnz, const T* x, int64_t ldx, int64_t l,       \
-                                                     T beta, T* res, int64_t ldres) {                                  \
-    return spmm_csr_c<T>(ctx, trans, values, col_idx, row_ptr, m, n, nnz, x, ldx, l, beta, res, ldres);                \
+  CORRLA_DEFINE_RSVD_CSR(corrla_rsvd_csr_##SUF, T, true)                                                               \
+  CORRLA_DEFINE_RSVD_CSR(corrla_rsvd_csr_dev_##SUF, T, false)                                                          \
+  CORRLA_DEFINE_PCA_CSR(corrla_pca_csr_##SUF, T, true)                                                                 \
+  CORRLA_DEFINE_PCA_CSR(corrla_pca_csr_dev_##SUF, T, false)                                                            \
+  CORRLA_API corrla_status corrla_spmm_csr_dev_##SUF(corrla_ctx* ctx, int trans, CORRLA_CSR_A(T), CORRLA_PRODUCT_REST(T)) { \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                          \
+      spmm_entry<HipDev, T>(c.dev, trans, values, col_idx, row_ptr, m, n, nnz, x, ldx, l, beta, res, ldres);           \
+    });                                                                                                                \
   }
 
 CORRLA_DEFINE_CSR(f32, float)

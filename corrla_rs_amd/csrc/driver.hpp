@@ -1062,7 +1062,7 @@ inline void small_svd_host(Dev& dev, const Skinny<T>& cd, int64_t l, int64_t k, 
 
 // ---- argument handling shared by the C ABI of the product and of the test emulation --------
 struct Layout {
-  bool fat;        // m < n (strict, random_svd.rs:71): work on A^T
+  bool fat;        // m < n (strict, random_svd.rs:71) and not forced tall: work on A^T
   bool row_major;  // the TALL view is row-major in memory
   bool needs_pack; // neither stride is 1, or vector alignment not met: repack first
   int64_t mt, nt, ld;
@@ -1077,9 +1077,11 @@ inline void validate_matrix(const void* a, int64_t m, int64_t n, int64_t rs, int
 }
 
 // Classify a (m, n, rs, cs) strided matrix into the tall row-/column-major views the kernels take.
-inline Layout classify(int64_t m, int64_t n, int64_t rs, int64_t cs) {
+// force_tall (sharded blocks, power_iter, the product hooks): the matrix is taken as given, never transposed
+// (random_svd.rs:15-59), whatever its shape.
+inline Layout classify(int64_t m, int64_t n, int64_t rs, int64_t cs, bool force_tall) {
   Layout L;
-  L.fat = m < n;
+  L.fat = !force_tall && m < n;
   L.mt = L.fat ? n : m;
   L.nt = L.fat ? m : n;
   // strides of the tall view

@@ -93,6 +93,60 @@ def test_emu_invalid_arguments():
         emu_rsvd(a, 2, -1, 2)
 
 
+def _layout(base, m, n, order):
+    """The four memory layouts of test_emu_layouts_and_shapes, cut from a (2m, 2n) base."""
+    if order == "C":
+        return np.ascontiguousarray(base[:m, :n])
+    if order == "F":
+        return np.asfortranarray(base[:m, :n])
+    if order == "strided":
+        return base[::2, ::2]
+    return base[:m, ::2]
+
+
+@pytest.mark.parametrize("order", ["C", "F", "strided", "strided_cols"])
+@pytest.mark.parametrize("shape", [(33, 70), (1, 9), (9, 1), (5, 5)])
+def test_emu_forced_tall_layouts(order, shape):
+    """matmul and power_iter never transpose (random_svd.rs:15-59 takes the matrix as given): fat, one-row, one-column
+    and square inputs in every layout go through the forced-tall classification of stage_input."""
+    rng = np.random.default_rng(17)
+    m, n = shape
+    a = _layout(rng.standard_normal((2 * m, 2 * n)), m, n, order)
+    ad = np.array(a)
+    for trans in (False, True):
+        x = rng.standard_normal((m if trans else n, 3))
+        ref = -0.75 * ((ad.T if trans else ad) @ x)
+        assert np.allclose(emu_matmul(a, x, trans, beta=-0.75), ref, rtol=0, atol=1e-12)
+    width = max(1, min(m, n) // 3)
+    om = rng.standard_normal((n, width))
+    for q in (0, 2):
+        qe = emu_power_iter(a, width, q, omega=om)
+        qo = orc.power_iter(ad, om, q)
+        assert qe.shape == (m, width)
+        assert orth_err(qe) < 1e-12
+        assert np.linalg.norm(qe @ qe.T - qo @ qo.T) < 1e-8
+
+
+@pytest.mark.parametrize("call,fragment", [
+    (lambda a: emu_rsvd(a, 0, 1, 2), "rank must be >= 1"),
+    (lambda a: emu_rsvd(a, 5, 1, 2), "rank exceeds min(m, n)"),
+    (lambda a: emu_rsvd(a, 2, -1, 2), "n_iter and n_oversamples must be >= 0"),
+    (lambda a: emu_rsvd(a, 2, 1, 2, bad_ldu=True), "ldu < m"),
+    (lambda a: emu_rsvd(a, 0, 1, 2, bad_ldu=True), "rank must be >= 1"),       # two faults: the rank is reported
+    (lambda a: emu_pca(a, 2, 1, 2, center="both"), "CORRLA_PCA_CENTER_FUSED and CORRLA_PCA_CENTER_COPY are mutually exclusive"),
+    (lambda a: emu_pca(np.ones((1, 1)), 1, 1, 0), "PCA needs at least two samples"),
+    (lambda a: emu_rsvd(a, 5, 1, 2, sharded=True), "rank must be in [1, short side] for the sharded path"),
+    (lambda a: emu_pca(a, 5, 1, 2, sharded=True), "rank must be in [1, n_dim] for the sample-sharded PCA"),
+], ids=["rank0", "rank_gt_min", "n_iter_neg", "bad_ldu", "rank0_and_bad_ldu", "pca_center_both", "pca_one_sample",
+        "sharded_rank_gt_n", "pca_sharded_rank_gt_n"])
+def test_emu_first_failing_check(call, fragment):
+    """Every invalid call ends with CORRLA_EINVAL (the harness raises ValueError for that status alone) and the message
+    of the FIRST check it fails."""
+    with pytest.raises(ValueError) as ei:
+        call(np.ones((6, 4)))
+    assert fragment in str(ei.value)
+
+
 def test_emu_zero_matrix():
     u, s, vt = emu_rsvd(np.zeros((12, 7)), 3, 2, 2, omega=np.ones((7, 5)))
     assert np.all(s == 0) and np.all(np.isfinite(u)) and np.all(np.isfinite(vt))
