@@ -224,28 +224,50 @@ struct RsvdDriver {
   // `rough`: stop after the first clean Cholesky pass -- enough for the in-loop re-orthonormalisations
   // (random_svd.rs:37-39), whose only role is to keep the sketch well conditioned; the span is unchanged.
   static constexpr size_t kStatusBytes = 32;  // one device status record (CholStatus)
-  int st_slots_ = 0;                          // records in the pool of the optimistic run (sized from n_iter)
-  struct Pending {
-    int slot, npass;
-    bool rough;
-    int per_pass;  // status records per pass: 1 (single factorisation) or 2 (2 x 2 blocked)
-    void* st = nullptr;  // scratch status records of a device-robust thin-Q (diagnostics only)
-    int st_per_pass = 1;
-    bool is_svd = false; // the convergence verdict of the core SVD's fixed number of sweeps
-    int flag_slot = -1;  // >= 0: a device-robust Cholesky-QR (orthonormalize_device); clean iff flags[flag_slot + npass - 1] == 0
-  };
   static constexpr int kRobustPasses = 8;  // most passes a device-robust thin-Q enqueues (2 always, the rest conditional)
-  bool robust_needs_more_ = false;         // pending_clean: a device-robust thin-Q ran out of enqueued passes
-  bool svd_needs_more_ = false;            // pending_clean: the core SVD ran out of enqueued sweeps
-  bool svd_needs_v_ = false;               // pending_clean: the core SVD's W-only shortcut failed its verification
-  bool null_cols_seen_ = false;            // pending_clean: some device thin-Q pass re-seeded null columns (rank-deficient sketch)
-  int* flags_pool_ = nullptr;              // device words: need_next of every pass of every robust thin-Q of the call
-  int flags_cap_ = 0, flags_used_ = 0;
-  bool defer_status_ = false;
-  bool optimistic_dirty_ = false;  // a pass of the optimistic run took the host-controlled loop: repeat the call
-  void* st_pool_ = nullptr;
-  int st_used_ = 0;
-  std::vector<Pending> pending_;
+  static constexpr T kPivotTol = (T)(4.0 * (double)std::numeric_limits<T>::epsilon());  // of every device Cholesky
+  // What a stage of an optimistic run leaves to be judged once the last kernel of the call is enqueued (attempt_verdict)
+  struct Pending {
+    enum Kind { kOptimisticChol, kRobustChol, kCoreSvd } kind;
+    int npass = 1;  // passes enqueued (both Cholesky kinds)
+    // kOptimisticChol: pool records [first_record, first_record + npass * records_per_pass), 1 record per pass (single
+    // factorisation) or 2 (2 x 2 blocked); all must be clean and, with verify_near_identity, the Gram of the last pass
+    // within 0.25 of I
+    int first_record = 0, records_per_pass = 1;
+    bool verify_near_identity = false;
+    // kRobustChol (orthonormalize_device): `always` passes ran unconditionally, pass i >= always ran iff
+    // flags[flag_slot + i - 1] != 0; clean iff flags[flag_slot + npass - 1] == 0.  flag_slot -1: best effort, not verified
+    int always = 0, flag_slot = -1;
+    void* st = nullptr;  // its scratch status records, st_per_pass of them per pass (diagnostics only)
+    int st_per_pass = 1;
+    int record = 0;  // kCoreSvd: pool record with the convergence verdict of the core SVD's fixed number of sweeps
+    static Pending optimistic_chol(int first_record, int npass, int records_per_pass, bool verify_near_identity) {
+      Pending p{kOptimisticChol, npass};
+      p.first_record = first_record, p.records_per_pass = records_per_pass, p.verify_near_identity = verify_near_identity;
+      return p;
+    }
+    static Pending robust_chol(int always, int npass, int flag_slot, void* st, int st_per_pass) {
+      Pending p{kRobustChol, npass};
+      p.always = always, p.flag_slot = flag_slot, p.st = st, p.st_per_pass = st_per_pass;
+      return p;
+    }
+    static Pending core_svd(int record) {
+      Pending p{kCoreSvd};
+      p.record = record;
+      return p;
+    }
+  };
+  // State of one optimistic attempt of a call (random_svd_tall starts every attempt from a fresh one)
+  struct Attempt {
+    bool defer = false;       // the attempt is being enqueued: status goes to the pools below, the host reads nothing back
+    void* st_pool = nullptr;  // device status records (sized from n_iter) ...
+    int st_slots = 0, st_used = 0;
+    int* flags_pool = nullptr;  // ... followed by device words: need_next of every pass of every robust thin-Q of the call
+    int flags_cap = 0, flags_used = 0;
+    std::vector<Pending> pending;
+    bool dirty = false;  // a pass took the host-controlled loop: repeat the call with the host in the loop
+  } att_;
+  void* status_record(int i) const { return (char*)att_.st_pool + (size_t)i * kStatusBytes; }
   // rows of the WHOLE tall matrix (all ranks), fetched lazily by one scalar all-reduce the first time a rank-invariant
   // decision needs it; -1 = unknown.  Unsharded calls use the local row count.
   int64_t m_local_ = 0, m_global_ = -1;
@@ -350,7 +372,7 @@ struct RsvdDriver {
     // leaving zero columns (in-loop, the completion re-seeds directions the next product with A can pick up again).
     // Sharded: every rank must take the same branch (complete_basis issues all-reduces), so the test uses the GLOBAL
     // row count -- the local one differs between uneven shards -- and r itself derives from all-reduced Gram matrices.
-    if (r < l && !defer_status_ && (sharded ? global_rows(true) : y.rows) >= l) r = complete_basis(y, r, sharded);
+    if (r < l && !att_.defer && (sharded ? global_rows(true) : y.rows) >= l) r = complete_basis(y, r, sharded);
     return r;
   }
 
@@ -374,6 +396,63 @@ struct RsvdDriver {
     const int64_t rc = orthonormalize_core(yc, tc, sharded, false);
     dev.copy_cols(yc, y, r, rc);
     return r + rc;
+  }
+
+  // One Cholesky-QR pass: G = Y^T Y into gd (all-reduced when the rows are sharded), R^-1 = factor(gd), Y <- Y R^-1 -- in
+  // place, or into tmp with the two pointers swapped.
+  template <class Factor>
+  void cholqr_pass(Skinny<T>& y, Skinny<T>& tmp, Skinny<T>& gd, bool sharded, bool inplace, Factor&& factor) {
+    const int64_t l = y.cols;
+    Skinny<T> yv = y.view_cols(l);
+    dev.gemm_nn(as_rowmajor_transposed(y, l), yv, gd, kNone);
+    if (sharded) dev.allreduce(gd.p, (size_t)gd.ld * (size_t)gd.cols_alloc);  // unconditional: ranks stay in step
+    const Skinny<T> md = factor(gd);
+    if (inplace) {
+      dev.apply_inplace(y, l, md);
+    } else {
+      dev.gemm_tn(as_rowmajor_transposed(y, l), md, tmp, kNone);
+      std::swap(y.p, tmp.p);
+    }
+  }
+
+  // Factors wider than one chol_inv_kernel (176 < l <= 352 in f32) are factorised and inverted 2 x 2 blocked on the device:
+  //   G = [G11 G12; G12^T G22],  R11 = chol(G11), R12 = R11^-T G12, R22 = chol(G22 - R12^T R12),
+  //   R^-1 = [X11, -X11 R12 X22; 0, X22]  with X = R^-1 of the diagonal blocks.
+  // `factor(block, n, which, x)` launches the factor-and-invert of diagonal block `which` (0 / 1, n x n) into x: plain
+  // (chol_inv) or robust (chol_inv_robust: a null column is a zero column of X, hence a zero row of R12).
+  struct BlockSplit {
+    int64_t n1 = 0, n2 = 0;
+    T* minus_one = nullptr;  // device scalar
+  };
+  BlockSplit block_split(int64_t l) {
+    BlockSplit s;
+    s.n1 = round_up((l + 1) / 2, (int64_t)4);
+    s.n2 = l - s.n1;
+    s.minus_one = dev.template alloc_scalar<T>(1);
+    dev.fill_const(s.minus_one, (int64_t)1, (T)-1);
+    return s;
+  }
+  template <class Factor>
+  void blocked_factor_inverse(const Skinny<T>& g, const BlockSplit& s, Skinny<T>& md, Factor&& factor) {
+    const int64_t n1 = s.n1, n2 = s.n2;
+    Skinny<T> g11 = dev.template alloc_skinny<T>(n1, n1), g12 = dev.template alloc_skinny<T>(n1, n2);
+    Skinny<T> g22 = dev.template alloc_skinny<T>(n2, n2), x11 = dev.template alloc_skinny<T>(n1, n1);
+    Skinny<T> x22 = dev.template alloc_skinny<T>(n2, n2), r12 = dev.template alloc_skinny<T>(n1, n2);
+    Skinny<T> t22 = dev.template alloc_skinny<T>(n2, n2), t12 = dev.template alloc_skinny<T>(n1, n2);
+    Skinny<T> x12 = dev.template alloc_skinny<T>(n1, n2);
+    dev.copy_block(g, 0, 0, n1, n1, g11, 0, 0);
+    dev.copy_block(g, 0, n1, n1, n2, g12, 0, 0);
+    dev.copy_block(g, n1, n1, n2, n2, g22, 0, 0);
+    factor(g11, n1, 0, x11);
+    dev.gemm_nn(as_rowmajor_transposed(x11, n1), g12, r12, kNone);  // R12 = X11^T G12
+    dev.gemm_nn(as_rowmajor_transposed(r12, n2), r12, t22, kNone);  // R12^T R12
+    dev.sub_inplace(g22, t22);                                      // Schur complement (carries the shift of G22)
+    factor(g22, n2, 1, x22);
+    dev.gemm_tn(as_rowmajor_transposed(r12, n2), x22, t12, kNone);        // R12 X22
+    dev.gemm_tn(as_rowmajor_transposed(x11, n1), t12, x12, s.minus_one);  // -X11 R12 X22
+    dev.copy_block(x11, 0, 0, n1, n1, md, 0, 0);
+    dev.copy_block(x12, 0, 0, n1, n2, md, 0, n1);
+    dev.copy_block(x22, 0, 0, n2, n2, md, n1, n1);
   }
 
   // Thin-Q without the host, whatever the conditioning or rank of the sketch (optimistic runs, l <= 144): iterated
@@ -415,7 +494,7 @@ struct RsvdDriver {
     const int npass_even = level;  // 2, 4, 8
     const int npass = inloop ? (level <= 2 ? 1 : npass_even - 1) : (polish ? (level <= 2 ? 1 : 3) : level);
     const int always = (polish || inloop) ? 1 : 2;
-    int* need = flags_pool_ + flags_used_;
+    int* need = att_.flags_pool + att_.flags_used;
     int* null_mask = dev.alloc_flags((int)l);
     int* need_blk = dev.alloc_flags(2);
     void* st_scratch = dev.alloc_zeroed_bytes((size_t)2 * npass * kStatusBytes);
@@ -439,19 +518,11 @@ struct RsvdDriver {
     // are re-seeded at random like the completion of the host-controlled path (which drops below 1e-2)
     float nullx = 1.f;
     if (const char* e = std::getenv("CORRLA_QR_NULL_EXCESS")) nullx = (float)std::atof(e);  // experiments
-    const int64_t n1 = single ? l : round_up((l + 1) / 2, (int64_t)4), n2 = l - n1;
-    T* minus_one = nullptr;
-    if (!single) {
-      minus_one = dev.template alloc_scalar<T>(1);
-      dev.fill_const(minus_one, (int64_t)1, (T)-1);
-    }
+    const BlockSplit split = single ? BlockSplit{} : block_split(l);
     for (int pass = 0; pass < npass; ++pass) {
       // gate: in place, the pass before; in pairs, the pass before the PAIR
       const int gate = pass < always ? -1 : (inplace ? pass - 1 : always + ((pass - always) / 2) * 2 - 1);
       dev.set_run_if(gate < 0 ? nullptr : need + gate);
-      Skinny<T> yv = y.view_cols(l);
-      dev.gemm_nn(as_rowmajor_transposed(y, l), yv, gd, kNone);
-      if (sharded) dev.allreduce(gd.p, (size_t)gd.ld * (size_t)gd.cols_alloc);  // unconditional: ranks stay in step
       const int shift_mode = polish ? 2 : (pass == 0 ? 1 : 0);
       // in-loop (rough): directions below the level one shifted pass can lift are re-seeded at random, like the
       // completion of the host-controlled path -- the next products with A pull the re-seeded columns back into range(A)
@@ -460,53 +531,33 @@ struct RsvdDriver {
       // crushed again for ever -- and is re-seeded too)
       const float nx = (!polish && pass >= 2) ? nullx : 0.f;
       const float need_ratio = (inloop && pass == 0) ? 1e-2f : 0.f;
-      if (single) {
-        dev.chol_inv_robust(gd, l, (T)(4.0 * eps0), (float)shift_rel, shift_mode, nx, md, st_scratch, pass, need + pass, null_mask,
-                            nullptr, need_ratio);
-      } else {
-        dev.gram_inspect(gd, l, (float)shift_rel, shift_mode, insp);
+      // (not in place: conditional passes come in pairs, so a skipped pair swaps y and tmp twice over untouched data)
+      cholqr_pass(y, tmp, gd, sharded, inplace, [&](Skinny<T>& g) {
+        if (single) {
+          dev.chol_inv_robust(g, l, kPivotTol, (float)shift_rel, shift_mode, nx, md, st_scratch, pass, need + pass, null_mask, nullptr,
+                              need_ratio);
+          return md;
+        }
+        dev.gram_inspect(g, l, (float)shift_rel, shift_mode, insp);
         const void* shp = dev.template inspect_shift_ptr<T>(insp);
-        Skinny<T> g11 = dev.template alloc_skinny<T>(n1, n1), g12 = dev.template alloc_skinny<T>(n1, n2);
-        Skinny<T> g22 = dev.template alloc_skinny<T>(n2, n2), x11 = dev.template alloc_skinny<T>(n1, n1);
-        Skinny<T> x22 = dev.template alloc_skinny<T>(n2, n2), r12 = dev.template alloc_skinny<T>(n1, n2);
-        Skinny<T> t22 = dev.template alloc_skinny<T>(n2, n2), t12 = dev.template alloc_skinny<T>(n1, n2);
-        Skinny<T> x12 = dev.template alloc_skinny<T>(n1, n2);
-        dev.copy_block(gd, 0, 0, n1, n1, g11, 0, 0);
-        dev.copy_block(gd, 0, n1, n1, n2, g12, 0, 0);
-        dev.copy_block(gd, n1, n1, n2, n2, g22, 0, 0);
-        dev.chol_inv_robust(g11, n1, (T)(4.0 * eps0), 0.f, 2, nx, x11, st_scratch, 2 * pass, need_blk, null_mask, shp, need_ratio);
-        dev.gemm_nn(as_rowmajor_transposed(x11, n1), g12, r12, kNone);  // R12 = X11^T G12 (zero rows for null columns)
-        dev.gemm_nn(as_rowmajor_transposed(r12, n2), r12, t22, kNone);  // R12^T R12
-        dev.sub_inplace(g22, t22);                                      // Schur complement (carries the shift of G22)
-        dev.chol_inv_robust(g22, n2, (T)(4.0 * eps0), 0.f, 2, nx, x22, st_scratch, 2 * pass + 1, need_blk + 1, null_mask + n1, shp,
-                            need_ratio);
-        dev.gemm_tn(as_rowmajor_transposed(r12, n2), x22, t12, kNone);      // R12 X22
-        dev.gemm_tn(as_rowmajor_transposed(x11, n1), t12, x12, minus_one);  // -X11 R12 X22
-        dev.copy_block(x11, 0, 0, n1, n1, md, 0, 0);
-        dev.copy_block(x12, 0, 0, n1, n2, md, 0, n1);
-        dev.copy_block(x22, 0, 0, n2, n2, md, n1, n1);
+        blocked_factor_inverse(g, split, md, [&](const Skinny<T>& blk, int64_t n, int which, Skinny<T>& x) {
+          dev.chol_inv_robust(blk, n, kPivotTol, 0.f, 2, nx, x, st_scratch, 2 * pass + which, need_blk + which,
+                              null_mask + which * split.n1, shp, need_ratio);
+        });
         dev.template combine_need<T>(need + pass, need_ratio > 0.f ? nullptr : insp, need_blk, need_blk + 1);
-      }
-      if (inplace) {
-        dev.apply_inplace(y, l, md);
-      } else {
-        dev.gemm_tn(as_rowmajor_transposed(y, l), md, tmp, kNone);
-        std::swap(y.p, tmp.p);  // conditional passes come in pairs: a skipped pair swaps twice over untouched data
-      }
+        return md;
+      });
       // (a re-seeded column needs a following pass to be orthonormalised: none after the last one; in-loop, the next
       // products with A and the next thin-Q take care of it)
-      if (pass + 1 < npass || inloop) dev.refill_null(y, l, null_mask, (uint64_t)(0x9e3779b97f4a7c15ull ^ (uint64_t)(977 * (flags_used_ + pass) + l)));
-      if (pass < always) ++tm.qr_passes;  // the conditional ones are counted when the flags are read (pending_clean)
+      if (pass + 1 < npass || inloop)
+        dev.refill_null(y, l, null_mask, (uint64_t)(0x9e3779b97f4a7c15ull ^ (uint64_t)(977 * (att_.flags_used + pass) + l)));
+      if (pass < always) ++tm.qr_passes;  // the conditional ones are counted when the flags are read (attempt_verdict)
     }
     dev.set_run_if(nullptr);
-    Pending pd{always, npass, rough, 0};
-    pd.st = st_scratch;
-    pd.st_per_pass = single ? 1 : 2;
     // in-loop: only the single pass of a level-2 context is verified (so that the context escalates); with a conditional
     // chain enqueued the in-loop thin-Q is best effort -- it only has to keep the sketch well conditioned
-    pd.flag_slot = (inloop && npass > 1) ? -1 : flags_used_;
-    pending_.push_back(pd);
-    flags_used_ += npass;
+    att_.pending.push_back(Pending::robust_chol(always, npass, (inloop && npass > 1) ? -1 : att_.flags_used, st_scratch, single ? 1 : 2));
+    att_.flags_used += npass;
     subphase(tm.qr_gram_ms, qt0);
     return l;
   }
@@ -516,109 +567,63 @@ struct RsvdDriver {
     int64_t r = l;
     // (sharded: the LOCAL row count says nothing -- and differs between ranks, which must all take the same branch;
     // a matrix with fewer global rows than l ends with need_next still set and repeats on the host-controlled path)
-    if (defer_status_ && (sharded || y.rows >= l) && flags_used_ + kRobustPasses <= flags_cap_ &&
+    if (att_.defer && (sharded || y.rows >= l) && att_.flags_used + kRobustPasses <= att_.flags_cap &&
         dev.template device_qr_robust_fits<T>(l))
       return orthonormalize_device(y, tmp, sharded, rough, polish);
-    if (dev.template device_chol_fits<T>(l)) {
+    // status records per pass: 1 = the factor fits one chol_inv_kernel, 2 = 2 x 2 blocked (blocked_factor_inverse), 0 = neither
+    const int rpp = dev.template device_chol_fits<T>(l) ? 1 : (dev.template device_chol_blocked_fits<T>(l) ? 2 : 0);
+    if (rpp > 0) {
       // Optimistic CholeskyQR2 entirely on the device: [Gram, Cholesky + inverse, apply] x2 are enqueued
-      // back to back and the two status records are read once at the end.  Anything unusual (a failed
+      // back to back and the two status records (blocked: four) are read once at the end.  Anything unusual (a failed
       // pivot, a second Gram that is not near I) falls through to the host-controlled robust loop below,
       // which simply continues from the current Y (every applied factor was non-singular, so the span is
       // unchanged; a failed pass applied the identity).
       PhaseTimer qt0;
-      const int npass = rough ? 1 : 2;
+      const int npass = rough ? 1 : 2, nrec = npass * rpp;
       Skinny<T> gd0 = dev.template alloc_skinny<T>(l, l);
-      Skinny<T> md0 = dev.template alloc_skinny<T>(l, l);
-      const bool defer = defer_status_ && st_used_ + npass <= st_slots_;
-      void* st_dev = defer ? (void*)((char*)st_pool_ + (size_t)st_used_ * kStatusBytes) : dev.alloc_bytes(2 * kStatusBytes);
-      const double eps0 = (double)std::numeric_limits<T>::epsilon();
+      Skinny<T> md0 = rpp == 1 ? dev.template alloc_skinny<T>(l, l) : Skinny<T>{};
+      const bool defer = att_.defer && att_.st_used + nrec <= att_.st_slots;
+      void* st_dev = defer ? status_record(att_.st_used) : dev.alloc_bytes((size_t)2 * rpp * kStatusBytes);
+      const BlockSplit split = rpp == 1 ? BlockSplit{} : block_split(l);
       for (int pass = 0; pass < npass; ++pass) {
-        Skinny<T> yv = y.view_cols(l);
-        dev.gemm_nn(as_rowmajor_transposed(y, l), yv, gd0, kNone);
-        if (sharded) dev.allreduce(gd0.p, (size_t)gd0.ld * (size_t)gd0.cols_alloc);
-        dev.chol_inv(gd0, l, (T)(4.0 * eps0), md0, st_dev, pass);
-        dev.gemm_tn(as_rowmajor_transposed(y, l), md0, tmp, kNone);
-        std::swap(y.p, tmp.p);
+        cholqr_pass(y, tmp, gd0, sharded, /*inplace=*/false, [&](Skinny<T>& g) {
+          if (rpp == 1) {
+            dev.chol_inv(g, l, kPivotTol, md0, st_dev, pass);
+            return md0;
+          }
+          Skinny<T> md = dev.template alloc_skinny<T>(l, l);
+          blocked_factor_inverse(g, split, md, [&](const Skinny<T>& blk, int64_t n, int which, Skinny<T>& x) {
+            dev.chol_inv(blk, n, kPivotTol, x, st_dev, 2 * pass + which);
+          });
+          return md;
+        });
         ++tm.qr_passes;
       }
       if (defer) {
         // verified once at the end of random_svd_tall; a record that is not clean reruns the whole
         // computation through the host-controlled path below
-        pending_.push_back({st_used_, npass, rough, 1});
-        st_used_ += npass;
-        subphase(tm.qr_gram_ms, qt0);
-        return l;
-      }
-      int fail[2] = {0, 0};
-      float min_ratio[2], dev_i[2];
-      dev.read_chol_status(st_dev, npass, fail, min_ratio, dev_i);
-      subphase(tm.qr_gram_ms, qt0);
-      for (int pass = 0; pass < npass; ++pass)
-        if (fail[pass] == 3) throw Error(ST_ENUMERIC, "non-finite Gram matrix in orthonormalisation");
-      if (fail[0] == 2) return 0;  // Y is the zero matrix
-      const bool ok = fail[0] == 0 && (rough || (fail[1] == 0 && dev_i[1] <= 0.25f));
-      if (ok) return l;
-    }
-    if (!dev.template device_chol_fits<T>(l) && dev.template device_chol_blocked_fits<T>(l)) {
-      // 176 < l <= 352: the same optimistic CholeskyQR2, with the factor-and-invert done 2 x 2 blocked on the device:
-      //   G = [G11 G12; G12^T G22],  R11 = chol(G11), R12 = R11^-T G12, R22 = chol(G22 - R12^T R12),
-      //   R^-1 = [X11, -X11 R12 X22; 0, X22]  with X = R^-1 of the diagonal blocks (chol_inv_kernel).
-      PhaseTimer qt0;
-      const int npass = rough ? 1 : 2;
-      const int64_t n1 = round_up((l + 1) / 2, (int64_t)4), n2 = l - n1;
-      Skinny<T> gd0 = dev.template alloc_skinny<T>(l, l);
-      const bool defer = defer_status_ && st_used_ + 2 * npass <= st_slots_;
-      void* st_dev = defer ? (void*)((char*)st_pool_ + (size_t)st_used_ * kStatusBytes) : dev.alloc_bytes(4 * kStatusBytes);
-      const double eps0 = (double)std::numeric_limits<T>::epsilon();
-      T* minus_one = dev.template alloc_scalar<T>(1);
-      dev.fill_const(minus_one, (int64_t)1, (T)-1);
-      for (int pass = 0; pass < npass; ++pass) {
-        Skinny<T> yv = y.view_cols(l);
-        dev.gemm_nn(as_rowmajor_transposed(y, l), yv, gd0, kNone);
-        if (sharded) dev.allreduce(gd0.p, (size_t)gd0.ld * (size_t)gd0.cols_alloc);
-        Skinny<T> g11 = dev.template alloc_skinny<T>(n1, n1), g12 = dev.template alloc_skinny<T>(n1, n2);
-        Skinny<T> g22 = dev.template alloc_skinny<T>(n2, n2), x11 = dev.template alloc_skinny<T>(n1, n1);
-        Skinny<T> x22 = dev.template alloc_skinny<T>(n2, n2), r12 = dev.template alloc_skinny<T>(n1, n2);
-        Skinny<T> t22 = dev.template alloc_skinny<T>(n2, n2), t12 = dev.template alloc_skinny<T>(n1, n2);
-        Skinny<T> x12 = dev.template alloc_skinny<T>(n1, n2), md0 = dev.template alloc_skinny<T>(l, l);
-        dev.copy_block(gd0, 0, 0, n1, n1, g11, 0, 0);
-        dev.copy_block(gd0, 0, n1, n1, n2, g12, 0, 0);
-        dev.copy_block(gd0, n1, n1, n2, n2, g22, 0, 0);
-        dev.chol_inv(g11, n1, (T)(4.0 * eps0), x11, st_dev, 2 * pass);
-        dev.gemm_nn(as_rowmajor_transposed(x11, n1), g12, r12, kNone);  // R12 = X11^T G12
-        dev.gemm_nn(as_rowmajor_transposed(r12, n2), r12, t22, kNone);  // R12^T R12
-        dev.sub_inplace(g22, t22);                                      // Schur complement
-        dev.chol_inv(g22, n2, (T)(4.0 * eps0), x22, st_dev, 2 * pass + 1);
-        dev.gemm_tn(as_rowmajor_transposed(r12, n2), x22, t12, kNone);  // R12 X22
-        dev.gemm_tn(as_rowmajor_transposed(x11, n1), t12, x12, minus_one);  // -X11 R12 X22
-        dev.copy_block(x11, 0, 0, n1, n1, md0, 0, 0);
-        dev.copy_block(x12, 0, 0, n1, n2, md0, 0, n1);
-        dev.copy_block(x22, 0, 0, n2, n2, md0, n1, n1);
-        dev.gemm_tn(as_rowmajor_transposed(y, l), md0, tmp, kNone);
-        std::swap(y.p, tmp.p);
-        ++tm.qr_passes;
-      }
-      if (defer) {
-        pending_.push_back({st_used_, npass, rough, 2});
-        st_used_ += 2 * npass;
+        att_.pending.push_back(Pending::optimistic_chol(att_.st_used, npass, rpp, /*verify_near_identity=*/!rough));
+        att_.st_used += nrec;
         subphase(tm.qr_gram_ms, qt0);
         return l;
       }
       int fail[4] = {0, 0, 0, 0};
       float min_ratio[4], dev_i[4];
-      dev.read_chol_status(st_dev, 2 * npass, fail, min_ratio, dev_i);
+      dev.read_chol_status(st_dev, nrec, fail, min_ratio, dev_i);
       subphase(tm.qr_gram_ms, qt0);
       bool ok = true;
-      for (int i = 0; i < 2 * npass; ++i) {
+      for (int i = 0; i < nrec; ++i) {
         if (fail[i] == 3) throw Error(ST_ENUMERIC, "non-finite Gram matrix in orthonormalisation");
         ok = ok && fail[i] == 0;
       }
-      if (ok && !rough) ok = dev_i[2 * (npass - 1)] <= 0.25f && dev_i[2 * (npass - 1) + 1] <= 0.25f;
+      if (rpp == 1 && fail[0] == 2) return 0;  // Y is the zero matrix
+      // the last pass must have seen a Gram within 0.25 of I (`rough`: one clean pass is enough)
+      for (int i = nrec - rpp; !rough && i < nrec; ++i) ok = ok && dev_i[i] <= 0.25f;
       if (ok) return l;
     }
     // host-controlled from here on: inside an optimistic run its outcome (a rank below l, columns left zero) is not
     // covered by the deferred status records, so the whole call is repeated with the host in the loop
-    if (defer_status_) optimistic_dirty_ = true;
+    if (att_.defer) att_.dirty = true;
     const double eps = (double)std::numeric_limits<T>::epsilon();
     std::vector<double> g((size_t)l * l), mm((size_t)l * l), uu, ss, vv;
     Skinny<T> gd = dev.template alloc_skinny<T>(l, l);
@@ -818,44 +823,43 @@ struct RsvdDriver {
       // non-finite input, ...) repeats the computation with the host in the loop.
       const Timings saved = tm;
       const auto mark = dev.arena_mark();  // a repeated attempt reuses the workspace of the abandoned one
-      for (int attempt = 0; attempt < 5; ++attempt) {
+      bool on_device = true;
+      for (int attempt = 0; attempt < 5 && on_device; ++attempt) {
         if (attempt > 0) dev.arena_rewind(mark);
+        att_ = Attempt{};
         // records: <= 2 per pass x <= 2 passes for each of the max(0, q - 3) in-loop, the final and the B^T thin-Q
-        st_slots_ = (int)std::min<int64_t>(4 * (std::max<int64_t>(0, n_iter - 3) + 2) + 1, 4096);  // + the core SVD's
+        att_.st_slots = (int)std::min<int64_t>(4 * (std::max<int64_t>(0, n_iter - 3) + 2) + 1, 4096);  // + the core SVD's
         // status records and verdict words share one zeroed allocation: ONE device-to-host copy reads both at the end
-        flags_cap_ = kRobustPasses * (int)std::min<int64_t>(std::max<int64_t>(0, n_iter - 3) + 4, 1024);
-        st_pool_ = dev.alloc_zeroed_bytes((size_t)st_slots_ * kStatusBytes + (size_t)flags_cap_ * sizeof(int));
-        st_used_ = 0;
-        flags_pool_ = (int*)((char*)st_pool_ + (size_t)st_slots_ * kStatusBytes);
-        flags_used_ = 0;
-        pending_.clear();
-        optimistic_dirty_ = false;
-        robust_needs_more_ = false;
-        svd_needs_more_ = false;
-        svd_needs_v_ = false;
-        null_cols_seen_ = false;
-        defer_status_ = true;
+        att_.flags_cap = kRobustPasses * (int)std::min<int64_t>(std::max<int64_t>(0, n_iter - 3) + 4, 1024);
+        att_.st_pool = dev.alloc_zeroed_bytes((size_t)att_.st_slots * kStatusBytes + (size_t)att_.flags_cap * sizeof(int));
+        att_.flags_pool = (int*)status_record(att_.st_slots);
+        att_.defer = true;
         try {
           random_svd_tall_body(a, k, l, n_iter, o, u_tall, s_dev, v_tall);
         } catch (...) {
-          defer_status_ = false;
+          att_.defer = false;
           throw;
         }
-        defer_status_ = false;
+        att_.defer = false;
         if (emit) emit();
-        if (pending_clean()) return;
+        const Verdict verdict = attempt_verdict();
+        if (verdict == Verdict::kClean) return;
         tm = saved;
         dev.phase_forget();  // the abandoned run still counts in total_ms, not in the phase slots
-        // a thin-Q that only ran out of enqueued passes: enqueue more from now on (this context) and repeat on the device
-        if (optimistic_dirty_) break;
-        if (robust_needs_more_ && dev.robust_passes() < kRobustPasses) {
-          dev.set_robust_passes(std::min(kRobustPasses, 2 * std::max(2, dev.robust_passes())));
-        } else if (svd_needs_more_ && dev.svd_more_sweeps()) {
-          // the context enqueues more Jacobi sweeps from now on; repeat on the device
-        } else if (svd_needs_v_ && dev.svd_force_v()) {
-          // the context accumulates V in the sweeps from now on; repeat on the device
-        } else {
-          break;
+        switch (verdict) {
+          case Verdict::kMorePasses:
+            // a thin-Q that only ran out of enqueued passes: enqueue more from now on (this context) and repeat on the device
+            on_device = dev.robust_passes() < kRobustPasses;
+            if (on_device) dev.set_robust_passes(std::min(kRobustPasses, 2 * std::max(2, dev.robust_passes())));
+            break;
+          case Verdict::kMoreSweeps:  // the context enqueues more Jacobi sweeps from now on; repeat on the device
+            on_device = dev.svd_more_sweeps();
+            break;
+          case Verdict::kNeedV:  // the context accumulates V in the sweeps from now on; repeat on the device
+            on_device = dev.svd_force_v();
+            break;
+          default:  // kRepeatOnHost
+            on_device = false;
         }
       }
       dev.arena_rewind(mark);
@@ -864,86 +868,83 @@ struct RsvdDriver {
     if (emit) emit();
   }
 
-  bool pending_clean() {
-    if (optimistic_dirty_) return false;
-    if (pending_.empty()) return true;
-    std::vector<int> fail((size_t)st_used_);
-    std::vector<float> min_ratio((size_t)st_used_), dev_i((size_t)st_used_);
-    std::vector<int> flags((size_t)flags_used_);
-    {
-      // one copy (and one synchronisation) for the records and the words: [0, st_used_ records) ... [flags)
-      struct Rec {
-        int fail;
-        float min_ratio, dev_i, gmax;
-        long long clk, wall;
-      };
-      static_assert(sizeof(Rec) == kStatusBytes, "status record layout");
-      const size_t bytes = (size_t)st_slots_ * kStatusBytes + (size_t)flags_used_ * sizeof(int);
-      std::vector<char> host(bytes);
-      dev.read_bytes(st_pool_, bytes, host.data());
-      for (int i = 0; i < st_used_; ++i) {
-        Rec r;
-        std::memcpy(&r, host.data() + (size_t)i * kStatusBytes, sizeof(r));
-        fail[(size_t)i] = r.fail;
-        min_ratio[(size_t)i] = r.min_ratio;
-        dev_i[(size_t)i] = r.dev_i;
-      }
-      if (flags_used_ > 0) std::memcpy(flags.data(), host.data() + (size_t)st_slots_ * kStatusBytes, (size_t)flags_used_ * sizeof(int));
-    }
+  // ---- the verdict of an optimistic attempt: one copy (and one synchronisation) brings back the status records and the
+  // need_next words; a non-finite input throws, then the pending records are judged in enqueue order and the first one
+  // that is not clean decides how the call is repeated ----
+  enum class Verdict { kClean, kRepeatOnHost, kMorePasses, kMoreSweeps, kNeedV };
+  struct StatusRecord {  // host view of the device's CholStatus
+    int fail;
+    float min_ratio, dev_i, gmax;
+    long long clk, wall;
+  };
+  static_assert(sizeof(StatusRecord) == kStatusBytes, "status record layout");
+  static void debug_record(int i, const char* what, const StatusRecord& r) {
+    if (std::getenv("CORRLA_DEBUG"))
+      std::fprintf(stderr, "[corrla] status record %d (%s): fail %d min_ratio %.3g dev_i %.3g\n", i, what, r.fail, r.min_ratio, r.dev_i);
+  }
+  Verdict attempt_verdict() {
+    const Attempt& at = att_;
+    if (at.dirty) return Verdict::kRepeatOnHost;
+    if (at.pending.empty()) return Verdict::kClean;
+    // pool layout: [0, st_used records) ... [st_slots records) [flags_used words)
+    const size_t words_at = (size_t)at.st_slots * kStatusBytes;
+    std::vector<char> host(words_at + (size_t)at.flags_used * sizeof(int));
+    dev.read_bytes(at.st_pool, host.size(), host.data());
+    std::vector<StatusRecord> rec((size_t)at.st_used);
+    std::vector<int> flags((size_t)at.flags_used);
+    if (!rec.empty()) std::memcpy(rec.data(), host.data(), rec.size() * sizeof(StatusRecord));
+    if (!flags.empty()) std::memcpy(flags.data(), host.data() + words_at, flags.size() * sizeof(int));
     // a non-finite Gram matrix or core is an error of the INPUT: nothing to escalate, nothing to repeat
-    for (int i = 0; i < flags_used_; ++i) {
-      if (flags[(size_t)i] & kFlagNonFinite) throw Error(ST_ENUMERIC, "non-finite Gram matrix in orthonormalisation");
-      if (flags[(size_t)i] & kFlagNullCols) null_cols_seen_ = true;
+    for (int f : flags)
+      if (f & kFlagNonFinite) throw Error(ST_ENUMERIC, "non-finite Gram matrix in orthonormalisation");
+    for (const Pending& p : at.pending) {
+      for (int i = 0; p.kind == Pending::kOptimisticChol && i < p.npass * p.records_per_pass; ++i)
+        if (rec[(size_t)(p.first_record + i)].fail == 3) throw Error(ST_ENUMERIC, "non-finite Gram matrix in orthonormalisation");
+      if (p.kind == Pending::kCoreSvd && rec[(size_t)p.record].fail == 3) throw Error(ST_ENUMERIC, "non-finite core matrix in small SVD");
     }
-    for (const Pending& p : pending_)
-      if (p.flag_slot < 0 && p.per_pass > 0)
-        for (int i = 0; i < (p.is_svd ? 1 : p.npass * p.per_pass); ++i)
-          if (fail[(size_t)p.slot + i] == 3)
-            throw Error(ST_ENUMERIC, p.is_svd ? "non-finite core matrix in small SVD" : "non-finite Gram matrix in orthonormalisation");
-    for (const Pending& p : pending_) {
-      if (p.flag_slot >= 0) {  // device-robust thin-Q: its last enqueued pass must not ask for another one
-        // (p.slot = number of unconditional passes; conditional pass i ran iff pass i - 1 asked for it)
-        for (int i = p.slot; i < p.npass; ++i)
-          if (flags[(size_t)p.flag_slot + i - 1] != 0) ++tm.qr_passes;
-        if (std::getenv("CORRLA_DEBUG")) {
-          std::fprintf(stderr, "[corrla] device thin-Q: %d passes enqueued, need_next =", p.npass);
-          for (int i = 0; i < p.npass; ++i) std::fprintf(stderr, " %d", flags[(size_t)p.flag_slot + i]);
-          const int nrec = p.npass * p.st_per_pass;
-          std::vector<int> f2((size_t)nrec);
-          std::vector<float> mr((size_t)nrec), di((size_t)nrec);
-          dev.read_chol_status(p.st, nrec, f2.data(), mr.data(), di.data());
-          std::fprintf(stderr, "; ||G - I||_max / min pivot ratio per factorisation:");
-          for (int i = 0; i < nrec; ++i) std::fprintf(stderr, " %.2g/%.2g", di[(size_t)i], mr[(size_t)i]);
-          std::fprintf(stderr, "\n");
-        }
-        if (flags[(size_t)p.flag_slot + p.npass - 1] != 0) {
-          robust_needs_more_ = true;
-          return false;
-        }
-        continue;
-      }
-      if (p.rough && p.per_pass == 0) continue;  // one shifted pass in-loop: nothing to verify
-      if (std::getenv("CORRLA_DEBUG") && p.flag_slot < 0 && p.per_pass > 0)
-        std::fprintf(stderr, "[corrla] status record %d (%s): fail %d min_ratio %.3g dev_i %.3g\n", p.slot, p.is_svd ? "core SVD" : "Cholesky",
-                     fail[(size_t)p.slot], min_ratio[(size_t)p.slot], dev_i[(size_t)p.slot]);
-      if (p.is_svd) {
-        if (fail[(size_t)p.slot] == 0) dev.svd_sweeps_used((int)dev_i[(size_t)p.slot]);
-        if (fail[(size_t)p.slot] == 1) {  // not converged within the sweeps that were enqueued
-          svd_needs_more_ = true;
-          return false;
-        }
-        if (fail[(size_t)p.slot] == 4) {  // the W-only shortcut was not valid for this core: accumulate V from now on
-          svd_needs_v_ = true;
-          return false;
-        }
-      }
-      for (int i = 0; i < p.npass * p.per_pass; ++i)
-        if (fail[p.slot + i] != 0) return false;
-      if (!p.rough)
-        for (int i = 0; i < p.per_pass; ++i)
-          if (!(dev_i[p.slot + (p.npass - 1) * p.per_pass + i] <= 0.25f)) return false;
+    for (const Pending& p : at.pending) {
+      const Verdict v = p.kind == Pending::kRobustChol ? judge_robust_chol(p, flags.data())
+                        : p.kind == Pending::kCoreSvd  ? judge_core_svd(p, rec[(size_t)p.record])
+                                                       : judge_optimistic_chol(p, &rec[(size_t)p.first_record]);
+      if (v != Verdict::kClean) return v;
     }
-    return true;
+    return Verdict::kClean;
+  }
+  // every record clean and, unless the thin-Q was a rough one, the Gram of the last pass within 0.25 of I
+  Verdict judge_optimistic_chol(const Pending& p, const StatusRecord* r) {
+    debug_record(p.first_record, "Cholesky", r[0]);
+    const int nrec = p.npass * p.records_per_pass;
+    for (int i = 0; i < nrec; ++i)
+      if (r[i].fail != 0) return Verdict::kRepeatOnHost;
+    for (int i = nrec - p.records_per_pass; p.verify_near_identity && i < nrec; ++i)
+      if (!(r[i].dev_i <= 0.25f)) return Verdict::kRepeatOnHost;
+    return Verdict::kClean;
+  }
+  // device-robust thin-Q: its last enqueued pass must not ask for another one
+  Verdict judge_robust_chol(const Pending& p, const int* flags) {
+    if (p.flag_slot < 0) return Verdict::kClean;  // in-loop behind a conditional chain: best effort, nothing to verify
+    const int* need = flags + p.flag_slot;
+    for (int i = p.always; i < p.npass; ++i)
+      if (need[i - 1] != 0) ++tm.qr_passes;  // conditional pass i ran iff pass i - 1 asked for it
+    if (std::getenv("CORRLA_DEBUG")) {
+      std::fprintf(stderr, "[corrla] device thin-Q: %d passes enqueued, need_next =", p.npass);
+      for (int i = 0; i < p.npass; ++i) std::fprintf(stderr, " %d", need[i]);
+      const int nrec = p.npass * p.st_per_pass;
+      std::vector<int> f2((size_t)nrec);
+      std::vector<float> mr((size_t)nrec), di((size_t)nrec);
+      dev.read_chol_status(p.st, nrec, f2.data(), mr.data(), di.data());
+      std::fprintf(stderr, "; ||G - I||_max / min pivot ratio per factorisation:");
+      for (int i = 0; i < nrec; ++i) std::fprintf(stderr, " %.2g/%.2g", di[(size_t)i], mr[(size_t)i]);
+      std::fprintf(stderr, "\n");
+    }
+    return need[p.npass - 1] != 0 ? Verdict::kMorePasses : Verdict::kClean;
+  }
+  Verdict judge_core_svd(const Pending& p, const StatusRecord& r) {
+    debug_record(p.record, "core SVD", r);
+    if (r.fail == 0) dev.svd_sweeps_used((int)r.dev_i);
+    if (r.fail == 1) return Verdict::kMoreSweeps;  // not converged within the sweeps that were enqueued
+    if (r.fail == 4) return Verdict::kNeedV;  // the W-only shortcut was not valid for this core: accumulate V from now on
+    return r.fail == 0 ? Verdict::kClean : Verdict::kRepeatOnHost;
   }
 
   void random_svd_tall_body(const TallA<T>& a, int64_t k, int64_t l, int64_t n_iter, const RunOpts& o, Skinny<T>& u_tall,
@@ -980,16 +981,14 @@ struct RsvdDriver {
     Skinny<T> m1 = dev.template alloc_skinny<T>(l, k);  // U~[:, :k] = Vc[:, :k]
     Skinny<T> m2 = dev.template alloc_skinny<T>(l, k);  // Uc[:, :k]
     void* svd_st = nullptr;
-    if (defer_status_ && st_used_ + 1 <= st_slots_) {
+    if (att_.defer && att_.st_used + 1 <= att_.st_slots) {
       // kernels that run a fixed number of sweeps report convergence here; checked with the Cholesky records
-      svd_st = (void*)((char*)st_pool_ + (size_t)st_used_ * kStatusBytes);
-      pending_.push_back({st_used_, 1, true, 1});
-      pending_.back().is_svd = true;
-      st_used_ += 1;
+      svd_st = status_record(att_.st_used);
+      att_.pending.push_back(Pending::core_svd(att_.st_used));
+      att_.st_used += 1;
     }
     dev.small_svd(ct, l, k, m2, m1, s_dev, svd_st);
-    int64_t nz_known = k;
-    if (defer_status_) {
+    if (att_.defer) {
       // One-sided Jacobi leaves the W / sigma factor (here m1 = U~) orthonormal only to the size of the last
       // rotations it skipped, which for clustered singular values is far above eps (6e-5 in f32 for the top 74 values
       // of a 1.25e6 x 512 Gaussian matrix).  One Cholesky-QR pass restores it to working precision: R is I + O(1e-4), so the
@@ -998,7 +997,7 @@ struct RsvdDriver {
       Skinny<T> m1b = dev.template alloc_skinny<T>(l, k);
       orthonormalize_core(m1, m1b, false, /*rough=*/true, /*polish=*/true);
     }
-    if (!defer_status_) {
+    if (!att_.defer) {
       // Exactly singular core (rank-deficient or zero input; only reachable through the host-controlled path): the
       // vectors w_j / sigma_j of its null triplets (here: columns of Vc, the Jacobi runs on C^T) do not exist.  Give
       // them an orthonormal completion, like the arbitrary-but-orthonormal null vectors of the reference's full SVD.
@@ -1010,13 +1009,11 @@ struct RsvdDriver {
       int64_t nz = 0;
       while (nz < k && sh[(size_t)nz] > null_tol) ++nz;
       if (nz < k) complete_basis(m1, nz, false);
-      nz_known = nz;
       if (nz == k) {
         Skinny<T> m1b = dev.template alloc_skinny<T>(l, k);
         orthonormalize_core(m1, m1b, false, /*rough=*/true);
       }
     }
-    (void)nz_known;
     phase(tm.small_svd_ms, pt);
     // V = Qb * Uc[:, :k]
     dev.gemm_tn(as_rowmajor_transposed(qb, l), m2, v_tall, kNone);

@@ -1763,7 +1763,7 @@ __global__ void combine_need_kernel(int* need, const GramInspect<T>* insp, const
   if (run_if && *run_if == 0) return;
   // insp == nullptr (the single pass of an in-loop thin-Q): the verdict is that of the two block factorisations alone
   // bit 0: another pass is needed; bit 1 (kNeedNonFinite): a non-finite Gram; bit 2 (kNeedNullCols): null columns were
-  // re-seeded -- the host reads the words once at the end of the call (driver.hpp: pending_clean)
+  // re-seeded -- the host reads the words once at the end of the call (driver.hpp: attempt_verdict)
   const int sub = *na | *nb;
   const int bad = (insp && insp->bad) ? kNeedNonFinite : 0;
   const int need1 = ((insp && (insp->shifted || insp->bad || insp->d2 > 0.05f)) || sub) ? 1 : 0;

@@ -318,6 +318,48 @@ def test_emu_blocked_cholesky_qr_for_wide_sketches(l):
     assert np.max(np.abs(u.T @ u - np.eye(k))) < 1e-10
 
 
+def _thin_q_route_input(dtype, l, spectrum):
+    """(l + 40) x l input whose sketch of width l spans its whole range, so S must match numpy's SVD to rounding."""
+    rng = np.random.default_rng(l)
+    m, n = l + 40, l
+    if spectrum == "flat":
+        a = rng.standard_normal((m, n))
+    else:
+        u, _ = np.linalg.qr(rng.standard_normal((m, n)))
+        v, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        a = (u * 0.7 ** np.arange(n)) @ v.T
+    return a.astype(dtype), rng.standard_normal((n, l)).astype(dtype)
+
+
+# (dtype, l, spectrum, qr_passes).  The widths straddle every switch of the thin-Q: the blocked floor (9), products in place
+# or conditional passes in pairs (144 | 145), one factor kernel or the 2 x 2 blocked form (f32 176 | 177, f64 152 | 153).
+# qr_passes as measured on commit 50e5020 (the parent of the thin-Q refactor), every row.
+_THIN_Q_ROUTES = [
+    (np.float32, 9, "flat", 5), (np.float32, 9, "decay", 5),
+    (np.float32, 144, "flat", 6), (np.float32, 144, "decay", 12),
+    (np.float32, 145, "flat", 6), (np.float32, 145, "decay", 12),
+    (np.float32, 176, "flat", 6), (np.float32, 176, "decay", 12),
+    (np.float32, 177, "flat", 6), (np.float32, 177, "decay", 13),
+    (np.float64, 152, "flat", 5), (np.float64, 152, "decay", 9),
+    (np.float64, 153, "flat", 5), (np.float64, 153, "decay", 9),
+]
+
+
+@pytest.mark.parametrize("dtype,l,spectrum,passes", _THIN_Q_ROUTES)
+def test_emu_thin_q_route_and_cost_per_width(dtype, l, spectrum, passes):
+    """Pins the route (through its cost, qr_passes) and the result of the thin-Q at every width where it switches."""
+    a, om = _thin_q_route_input(dtype, l, spectrum)
+    k = l - 2
+    # (no power iterations: they would put the small singular values of these inputs below the rounding level of the sketch)
+    u, s, vt, got = emu_rsvd(a, k, 0, 2, omega=om, return_passes=True)
+    assert got == passes
+    tol = 1e-10 if dtype == np.float64 else 2e-4
+    assert np.max(np.abs(u.T.astype(np.float64) @ u - np.eye(k))) < tol
+    assert np.max(np.abs(vt.astype(np.float64) @ vt.T - np.eye(k))) < tol
+    ex = np.linalg.svd(a.astype(np.float64), compute_uv=False)[:k]
+    assert np.allclose(s.ravel(), ex, atol=(1e-9 if dtype == np.float64 else 2e-4) * max(ex[0], 1.0))
+
+
 # ---- Householder TSQR thin-Q (CORRLA_QR_HOUSEHOLDER): same panel partition / pairwise tree / reverse application as
 # csrc/tsqr_kernels.hpp, run by the emulation backend through the real driver --------------------------------------
 @pytest.mark.parametrize("m,n,width", [(40, 12, 12), (700, 30, 17), (1301, 64, 40), (97, 48, 48), (5000, 20, 9)])

@@ -75,6 +75,34 @@ def test_non_finite_core_is_an_error_in_every_svd_kernel_family(ctx, monkeypatch
     assert np.max(np.abs(s.ravel().astype(np.float64) - so.ravel())) <= (3e-5 if dtype == np.float32 else 1e-10) * so[0, 0]
 
 
+# ---- the two thin-Q widths beyond the l = 138 rows above, at the smallest shapes that reach them: l = 145 (two column
+# blocks: products out of place, conditional passes in pairs) and l = 177 (2 x 2 blocked robust factor); the decaying
+# spectrum makes the context escalate to the conditional passes.  Same assertions as the clean half of the test above.
+# No power iterations: they raise the condition number of the sketch to (sigma_1 / sigma_l)^(2q + 1), which for 0.7^i
+# leaves f32 a dozen directions above its rounding level while the f64 oracle keeps them all -- S against the oracle
+# would then measure f32 against f64, not the thin-Q; at q = 0 what f32 loses lies below eps * cond(Omega) * sigma_1.
+@pytest.mark.parametrize("spectrum", ["flat", "decay"])
+@pytest.mark.parametrize("l,n", [(145, 256), (177, 320)])
+def test_thin_q_paired_passes_and_blocked_robust_factor(l, n, spectrum):
+    import corrla_rs_amd as cr
+    rng = np.random.default_rng(l)
+    m = 2048
+    if spectrum == "flat":
+        a = rng.standard_normal((m, n))
+    else:
+        qu, _ = np.linalg.qr(rng.standard_normal((m, n)))
+        qv, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        a = (qu * 0.7 ** np.arange(n)) @ qv.T
+    a = a.astype(np.float32)
+    p = 8
+    k = l - p
+    om = rng.standard_normal((n, l)).astype(np.float32)
+    u, s, vt = cr.Context(0).rsvd(a, k, 0, p, omega=om)  # a fresh context: two unconditional passes enqueued, no more
+    uo, so, vto = orc.random_svd(a, k, 0, p, omega=om)
+    assert np.all(np.isfinite(u)) and np.all(np.isfinite(s)) and np.all(np.isfinite(vt))
+    assert np.max(np.abs(s.ravel().astype(np.float64) - so.ravel())) <= 3e-5 * so[0, 0]
+
+
 # ---- sketches wider than the device Cholesky serves (l > 352): the host-controlled thin-Q, block / host core SVD ------
 # random_svd.rs:76-77 puts no limit on l = min(rank + p, n); rank 512 of a few-thousand-column matrix is an ordinary call
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
