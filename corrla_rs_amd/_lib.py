@@ -31,7 +31,7 @@ class Timings(C.Structure):
     _fields_ = [("total_ms", dbl), ("sketch_ms", dbl), ("power_ms", dbl), ("qr_ms", dbl), ("project_ms", dbl),
                 ("small_svd_ms", dbl), ("finalize_ms", dbl), ("qr_passes", i32), ("n_collectives", i32),
                 ("sketch_kernel_ms", dbl), ("host_enqueue_ms", dbl), ("collective_bytes", dbl), ("n_mixed_products", i32),
-                ("reserved_", i32), ("knn_ms", dbl), ("fit_ms", dbl)]
+                ("n_bf16_products", i32), ("knn_ms", dbl), ("fit_ms", dbl)]
 
 
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
@@ -73,6 +73,10 @@ def _sigs():
         s["corrla_fill_normal_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])
+    # dense bf16 input: A is uint16 bit patterns, every other array f32; argument lists of the f32 twins
+    s["corrla_rsvd_bf16"] = s["corrla_rsvd_dev_bf16"] = s["corrla_rsvd_f32"]
+    s["corrla_pca_bf16"] = s["corrla_pca_dev_bf16"] = s["corrla_pca_f32"]
+    s["corrla_matmul_dev_bf16"] = s["corrla_matmul_dev_f32"]
     grad = [vp, vp, i64, i64, vp, vp, i64, C.c_int, i64, dbl, vp, i64, C.POINTER(C.c_int)]
     s["corrla_grad_mat_f64"] = (C.c_int, grad)
     s["corrla_grad_mat_dev_f64"] = (C.c_int, grad)

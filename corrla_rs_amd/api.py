@@ -10,7 +10,8 @@ column, not 1-D -- and Vt (k, n), column-major in memory like the reference's ow
 `ctx`.  numpy inputs take the host-pointer entry points (H2D + D2H around the device path); torch
 CUDA tensors take the device-pointer entry points and return torch tensors on the same device.
 float32 input runs the f32 path (the pyo3 surface is f64-only; anything that is not f32 is
-converted to f64, as PyReadonlyArray2<f64> extraction would require).
+converted to f64, as PyReadonlyArray2<f64> extraction would require).  torch.bfloat16 tensors are the
+exception: they stay as they are and take the corrla_*_bf16 entries (float32 results; see _as_dense).
 """
 import atexit
 import ctypes as C
@@ -116,8 +117,30 @@ def _as_csr(x):
 
 
 def _suffix(dtype):
-    """Symbol suffix of a numpy or torch dtype (inputs are float32 or float64 by the time they get here)."""
-    return "f32" if str(dtype).endswith("float32") else "f64"
+    """Symbol suffix of a numpy or torch dtype (inputs are float32, float64 or torch.bfloat16 by the time they get here)."""
+    name = str(dtype)
+    if name.endswith("bfloat16"):
+        return "bf16"
+    return "f32" if name.endswith("float32") else "f64"
+
+
+def _is_bf16(x):
+    return _is_torch(x) and str(x.dtype) == "torch.bfloat16"
+
+
+def _reject_bf16(x, what):
+    """Surfaces without a bf16 entry say so: widening silently would quadruple the caller's memory behind their back."""
+    if _is_bf16(x):
+        raise ValueError(f"{what} has no bfloat16 entry: pass .float() (or use rsvd / pca, which take bfloat16 tensors)")
+
+
+def _f32_like(a):
+    """An empty float32 array of the kind and device of `a`: what the outputs of a bf16 call are modelled on.  A CPU
+    tensor gives numpy outputs, as every host input does."""
+    if _is_torch(a) and a.is_cuda:
+        import torch
+        return torch.empty(0, dtype=torch.float32, device=a.device)
+    return np.empty(0, dtype=np.float32)
 
 
 def _ptr(t):
@@ -132,7 +155,13 @@ def _c_args(operand):
 
 def _as_dense(x, what):
     """The one normaliser of dense inputs -> (array, on_device): a torch CUDA tensor stays on its device, everything else
-    becomes a numpy array without negative strides (torch has none).  float32 stays float32, the rest becomes float64."""
+    becomes a numpy array without negative strides (torch has none).  float32 stays float32, the rest becomes float64.
+    A torch.bfloat16 tensor is kept as it is, never widened here: on its device for a CUDA tensor, as the CPU tensor
+    (numpy has no bfloat16) for the host entries."""
+    if _is_bf16(x):
+        if x.dim() != 2:
+            raise ValueError(f"{what} must be 2-D")
+        return x.detach(), bool(x.is_cuda)
     if _is_torch(x) and x.is_cuda:
         import torch
         if x.dim() != 2:
@@ -304,9 +333,10 @@ class Context:
     def _entry(self, stem, on_device, dtype):
         return getattr(self._lib, stem + ("dev_" if on_device else "") + _suffix(dtype))
 
-    def _run_rsvd(self, stem, operand, m, n, nt, like, on_device, k, q, p, seed, omega, flags):
-        """The one caller of the rsvd entries `stem`[dev_]{f32,f64}: `operand` describes the m x n matrix (its arrays and
-        integer arguments, see _c_args), `like` an array of the kind, dtype and device the outputs take.
+    def _run_rsvd(self, stem, operand, m, n, nt, like, on_device, k, q, p, seed, omega, flags, in_dtype=None):
+        """The one caller of the rsvd entries `stem`[dev_]{f32,f64,bf16}: `operand` describes the m x n matrix (its arrays
+        and integer arguments, see _c_args), `like` an array of the kind, dtype and device the outputs and Omega take,
+        `in_dtype` the operand's dtype where it differs from theirs (bf16 input: float32 outputs).
         -> (U (m, k), S (k, 1), Vt (k, n))"""
         l = min(k + max(p, 0), nt)
         o, keep = self._opts(seed, omega, nt, l, like.dtype, on_device, flags)
@@ -314,12 +344,13 @@ class Context:
         u, s, vt = (_empty_colmajor(like, *shape) for shape in ((m, kk), (kk, 1), (kk, n)))
         if on_device:
             _sync_stream(like)  # after _opts: the device copy of omega is made on torch's stream too
-        L.check(self._entry(stem, on_device, like.dtype)(self._h, *_c_args(operand), k, q, p, C.byref(o) if o is not None else None,
-                                                         _ptr(u), m, _ptr(s), _ptr(vt), kk))
+        L.check(self._entry(stem, on_device, in_dtype or like.dtype)(self._h, *_c_args(operand), k, q, p,
+                                                                     C.byref(o) if o is not None else None,
+                                                                     _ptr(u), m, _ptr(s), _ptr(vt), kk))
         del keep
         return u, s, vt
 
-    def _run_pca(self, stem, operand, m, n, nt, like, on_device, rank, n_iter, n_oversamples, seed, omega, flags):
+    def _run_pca(self, stem, operand, m, n, nt, like, on_device, rank, n_iter, n_oversamples, seed, omega, flags, in_dtype=None):
         """The same for the PCA entries.  -> (means (1, n), S (k, 1), components (k, n)); n_iter / n_oversamples default as
         in pca_rsvd.rs:65-66."""
         q = 20 if n_iter is None else int(n_iter)
@@ -330,8 +361,9 @@ class Context:
         means, s, comps = (_empty_colmajor(like, *shape) for shape in ((1, n), (kk, 1), (kk, n)))
         if on_device:
             _sync_stream(like)  # after _opts, as in _run_rsvd
-        L.check(self._entry(stem, on_device, like.dtype)(self._h, *_c_args(operand), rank, q, p, C.byref(o) if o is not None else None,
-                                                         _ptr(means), _ptr(s), _ptr(comps), kk))
+        L.check(self._entry(stem, on_device, in_dtype or like.dtype)(self._h, *_c_args(operand), rank, q, p,
+                                                                     C.byref(o) if o is not None else None,
+                                                                     _ptr(means), _ptr(s), _ptr(comps), kk))
         del keep
         return means, s, comps
 
@@ -346,6 +378,8 @@ class Context:
         return self._rsvd_dense(a_mat, k, q, p, seed, omega, qr=qr, fused=fused, mixed=mixed)
 
     def _rsvd_dense(self, a_mat, k, q, p, seed, omega, sharded=False, qr=None, fused=False, shard_cols=False, mixed=None):
+        if sharded:
+            _reject_bf16(a_mat, "rsvd_sharded")
         a, on_dev = _as_dense(a_mat, "a_mat")
         if on_dev:
             self._on_my_device(a)
@@ -360,6 +394,9 @@ class Context:
         rs, cs = (max(n, 1), 1) if empty_shard else _strides(a)
         nt = (m if shard_cols else n) if sharded else min(m, n)
         flags = self._qr_flag(qr) | (L.POWER_FUSED if fused else 0) | (L.SHARD_COLS if shard_cols else 0) | self._mixed_flag(mixed)
+        if _is_bf16(a):  # float32 outputs and Omega; fused / mixed have no bf16-input kernels and are ignored
+            return self._run_rsvd("corrla_rsvd_", (a, m, n, rs, cs), m, n, nt, _f32_like(a), on_dev, k, q, p, seed, omega, flags,
+                                  in_dtype=a.dtype)
         return self._run_rsvd("corrla_rsvd_sharded_" if sharded else "corrla_rsvd_", (a, m, n, rs, cs), m, n, nt, a, on_dev,
                               k, q, p, seed, omega, flags)
 
@@ -377,14 +414,22 @@ class Context:
     # ---- PCA caller (pca_rsvd.rs:56-82) ---------------------------------------------------
     def _pca_dense(self, x_mat, rank, n_iter, n_oversamples, seed, omega, center, sharded):
         cflags = {None: 0, "fused": L.PCA_CENTER_FUSED, "copy": L.PCA_CENTER_COPY}[center]
+        if sharded:
+            _reject_bf16(x_mat, "pca_sharded")
         x, on_dev = _as_dense(x_mat, "x_mat")
         m, n = x.shape
+        if _is_bf16(x):
+            if on_dev:
+                self._on_my_device(x)
+            return self._run_pca("corrla_pca_", (x, m, n, *_strides(x)), m, n, min(m, n), _f32_like(x), on_dev, int(rank), n_iter,
+                                 n_oversamples, seed, omega, cflags, in_dtype=x.dtype)
         return self._run_pca("corrla_pca_sharded_" if sharded else "corrla_pca_", (x, m, n, *_strides(x)), m, n,
                              n if sharded else min(m, n), x, on_dev, int(rank), n_iter, n_oversamples, seed, omega, cflags)
 
     def pca_sharded(self, x_local, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None):
         """PcaRsvd::new on SAMPLE-sharded data (one process per GPU, `comm_init` done): `x_local` = this rank's samples
         (CUDA tensor m_local x n_dim).  Returns (means, S, components), replicated on every rank."""
+        _reject_bf16(x_local, "pca_sharded")
         if not (_is_torch(x_local) and x_local.is_cuda):
             raise ValueError("pca_sharded takes torch CUDA tensors")
         return self._pca_dense(x_local, rank, n_iter, n_oversamples, seed, omega, center, sharded=True)
@@ -392,8 +437,8 @@ class Context:
     def pca(self, x_mat, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None):
         """PcaRsvd::new(x, rank): returns (means (1, n), singular values (k, 1), components (k, n)).
         n_iter / n_oversamples default to the reference's hard-coded 20 / min(n_dim, 10) (pca_rsvd.rs:65-66).
-        center: None (library default: implicit rank-1 corrections for f64, a centred copy for f32), "fused" or
-        "copy" (CORRLA_PCA_CENTER_* in include/corrla_rsvd.h).  Sparse x_mat (see _as_csr): always "fused"; "copy" raises."""
+        center: None (library default: implicit rank-1 corrections for f64 and bfloat16, a centred copy for f32), "fused"
+        or "copy" (CORRLA_PCA_CENTER_* in include/corrla_rsvd.h; "copy" on a bfloat16 tensor centres a widened f32 copy).  Sparse x_mat (see _as_csr): always "fused"; "copy" raises."""
         rank = int(rank)
         if center not in (None, "fused", "copy"):
             raise ValueError("center must be None, 'fused' or 'copy'")
@@ -406,16 +451,16 @@ class Context:
                              L.PCA_CENTER_FUSED)
 
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
-    def _run_product(self, name, operand, m, n, xt, trans, beta):
+    def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
         """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that
-        describe A); xt a device tensor with as many rows as op(A) has columns."""
+        describe A); xt a device tensor with as many rows as op(A) has columns; in_dtype: A's dtype where it is not xt's."""
         import torch
         xin, xout = (m, n) if trans else (n, m)
         l = xt.shape[1]
         xc = xt.t().contiguous()  # column-major (xin, l)
         res = torch.empty((l, xout), dtype=xt.dtype, device=xt.device)
         _sync_stream(xt)
-        L.check(self._entry(name, True, xt.dtype)(self._h, 1 if trans else 0, *_c_args(operand), xc.data_ptr(), xin, l, float(beta),
+        L.check(self._entry(name, True, in_dtype or xt.dtype)(self._h, 1 if trans else 0, *_c_args(operand), xc.data_ptr(), xin, l, float(beta),
                                                   res.data_ptr(), xout))
         return res.t()
 
@@ -435,8 +480,16 @@ class Context:
                                  m, n, xt, trans, beta)
 
     def matmul(self, a, x, trans=False, beta=1.0):
-        """res = beta * op(a) @ x on device tensors (par_matmul_helper, mat_utils.rs:20-33)."""
+        """res = beta * op(a) @ x on device tensors (par_matmul_helper, mat_utils.rs:20-33).  A bfloat16 `a` takes a
+        float32 `x` and gives a float32 result (corrla_matmul_dev_bf16); a bfloat16 `x` is an error."""
         m, n = a.shape
+        if _is_bf16(x):
+            raise ValueError("matmul: x must be float32 or float64 (only the matrix a may be bfloat16)")
+        if _is_bf16(a):
+            if not str(x.dtype).endswith("float32"):
+                raise ValueError("matmul: a bfloat16 a takes a float32 x")
+            assert x.shape[0] == (m if trans else n)
+            return self._run_product("corrla_matmul_", (a, m, n, *a.stride()), m, n, x, trans, beta, in_dtype=a.dtype)
         assert x.shape[0] == (m if trans else n) and x.dtype == a.dtype
         return self._run_product("corrla_matmul_", (a, m, n, *a.stride()), m, n, x, trans, beta)
 
@@ -475,6 +528,7 @@ class Context:
 
     # ---- power_iter ----------------------------------------------------------------------
     def power_iter(self, a_mat, omega_rank, n_iter, *, seed=None, omega=None, qr=None):
+        _reject_bf16(a_mat, "power_iter")
         a = np.asarray(a_mat)
         if a.ndim != 2:
             raise ValueError("a_mat must be 2-D")

@@ -144,11 +144,11 @@ inline TallA<T> stage_input(Dev& dev, bool host_ptrs, const T* a, int64_t m, int
   return tall_over<T>(buf, L.row_major, L.mt, L.nt, mem_rows, mem_cols, ldp, ldp);
 }
 
-// The options of one rsvd / PCA call.  Sparse operands: CORRLA_POWER_FUSED and CORRLA_SKETCH_BF16X3 / X6 have no sparse
-// kernels and are ignored, as documented for every operand outside their domain.
-inline RunOpts call_opts(const corrla_opts* o, bool host_ptrs, bool sharded, bool sparse) {
+// The options of one rsvd / PCA call.  Sparse and bf16-stored operands (not_dense_f32): CORRLA_POWER_FUSED and
+// CORRLA_SKETCH_BF16X3 / X6 only have dense f32 kernels and are ignored, as documented for every operand outside their domain.
+inline RunOpts call_opts(const corrla_opts* o, bool host_ptrs, bool sharded, bool not_dense_f32) {
   RunOpts ro = parse_opts(o, !host_ptrs);
-  if (sparse) {
+  if (not_dense_f32) {
     ro.power_fused = false;
     ro.mixed_planes = 0;
   }
@@ -228,6 +228,7 @@ struct RsvdCall {
   Timings* tm_out;
   bool profile;
   bool sharded = false, sparse = false, fat = false, empty_shard = false;
+  bool bf16 = false;  // the operand arrived in bfloat16 (in place or widened: the stage decides)
 };
 
 // The one body of random_svd (random_svd.rs:63-110) for every operand.  `validate` checks the operand and the rank;
@@ -251,7 +252,7 @@ inline void rsvd_body(Dev& dev, const RsvdCall<T>& c, Validate&& validate, Stage
         validate();
         if (c.ldu < c.m) throw Error(ST_EINVAL, "ldu < m");
         if (c.ldvt < c.rank) throw Error(ST_EINVAL, "ldvt < rank");
-        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse);
+        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse || c.bf16);
         draw_seed(dev, ro);
       },
       [&] {
@@ -335,6 +336,7 @@ struct PcaCall {
   Timings* tm_out;
   bool profile;
   bool sharded = false, sparse = false;
+  bool bf16 = false;  // as RsvdCall::bf16; the default centring is the fused one
 };
 
 // The one body of PcaRsvd::new (pca_rsvd.rs:56-82) for every operand: means, centring (implicit rank-1 corrections or
@@ -356,7 +358,7 @@ inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&&
         validate();
         if (c.ldc < c.rank) throw Error(ST_EINVAL, "ldc < rank");
         if (c.sparse) need_two_samples(c.m);  // never sharded: the sample count is known before anything is staged
-        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse);
+        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse || c.bf16);
         if (c.sparse && ro.pca_center == 2)
           throw Error(ST_EINVAL, "CORRLA_PCA_CENTER_COPY on CSR input: a centred copy would densify the matrix (use the fused centring)");
         draw_seed(dev, ro);
@@ -379,7 +381,7 @@ inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&&
   else
     drv.a_times(ta, ones, mu, inv_m);            // tall view = x^T (n x m): mu (n) = x^T 1 / m
   TallA<T> tc = ta;
-  const bool fused = c.sparse || ro.pca_center == 1 || (ro.pca_center == 0 && sizeof(T) == 8);
+  const bool fused = c.sparse || ro.pca_center == 1 || (ro.pca_center == 0 && (sizeof(T) == 8 || c.bf16));
   if (fused) {
     // the centred matrix is never formed.  Tall view (i, j) = x(i, j) for tall inputs (means run
     // along the SHORT side), = x(j, i) for fat inputs (means run along the TALL side).
@@ -485,7 +487,10 @@ inline void product_body(Dev& dev, int trans, int64_t m, int64_t n, const T* x, 
     drv.a_times(ta, xs, out, beta_dev);
   if (!out.external) dev.copy_out(out, l, res, ldres, false, false);
   dev.end_call();
-  if (tm_out) tm_out->n_mixed_products = drv.tm.n_mixed_products;
+  if (tm_out) {
+    tm_out->n_mixed_products = drv.tm.n_mixed_products;
+    tm_out->n_bf16_products = drv.tm.n_bf16_products;
+  }
 }
 
 // mat_utils.rs:20-33 for the two hot-path shapes
@@ -590,6 +595,109 @@ inline void spmm_entry(Dev& dev, int trans, const T* values, const int32_t* ci, 
   product_body(
       dev, trans, m, n, x, ldx, l, beta, res, ldres, (Timings*)nullptr, [&] { validate_csr_args(values, ci, rp, m, n, nnz); },
       [&] { return stage_csr<Dev, T>(dev, false, values, ci, rp, m, n, nnz, /*keep_orientation=*/true); });
+}
+
+// ---- dense bf16 input ------------------------------------------------------------------------------------------------
+// A arrives in bfloat16 (bit patterns, strides in elements); every other array of the call is f32 and the call is the f32
+// call on the same values.  The stage decides ONCE, from the layout, the alignment and the sketch width l, whether both
+// tall products of the call are in the domain of gemm_bf16a_kernel (Dev::bf16a_fits): then they run on A in place and
+// A is never widened or copied (host pointers: the 2-byte matrix is staged, H2D of 2 bytes per element); otherwise A
+// is widened once into a padded f32 workspace and the call proceeds as the plain f32 call it then is -- never half and
+// half.  Only instantiated for backends that carry the kernel (dev_has_bf16in).
+template <class Dev>
+inline TallA<float> stage_bf16(Dev& dev, bool host_ptrs, const uint16_t* a, int64_t m, int64_t n, int64_t rs, int64_t cs,
+                               bool force_tall, int64_t l, bool force_widen) {
+  static_assert(dev_has_bf16in<Dev>::value, "bf16 entries need a backend with the bf16-input kernel");
+  validate_matrix(a, m, n, rs, cs);
+  const Layout L = classify(m, n, rs, cs, force_tall);
+  const int64_t mem_rows = L.row_major ? L.mt : L.nt;
+  const int64_t mem_cols = L.row_major ? L.nt : L.mt;
+  const int64_t trs = L.fat ? cs : rs, tcs = L.fat ? rs : cs;  // tall view strides
+  const int64_t vrs = L.row_major ? trs : tcs, vcs = L.row_major ? tcs : trs;  // strides of the memory-row-major view
+  const int64_t ldp = round_up(mem_cols, kLdPad);
+  // the 2-byte matrix as the device sees it: src + r * src_rs + c * src_cs
+  const uint16_t* src = a;
+  int64_t src_rs = vrs, src_cs = vcs;
+  Big<uint16_t> b16;  // a row-major view of it, when there is one
+  if (host_ptrs) {
+    uint16_t* buf = (uint16_t*)dev.alloc_bytes((size_t)mem_rows * (size_t)ldp * sizeof(uint16_t));
+    dev.memset_zero(buf, (size_t)mem_rows * (size_t)ldp * sizeof(uint16_t));
+    if (L.needs_pack || vcs != 1) {
+      std::vector<uint16_t> packed((size_t)mem_rows * (size_t)mem_cols);
+      for (int64_t r = 0; r < mem_rows; ++r)
+        for (int64_t c = 0; c < mem_cols; ++c) packed[(size_t)r * mem_cols + c] = a[r * vrs + c * vcs];
+      dev.h2d_2d(buf, ldp, packed.data(), mem_cols, mem_cols, mem_rows);
+    } else {
+      dev.h2d_2d(buf, ldp, a, mem_rows == 1 ? mem_cols : vrs, mem_cols, mem_rows);
+    }
+    src = buf, src_rs = ldp, src_cs = 1;
+    b16.p = buf, b16.rows = mem_rows, b16.cols = mem_cols, b16.ld = ldp, b16.cols_readable = ldp;
+  } else if (!L.needs_pack) {
+    b16.p = a, b16.rows = mem_rows, b16.cols = mem_cols, b16.ld = L.ld, b16.cols_readable = mem_cols;
+  }
+  if (!force_widen && b16.p && dev.bf16a_fits(b16, l)) {
+    TallA<float> ta;
+    ta.mt = L.mt;
+    ta.nt = L.nt;
+    ta.row_major = L.row_major;
+    ta.bf16 = true;
+    ta.mem16 = b16;
+    return ta;
+  }
+  float* wide = (float*)dev.alloc_bytes((size_t)mem_rows * (size_t)ldp * sizeof(float));
+  dev.memset_zero(wide, (size_t)mem_rows * (size_t)ldp * sizeof(float));
+  dev.widen_bf16(src, mem_rows, mem_cols, src_rs, src_cs, wide, ldp);
+  return tall_over<float>(wide, L.row_major, L.mt, L.nt, mem_rows, mem_cols, ldp, ldp);
+}
+
+template <class Dev>
+inline void rsvd_bf16_entry(Dev& dev, bool host_ptrs, const uint16_t* a, int64_t m, int64_t n, int64_t rs, int64_t cs,
+                            int64_t rank, int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, float* u, int64_t ldu,
+                            float* s, float* vt, int64_t ldvt, Timings* tm_out, bool profile) {
+  RsvdCall<float> c{host_ptrs, m, rank, n_iter, n_oversamples, opts, u, ldu, s, vt, ldvt, tm_out, profile};
+  c.fat = m < n;
+  c.bf16 = true;
+  rsvd_body(
+      dev, c,
+      [&] {
+        validate_matrix(a, m, n, rs, cs);
+        if (opts && (opts->flags & CORRLA_SHARD_COLS)) throw Error(ST_EINVAL, "CORRLA_SHARD_COLS is only valid for sharded entry points");
+        validate_rank(m, n, rank, n_iter, n_oversamples);
+      },
+      [&] {
+        const int64_t l = std::min<int64_t>(rank + n_oversamples, std::min(m, n));
+        return stage_bf16(dev, host_ptrs, a, m, n, rs, cs, false, l, false);
+      });
+}
+
+// PCA of bf16 data: the fused centring by default (A stays in place, the means are A^T 1 / m through the same product
+// kernel); CORRLA_PCA_CENTER_COPY needs an f32 copy to centre, so that call runs widened.
+template <class Dev>
+inline void pca_bf16_entry(Dev& dev, bool host_ptrs, const uint16_t* x, int64_t m, int64_t n, int64_t rs, int64_t cs, int64_t rank,
+                           int64_t n_iter, int64_t n_oversamples, const corrla_opts* opts, float* means, float* s, float* comps,
+                           int64_t ldc, Timings* tm_out, bool profile) {
+  PcaCall<float> c{host_ptrs, m, n, rank, n_iter, n_oversamples, opts, means, s, comps, ldc, tm_out, profile};
+  c.bf16 = true;
+  pca_body(
+      dev, c,
+      [&] {
+        validate_matrix(x, m, n, rs, cs);
+        validate_rank(m, n, rank, n_iter, n_oversamples);
+      },
+      [&] {
+        const int64_t l = std::min<int64_t>(rank + n_oversamples, std::min(m, n));
+        const bool copy = opts && (opts->flags & CORRLA_PCA_CENTER_COPY) != 0;
+        return stage_bf16(dev, host_ptrs, x, m, n, rs, cs, false, l, copy);
+      });
+}
+
+// res = beta * op(A) * X for a device bf16 matrix A and f32 X (test hook, the bf16 twin of matmul_entry)
+template <class Dev>
+inline void matmul_bf16_entry(Dev& dev, int trans, const uint16_t* a, int64_t m, int64_t n, int64_t rs, int64_t cs, const float* x,
+                              int64_t ldx, int64_t l, float beta, float* res, int64_t ldres, Timings* tm_out) {
+  product_body(
+      dev, trans, m, n, x, ldx, l, beta, res, ldres, tm_out, [&] { validate_matrix(a, m, n, rs, cs); },
+      [&] { return stage_bf16(dev, false, a, m, n, rs, cs, true, l, false); });
 }
 
 }  // namespace corrla

@@ -150,7 +150,7 @@ CORRLA_API corrla_status corrla_ctx_get_timings(corrla_ctx* ctx, corrla_timings*
     out->sketch_kernel_ms = t.sketch_kernel_ms;
     out->host_enqueue_ms = t.host_enqueue_ms;
     out->n_mixed_products = t.n_mixed_products;
-    out->reserved_ = 0;
+    out->n_bf16_products = t.n_bf16_products;
     out->knn_ms = t.knn_ms;
     out->fit_ms = t.fit_ms;
   });
@@ -241,6 +241,29 @@ CORRLA_DEFINE(f64, double)
 
 CORRLA_DEFINE_CSR(f32, float)
 CORRLA_DEFINE_CSR(f64, double)
+
+// ---- dense bf16 input (A: bfloat16 bit patterns; every other array f32) --------------------------------------------------
+#define CORRLA_DEFINE_RSVD_BF16(NAME, HOST)                                                                             \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(uint16_t, a), CORRLA_RSVD_REST(float)) {                  \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                           \
+      rsvd_bf16_entry<HipDev>(c.dev, HOST, a, m, n, rs, cs, rank, n_iter, p, o, u, ldu, s, vt, ldvt, &c.last, c.profile); \
+    });                                                                                                                 \
+  }
+#define CORRLA_DEFINE_PCA_BF16(NAME, HOST)                                                                              \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(uint16_t, x), CORRLA_PCA_REST(float)) {                   \
+    return ctx_call(ctx, [&](corrla_ctx& c) {                                                                           \
+      pca_bf16_entry<HipDev>(c.dev, HOST, x, m, n, rs, cs, rank, n_iter, p, o, means, s, comps, ldc, &c.last, c.profile); \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_RSVD_BF16(corrla_rsvd_bf16, true)
+CORRLA_DEFINE_RSVD_BF16(corrla_rsvd_dev_bf16, false)
+CORRLA_DEFINE_PCA_BF16(corrla_pca_bf16, true)
+CORRLA_DEFINE_PCA_BF16(corrla_pca_dev_bf16, false)
+CORRLA_API corrla_status corrla_matmul_dev_bf16(corrla_ctx* ctx, int trans, CORRLA_DENSE(uint16_t, a), CORRLA_PRODUCT_REST(float)) {
+  return ctx_call(ctx, [&](corrla_ctx& c) {
+    matmul_bf16_entry<HipDev>(c.dev, trans, a, m, n, rs, cs, x, ldx, l, beta, res, ldres, &c.last);
+  });
+}
 
 // ---- active-subspace gradient stage ------------------------------------------------------
 static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,

@@ -90,6 +90,12 @@ struct dev_has_spmm : std::false_type {};
 template <class D>
 struct dev_has_spmm<D, std::void_t<decltype(D::kHasSpmm)>> : std::true_type {};
 
+// ... and those that carry the bf16-input product kernel with kHasBf16In.
+template <class D, class = void>
+struct dev_has_bf16in : std::false_type {};
+template <class D>
+struct dev_has_bf16in<D, std::void_t<decltype(D::kHasBf16In)>> : std::true_type {};
+
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).
 template <class T>
@@ -105,6 +111,10 @@ struct TallA {
   // products of the range finder are row gathers.  For a fat input the caller's CSR is csr_t (no copy).
   bool sparse = false;
   CsrView<T> csr, csr_t;
+  // Operand stored in bfloat16 (T = float only): `mem` is unused; mem16 is the same row-major view of the 2-byte matrix
+  // (bit patterns, ld and cols_readable in elements).  Both products run on it in place; the results are f32.
+  bool bf16 = false;
+  Big<uint16_t> mem16;
 };
 
 struct RunOpts {
@@ -136,6 +146,7 @@ struct Timings {
   double collective_bytes = 0;  // payload bytes of those all-reduces
   double knn_ms = 0, fit_ms = 0;  // gradient stage (corrla_grad_mat_*): neighbour scan / local fits
   int n_mixed_products = 0;     // tall products that ran on the bf16-split kernels (RunOpts::mixed_planes)
+  int n_bf16_products = 0;      // tall products that ran on the bf16-input kernel (TallA::bf16)
   // breakdown of qr_ms (only filled when phase profiling is on): Gram GEMM, D2H + analysis, host Cholesky /
   // inverse, H2D + apply GEMM
   double qr_gram_ms = 0, qr_down_ms = 0, qr_host_ms = 0, qr_apply_ms = 0;
@@ -174,9 +185,18 @@ struct RsvdDriver {
     else
       throw Error(ST_EINVAL, "this backend has no SpMM kernels: sparse operands are not supported");
   }
+  // op(R) X for the bf16-stored operand: tn = false is R X, tn = true is R^T X
+  void bf16_times(bool tn, const Big<uint16_t>& r, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev) {
+    if constexpr (dev_has_bf16in<Dev>::value && std::is_same<T, float>::value)
+      dev.gemm_bf16a(tn, r, x, y, scale_dev), ++tm.n_bf16_products;
+    else
+      throw Error(ST_EINVAL, "this backend has no bf16-input kernels: bf16 operands are not supported");
+  }
   void a_times(const TallA<T>& a, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev) {
     if (a.sparse)
       sparse_times(a.csr, x, y, scale_dev);
+    else if (a.bf16)
+      bf16_times(!a.row_major, a.mem16, x, y, scale_dev);
     else if (mixed_planes_ && dev.template mixed_fits<T>(!a.row_major, a.mem, x, y))
       dev.gemm_mixed(!a.row_major, a.mem, x, y, scale_dev, mixed_planes_), ++tm.n_mixed_products;
     else if (a.row_major)
@@ -194,6 +214,8 @@ struct RsvdDriver {
   void at_times(const TallA<T>& a, const Skinny<T>& y, Skinny<T>& z, const T* scale_dev, bool sharded) {
     if (a.sparse)
       sparse_times(a.csr_t, y, z, scale_dev);
+    else if (a.bf16)
+      bf16_times(a.row_major, a.mem16, y, z, scale_dev);
     else if (mixed_planes_ && dev.template mixed_fits<T>(a.row_major, a.mem, y, z))
       dev.gemm_mixed(a.row_major, a.mem, y, z, scale_dev, mixed_planes_), ++tm.n_mixed_products;
     else if (a.row_major)

@@ -8,7 +8,8 @@
 // Families.  GENERAL: gemm_nn_kernel / gemm_tn_kernel<T, MW, NT, NW> (hip_kernels.hpp), any shape.  GRAM ALIAS: the
 // aliased gemm_nn_kernel<T, 2, NT, true> for G = Y^T Y with l <= 128.  TALL APPLY / TALL GRAM: the register-resident
 // kernels of tall_kernels.hpp for Y M and Y^T Y of a very tall sketch with l <= 96 (f32) / 64 (f64).  BF16 SPLIT:
-// gemm_bf16s_kernel<NT, NP, TN> (mixed_kernels.hpp), only when the caller asks for NP = 2 / 3 planes.
+// gemm_bf16s_kernel<NT, NP, TN> (mixed_kernels.hpp), only when the caller asks for NP = 2 / 3 planes.  BF16 STORED:
+// gemm_bf16a_kernel<NT, TN> (bf16in_kernels.hpp), whenever the big operand is stored in bfloat16 (no size threshold).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -83,6 +84,15 @@ constexpr int kMxASlots = 3, kMxBSlots = 2;
 CORRLA_HD constexpr int mx_bslot_bytes(int nt, int np) { return np * mx_plane_bytes(nt); }
 CORRLA_HD constexpr int mx_lds_bytes(int nt, int np) { return kMxASlots * kMxBigBytes + kMxBSlots * mx_bslot_bytes(nt, np) + 1024; }
 
+// ---- bf16-stored kernels (bf16in_kernels.hpp): the workgroup shape of the bf16-split kernels, R in 2-byte elements ----
+constexpr int kBaPlanes = 3;                            // the skinny operand is always split into three bf16 pieces
+constexpr int kBaBigBytes = kMxOuter * kMxKT * 2;       // 16 KiB: one 32-deep tile of R
+// The big operand runs THREE tiles ahead (4 slots of 16 KiB: as many bytes of HBM latency in flight as the f32 kernel's two
+// tiles of 32 KiB), the planes two ahead (3 slots), so that the counted wait of a tile leaves two big tiles in flight.
+constexpr int kBaASlots = 4, kBaBSlots = 3;
+CORRLA_HD constexpr int ba_bslot_bytes(int nt) { return kBaPlanes * mx_plane_bytes(nt); }
+CORRLA_HD constexpr int ba_lds_bytes(int nt) { return kBaASlots * kBaBigBytes + kBaBSlots * ba_bslot_bytes(nt) + 1024; }
+
 }  // namespace k
 
 // Geometry knobs of the tall products, read once when a device context is created (hip_backend.hpp).
@@ -114,9 +124,10 @@ struct GemmShape {
   bool same = false;  // R and X are the same memory (Gram matrices)
   int np = 0;         // bf16 planes: 0 = exact products, 2 / 3 = the bf16-split kernels
   int num_cus = 256;
+  bool r_bf16 = false;  // R is stored in bfloat16 (r.ld, r.cols_readable in 2-byte elements); X and out stay f32
 };
 
-enum class GemmFamily { general, gram_alias, tall_apply, tall_gram, bf16_split };
+enum class GemmFamily { general, gram_alias, tall_apply, tall_gram, bf16_split, bf16_stored };
 enum class SlabReduce { none, plain, deep };  // slab_reduce_kernel / slab_reduce_deep_kernel
 
 // Sum of `slabs` partial results (stride apart) into rows x cols of the output.
@@ -162,6 +173,18 @@ inline bool gemm_mixed_domain(const GemmShape& s, const GemmKnobs& kn) {
   if (s.x.ld < (red_n + k::kMxKT - 1) / k::kMxKT * k::kMxKT || s.out.ld < outer_n || s.out.rows != outer_n) return false;
   if (s.same) return false;
   return outer_n >= 1 && red_n >= 1 && (double)outer_n * (double)red_n >= kn.mixed_min_work;
+}
+
+// The bf16-stored kernels' domain: row-major bf16 R (unit stride along its memory rows) with a 16-byte aligned base, a
+// leading dimension and a readable row length that are multiples of 8 elements, f32 X and out in the padded layout, one
+// column block (<= 144 columns).  No size threshold: every product in the domain takes the kernel.
+inline bool gemm_bf16a_domain(const GemmShape& s) {
+  const int64_t outer_n = s.tn ? s.r.cols : s.r.rows, red_n = s.tn ? s.r.rows : s.r.cols;
+  if (!s.r_bf16 || s.esz != 4 || s.x.external || col_blocking(s.x.cols).nblk != 1) return false;
+  if (!s.r.aligned || (s.r.ld % 8) || (s.r.cols_readable % 8) || !s.x.aligned || (s.x.ld % 64)) return false;
+  if (s.x.ld < (red_n + k::kMxKT - 1) / k::kMxKT * k::kMxKT || s.out.ld < outer_n || s.out.rows != outer_n) return false;
+  if (s.same) return false;
+  return outer_n >= 1 && red_n >= 1;
 }
 
 namespace gemm_plan_detail {
@@ -226,19 +249,15 @@ inline bool plan_tall(const GemmShape& s, const GemmKnobs& kn, int64_t outer_n, 
   return true;
 }
 
-inline GemmPlan plan_bf16_split(const GemmShape& s, const GemmKnobs& kn, int64_t outer_n, int64_t red_n,
-                                const ColBlocking& cb) {
-  GemmPlan p;
-  p.family = GemmFamily::bf16_split;
-  p.np = s.np;
-  p.block = 64 * (k::kMxWaves + k::kMxLoaders);
-  if (s.np != 2 && s.np != 3) return rejected(p, "internal: bf16 split takes 2 or 3 planes");
-  if (!gemm_mixed_domain(s, kn)) return rejected(p, "internal: operands outside the bf16-split kernels' domain");
+// What the bf16-split and the bf16-stored kernels share: the np planes of the skinny operand, 32-deep reduction tiles,
+// one workgroup per 256 outer indices and CU (`lds` bytes of LDS), the reduction split that fills the chip
+inline GemmPlan plan_mx_launch(GemmPlan p, const GemmShape& s, int64_t outer_n, int64_t red_n, const ColBlocking& cb, int lds,
+                               int split_override) {
   if (!padding_fits(s, cb)) return rejected(p, "internal: skinny column padding too small for the column blocking");
-  // the skinny operand in np bf16 planes, reduction index in MFMA fragment order
+  // the skinny operand in np bf16 planes
   p.plane_cols = cb.cols_alloc;
   p.plane_stride = s.x.ld * cb.cols_alloc;
-  p.plane_bytes = (size_t)s.np * (size_t)p.plane_stride * 2;
+  p.plane_bytes = (size_t)p.np * (size_t)p.plane_stride * 2;
   p.split_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (p.plane_stride / 8 + 255) / 256));
   const int64_t tiles64 = (red_n + k::kMxKT - 1) / k::kMxKT;
   if (tiles64 > 0x7fffffff) return rejected(p, "reduction dimension too large");
@@ -249,7 +268,7 @@ inline GemmPlan plan_bf16_split(const GemmShape& s, const GemmKnobs& kn, int64_t
   int nsplit = 1;
   if (outer_tiles < s.num_cus)
     nsplit = (int)std::min<int64_t>((s.num_cus + outer_tiles / 2) / outer_tiles, std::max(1, p.tiles_total / 16));
-  if (kn.mixed_split) nsplit = kn.mixed_split;
+  if (split_override) nsplit = split_override;
   p.nsplit = std::max(1, std::min(std::min(nsplit, p.tiles_total), 65535));
   p.tiles_per_split = (p.tiles_total + p.nsplit - 1) / p.nsplit;
   p.outer_blocks = (int)outer_tiles;
@@ -258,9 +277,30 @@ inline GemmPlan plan_bf16_split(const GemmShape& s, const GemmKnobs& kn, int64_t
   p.slab_stride = s.out.ld * cb.cols_alloc;
   if (p.nsplit > 1) p.slab_bytes = (size_t)p.nsplit * (size_t)p.slab_stride * 4;
   p.nlaunch = 1;
-  p.launch[0] = {{(unsigned)outer_tiles, 1, (unsigned)p.nsplit}, cb.nt, 0, 0, k::mx_lds_bytes(cb.nt, s.np)};
+  p.launch[0] = {{(unsigned)outer_tiles, 1, (unsigned)p.nsplit}, cb.nt, 0, 0, lds};
   if (!plan_reduce(p, outer_n, cb.cols_alloc)) p.error = "problem too large for the launch grid";
   return p;
+}
+
+inline GemmPlan plan_bf16_split(const GemmShape& s, const GemmKnobs& kn, int64_t outer_n, int64_t red_n,
+                                const ColBlocking& cb) {
+  GemmPlan p;
+  p.family = GemmFamily::bf16_split;
+  p.np = s.np;
+  p.block = 64 * (k::kMxWaves + k::kMxLoaders);
+  if (s.np != 2 && s.np != 3) return rejected(p, "internal: bf16 split takes 2 or 3 planes");
+  if (!gemm_mixed_domain(s, kn)) return rejected(p, "internal: operands outside the bf16-split kernels' domain");
+  return plan_mx_launch(p, s, outer_n, red_n, cb, k::mx_lds_bytes(cb.nt, s.np), kn.mixed_split);
+}
+
+// R stored in bfloat16: gemm_bf16a_kernel<NT, TN>, X in three planes whose reduction index is in memory order
+inline GemmPlan plan_bf16_stored(const GemmShape& s, int64_t outer_n, int64_t red_n, const ColBlocking& cb) {
+  GemmPlan p;
+  p.family = GemmFamily::bf16_stored;
+  p.np = k::kBaPlanes;
+  p.block = 64 * (k::kMxWaves + k::kMxLoaders);
+  if (!gemm_bf16a_domain(s)) return rejected(p, "internal: operands outside the bf16-stored kernels' domain");
+  return plan_mx_launch(p, s, outer_n, red_n, cb, k::ba_lds_bytes(cb.nt), 0);
 }
 
 }  // namespace gemm_plan_detail
@@ -269,6 +309,7 @@ inline GemmPlan gemm_plan(const GemmShape& s, const GemmKnobs& kn) {
   using namespace gemm_plan_detail;
   const int64_t outer_n = s.tn ? s.r.cols : s.r.rows, red_n = s.tn ? s.r.rows : s.r.cols;
   const ColBlocking cb = col_blocking(s.x.cols);
+  if (s.r_bf16) return plan_bf16_stored(s, outer_n, red_n, cb);
   if (s.np) return plan_bf16_split(s, kn, outer_n, red_n, cb);
   GemmPlan p;
   const int vec = k::gemm_vec(s.esz), kt = k::gemm_kt(s.esz);

@@ -24,6 +24,7 @@
 #include "ata_kernels.hpp"
 #include "tall_kernels.hpp"
 #include "mixed_kernels.hpp"
+#include "bf16in_kernels.hpp"
 #include "grad_kernels.hpp"
 #include "knn2_kernels.hpp"
 #include "grad_wide_kernels.hpp"
@@ -455,6 +456,66 @@ class HipDev {
     });
     CORRLA_HIP(hipGetLastError());
     slab_reduce<float>(p.reduce, slab, p.slab_stride, out.p, out.ld, scale_dev, run_if_);
+  }
+
+  // ---- dense bf16 input (bf16in_kernels.hpp): R stored in bfloat16, f32 skinny operands, f32 accumulate ---------------
+  static constexpr bool kHasBf16In = true;  // driver.hpp: dev_has_bf16in
+  // both products of a call with this operand and an l-column sketch are in the kernel's domain (gemm_bf16a_domain):
+  // asked ONCE per call by the entry layer, which widens the matrix otherwise
+  bool bf16a_fits(const Big<uint16_t>& r, int64_t l) const {
+    for (int tn = 0; tn < 2; ++tn) {
+      const int64_t xr = tn ? r.rows : r.cols, outr = tn ? r.cols : r.rows;
+      GemmShape s;
+      s.tn = tn != 0;
+      s.r = {r.rows, r.cols, r.ld, r.cols_readable, 0, false, (uintptr_t)r.p % 16 == 0};
+      s.x = {xr, l, round_up(std::max<int64_t>(xr, 1), kLdPad), 0, col_blocking(l).cols_alloc, false, true};
+      s.out = {outr, l, round_up(std::max<int64_t>(outr, 1), kLdPad), 0, col_blocking(l).cols_alloc, false, true};
+      s.r_bf16 = true;
+      s.num_cus = num_cus;
+      if (!gemm_bf16a_domain(s)) return false;
+    }
+    return true;
+  }
+  // out = scale * op(R) * X on gemm_bf16a_kernel; a product outside its domain is an error (no fallback here)
+  void gemm_bf16a(bool tn, const Big<uint16_t>& r, const Skinny<float>& x, Skinny<float>& out, const float* scale_dev) {
+    if (x.rows != (tn ? r.rows : r.cols)) throw Error(ST_EINVAL, "gemm_bf16a: inner dimensions differ");
+    Big<float> shape_only;  // the plan reads sizes and alignment, never the element type
+    shape_only.p = (const float*)(const void*)r.p;
+    shape_only.rows = r.rows, shape_only.cols = r.cols, shape_only.ld = r.ld, shape_only.cols_readable = r.cols_readable;
+    GemmShape s = gemm_shape(tn, shape_only, x, out, 0);
+    s.r_bf16 = true;
+    const GemmPlan p = gemm_plan(s, gemm_knobs_);
+    if (p.error) throw Error(ST_EINVAL, p.error);
+    // the skinny operand in three bf16 planes, reduction index in memory order
+    __bf16* planes = (__bf16*)alloc_bytes(p.plane_bytes);
+    hipLaunchKernelGGL((k::split_planes_kernel<k::kBaPlanes, false>), dim3(p.split_grid), dim3(256), 0, stream, (const float*)x.p, x.ld,
+                       p.plane_cols, planes, p.plane_stride, run_if_);
+    CORRLA_HIP(hipGetLastError());
+    float* slab = p.reduce.kind != SlabReduce::none ? (float*)alloc_bytes(p.slab_bytes) : nullptr;
+    const k::BaArgs a{r.p, r.rows, r.cols, r.ld, r.cols_readable,  // big operand
+                      planes, x.ld, p.plane_stride,                // skinny operand
+                      out.p, out.ld, p.out_cols,                   // output
+                      slab, p.slab_stride, scale_dev, (const float*)zero_page_,
+                      p.tiles_total, p.tiles_per_split, p.nsplit, run_if_, p.vec_store, 0};
+    const GemmLaunch& L = p.launch[0];
+    with_nt<kMaxColTiles>(L.nt, [&](auto nt) {
+      constexpr int NT = decltype(nt)::value;
+      const dim3 grid(L.grid[0], L.grid[1], L.grid[2]), block(p.block);
+      if (tn)
+        hipLaunchKernelGGL((k::gemm_bf16a_kernel<NT, true>), grid, block, L.lds, stream, a);
+      else
+        hipLaunchKernelGGL((k::gemm_bf16a_kernel<NT, false>), grid, block, L.lds, stream, a);
+    });
+    CORRLA_HIP(hipGetLastError());
+    slab_reduce<float>(p.reduce, slab, p.slab_stride, out.p, out.ld, scale_dev, run_if_);
+  }
+  // strided bf16 view -> zero-padded row-major f32 (dst already cleared): the widened route of the entry layer
+  void widen_bf16(const uint16_t* src, int64_t rows, int64_t cols, int64_t rs, int64_t cs, float* dst, int64_t ldd) {
+    const int64_t tiles_c = (cols + 31) / 32, tiles_r = (rows + 31) / 32;
+    if (tiles_c * tiles_r > 0x7fffffff) throw Error(ST_EINVAL, "problem too large for the launch grid");
+    hipLaunchKernelGGL(k::widen_bf16_kernel, dim3((unsigned)(tiles_c * tiles_r)), dim3(256), 0, stream, src, rows, cols, rs, cs, dst, ldd,
+                       tiles_c);
+    CORRLA_HIP(hipGetLastError());
   }
 
   // ---- one-sweep Z' = A^T (A Z) (ata_kernels.hpp): row-major f32 A with n <= 512, l <= 80 -----------
@@ -1406,6 +1467,7 @@ class HipDev {
     set_mixed_limits<2, true>();
     set_mixed_limits<3, false>();
     set_mixed_limits<3, true>();
+    set_bf16a_limits();
     // nearest neighbours and local fits of the gradient stage (corrla_rsvd.hip)
     lds_limit((const void*)k::knn_kernel, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);
@@ -1468,6 +1530,12 @@ class HipDev {
   static void set_mixed_limits() {
     for_each_nt<kMaxColTiles>([](auto nt) {
       lds_limit((const void*)k::gemm_bf16s_kernel<decltype(nt)::value, NP, TN>, k::mx_lds_bytes(nt, NP));
+    });
+  }
+  static void set_bf16a_limits() {
+    for_each_nt<kMaxColTiles>([](auto nt) {
+      lds_limit((const void*)k::gemm_bf16a_kernel<decltype(nt)::value, false>, k::ba_lds_bytes(nt));
+      lds_limit((const void*)k::gemm_bf16a_kernel<decltype(nt)::value, true>, k::ba_lds_bytes(nt));
     });
   }
   // ---- launchers of the tall products (gemm_plan.hpp) ----

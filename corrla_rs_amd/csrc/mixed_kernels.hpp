@@ -84,7 +84,9 @@ __device__ __forceinline__ void mx_split8(const float (&x)[8], bf16x8 (&frag)[NP
 // x: column-major, ld elements per column, zero padded (rows [rows, ld) and columns up to ncols are readable zeros).
 // planes[p][col][q]: ld bf16 per column; q = 32 t + 8 g + j holds piece p of x(32 t + kmap(g, j), col).  One thread
 // per 16-byte output slot (8 positions).  run_if: see GemmArgs.
-template <int NP>
+// KMAP false (bf16in_kernels.hpp): the identity map, q holds piece p of x(q, col) -- the order a bf16 row of the big
+// operand is read in.
+template <int NP, bool KMAP = true>
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, int64_t ld, int64_t ncols, __bf16* planes,
                                                            int64_t plane_stride, const int* run_if) {
   if (run_if && *run_if == 0) return;
@@ -95,8 +97,8 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
     const int64_t t = sl >> 2;
     const int g = (int)(sl & 3);
     const float* src = x + col * ld + 32 * t;
-    const f32x4 lo4 = *(const f32x4*)(src + 4 * g);
-    const f32x4 hi4 = *(const f32x4*)(src + 16 + 4 * g);
+    const f32x4 lo4 = *(const f32x4*)(src + (KMAP ? 4 * g : 8 * g));
+    const f32x4 hi4 = *(const f32x4*)(src + (KMAP ? 16 + 4 * g : 8 * g + 4));
     const float v[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
     bf16x8 fr[NP];
     mx_split8<NP>(v, fr);
@@ -105,8 +107,9 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   }
 }
 
-struct MxArgs {
-  const float* r;        // big operand, row-major f32
+template <class R>
+struct MxArgsT {
+  const R* r;            // big operand, row-major (f32; bf16 bit patterns for bf16in_kernels.hpp)
   int64_t r_rows, r_cols, r_ld, r_cols_readable;
   const __bf16* planes;  // NP planes of the skinny operand (split_planes_kernel), x_ld bf16 per column
   int64_t x_ld, plane_stride;
@@ -121,6 +124,7 @@ struct MxArgs {
   int vec_store;
   int debug_flags;       // timing-only ablations (wrong results): 2 = no plane DMA, 4 = no big-operand DMA after the first tile
 };
+typedef MxArgsT<float> MxArgs;
 
 // swizzles of the two LDS images (both applied on the DMA's per-lane SOURCE address and again on the read):
 //   big image, 128-byte rows (8 slots):  physical slot = logical ^ ((row >> 1) & 7)   -- two rows per 256-byte bank line
@@ -130,8 +134,8 @@ struct MxArgs {
 __host__ __device__ constexpr int mx_big_swz(int row) { return (row >> 1) & 7; }
 __host__ __device__ constexpr int mx_plane_swz(int row) { return (-(row >> 2)) & 3; }
 
-template <int NT, int NP>
-__device__ __forceinline__ void mx_store(const MxArgs& g, const f32x4 (&acc)[NT], int64_t outer0, int64_t outer_limit, int lane) {
+template <int NT, int NP, class Args>
+__device__ __forceinline__ void mx_store(const Args& g, const f32x4 (&acc)[NT], int64_t outer0, int64_t outer_limit, int lane) {
   float* dst;
   float sc = 1.f;
   if (g.nsplit > 1) {

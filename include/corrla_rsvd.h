@@ -136,7 +136,7 @@ typedef struct corrla_timings {
   double host_enqueue_ms;  /* host wall clock spent enqueueing the call: the host runs ahead of the device */
   double collective_bytes; /* payload bytes of those all-reduces (n x l factors, l x l Gram matrices, scalars) */
   int32_t n_mixed_products; /* tall products of this call that ran on the bf16-split kernels (CORRLA_SKETCH_BF16X3 / X6) */
-  int32_t reserved_;
+  int32_t n_bf16_products;  /* tall products of this call that ran on the bf16-input kernel (corrla_*_bf16); 0 when the call was widened */
   double knn_ms;        /* corrla_grad_mat_*: device time of the neighbour scan (hipEvents around its launches) */
   double fit_ms;        /* corrla_grad_mat_*: device time of the local least-squares fits; both 0 after any other call */
 } corrla_timings;
@@ -255,6 +255,37 @@ CORRLA_API corrla_status corrla_matmul_dev_f32(corrla_ctx* ctx, int trans, const
 CORRLA_API corrla_status corrla_matmul_dev_f64(corrla_ctx* ctx, int trans, const double* a, int64_t m, int64_t n,
                                     int64_t row_stride, int64_t col_stride, const double* x, int64_t ldx, int64_t l,
                                     double beta, double* res, int64_t ldres);
+
+/* ---- dense bfloat16 input -------------------------------------------------------------
+ * random_svd, PcaRsvd::new and the product hook for a dense matrix STORED in bfloat16 (the upper 16 bits of an IEEE
+ * binary32; torch.bfloat16).  A is `const uint16_t*` (bit patterns), strides in ELEMENTS; every other pointer -- U, S,
+ * Vt, means, components, Omega (corrla_opts.omega), x, res -- is float, with the shapes and layouts of the f32 entries.
+ * The result is what the f32 entry gives on the same matrix widened to float, to f32 rounding: the products accumulate
+ * in f32 and the skinny operand keeps all 24 bits (three bf16 pieces).
+ * When the memory rows of the tall view have unit stride, a 16-byte aligned base, a leading dimension and a length
+ * that are multiples of 8 elements, and l = min(rank + n_oversamples, min(m, n)) <= 144, both tall products of the call
+ * read A in place at 2 bytes per element and A is never copied or widened; corrla_timings.n_bf16_products counts them.
+ * Any other call (and CORRLA_PCA_CENTER_COPY) widens A once into an f32 workspace and runs as the f32 call
+ * (n_bf16_products == 0); a call is never half and half.  corrla_pca_*_bf16 defaults to CORRLA_PCA_CENTER_FUSED.
+ * CORRLA_QR_HOUSEHOLDER is honoured; CORRLA_POWER_FUSED and CORRLA_SKETCH_BF16X3 / X6 are ignored, as for every operand
+ * outside their domain.  The host-pointer entries stage the 2-byte matrix (H2D of 2 bytes per element).
+ * No sharded variants and no power_iter variant. */
+CORRLA_API corrla_status corrla_rsvd_bf16(corrla_ctx* ctx, const uint16_t* a, int64_t m, int64_t n, int64_t row_stride,
+                                    int64_t col_stride, int64_t rank, int64_t n_iter, int64_t n_oversamples,
+                                    const corrla_opts* opts, float* u, int64_t ldu, float* s, float* vt, int64_t ldvt);
+CORRLA_API corrla_status corrla_rsvd_dev_bf16(corrla_ctx* ctx, const uint16_t* a, int64_t m, int64_t n, int64_t row_stride,
+                                    int64_t col_stride, int64_t rank, int64_t n_iter, int64_t n_oversamples,
+                                    const corrla_opts* opts, float* u, int64_t ldu, float* s, float* vt, int64_t ldvt);
+CORRLA_API corrla_status corrla_pca_bf16(corrla_ctx* ctx, const uint16_t* x, int64_t n_samples, int64_t n_dim, int64_t row_stride,
+                                    int64_t col_stride, int64_t rank, int64_t n_iter, int64_t n_oversamples,
+                                    const corrla_opts* opts, float* means, float* s, float* components, int64_t ldc);
+CORRLA_API corrla_status corrla_pca_dev_bf16(corrla_ctx* ctx, const uint16_t* x, int64_t n_samples, int64_t n_dim, int64_t row_stride,
+                                    int64_t col_stride, int64_t rank, int64_t n_iter, int64_t n_oversamples,
+                                    const corrla_opts* opts, float* means, float* s, float* components, int64_t ldc);
+/* res = beta * op(A) * X as corrla_matmul_dev_f32, A in bfloat16, X and res float.  DEVICE pointers. */
+CORRLA_API corrla_status corrla_matmul_dev_bf16(corrla_ctx* ctx, int trans, const uint16_t* a, int64_t m, int64_t n,
+                                    int64_t row_stride, int64_t col_stride, const float* x, int64_t ldx, int64_t l,
+                                    float beta, float* res, int64_t ldres);
 
 /* ---- CSR sparse input ----------------------------------------------------------------
  * random_svd (random_svd.rs:63-110) and PcaRsvd::new (pca_rsvd.rs:56-82) for a matrix that is not dense: the

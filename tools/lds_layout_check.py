@@ -7,6 +7,9 @@ destination, swizzled SOURCE) and what the MFMA waves read back, and verifies
   * every ds_read_b128 (four 16-lane groups, MI355X_MICROARCH.md LDS table) and ds_read_b32 (two 32-lane groups) of the
     kernels is bank-conflict free,
   * split_planes_kernel's position -> reduction index map equals the fragment order the big operand is read in.
+and the same for the two images of corrla_rs_amd/csrc/bf16in_kernels.hpp (big operand stored in bf16, 16-KiB tiles): the
+ds_read_b128 of the nn image, the two ds_read_b64_tr_b16 of the tn image (addresses 8-byte aligned, the 4 x 16 block each
+16-lane group gathers, conflict freedom per 32-lane half on 64 banks) and the identity reduction map of its planes.
 Run: python tools/lds_layout_check.py"""
 import itertools
 import sys
@@ -125,6 +128,100 @@ def check(nt, np_, tn):
         assert conflict_free_b128(addrs), ("plane", t, p)
 
 
+# ---- bf16in_kernels.hpp ----------------------------------------------------------------------------------------------
+BA_BIG = 16384
+
+
+def ba_tn_swz(kr):
+    return (kr & 3) | ((kr >> 1) & 4)
+
+
+def ba_fill_big(tn):
+    """LDS 16-byte slot index -> (row, the 8 element indices along the row) after the DMA of one big tile."""
+    lds = {}
+    for c in range(BA_BIG // 1024):
+        for lane in range(64):
+            dst = (c * 1024 + 16 * lane) // 16
+            if not tn:
+                row = 16 * c + (lane >> 2)
+                ls = (lane & 3) ^ plane_swz(row)
+                lds[dst] = (row, tuple(8 * ls + e for e in range(8)))                 # outer row, reduction indices
+            else:
+                kr = 2 * c + (lane >> 5)
+                sp = lane & 31
+                lb = (sp >> 1) ^ ba_tn_swz(kr)
+                lds[dst] = (kr, tuple(16 * lb + 8 * (sp & 1) + e for e in range(8)))  # reduction row, outer columns
+    assert len(lds) == BA_BIG // 16
+    return lds
+
+
+def conflict_free_b64(addrs):
+    """ds_read_b64 / ds_read_b64_tr_b16: 64 banks of 4 bytes, the two 32-lane halves"""
+    for grp in (range(0, 32), range(32, 64)):
+        banks = {}
+        for lane in grp:
+            for d in range(2):
+                b = (addrs[lane] // 4 + d) % 64
+                if b in banks and banks[b] != addrs[lane] // 4 + d:
+                    return False
+                banks[b] = addrs[lane] // 4 + d
+    return True
+
+
+def check_bf16a(tn):
+    lds = ba_fill_big(tn)
+    for wave, mw in itertools.product(range(8), range(2)):
+        if not tn:
+            addrs = {}
+            for lane in range(64):
+                fr, fg = lane & 15, lane >> 4
+                addr = (32 * wave + 16 * mw + fr) * 64 + ((fg ^ plane_swz(fr)) << 4)
+                addrs[lane] = addr
+                row, ks = lds[addr // 16]
+                assert row == 32 * wave + 16 * mw + fr, (wave, mw, lane, row)
+                assert list(ks) == [8 * fg + j for j in range(8)], (lane, ks)       # identity reduction map
+            assert conflict_free_b128(addrs), ("bf16a nn", wave, mw)
+        else:
+            for half in range(2):
+                addrs = {}
+                for lane in range(64):
+                    fr, fg = lane & 15, lane >> 4
+                    kr = 8 * fg + (fr >> 2)
+                    addr = kr * 512 + (((2 * wave + mw) ^ ba_tn_swz(kr)) << 5) + ((fr & 3) << 3) + half * 4 * 512
+                    assert addr % 8 == 0 and addr + 8 <= BA_BIG
+                    addrs[lane] = addr
+                # the hardware transpose: lane 4 q + p of a 16-lane group supplies row q, columns 4 p .. 4 p + 3 of the block;
+                # lane i receives column i of the four rows, row q in element q
+                for lane in range(64):
+                    fr, fg = lane & 15, lane >> 4
+                    for q in range(4):
+                        src = addrs[16 * fg + 4 * q + (fr >> 2)]
+                        row, cols = lds[src // 16]
+                        col = cols[(src % 16) // 2 + (fr & 3)]
+                        assert row == 8 * fg + 4 * half + q, (lane, q, row)        # reduction index 8 g + j, j = 4 half + q
+                        assert col == 32 * wave + 16 * mw + fr, (lane, q, col)
+                assert conflict_free_b64(addrs), ("bf16a tn", wave, mw, half)
+
+
+def check_bf16a_planes(nt):
+    """plane images as in check(), filled by split_planes_kernel<3, false>: position q of a column holds reduction index q"""
+    plane = nt * 16 * KT * 2
+    lds = {}
+    for p, ct, lane in itertools.product(range(3), range(nt), range(64)):
+        row = 16 * ct + (lane >> 2)
+        ls = (lane & 3) ^ plane_swz(row)
+        lds[(p * plane + ct * 1024 + 16 * lane) // 16] = (p, row, tuple(8 * ls + j for j in range(8)))
+    for t, p in itertools.product(range(nt), range(3)):
+        addrs = {}
+        for lane in range(64):
+            fr, fg = lane & 15, lane >> 4
+            addr = fr * 64 + ((fg ^ plane_swz(fr)) << 4) + t * 1024 + p * plane
+            addrs[lane] = addr
+            pp, col, ks = lds[addr // 16]
+            assert pp == p and col == 16 * t + fr and list(ks) == [8 * fg + j for j in range(8)], (t, p, lane)
+        assert conflict_free_b128(addrs), ("bf16a plane", t, p)
+
+
 if __name__ == "__main__":
     assert sorted(kmap(p) for p in range(32)) == list(range(32))
     n = 0
@@ -132,3 +229,8 @@ if __name__ == "__main__":
         check(nt, np_, tn)
         n += 1
     print(f"{n} kernel variants: fragment maps and bank-conflict freedom OK")
+    for tn in (False, True):
+        check_bf16a(tn)
+    for nt in range(1, 10):
+        check_bf16a_planes(nt)
+    print("bf16-input kernel: nn / tn big images and plane images for NT = 1..9 OK")
