@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "capi_impl.hpp"
+#include "grad_stage.hpp"
 #include "hip_backend.hpp"
 
 using namespace corrla;
@@ -269,219 +270,43 @@ CORRLA_API corrla_status corrla_matmul_dev_bf16(corrla_ctx* ctx, int trans, CORR
 static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,
                                 const double* xq, int64_t n_q, int est_order, int64_t n_nbrs, double out_scale, double* g,
                                 int64_t ldg, int* n_regularised) {
-  return guarded([&] {
-    corrla_ctx* c = need(ctx);
+  return ctx_call(ctx, [&](corrla_ctx& c) {
+    HipDev& dev = c.dev;
     if (!x || !y || !xq || !g) throw Error(ST_EINVAL, "NULL argument");
     if (n_pts < 1 || n_q < 1 || kf < 1) throw Error(ST_EINVAL, "empty point set");
     if (ldg < kf) throw Error(ST_EINVAL, "ldg < k");
-    // which scan and which fit (grad_plan.hpp); a call the limited kernels cannot take goes to the wide ones
+    // which scan and which fit, every grid and workspace (grad_plan.hpp)
     const GradPlan plan = grad_plan(n_pts, kf, n_q, est_order, n_nbrs, env_int("CORRLA_KNN", 0), env_int("CORRLA_FIT", 0),
-                                    c->dev.num_cus, kGradWideBudgetBytes);
+                                    dev.num_cus, kGradWideBudgetBytes, env_int("CORRLA_KNN2_WGS_PER_CU", 1));
     if (plan.error) throw Error(ST_EINVAL, plan.error);
-    locked_call(c, [&] {
-    HipDev& dev = c->dev;
     dev.begin_call();
-    const int kk = (int)kf, nn = (int)n_nbrs;
-    const double* xd = x;
-    const double* yd = y;
-    const double* qd = xq;
-    double* gd = g;
-    if (host_ptrs) {
-      double* xb = (double*)dev.alloc_bytes(sizeof(double) * (size_t)n_pts * kf);
-      double* yb = (double*)dev.alloc_bytes(sizeof(double) * (size_t)n_pts);
-      double* qb = (double*)dev.alloc_bytes(sizeof(double) * (size_t)n_q * kf);
-      CORRLA_HIP(hipMemcpyAsync(xb, x, sizeof(double) * (size_t)n_pts * kf, hipMemcpyHostToDevice, dev.stream));
-      CORRLA_HIP(hipMemcpyAsync(yb, y, sizeof(double) * (size_t)n_pts, hipMemcpyHostToDevice, dev.stream));
-      CORRLA_HIP(hipMemcpyAsync(qb, xq, sizeof(double) * (size_t)n_q * kf, hipMemcpyHostToDevice, dev.stream));
-      xd = xb;
-      yd = yb;
-      qd = qb;
-      gd = (double*)dev.alloc_bytes(sizeof(double) * (size_t)n_q * kf);
-    }
-    const int64_t ldt = round_up(n_pts, 64);
-    const bool wide_scan = plan.scan == GradScan::kWide;
-    double* xt = wide_scan ? nullptr : (double*)dev.alloc_bytes(sizeof(double) * (size_t)ldt * kf);
-    int* nbr = (int*)dev.alloc_bytes(sizeof(int) * (size_t)n_q * nn);
-    int* status = (int*)dev.alloc_bytes(sizeof(int) * (size_t)n_q);
-    // the wide kernels' workspaces, before the first launch
-    k::WideScanArgs wsa{};
-    if (wide_scan) {
-      wsa.list_d = (double*)dev.alloc_bytes((size_t)plan.scan_wgs * k::kWsQ * (size_t)n_nbrs * sizeof(double));
-      wsa.cand_d = (double*)dev.alloc_bytes((size_t)plan.scan_wgs * k::kWsQ * k::kWsCap * sizeof(double));
-      wsa.cand_i = (int*)dev.alloc_bytes((size_t)plan.scan_wgs * k::kWsQ * k::kWsCap * sizeof(int));
-    }
-    double* wf_ws = plan.fit == GradFit::kWide ? (double*)dev.alloc_bytes(plan.fit_ws) : nullptr;
-    if (!wide_scan)
-      hipLaunchKernelGGL(k::grad_transpose_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, dev.stream, xd, n_pts, kk, xt,
-                         ldt);
-    // Both kernels spend ~n_nbrs ln(n_pts / n_nbrs) list insertions per query; the MFMA distance tile only pays off
-    // once the scan itself dominates (measured: 5e4 points 0.10 s VALU / 0.14 s MFMA, 1e5 0.28 / 0.30, 2e5 0.93 / 0.45)
-    dev.event_mark(0);  // corrla_timings.knn_ms / fit_ms: events 0-1 around the scan, 1-2 around the fits
-    // knn2_kernels.hpp (round 3): bf16x3 MFMA filter + batched bitonic list merges; n_nbrs <= 128.  Small clouds keep the
-    // VALU scan (its per-query lists live in LDS and there is too little work to amortise the split of the cloud).
-    if (wide_scan) {
-      wsa.x = xd;
-      wsa.xq = qd;
-      wsa.n_pts = n_pts;
-      wsa.n_q = n_q;
-      wsa.n_nbrs = n_nbrs;
-      wsa.ntiles = (n_q + k::kWsQ - 1) / k::kWsQ;
-      wsa.k = kk;
-      wsa.nbr = nbr;
-      hipLaunchKernelGGL(k::knn_wide_kernel, dim3((unsigned)plan.scan_wgs), dim3(64 * k::kWsWaves), plan.scan_lds, dev.stream, wsa);
-    } else if (plan.scan == GradScan::kKnn2) {
-      const int S = plan.scan_s;
-      const int64_t nchunks = (n_pts + k::kK2Chunk - 1) / k::kK2Chunk;
-      __bf16* pb = (__bf16*)dev.alloc_bytes((size_t)nchunks * (size_t)k::k2_chunk_bytes(S));
-      float* pnf = (float*)dev.alloc_bytes((size_t)nchunks * k::kK2Chunk * 4 * sizeof(float));  // -c_p, four copies per point
-      double* mean = (double*)dev.alloc_bytes(64 * sizeof(double));
-      const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n_pts + 4095) / 4096));
-      const int64_t rpb = (n_pts + nb - 1) / nb;
-      double* partial = (double*)dev.alloc_bytes((size_t)nb * 64 * sizeof(double));
-      hipLaunchKernelGGL(k::knn2_colsum_kernel, dim3((unsigned)nb), dim3(256), 0, dev.stream, xd, n_pts, kk, rpb, partial);
-      hipLaunchKernelGGL(k::knn2_mean_kernel, dim3(1), dim3(64), 0, dev.stream, (const double*)partial, nb, n_pts, kk, mean);
-      hipLaunchKernelGGL(k::knn2_prep_kernel, dim3((unsigned)nchunks), dim3(256), 0, dev.stream, xd, n_pts, kk, (const double*)mean, S,
-                         pb, pnf);
-      k::Knn2Args ka;
-      ka.pb = pb;
-      ka.pn = pnf;
-      ka.x = xd;
-      ka.xq = qd;
-      ka.mean = mean;
-      ka.n_pts = n_pts;
-      ka.n_q = n_q;
-      ka.nchunks = nchunks;
-      ka.ntiles = (n_q + k::kK2Q - 1) / k::kK2Q;
-      ka.k = kk;
-      ka.n_nbrs = nn;
-      const int64_t wgs = std::min<int64_t>(ka.ntiles, (int64_t)dev.num_cus * std::max(1, env_int("CORRLA_KNN2_WGS_PER_CU", 1)));
-      ka.cand = (int*)dev.alloc_bytes((size_t)wgs * k::kK2Q * k::kK2Cap * sizeof(int));
-      ka.list_d = (double*)dev.alloc_bytes((size_t)wgs * k::kK2Q * k::kK2List * sizeof(double));
-      ka.list_i = (int*)dev.alloc_bytes((size_t)wgs * k::kK2Q * k::kK2List * sizeof(int));
-      ka.nbr = nbr;
-      ka.prof = nullptr;
-      const bool k2prof = env_int("CORRLA_KNN2_PROF", 0) != 0;
-      if (k2prof) {
-        ka.prof = (unsigned long long*)dev.alloc_bytes(4 * sizeof(unsigned long long));
-        CORRLA_HIP(hipMemsetAsync(ka.prof, 0, 4 * sizeof(unsigned long long), dev.stream));
-      }
-      if (S == 1)
-        hipLaunchKernelGGL((k::knn2_kernel<1>), dim3((unsigned)wgs), dim3(64 * k::kK2Waves), k::k2_lds_bytes(1), dev.stream, ka);
-      else
-        hipLaunchKernelGGL((k::knn2_kernel<2>), dim3((unsigned)wgs), dim3(64 * k::kK2Waves), k::k2_lds_bytes(2), dev.stream, ka);
-      CORRLA_HIP(hipGetLastError());
-      if (k2prof) {  // diagnostic only: synchronises
-        unsigned long long h[4];
-        CORRLA_HIP(hipMemcpyAsync(h, ka.prof, sizeof(h), hipMemcpyDeviceToHost, dev.stream));
-        CORRLA_HIP(hipStreamSynchronize(dev.stream));
-        std::fprintf(stderr, "knn2 prof (wave 0 of %lld workgroups, 100 MHz ticks): total %llu, flushes %llu (%.1f %%), chunk waits %llu (%.1f %%), "
-                     "%llu merge batches\n", (long long)wgs, h[2], h[0], 100.0 * h[0] / (double)h[2], h[1], 100.0 * h[1] / (double)h[2], h[3]);
-      }
-    } else if (plan.scan == GradScan::kValu) {
-      // (also when the MFMA scan's per-query lists outgrow LDS: n_nbrs > ~400 at k = 64 -- the VALU scan's fit up to the
-      //  interface's 512)
-      const size_t lds_knn = plan.scan_lds;
-      const int64_t knn_blocks = (n_q + k::kKnnQueries - 1) / k::kKnnQueries;
-      hipLaunchKernelGGL(k::knn_kernel, dim3((unsigned)knn_blocks), dim3(64 * k::kKnnWaves), lds_knn, dev.stream, (const double*)xt,
-                         ldt, n_pts, kk, qd, n_q, nn, nbr);
-    } else {
-      double* pnorm = (double*)dev.alloc_bytes(sizeof(double) * (size_t)n_pts);
-      hipLaunchKernelGGL(k::point_norms_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, dev.stream, (const double*)xt, ldt,
-                         n_pts, kk, pnorm);
-      const int waves = plan.scan_w;
-      const size_t lds_knn = plan.scan_lds;
-      const int64_t knn_blocks = (n_q + 16 * waves - 1) / (16 * waves);
-      const int nks = plan.scan_nks;
-#define CORRLA_KNN_LAUNCH(W_, S_)                                                                                              \
-  hipLaunchKernelGGL((k::knn_mfma_kernel<W_, S_>), dim3((unsigned)knn_blocks), dim3(64 * W_), lds_knn, dev.stream, (const double*)xt, \
-                     ldt, (const double*)pnorm, n_pts, kk, qd, n_q, nn, nbr)
-      if (waves == 4) {
-        if (nks == 4) CORRLA_KNN_LAUNCH(4, 4);
-        else if (nks == 8) CORRLA_KNN_LAUNCH(4, 8);
-        else CORRLA_KNN_LAUNCH(4, 16);
-      } else {
-        if (nks == 4) CORRLA_KNN_LAUNCH(2, 4);
-        else if (nks == 8) CORRLA_KNN_LAUNCH(2, 8);
-        else CORRLA_KNN_LAUNCH(2, 16);
-      }
-#undef CORRLA_KNN_LAUNCH
-    }
-    const int64_t ldgd = host_ptrs ? kf : ldg;
-    dev.event_mark(1);
-    // order 1: the MFMA-built normal equations (round 3; CORRLA_FIT=1 keeps the general kernel)
-    if (plan.fit == GradFit::kWide) {
-      k::WideFitArgs wfa;
-      wfa.x = xd;
-      wfa.y = yd;
-      wfa.xq = qd;
-      wfa.nbr = nbr;
-      wfa.n_q = n_q;
-      wfa.n_nbrs = n_nbrs;
-      wfa.P = k::grad_design_cols(kf, est_order);
-      wfa.k = kk;
-      wfa.order = est_order;
-      wfa.out_scale = out_scale;
-      wfa.g = gd;
-      wfa.ldg = ldgd;
-      wfa.status = status;
-      wfa.ws = wf_ws;
-      hipLaunchKernelGGL(k::grad_fit_wide_kernel, dim3((unsigned)plan.fit_wgs), dim3(256), plan.fit_lds, dev.stream, wfa);
-    } else if (plan.fit == GradFit::kLin) {
-      const size_t lds_lin = plan.fit_lds;
-      const int ntt = plan.fit_ntt;
-      const k::FitRowTab rtab = k::grad_fit_lin_row_table(kk + 1);
-      unsigned long long* fprof = nullptr;
-      if (env_int("CORRLA_KNN2_PROF", 0)) {
-        fprof = (unsigned long long*)dev.alloc_bytes(4 * sizeof(unsigned long long));
-        CORRLA_HIP(hipMemsetAsync(fprof, 0, 4 * sizeof(unsigned long long), dev.stream));
-      }
-#define CORRLA_FIT_LAUNCH(N_)                                                                                               \
-  hipLaunchKernelGGL((k::grad_fit_lin_kernel<N_>), dim3((unsigned)n_q), dim3(64), lds_lin, dev.stream, xd, yd, kk, qd, n_q, \
-                     (const int*)nbr, nn, out_scale, gd, ldgd, status, fprof, rtab)
-      switch (ntt) {
-        case 1: CORRLA_FIT_LAUNCH(1); break;
-        case 2: CORRLA_FIT_LAUNCH(2); break;
-        case 3: CORRLA_FIT_LAUNCH(3); break;
-        case 4: CORRLA_FIT_LAUNCH(4); break;
-        default: CORRLA_FIT_LAUNCH(5); break;
-      }
-#undef CORRLA_FIT_LAUNCH
-      if (fprof) {  // diagnostic only: synchronises
-        unsigned long long h[4];
-        CORRLA_HIP(hipMemcpyAsync(h, fprof, sizeof(h), hipMemcpyDeviceToHost, dev.stream));
-        CORRLA_HIP(hipStreamSynchronize(dev.stream));
-        const double tot = (double)(h[0] + h[1] + h[2]);
-        std::fprintf(stderr, "fit prof (%llu queries, 100 MHz ticks per query): gather + normal equations %.0f (%.0f %%), Cholesky %.0f (%.0f %%), "
-                     "solves %.0f (%.0f %%)\n", h[3], h[0] / (double)h[3], 100.0 * h[0] / tot, h[1] / (double)h[3], 100.0 * h[1] / tot,
-                     h[2] / (double)h[3], 100.0 * h[2] / tot);
-      }
-    } else if (plan.fit == GradFit::kLds) {
-      hipLaunchKernelGGL(k::grad_fit_kernel, dim3((unsigned)n_q), dim3(64), plan.fit_lds, dev.stream, xd, yd, kk, qd, n_q, (const int*)nbr,
-                         nn, est_order, out_scale, gd, ldgd, status, (double*)nullptr, (int64_t)0);
-    } else {
-      const int64_t wgs = plan.fit_wgs;
-      const size_t melems = k::grad_fit_m_elems(kk, est_order);
-      double* mg = (double*)dev.alloc_bytes((size_t)wgs * melems * sizeof(double));
-      hipLaunchKernelGGL(k::grad_fit_kernel, dim3((unsigned)wgs), dim3(64), plan.fit_lds, dev.stream, xd, yd, kk, qd, n_q, (const int*)nbr,
-                         nn, est_order, out_scale, gd, ldgd, status, mg, (int64_t)melems);
-    }
-    CORRLA_HIP(hipGetLastError());
+    auto dbl = [&](int64_t n) { return (double*)dev.alloc_bytes(sizeof(double) * (size_t)n); };
+    auto staged = [&](const double* h, int64_t n) {  // a host array on the device
+      if (!host_ptrs) return h;
+      double* d = dbl(n);
+      CORRLA_HIP(hipMemcpyAsync(d, h, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, dev.stream));
+      return (const double*)d;
+    };
+    const GradCall call{staged(x, n_pts * kf), staged(y, n_pts), staged(xq, n_q * kf), host_ptrs ? dbl(n_q * kf) : g,
+                        host_ptrs ? kf : ldg, n_pts, kf, n_q, n_nbrs, est_order, out_scale,
+                        (int*)dev.alloc_bytes(sizeof(int) * (size_t)(n_q * n_nbrs)), (int*)dev.alloc_bytes(sizeof(int) * (size_t)n_q),
+                        env_int("CORRLA_KNN2_PROF", 0) != 0};
+    grad_stage::run(dev, call, plan);
     // how many queries needed the ridge / failed: a short reduction on the host (n_q ints)
     std::vector<int> hs((size_t)n_q);
-    CORRLA_HIP(hipMemcpyAsync(hs.data(), status, sizeof(int) * (size_t)n_q, hipMemcpyDeviceToHost, dev.stream));
+    CORRLA_HIP(hipMemcpyAsync(hs.data(), call.status, sizeof(int) * (size_t)n_q, hipMemcpyDeviceToHost, dev.stream));
     if (host_ptrs)
-      CORRLA_HIP(hipMemcpy2DAsync(g, sizeof(double) * (size_t)ldg, gd, sizeof(double) * (size_t)kf, sizeof(double) * (size_t)kf,
+      CORRLA_HIP(hipMemcpy2DAsync(g, sizeof(double) * (size_t)ldg, call.g, sizeof(double) * (size_t)kf, sizeof(double) * (size_t)kf,
                                   (size_t)n_q, hipMemcpyDeviceToHost, dev.stream));
     dev.event_mark(2);
     dev.end_call();
-    c->last = Timings();
-    c->last.knn_ms = dev.event_elapsed_ms(0, 1);
-    c->last.fit_ms = dev.event_elapsed_ms(1, 2);
-    c->last.total_ms = c->last.knn_ms + c->last.fit_ms;
+    c.last = Timings();
+    c.last.knn_ms = dev.event_elapsed_ms(0, 1);
+    c.last.fit_ms = dev.event_elapsed_ms(1, 2);
+    c.last.total_ms = c.last.knn_ms + c.last.fit_ms;
     int bad = 0;
     for (int v : hs) bad += v != 0;
     if (n_regularised) *n_regularised = bad;
-    });
   });
 }
 CORRLA_API corrla_status corrla_grad_mat_f64(corrla_ctx* ctx, const double* x, int64_t n_pts, int64_t k, const double* y,

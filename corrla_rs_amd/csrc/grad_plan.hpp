@@ -1,6 +1,7 @@
-// The gradient stage's plan (corrla_grad_mat_*, corrla_rsvd.hip): which nearest-neighbour scan and which local-fit kernel
-// serve a call, their LDS and workspace, or why the call is rejected -- and the LDS arithmetic those choices rest on.
-// Host code only, no HIP call: tests/test_grad_plan.py compiles this header with the host compiler and pins the choice.
+// The gradient stage's plan (corrla_grad_mat_*): everything about the launches of a call -- which nearest-neighbour scan and
+// which local-fit kernel serve it, their instantiation, grid, workgroup size, LDS and workspaces, or why the call is rejected
+// -- and the LDS arithmetic those choices rest on.  grad_stage.hpp launches what the plan says and computes none of it again.
+// Host code only, no HIP call: tests/test_grad_plan.py compiles this header with the host compiler and pins every field.
 // The kernels that use the size helpers on the device include it through grad_kernels.hpp and knn2_kernels.hpp.
 //
 // Two families.  The LIMITED kernels (grad_kernels.hpp, knn2_kernels.hpp) keep per-query state in LDS and registers:
@@ -145,20 +146,31 @@ struct GradPlan {
   int scan_w = 0;               // kMfma: waves (4 or 2)
   int scan_nks = 0;             // kMfma: 4-dimension MFMA slices compiled in (4, 8, 16)
   int scan_s = 0;               // kKnn2: 32-dimension bf16 MFMA steps (1, 2)
+  int scan_block = 0;           // threads per workgroup
+  int64_t scan_wgs = 0;         // workgroups (kKnn2, kWide: persistent, each takes query tiles in turn)
+  int64_t scan_tiles = 0;       // kKnn2, kWide: query tiles
   size_t scan_lds = 0;          // dynamic LDS of the scan kernel
-  size_t scan_ws = 0;           // kWide: list and candidate workspace (other scans: 0 here; corrla_rsvd.hip sizes theirs)
-  int64_t scan_wgs = 0;         // kWide: persistent workgroups
+  size_t scan_ws = 0;           // every workspace of the scan and of the kernels that prepare it
+  int64_t ldt = 0;              // limited scans: pitch of the transposed cloud (k x ldt doubles)
+  int64_t pts_wgs = 0;          // limited scans: 256-thread blocks over the points (grad_transpose_kernel, point_norms_kernel)
+  struct Knn2 {                 // kKnn2: the prepared cloud and the per-workgroup lists
+    int64_t nchunks = 0;        //   chunks of kK2Chunk points = workgroups of knn2_prep_kernel
+    int nb = 0;                 //   workgroups of knn2_colsum_kernel
+    int64_t rpb = 0;            //   ... and the rows each one sums
+    size_t pb = 0, pn = 0, cand = 0, list_d = 0, list_i = 0;  // bytes of Knn2Args' arrays of those names
+  } k2;
   GradFit fit = GradFit::kLin;
   int fit_ntt = 0;              // kLin: 16-column tiles of the design
   size_t fit_lds = 0;
   size_t fit_ws = 0;            // kGlobal, kWide: per-workgroup slices in all
-  int64_t fit_wgs = 0;          // kGlobal, kWide: workgroups (else one per query)
+  int64_t fit_wgs = 0;          // workgroups (kLin, kLds: one per query; kGlobal, kWide: persistent)
 };
 
 // knn_mode = CORRLA_KNN (0 by size, 1 VALU, 2 f32-MFMA, 3 bf16-filter, 4 wide), fit_mode = CORRLA_FIT (0 default, 1 the
 // general kernel for order 1 too, 2 wide).  budget = bytes the workspace of each wide kernel may take.
+// knn2_wgs_per_cu = CORRLA_KNN2_WGS_PER_CU: persistent workgroups of knn2_kernel per CU (at least 1).
 inline GradPlan grad_plan(int64_t n_pts, int64_t kf, int64_t n_q, int order, int64_t n_nbrs, int knn_mode, int fit_mode,
-                          int num_cus, size_t budget) {
+                          int num_cus, size_t budget, int knn2_wgs_per_cu = 1) {
   GradPlan p;
   auto reject = [&](const char* m) {
     p.error = m;
@@ -176,29 +188,63 @@ inline GradPlan grad_plan(int64_t n_pts, int64_t kf, int64_t n_q, int order, int
   const bool small = kf <= k::kGradMaxDim && n_nbrs <= k::kGradMaxNbr;  // every limited scan's list fits
   const int kk = (int)(small ? kf : 0), nn = (int)(small ? n_nbrs : 0);
   const bool limited_fit = small && k::grad_fit_lds_bytes(kk, nn, order, /*m_in_lds=*/false) <= kMax;
+  auto ceil_div = [](int64_t a, int64_t b) { return (a + b - 1) / b; };
   // ---- scan ----
   if (knn_mode == 4 || !small) {
     p.scan = GradScan::kWide;
+    p.scan_block = 64 * k::kWsWaves;
     p.scan_lds = k::ws_lds_bytes();
     const size_t per_wg = k::ws_wg_bytes(n_nbrs);
     if (per_wg > budget) return reject("the wide scan's lists of one workgroup exceed the 4 GiB workspace budget");
-    const int64_t ntiles = (n_q + k::kWsQ - 1) / k::kWsQ;
-    int64_t wgs = ntiles < 2 * (int64_t)num_cus ? ntiles : 2 * (int64_t)num_cus;
+    p.scan_tiles = ceil_div(n_q, k::kWsQ);
+    int64_t wgs = p.scan_tiles < 2 * (int64_t)num_cus ? p.scan_tiles : 2 * (int64_t)num_cus;
     if ((size_t)wgs * per_wg > budget) wgs = (int64_t)(budget / per_wg);
     p.scan_wgs = wgs;
     p.scan_ws = (size_t)wgs * per_wg;
-  } else if ((knn_mode == 3 || (knn_mode == 0 && n_pts >= 8192)) && nn <= k::kK2List) {
-    p.scan = GradScan::kKnn2;
-    p.scan_s = kk <= 32 ? 1 : 2;
-    p.scan_lds = (size_t)k::k2_lds_bytes(p.scan_s);
-  } else if (knn_mode == 1 || (knn_mode == 0 && n_pts < 131072) || k::knn_mfma_lds_bytes(kk, nn, 2) > kMax) {
-    p.scan = GradScan::kValu;
-    p.scan_lds = k::knn_lds_bytes(kk, nn);
   } else {
-    p.scan = GradScan::kMfma;
-    p.scan_w = k::knn_mfma_lds_bytes(kk, nn, 4) <= kMax ? 4 : 2;
-    p.scan_nks = k::knn_mfma_slices(kk);
-    p.scan_lds = k::knn_mfma_lds_bytes(kk, nn, p.scan_w);
+    // every limited scan is launched behind the transposed cloud (the bf16 scan does not read it)
+    p.ldt = ceil_div(n_pts, 64) * 64;
+    p.pts_wgs = ceil_div(n_pts, 256);
+    p.scan_ws = (size_t)p.ldt * kk * sizeof(double);
+    if ((knn_mode == 3 || (knn_mode == 0 && n_pts >= 8192)) && nn <= k::kK2List) {
+      // small clouds keep the VALU scan: its lists live in LDS and there is too little work to amortise the split of the cloud
+      p.scan = GradScan::kKnn2;
+      p.scan_s = kk <= 32 ? 1 : 2;
+      p.scan_block = 64 * k::kK2Waves;
+      p.scan_lds = (size_t)k::k2_lds_bytes(p.scan_s);
+      p.scan_tiles = ceil_div(n_q, k::kK2Q);
+      const int64_t cap = (int64_t)num_cus * (knn2_wgs_per_cu > 1 ? knn2_wgs_per_cu : 1);
+      p.scan_wgs = p.scan_tiles < cap ? p.scan_tiles : cap;
+      GradPlan::Knn2& g = p.k2;
+      g.nchunks = ceil_div(n_pts, k::kK2Chunk);
+      const int64_t nb = ceil_div(n_pts, 4096);
+      g.nb = (int)(nb < 1024 ? nb : 1024);
+      g.rpb = ceil_div(n_pts, g.nb);
+      g.pb = (size_t)g.nchunks * (size_t)k::k2_chunk_bytes(p.scan_s);
+      g.pn = (size_t)g.nchunks * k::kK2Chunk * 4 * sizeof(float);  // -c_p, four copies per point
+      const size_t lists = (size_t)p.scan_wgs * k::kK2Q;
+      g.cand = lists * k::kK2Cap * sizeof(int);
+      g.list_d = lists * k::kK2List * sizeof(double);
+      g.list_i = lists * k::kK2List * sizeof(int);
+      // + the column sums of the g.nb blocks and the mean, 64 doubles each
+      p.scan_ws += g.pb + g.pn + (size_t)(g.nb + 1) * 64 * sizeof(double) + g.cand + g.list_d + g.list_i;
+    } else if (knn_mode == 1 || (knn_mode == 0 && n_pts < 131072) || k::knn_mfma_lds_bytes(kk, nn, 2) > kMax) {
+      // (also when the MFMA scan's per-query lists outgrow LDS: n_nbrs > ~400 at k = 64)
+      p.scan = GradScan::kValu;
+      p.scan_block = 64 * k::kKnnWaves;
+      p.scan_lds = k::knn_lds_bytes(kk, nn);
+      p.scan_wgs = ceil_div(n_q, k::kKnnQueries);
+    } else {
+      // Both spend ~n_nbrs ln(n_pts / n_nbrs) list insertions per query; the MFMA distance tile only pays off once the scan
+      // itself dominates (measured: 5e4 points 0.10 s VALU / 0.14 s MFMA, 1e5 0.28 / 0.30, 2e5 0.93 / 0.45)
+      p.scan = GradScan::kMfma;
+      p.scan_w = k::knn_mfma_lds_bytes(kk, nn, 4) <= kMax ? 4 : 2;
+      p.scan_nks = k::knn_mfma_slices(kk);
+      p.scan_block = 64 * p.scan_w;
+      p.scan_lds = k::knn_mfma_lds_bytes(kk, nn, p.scan_w);
+      p.scan_wgs = ceil_div(n_q, 16 * p.scan_w);
+      p.scan_ws += (size_t)n_pts * sizeof(double);  // the points' squared norms
+    }
   }
   // ---- fit ----
   if (fit_mode == 2 || !limited_fit) {
@@ -212,13 +258,15 @@ inline GradPlan grad_plan(int64_t n_pts, int64_t kf, int64_t n_q, int order, int
     p.fit_wgs = wgs;
     p.fit_ws = (size_t)wgs * slice;
   } else if (order == 1 && fit_mode != 1) {
-    p.fit = GradFit::kLin;
+    p.fit = GradFit::kLin;  // order 1: the MFMA-built normal equations (CORRLA_FIT=1 keeps the general kernel)
     const int ntt = (kk + 2 + 15) / 16;
     p.fit_ntt = ntt < 5 ? ntt : 5;
     p.fit_lds = k::grad_fit_lin_lds_bytes(kk, nn);
+    p.fit_wgs = n_q;
   } else if (k::grad_fit_lds_bytes(kk, nn, order, true) <= kMax) {
     p.fit = GradFit::kLds;
     p.fit_lds = k::grad_fit_lds_bytes(kk, nn, order, true);
+    p.fit_wgs = n_q;
   } else {
     p.fit = GradFit::kGlobal;
     p.fit_lds = k::grad_fit_lds_bytes(kk, nn, order, false);

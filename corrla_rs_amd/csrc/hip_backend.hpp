@@ -61,6 +61,28 @@ struct NcclType<double> {
   static constexpr ncclDataType_t v = ncclDouble;
 };
 
+// the instantiations of a kernel over its column tiles (or planes, waves, ...): with_nt calls
+// f(std::integral_constant<int, n>) for one n in [N, MAX], with_one_of for one n of the listed values, for_each_nt for
+// every n in [N, MAX].  A value without an instantiation is an error, never another kernel.
+template <int MAX, int N = 1, class F>
+inline void with_nt(int n, const F& f) {
+  if constexpr (N < MAX) {
+    if (n > N) return with_nt<MAX, N + 1>(n, f);
+  }
+  if (n != N) throw Error(ST_EINVAL, "internal: no kernel instantiation for " + std::to_string(n));
+  f(std::integral_constant<int, N>{});
+}
+template <int... Vs, class F>
+inline void with_one_of(int n, const F& f) {
+  if (!((n == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...))
+    throw Error(ST_EINVAL, "internal: no kernel instantiation for " + std::to_string(n));
+}
+template <int MAX, int N = 1, class F>
+inline void for_each_nt(const F& f) {
+  f(std::integral_constant<int, N>{});
+  if constexpr (N < MAX) for_each_nt<MAX, N + 1>(f);
+}
+
 class HipDev {
  public:
   int device = 0;
@@ -1029,17 +1051,10 @@ class HipDev {
     const T floor2 = (T)((double)l * eps * eps);  // squared norm of a numerically zero column (see the kernel)
     auto enqueue_sweeps = [&](int s0, int s1) {
       for (int sw = s0; sw < s1; ++sw)
-        for (int step = 0; step < nblocks - 1; ++step) switch (nc) {
-            case 1: jmc_launch_step<T, 1>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            case 2: jmc_launch_step<T, 2>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            case 3: jmc_launch_step<T, 3>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            case 4: jmc_launch_step<T, 4>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            case 5: jmc_launch_step<T, 5>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            case 6: jmc_launch_step<T, 6>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            case 7: jmc_launch_step<T, 7>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            case 8: jmc_launch_step<T, 8>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-            default: jmc_launch_step<T, 9>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl); break;
-          }
+        for (int step = 0; step < nblocks - 1; ++step)
+          with_nt<9>(nc, [&](auto nc_c) {
+            jmc_launch_step<T, decltype(nc_c)::value>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl);
+          });
       CORRLA_HIP(hipGetLastError());
     };
     const size_t lds_fin = (size_t)(l + 2) * sizeof(T) + (size_t)(l + 2) * sizeof(int) + 64;
@@ -1196,17 +1211,11 @@ class HipDev {
     const int n2 = 2 * np;
     k::RotEntry<T>* rot = (k::RotEntry<T>*)alloc_bytes((size_t)max_sw * n2 * k::kRingProcPad * sizeof(k::RotEntry<T>));
     int* rank_g = (int*)alloc_bytes(sizeof(int) * (size_t)n2);
-#define CORRLA_RING_W(EE)                                                                                             \
-  hipLaunchKernelGGL((k::jacobi_ring_w_kernel<T, EE, 8>), dim3(1), block, ring_lds, stream, (const T*)c.p, c.ld, (int)l, \
-                     m2.p, m2.ld, s_dev, (int)k, tol, tol_early, max_sw, rot, rank_g, info)
     constexpr int kBigE = sizeof(T) == 4 ? 20 : 18;
-    switch (e) {
-      case 8: CORRLA_RING_W(8); break;
-      case 12: CORRLA_RING_W(12); break;
-      case 16: CORRLA_RING_W(16); break;
-      default: CORRLA_RING_W(kBigE); break;
-    }
-#undef CORRLA_RING_W
+    with_one_of<8, 12, 16, kBigE>(e, [&](auto ee) {
+      hipLaunchKernelGGL((k::jacobi_ring_w_kernel<T, decltype(ee)::value, 8>), dim3(1), block, ring_lds, stream, (const T*)c.p, c.ld,
+                         (int)l, m2.p, m2.ld, s_dev, (int)k, tol, tol_early, max_sw, rot, rank_g, info);
+    });
     CORRLA_HIP(hipGetLastError());
     hipLaunchKernelGGL((k::jacobi_replay_v_kernel<T>), dim3((unsigned)((l + 256 / k::kReplayLanes - 1) / (256 / k::kReplayLanes))), dim3(256), 0,
                        stream,
@@ -1468,7 +1477,7 @@ class HipDev {
     set_mixed_limits<3, false>();
     set_mixed_limits<3, true>();
     set_bf16a_limits();
-    // nearest neighbours and local fits of the gradient stage (corrla_rsvd.hip)
+    // nearest neighbours and local fits of the gradient stage (grad_stage.hpp)
     lds_limit((const void*)k::knn_kernel, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 8>, kMax);
@@ -1558,21 +1567,6 @@ class HipDev {
     const GemmPlan p = gemm_plan(gemm_shape(tn, r, x, out, np), gemm_knobs_);
     if (p.error) throw Error(ST_EINVAL, p.error);
     return p;
-  }
-  // the instantiations of a kernel over its column tiles (or planes): with_nt calls f(std::integral_constant<int, n>)
-  // for one n in [N, MAX], for_each_nt for every one
-  template <int MAX, int N = 1, class F>
-  static void with_nt(int n, const F& f) {
-    if constexpr (N < MAX) {
-      if (n > N) return with_nt<MAX, N + 1>(n, f);
-    }
-    if (n != N) throw Error(ST_EINVAL, "internal: no kernel instantiation for " + std::to_string(n));
-    f(std::integral_constant<int, N>{});
-  }
-  template <int MAX, int N = 1, class F>
-  static void for_each_nt(const F& f) {
-    f(std::integral_constant<int, N>{});
-    if constexpr (N < MAX) for_each_nt<MAX, N + 1>(f);
   }
   // sum of the partial results of a split reduction (slab_reduce_kernel / slab_reduce_deep_kernel)
   template <class T>

@@ -3,7 +3,8 @@ with the host compiler in a temporary directory.
 
 Every call the stage accepted before the wide kernels existed must keep its kernels: EXPECTED_* below is that routing and
 those LDS sizes, written from corrla_rsvd.hip's grad_mat_c as it was (the validation, then the scan and fit choices and
-the LDS helpers of grad_kernels.hpp / knn2_kernels.hpp), independent of grad_plan."""
+the LDS helpers of grad_kernels.hpp / knn2_kernels.hpp), independent of grad_plan.  old_launches further down restates in
+the same way the grids, workgroup sizes and workspaces that function computed beside the plan before the plan carried them."""
 import itertools
 import os
 import subprocess
@@ -87,24 +88,32 @@ def old_routing(n_pts, k, n_q, order, n, knn_mode, fit_mode):
 
 MAIN = r"""
 #include <cstdio>
+#include <cstdlib>
 #include "grad_plan.hpp"
 int main(int argc, char** argv) {
   const char* scans[] = {"valu", "mfma", "knn2", "wide"};
   const char* fits[] = {"lin", "lds", "global", "wide"};
   long long np, kf, nq, n, budget;
   int order, km, fm;
+  const int wgs_per_cu = argc > 1 ? std::atoi(argv[1]) : 1;   // CORRLA_KNN2_WGS_PER_CU
   while (std::scanf("%lld %lld %lld %d %lld %d %d %lld", &np, &kf, &nq, &order, &n, &km, &fm, &budget) == 8) {
-    const corrla::GradPlan p = corrla::grad_plan(np, kf, nq, order, n, km, fm, 256, (size_t)budget);
+    const corrla::GradPlan p = corrla::grad_plan(np, kf, nq, order, n, km, fm, 256, (size_t)budget, wgs_per_cu);
     if (p.error) {
       std::printf("reject %s\n", p.error);
       continue;
     }
-    std::printf("%s %d %d %d %zu %s %d %zu %lld %zu %lld %zu\n", scans[(int)p.scan], p.scan_w, p.scan_nks, p.scan_s, p.scan_lds,
+    std::printf("%s %d %d %d %zu %s %d %zu %lld %zu %lld %zu", scans[(int)p.scan], p.scan_w, p.scan_nks, p.scan_s, p.scan_lds,
                 fits[(int)p.fit], p.fit_ntt, p.fit_lds, (long long)p.scan_wgs, p.scan_ws, (long long)p.fit_wgs, p.fit_ws);
+    std::printf(" %d %lld %lld %lld %lld %d %lld %zu %zu %zu %zu %zu\n", p.scan_block, (long long)p.scan_tiles, (long long)p.ldt,
+                (long long)p.pts_wgs, (long long)p.k2.nchunks, p.k2.nb, (long long)p.k2.rpb, p.k2.pb, p.k2.pn, p.k2.cand,
+                p.k2.list_d, p.k2.list_i);
   }
   return 0;
 }
 """
+
+
+GEOMETRY = ("block", "tiles", "ldt", "pts_wgs", "nchunks", "nb", "rpb", "pb", "pn", "cand", "list_d", "list_i")
 
 
 @pytest.fixture(scope="module")
@@ -116,9 +125,10 @@ def plan(tmp_path_factory):
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "corrla_rs_amd", "csrc"),
                            str(src), "-o", str(exe)])
 
-    def run(cases, budget=BUDGET):
+    def run(cases, budget=BUDGET, wgs_per_cu=None):
         inp = "".join("%d %d %d %d %d %d %d %d\n" % (*c, budget) for c in cases)
-        out = subprocess.run([str(exe)], input=inp, capture_output=True, text=True, check=True).stdout.splitlines()
+        argv = [str(exe)] + ([] if wgs_per_cu is None else [str(wgs_per_cu)])
+        out = subprocess.run(argv, input=inp, capture_output=True, text=True, check=True).stdout.splitlines()
         assert len(out) == len(cases)
         res = []
         for line in out:
@@ -127,7 +137,7 @@ def plan(tmp_path_factory):
             else:
                 f = line.split()
                 res.append(((f[0], int(f[1]), int(f[2]), int(f[3]), int(f[4])), (f[5], int(f[6]), int(f[7])),
-                            (int(f[8]), int(f[9]), int(f[10]), int(f[11]))))
+                            (int(f[8]), int(f[9]), int(f[10]), int(f[11])), dict(zip(GEOMETRY, map(int, f[12:])))))
         return res
     return run
 
@@ -257,3 +267,109 @@ def test_memory_rejection_starts_at_the_budget(plan):
     assert got[0][2][2] == 3
     got = plan([(3000, 1024, 1000, 1, 1100, 0, 0)], budget=slice_bytes(P) - 1)
     assert got[0][0] == "reject"
+
+
+# ---- every launch: grids, workgroup sizes, the bf16 scan's geometry, workspaces ----------------------------------------
+def old_launches(c, scan, fit, wgs_per_cu=1):
+    """What grad_mat_c computed beside the plan when it launched (scan, fit) for the call c, written from that function as
+    it was: (scan grid, scan workspace, fit grid, fit workspace) and the GEOMETRY fields."""
+    n_pts, k, n_q, order, n = c[:5]
+    P = k + 1 if order == 1 else k + k * (k + 1) // 2 + 1
+    geo = dict.fromkeys(GEOMETRY, 0)
+    if scan == "wide":                                    # three arrays per workgroup: list_d, cand_d, cand_i
+        geo.update(block=64 * 4, tiles=(n_q + 63) // 64)
+        scan_wgs = min(geo["tiles"], 2 * NUM_CUS)
+        scan_ws = scan_wgs * 64 * n * 8 + scan_wgs * 64 * 512 * 8 + scan_wgs * 64 * 512 * 4
+    else:                                                 # xt, by grad_transpose_kernel on (n_pts + 255) / 256 blocks
+        geo.update(ldt=(n_pts + 63) // 64 * 64, pts_wgs=(n_pts + 255) // 256)
+        scan_ws = geo["ldt"] * k * 8
+    if scan == "valu":
+        geo.update(block=64 * 4)
+        scan_wgs = (n_q + 16 - 1) // 16
+    elif scan == "mfma":
+        waves = 4 if knn_mfma_lds(k, n, 4) <= KMAX else 2
+        geo.update(block=64 * waves)
+        scan_wgs = (n_q + 16 * waves - 1) // (16 * waves)
+        scan_ws += n_pts * 8                              # pnorm
+    elif scan == "knn2":
+        s = 1 if k <= 32 else 2
+        nchunks = (n_pts + 63) // 64
+        nb = max(1, min(1024, (n_pts + 4095) // 4096))
+        geo.update(block=64 * 12, tiles=(n_q + 384 - 1) // 384, nchunks=nchunks, nb=nb, rpb=(n_pts + nb - 1) // nb)
+        scan_wgs = min(geo["tiles"], NUM_CUS * max(1, wgs_per_cu))
+        geo.update(pb=nchunks * s * 8192, pn=nchunks * 64 * 4 * 4, cand=scan_wgs * 384 * 256 * 4,
+                   list_d=scan_wgs * 384 * 128 * 8, list_i=scan_wgs * 384 * 128 * 4)
+        scan_ws += geo["pb"] + geo["pn"] + 64 * 8 + nb * 64 * 8 + geo["cand"] + geo["list_d"] + geo["list_i"]   # + mean, partial
+    if fit in ("lin", "lds"):
+        fit_wgs, fit_ws = n_q, 0
+    elif fit == "global":
+        fit_wgs = min(n_q, 2 * NUM_CUS)
+        fit_ws = fit_wgs * P * ((P + 1) | 1) * 8
+    else:
+        fit_wgs = min(n_q, NUM_CUS)
+        fit_ws = fit_wgs * ((P + 1) ** 2 + 2 * (P + 1)) * 8
+    return (scan_wgs, scan_ws, fit_wgs, fit_ws), geo
+
+
+# beyond the limits and forced (scan and fit wide, each alone, many query tiles), and the accepted grid's kernels with enough
+# queries that the persistent grids bind (1e6 / 384 = 2605 and 150000 / 384 = 391 bf16-scan tiles against 256 and 512)
+WIDE_ROWS = [(6000, 96, 10, 1, 101, 0, 0), (20000, 64, 1000, 1, 600, 0, 0), (300, 5, 10, 2, 30, 4, 2),
+             (20000, 64, 100000, 1, 80, 4, 0), (20000, 64, 10, 1, 80, 0, 2), (3000, 1024, 1000, 1, 1100, 0, 0)]
+MANY_QUERIES = [(1000000, 64, 1000000, 1, 80, 0, 0), (150000, 20, 150000, 1, 30, 0, 1), (9000, 5, 385, 1, 12, 3, 0),
+                (200000, 16, 1001, 1, 150, 0, 0), (200000, 64, 1001, 1, 130, 2, 0), (5000, 64, 1001, 1, 80, 1, 0),
+                (4000, 20, 1000, 2, 300, 1, 0), (4000, 20, 511, 2, 300, 1, 0), (400000, 33, 100000, 2, 600, 3, 0)]
+
+
+@pytest.mark.parametrize("wgs_per_cu", [None, 0, 1, 2])
+def test_every_launch_is_sized_by_the_plan(plan, wgs_per_cu):
+    cases = _accepted_grid() + WIDE_ROWS + MANY_QUERIES
+    got = plan(cases, wgs_per_cu=wgs_per_cu)
+    bad = []
+    for c, g in zip(cases, got):
+        assert g[0] != "reject", (c, g)
+        exp = old_launches(c, g[0][0], g[1][0], 1 if wgs_per_cu is None else wgs_per_cu)
+        if (g[2], g[3]) != exp:
+            bad.append((c, g, exp))
+    assert not bad, bad[:3]
+    kinds = {g[0][0] for g in got} | {g[1][0] for g in got}
+    assert kinds == {"valu", "mfma", "knn2", "wide", "lin", "lds", "global"}
+    # the knob binds: 2605 tiles on 256 or 512 workgroups, 391 tiles on 256 or all
+    big = {c: g[2][0] for c, g in zip(cases, got) if c in MANY_QUERIES[:2]}
+    assert list(big.values()) == ([512, 391] if wgs_per_cu == 2 else [256, 256])
+
+
+# The smallest call that reaches each instantiation the dispatch can select: (features k, neighbours, order, CORRLA_KNN,
+# CORRLA_FIT) on a 3000-point cloud with 64 queries -> (scan, waves, slices, steps, fit, tiles).  tests/test_gpu_grad_routes.py
+# runs every row on the device.
+ROUTES = [
+    ((6, 12, 1, 0, 0), ("valu", 0, 0, 0, "lin", 1)),
+    ((20, 30, 1, 0, 0), ("valu", 0, 0, 0, "lin", 2)),
+    ((40, 60, 1, 0, 0), ("valu", 0, 0, 0, "lin", 3)),
+    ((50, 60, 1, 0, 0), ("valu", 0, 0, 0, "lin", 4)),
+    ((64, 80, 1, 0, 0), ("valu", 0, 0, 0, "lin", 5)),
+    ((16, 150, 1, 2, 0), ("mfma", 4, 4, 0, "lin", 2)),
+    ((32, 140, 1, 2, 0), ("mfma", 4, 8, 0, "lin", 3)),
+    ((40, 60, 1, 2, 0), ("mfma", 4, 16, 0, "lin", 3)),
+    ((16, 200, 1, 2, 0), ("mfma", 2, 4, 0, "lin", 2)),
+    ((32, 200, 1, 2, 0), ("mfma", 2, 8, 0, "lin", 3)),
+    ((64, 130, 1, 2, 0), ("mfma", 2, 16, 0, "lin", 5)),
+    ((5, 12, 1, 3, 0), ("knn2", 0, 0, 1, "lin", 1)),
+    ((40, 50, 1, 3, 0), ("knn2", 0, 0, 2, "lin", 3)),
+    ((3, 14, 2, 0, 0), ("valu", 0, 0, 0, "lds", 0)),
+    ((5, 12, 1, 0, 1), ("valu", 0, 0, 0, "lds", 0)),
+    ((20, 300, 2, 1, 0), ("valu", 0, 0, 0, "global", 0)),
+    ((5, 30, 2, 4, 2), ("wide", 0, 0, 0, "wide", 0)),
+]
+
+
+def route_points(k, order):
+    return max(3000, k * (k + 3) // 2 + 100 if order == 2 else 0)
+
+
+def test_route_table_reaches_what_it_names(plan):
+    got = plan([(route_points(k, order), k, 64, order, n, km, fm) for (k, n, order, km, fm), _ in ROUTES])
+    for (c, exp), g in zip(ROUTES, got):
+        assert g[0] != "reject" and (g[0][0], g[0][1], g[0][2], g[0][3], g[1][0], g[1][1]) == exp, (c, g)
+    reached = {e[:4] for _, e in ROUTES} | {e[4:] for _, e in ROUTES}
+    assert reached >= {("mfma", w, s, 0) for w in (4, 2) for s in (4, 8, 16)} | {("knn2", 0, 0, 1), ("knn2", 0, 0, 2)}
+    assert reached >= {("lin", t) for t in range(1, 6)} | {("lds", 0), ("global", 0), ("wide", 0), ("valu", 0, 0, 0), ("wide", 0, 0, 0)}
