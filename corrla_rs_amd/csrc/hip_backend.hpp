@@ -14,6 +14,7 @@
 #include <random>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "core_svd_plan.hpp"
@@ -63,7 +64,8 @@ struct NcclType<double> {
 
 // the instantiations of a kernel over its column tiles (or planes, waves, ...): with_nt calls
 // f(std::integral_constant<int, n>) for one n in [N, MAX], with_one_of for one n of the listed values, for_each_nt for
-// every n in [N, MAX].  A value without an instantiation is an error, never another kernel.
+// every n in [N, MAX], for_each_of for every listed value (a list named once, as a std::integer_sequence, serves both
+// the launch and the LDS limits).  A value without an instantiation is an error, never another kernel.
 template <int MAX, int N = 1, class F>
 inline void with_nt(int n, const F& f) {
   if constexpr (N < MAX) {
@@ -77,10 +79,28 @@ inline void with_one_of(int n, const F& f) {
   if (!((n == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...))
     throw Error(ST_EINVAL, "internal: no kernel instantiation for " + std::to_string(n));
 }
+template <int... Vs, class F>
+inline void with_one_of(std::integer_sequence<int, Vs...>, int n, const F& f) {
+  with_one_of<Vs...>(n, f);
+}
 template <int MAX, int N = 1, class F>
 inline void for_each_nt(const F& f) {
   f(std::integral_constant<int, N>{});
   if constexpr (N < MAX) for_each_nt<MAX, N + 1>(f);
+}
+template <int... Vs, class F>
+inline void for_each_of(std::integer_sequence<int, Vs...>, const F& f) {
+  (f(std::integral_constant<int, Vs>{}), ...);
+}
+
+// Every kernel launched with more dynamic LDS than the default gets its limit once per device: a function attribute
+// applies to the device that is current when it is set (the HipDev constructor has made its own current).
+inline void lds_limit(const void* fn, size_t bytes) {
+  CORRLA_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
+namespace core_svd_stage {
+template <class T>
+void set_lds_limits();  // core_svd_stage.hpp: the core SVD's kernels
 }
 
 class HipDev {
@@ -115,8 +135,6 @@ class HipDev {
       entropy_ = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
     }
     no_device_chol_ = env_int("CORRLA_HOST_CHOL", 0) != 0;
-    jmc_min_l_ = env_int("CORRLA_JMC_MIN_L", 96);  // below: the single-workgroup ring kernel + replay is as fast (one launch)
-    jmc_max_b_ = std::min(32, std::max(2, env_int("CORRLA_JMC_MAX_B", 24)));
     robust_passes_ = std::max(2, env_int("CORRLA_ROBUST_PASSES", 2));
     robust_qr_ = env_int("CORRLA_DEVICE_ROBUST_QR", 1) != 0;  // 0: the round-1 optimistic CholeskyQR2 + host-controlled repeat
     gemm_debug_flags_ = env_int("CORRLA_GEMM_DEBUG", 0);  // timing-only ablations, results are wrong
@@ -734,20 +752,20 @@ class HipDev {
   void set_robust_passes(int n) { robust_passes_ = n; }
   // the core SVD of a call did not converge within the sweeps enqueued: enqueue 8 more from now on (false: at the cap)
   bool svd_more_sweeps() {
-    if (jmc_extra_sweeps_ >= 24) return false;
-    jmc_extra_sweeps_ += 8;
-    jmc_sweeps_hint_ = 0;
+    if (svd_state_.extra_sweeps >= 24) return false;
+    svd_state_.extra_sweeps += 8;
+    svd_state_.sweeps_hint = 0;
     return true;
   }
   // the W-only shortcut of the block Jacobi failed its verification: accumulate V from now on (false: already does)
   bool svd_force_v() {
-    if (jmc_force_v_) return false;
-    jmc_force_v_ = true;
+    if (svd_state_.force_v) return false;
+    svd_state_.force_v = true;
     return true;
   }
   // sweeps the last converged core SVD of this context used: the next call enqueues two more than that instead of the
   // default (the sweeps enqueued beyond convergence are launches that only test a flag: 15 x 4.6 us at C2)
-  void svd_sweeps_used(int n) { jmc_sweeps_hint_ = std::max(jmc_sweeps_hint_ - 1, n); }
+  void svd_sweeps_used(int n) { svd_state_.sweeps_hint = std::max(svd_state_.sweeps_hint - 1, n); }
   int* alloc_flags(int n) { return (int*)alloc_zeroed(sizeof(int) * (size_t)std::max(n, 1)); }
   void* alloc_zeroed_bytes(size_t bytes) { return alloc_zeroed(bytes); }
   void read_bytes(const void* dev_p, size_t bytes, void* host) {
@@ -792,8 +810,8 @@ class HipDev {
   int sharded_handshake(int local_status) {
     if (comm_size <= 1 && !(comm && env_int("CORRLA_FORCE_ALLREDUCE", 0))) return local_status;
     if (!comm) throw Error(ST_ECOMM, "communicator not initialised");
-    double h[8] = {(double)local_status, (double)robust_passes_, (double)jmc_extra_sweeps_, (double)jmc_sweeps_hint_,
-                   jmc_force_v_ ? 1.0 : 0.0, 0.0, 0.0, 0.0};
+    double h[8] = {(double)local_status, (double)robust_passes_, (double)svd_state_.extra_sweeps, (double)svd_state_.sweeps_hint,
+                   svd_state_.force_v ? 1.0 : 0.0, 0.0, 0.0, 0.0};
     double* d = (double*)alloc_bytes(sizeof(h));
     CORRLA_HIP(hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, stream));
     CORRLA_NCCL(ncclAllReduce(d, d, 8, ncclDouble, ncclMax, comm, stream));
@@ -802,9 +820,9 @@ class HipDev {
     CORRLA_HIP(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, stream));
     sync();
     robust_passes_ = (int)h[1];
-    jmc_extra_sweeps_ = (int)h[2];
-    jmc_sweeps_hint_ = (int)h[3];
-    jmc_force_v_ = h[4] != 0.0;
+    svd_state_.extra_sweeps = (int)h[2];
+    svd_state_.sweeps_hint = (int)h[3];
+    svd_state_.force_v = h[4] != 0.0;
     return (int)h[0];
   }
   void read_flags(const int* dev_p, int n, int* host) {
@@ -1000,234 +1018,9 @@ class HipDev {
   }
   int rank() const { return comm_rank; }
 
-  // ---- multi-workgroup block Jacobi (jacobi_mc_kernels.hpp) ------------------------------------------------
-  // lanes per Jacobi processor.  (8-lane processors -- half the waves for the same block pair, twice the column per
-  // lane -- measured 6 % slower at l = 138 f32: the rounds are bound by the per-lane column traffic, not by the
-  // rotation arithmetic they would amortise; the kernel keeps the template parameter, nothing instantiates 8.)
+  // SVD of the l x l core (random_svd.rs:89), defined in core_svd_stage.hpp with the launchers it switches into
   template <class T>
-  int jmc_lanes(int64_t) const {
-    return 16;
-  }
-  // geometry for an l x l core (core_svd_plan.hpp); false when it does not fit
-  template <class T>
-  bool jmc_geometry(int64_t l, int* nc_out, int* np_out, int* b_out) const {
-    return corrla::jmc_geometry(l, (int)sizeof(T), jmc_lanes<T>(l), jmc_max_b_, env_int("CORRLA_JMC_LOCAL", 1),
-                                env_int("CORRLA_JMC_NP", 0), nc_out, np_out, b_out);
-  }
-  template <class T, int NC>
-  void jmc_launch_step(int lanes, int np, int b, T* w, T* v, int nblocks, int step, int sweep, T tol, T tol_early, T floor2, k::JmcCtl* ctl) {
-    const size_t lds = k::jmc_lds_bytes(NC, b, sizeof(T), lanes);
-    const unsigned threads = (unsigned)((b * lanes + 63) / 64 * 64);
-    hipLaunchKernelGGL((k::jmc_step_kernel<T, NC, 16>), dim3((unsigned)np), dim3(threads), lds, stream, w, v, b, nblocks, step,
-                       sweep, step == 0 ? 1 : 0, tol, tol_early, floor2, ctl, jmc_local_);
-  }
-  // conv_status: device CholStatus record that receives the convergence verdict of the fixed number of sweeps
-  // enqueued without any synchronisation (the caller checks it later); nullptr: sweeps are enqueued in groups and the
-  // host waits for each group until the iteration has converged
-  template <class T>
-  void small_svd_mc(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev, void* conv_status) {
-    int nc = 0, np = 0, b = 0;
-    if (!jmc_geometry<T>(l, &nc, &np, &b)) throw Error(ST_EINVAL, "internal: core too large for the multi-workgroup Jacobi");
-    jmc_local_ = env_int("CORRLA_JMC_LOCAL", 1);  // 1: wave-local sub-block schedule (jacobi_mc_kernels.hpp), 0: ring schedule
-    // global column pitch = LDS column pitch: a block of b columns is one contiguous byte range in both
-    const int lanes = jmc_lanes<T>(l);
-    const int rp = k::jmc_pitch(nc, (int)sizeof(T), lanes), nblocks = 2 * np, ncols_pad = nblocks * b;
-    T* wj = (T*)alloc_bytes((size_t)rp * ncols_pad * sizeof(T));
-    T* vj = (T*)alloc_bytes((size_t)rp * ncols_pad * sizeof(T));
-    k::JmcCtl* ctl = (k::JmcCtl*)alloc_bytes(sizeof(k::JmcCtl));
-    k::CholStatus* st = conv_status ? (k::CholStatus*)conv_status : (k::CholStatus*)alloc_bytes(sizeof(k::CholStatus));
-    // optimistic calls (conv_status given) may use the W-only mode when the core is well conditioned; the
-    // host-controlled repeat always accumulates V
-    const int force_v = (conv_status == nullptr || jmc_force_v_ || env_int("CORRLA_JMC_FORCE_V", 0)) ? 1 : 0;
-    hipLaunchKernelGGL((k::jmc_init_kernel<T>), dim3(1), dim3(1024), 0, stream, (const T*)c.p, c.ld, (int)l, wj, vj, rp,
-                       ncols_pad, force_v, ctl);
-    const double eps = (double)std::numeric_limits<T>::epsilon();
-    const T tol = (T)(std::sqrt((double)l) * eps);
-    // The iteration ends with the sweep in which no pair exceeded sqrt(eps) (quadratic convergence).  Clustered
-    // singular values do not converge quadratically: the W / sigma factor of a 1.25e6 x 512 Gaussian sketch came out
-    // orthonormal to 6e-5 only.  Running to a sweep without any rotation costs two more sweeps; the driver instead
-    // re-orthonormalises that factor with one Cholesky-QR pass (a first-order (I + E)^-1/2 here), which is cheaper.
-    const T tol_early = env_int("CORRLA_JACOBI_STRICT", 0) ? tol : (T)std::sqrt(eps);
-    const T floor2 = (T)((double)l * eps * eps);  // squared norm of a numerically zero column (see the kernel)
-    auto enqueue_sweeps = [&](int s0, int s1) {
-      for (int sw = s0; sw < s1; ++sw)
-        for (int step = 0; step < nblocks - 1; ++step)
-          with_nt<9>(nc, [&](auto nc_c) {
-            jmc_launch_step<T, decltype(nc_c)::value>(lanes, np, b, wj, vj, nblocks, step, sw, tol, tol_early, floor2, ctl);
-          });
-      CORRLA_HIP(hipGetLastError());
-    };
-    const size_t lds_fin = (size_t)(l + 2) * sizeof(T) + (size_t)(l + 2) * sizeof(int) + 64;
-    auto finish = [&](int nsw) {
-      hipLaunchKernelGGL((k::jmc_finish_kernel<T>), dim3(1), dim3(1024), lds_fin, stream, (const T*)wj, (const T*)vj, rp, (int)l,
-                         nsw, (const k::JmcCtl*)ctl, m1.p, m1.ld, m2.p, m2.ld, s_dev, (int)k, st);
-      // W-only mode: the accumulated-rotation factor is recovered from the core itself (no-op otherwise)
-      const unsigned groups = (unsigned)(l * k);
-      hipLaunchKernelGGL((k::jmc_other_factor_kernel<T>), dim3((groups * 16 + 255) / 256), dim3(256), 0, stream, (const T*)c.p,
-                         c.ld, (int)l, (int)k, (const T*)m2.p, m2.ld, (const T*)s_dev, (const k::JmcCtl*)ctl, m1.p, m1.ld);
-      CORRLA_HIP(hipGetLastError());
-    };
-    if (conv_status) {
-      const int nsw_default = std::max(1, env_int("CORRLA_JMC_SWEEPS", sizeof(T) == 4 ? 10 : 13));
-      const int nsw = std::min(k::kJmcMaxSweeps, (jmc_sweeps_hint_ > 0 ? std::min(nsw_default, jmc_sweeps_hint_ + 2) : nsw_default) + jmc_extra_sweeps_);
-      enqueue_sweeps(0, nsw);
-      finish(nsw);
-      if (env_int("CORRLA_DEBUG", 0)) {
-        k::JmcCtl hd;
-        CORRLA_HIP(hipMemcpyAsync(&hd, ctl, sizeof(hd), hipMemcpyDeviceToHost, stream));
-        sync();
-        int used = 0;
-        while (used < nsw && hd.rot[used] && hd.big[used]) ++used;
-        std::fprintf(stderr, "[corrla] jacobi_svd (multi-workgroup, %d sweeps enqueued, %s) l=%d np=%d b=%d nc=%d sweeps run=%d rounds(wg0)=%llu "
-                             "cycles/round=%.0f ns/round=%.0f (%.0f MHz)\n", nsw, hd.with_v ? "V accumulated" : "W only", (int)l, np, b, nc, std::min(used + 1, nsw),
-                     hd.rounds, hd.rounds ? (double)hd.clk / hd.rounds : 0.0, hd.rounds ? 10.0 * hd.wall / hd.rounds : 0.0,
-                     hd.wall ? 100.0 * hd.clk / hd.wall : 0.0);
-        if (hd.steps)
-          std::fprintf(stderr, "[corrla]   per step (wg0, us): load %.2f norms %.2f rounds %.2f store %.2f total %.2f over %llu steps\n",
-                       0.01 * hd.t_load / hd.steps, 0.01 * hd.t_norm / hd.steps, 0.01 * hd.wall / hd.steps,
-                       0.01 * hd.t_store / hd.steps, 0.01 * hd.t_total / hd.steps, hd.steps);
-        if (hd.steps > 1)
-          std::fprintf(stderr, "[corrla]   span first-start..last-end over all workgroups: %.2f us per step\n",
-                       0.01 * hd.t_span / (hd.steps - 1));
-      }
-      return;
-    }
-    int done = 0;
-    k::JmcCtl h;
-    while (done < k::kJmcMaxSweeps) {
-      const int s1 = std::min(k::kJmcMaxSweeps, done + 8);
-      enqueue_sweeps(done, s1);
-      CORRLA_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, stream));
-      sync();
-      bool conv = false;
-      for (int s_ = 0; s_ < s1; ++s_) conv = conv || !(h.rot[s_] && h.big[s_]);
-      done = s1;
-      if (conv || h.bad) break;
-    }
-    if (h.bad) throw Error(ST_ENUMERIC, "non-finite core matrix in small SVD");
-    finish(done);
-    if (env_int("CORRLA_DEBUG", 0)) {
-      int used = 0;
-      while (used < done && h.rot[used] && h.big[used]) ++used;
-      std::fprintf(stderr, "[corrla] jacobi_svd (multi-workgroup) l=%d np=%d b=%d sweeps=%d\n", (int)l, np, b, used + 1);
-    }
-  }
-
-  // SVD of the l x l core (random_svd.rs:89): the kernel family core_svd_plan (core_svd_plan.hpp) picks for l and the
-  // knobs, read on every call.
-  template <class T>
-  void small_svd(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev, void* conv_status) {
-    // conv_status (optional): a device status record; kernels that run a FIXED number of sweeps report there
-    // whether they converged, the others (loop to convergence inside one launch) leave it cleared = converged
-    if (conv_status) memset_zero(conv_status, sizeof(k::CholStatus));
-    CoreSvdKnobs kn;
-    kn.mode = std::getenv("CORRLA_SVD");
-    kn.host_svd = env_int("CORRLA_HOST_SVD", 0) != 0;
-    kn.jmc_min_l = jmc_min_l_;
-    kn.jmc_max_b = jmc_max_b_;
-    kn.jmc_local = env_int("CORRLA_JMC_LOCAL", 1);
-    kn.jmc_np = env_int("CORRLA_JMC_NP", 0);
-    const CoreSvdPlan plan = core_svd_plan((int)sizeof(T), l, kn);
-    switch (plan.family) {
-      case CoreSvd::kMultiWg:
-        small_svd_mc(c, l, k, m1, m2, s_dev, conv_status);
-        return;
-      case CoreSvd::kHost:
-        small_svd_host(*this, c, l, k, m1, m2, s_dev);
-        return;
-      case CoreSvd::kBlock:
-        core_finite_check<T>(c, l, conv_status);
-        small_svd_block(c, l, k, m1, m2, s_dev);
-        return;
-      case CoreSvd::kRing:
-        core_finite_check<T>(c, l, conv_status);
-        small_svd_ring(c, l, k, m1, m2, s_dev, plan.ring_e);
-        return;
-    }
-  }
-  // The ring and block Jacobi kernels carry no status word: a non-finite core would come back as a triplet of zeros.
-  // One small launch scans the core first: optimistic runs find fail = 3 in the status record at the end of the call,
-  // host-controlled ones read the word now.
-  template <class T>
-  void core_finite_check(const Skinny<T>& c, int64_t l, void* conv_status) {
-    int* bad = conv_status ? nullptr : alloc_flags(1);
-    hipLaunchKernelGGL((k::core_finite_check_kernel<T>), dim3(1), dim3(1024), 0, stream, (const T*)c.p, c.ld, (int)l,
-                       (k::CholStatus*)conv_status, bad);
-    CORRLA_HIP(hipGetLastError());
-    if (bad) {
-      int h = 0;
-      read_flags(bad, 1, &h);
-      if (h) throw Error(ST_ENUMERIC, "non-finite core matrix in small SVD");
-    }
-  }
-
-  template <class T>
-  void small_svd_block(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev) {
-    const int nb = (int)(2 * ((l + 15) / 16));          // even number of 8-column blocks
-    const int cols_pad = nb * 8;
-    const int rows_pad = (int)round_up(l, 16);
-    const int64_t ld = rows_pad;
-    T* wj = (T*)alloc_bytes((size_t)ld * cols_pad * sizeof(T));
-    T* vj = (T*)alloc_bytes((size_t)ld * cols_pad * sizeof(T));
-    k::JacobiCtl* ctl = (k::JacobiCtl*)alloc_bytes(sizeof(k::JacobiCtl));
-    hipLaunchKernelGGL((k::jacobi_init_kernel<T>), dim3(64), dim3(256), 0, stream, (const T*)c.p, c.ld, (int)l, wj, ld, vj,
-                       ld, cols_pad, rows_pad, ctl);
-    const double eps = (double)std::numeric_limits<T>::epsilon();
-    const float tol_early = (float)std::sqrt(eps);
-    const size_t lds = (size_t)(2 * 16 * (rows_pad + 1) + 7 * 16 * 17 + 32) * sizeof(T) + 16 * sizeof(int) + 64;
-    const int max_sweeps = env_int("CORRLA_JACOBI_SWEEPS", 12), inner = env_int("CORRLA_JACOBI_INNER", 1);
-    for (int sw = 0; sw < max_sweeps; ++sw) {
-      for (int round = 0; round < nb - 1; ++round)
-        hipLaunchKernelGGL((k::jacobi_block_round_kernel<T>), dim3(nb / 2), dim3(256), lds, stream, wj, ld, vj, ld, rows_pad,
-                           nb, round, inner, ctl);
-      hipLaunchKernelGGL(k::jacobi_sweep_end_kernel, dim3(1), dim3(1), 0, stream, ctl, tol_early);
-    }
-    const size_t lds_fin = (size_t)(l + 2) * sizeof(T) + (size_t)(l + 2) * sizeof(int) + 64;
-    hipLaunchKernelGGL((k::jacobi_finish_kernel<T>), dim3(1), dim3(1024), lds_fin, stream, (const T*)wj, ld, (const T*)vj,
-                       ld, (int)l, m1.p, m1.ld, m2.p, m2.ld, s_dev, (int)k);
-    CORRLA_HIP(hipGetLastError());
-    if (env_int("CORRLA_DEBUG", 0)) {
-      k::JacobiCtl h;
-      CORRLA_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, stream));
-      sync();
-      std::fprintf(stderr, "[corrla] block jacobi l=%d nb=%d sweeps=%u done=%u\n", (int)l, nb, h.sweeps, h.done);
-    }
-  }
-
-  // single-workgroup ring Jacobi: W in registers, 8 lanes x e rows per column (jacobi_ring_w_kernel), then V from the
-  // recorded rotations (jacobi_replay_v_kernel)
-  template <class T>
-  void small_svd_ring(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev, int e) {
-    int* info = (int*)alloc_bytes(sizeof(int) * 4);
-    const double eps = (double)std::numeric_limits<T>::epsilon();
-    const T tol = (T)(std::sqrt((double)l) * eps);
-    // quadratic convergence: a sweep that starts below sqrt(eps) ends below tol -- except for clustered singular
-    // values, whose W / sigma factor the driver re-orthonormalises afterwards (see small_svd_mc)
-    const T tol_early = env_int("CORRLA_JACOBI_STRICT", 0) ? tol : (T)std::sqrt(eps);
-    const size_t ring_lds = k::jacobi_ring_w_lds_bytes((int)l, 8 * e, sizeof(T));
-    const int np = (int)((l + 1) / 2);
-    const dim3 block((unsigned)(np * 8));  // a partial last wave: no idle processors, no LDS slots for them
-    const int max_sw = env_int("CORRLA_JACOBI_SWEEPS", 40);
-    const int n2 = 2 * np;
-    k::RotEntry<T>* rot = (k::RotEntry<T>*)alloc_bytes((size_t)max_sw * n2 * k::kRingProcPad * sizeof(k::RotEntry<T>));
-    int* rank_g = (int*)alloc_bytes(sizeof(int) * (size_t)n2);
-    constexpr int kBigE = sizeof(T) == 4 ? 20 : 18;
-    with_one_of<8, 12, 16, kBigE>(e, [&](auto ee) {
-      hipLaunchKernelGGL((k::jacobi_ring_w_kernel<T, decltype(ee)::value, 8>), dim3(1), block, ring_lds, stream, (const T*)c.p, c.ld,
-                         (int)l, m2.p, m2.ld, s_dev, (int)k, tol, tol_early, max_sw, rot, rank_g, info);
-    });
-    CORRLA_HIP(hipGetLastError());
-    hipLaunchKernelGGL((k::jacobi_replay_v_kernel<T>), dim3((unsigned)((l + 256 / k::kReplayLanes - 1) / (256 / k::kReplayLanes))), dim3(256), 0,
-                       stream,
-                       (const k::RotEntry<T>*)rot, (const int*)info, (const int*)rank_g, (int)l, (int)k, m1.p, m1.ld);
-    CORRLA_HIP(hipGetLastError());
-    if (env_int("CORRLA_DEBUG", 0)) {
-      int h[4] = {0, 0, 0, 0};
-      CORRLA_HIP(hipMemcpyAsync(h, info, sizeof(int), hipMemcpyDeviceToHost, stream));
-      sync();
-      std::fprintf(stderr, "[corrla] jacobi_svd (ring) l=%d sweeps=%d\n", (int)l, h[0]);
-    }
-  }
+  void small_svd(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, Skinny<T>& m2, T* s_dev, void* conv_status);
   // skinny (rows x ncols) -> column-major destination, optionally transposed (ncols x rows)
   template <class T>
   void copy_out(const Skinny<T>& src, int64_t ncols, T* dst, int64_t ldd, bool transpose, bool to_host) {
@@ -1447,28 +1240,23 @@ class HipDev {
   GemmKnobs gemm_knobs_;
   uint64_t entropy_ = 0, calls_ = 0, calls_sharded_ = 0;
   bool no_device_chol_ = false;
-  int jmc_min_l_ = 96, jmc_max_b_ = 24, jmc_local_ = 1;
   const int* run_if_ = nullptr;
   bool phase_events_ = true;
   bool robust_qr_ = true;
   int robust_passes_ = 2;
-  int jmc_extra_sweeps_ = 0, jmc_sweeps_hint_ = 0;
-  bool jmc_force_v_ = false;
+  CoreSvdState svd_state_;  // core_svd_plan.hpp
 
   static void check_grid(const dim3& g) {
     if (g.y > 65535u || g.z > 65535u) throw Error(ST_EINVAL, "problem too large for the launch grid");
   }
 
-  // ---- dynamic-LDS limits ----
-  // Every kernel launched with more dynamic LDS than the default gets its limit here, once per device: a function
-  // attribute applies to the device that is current when it is set (the constructor has made this one current).
-  static void lds_limit(const void* fn, size_t bytes) {
-    CORRLA_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  }
+  // ---- dynamic-LDS limits (lds_limit) ----
   static void set_lds_limits() {
     constexpr size_t kMax = k::kLdsMaxBytes;
     set_lds_limits_typed<float>();
     set_lds_limits_typed<double>();
+    core_svd_stage::set_lds_limits<float>();
+    core_svd_stage::set_lds_limits<double>();
     set_ata_limits<2>();
     set_ata_limits<4>();
     set_ata_limits<8>();
@@ -1511,13 +1299,6 @@ class HipDev {
     lds_limit((const void*)k::hh_tree_factor_kernel<T, true>, kMax);
     lds_limit((const void*)k::hh_tree_apply_kernel<T, true>, kMax);
     lds_limit((const void*)k::hh_leaf_apply_kernel<T, true>, kMax);
-    constexpr int kBigE = sizeof(T) == 4 ? 20 : 18;  // core SVD kernels
-    lds_limit((const void*)k::jacobi_ring_w_kernel<T, 8, 8>, kMax);
-    lds_limit((const void*)k::jacobi_ring_w_kernel<T, 12, 8>, kMax);
-    lds_limit((const void*)k::jacobi_ring_w_kernel<T, 16, 8>, kMax);
-    lds_limit((const void*)k::jacobi_ring_w_kernel<T, kBigE, 8>, kMax);
-    lds_limit((const void*)k::jacobi_block_round_kernel<T>, kMax);
-    for_each_nt<9>([](auto nc) { lds_limit((const void*)k::jmc_step_kernel<T, decltype(nc)::value, 16>, k::kLdsMaxBytes); });
   }
   template <class T, int NT>
   static void set_gemm_limits() {

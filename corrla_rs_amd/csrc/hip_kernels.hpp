@@ -1067,7 +1067,6 @@ __device__ __forceinline__ double ring_sum(double x) {
   x += dpp(x, std::integral_constant<int, 0x141>{});
   return x;
 }
-constexpr int kRingProcPad = 72;  // processors per stream row (padded)
 template <class T>
 struct RotEntry {
   T cs, sn;
@@ -1289,7 +1288,6 @@ __global__ __launch_bounds__(kRingProcPad * G) void jacobi_ring_w_kernel(const T
 // columns swap positions); in odd rounds positions n - 1 and 0 are idle and position 0 changes sign (the pseudo
 // pair of the last processor).
 constexpr int kReplayChunk = 16;  // rounds staged in LDS at a time
-constexpr int kReplayLanes = 16;  // lanes per row of V (one DPP row): 10 line positions per lane (32 lanes: 6)
 // value of the previous / next lane inside the 16-lane DPP row (the 8-lane groups are row-aligned)
 __device__ __forceinline__ float dpp_from_prev(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x111, 0xf, 0xf, true));

@@ -39,7 +39,6 @@
 namespace corrla {
 namespace k {
 
-constexpr int kJmcMaxSweeps = 40;
 constexpr float kJmcFastCond = 16.f;   // W-only mode when max |diag| <= 16 min |diag| ...
 constexpr float kJmcVerifyCond = 64.f; // ... and accepted when the computed sigma_max <= 64 sigma_min
 struct JmcCtl {
