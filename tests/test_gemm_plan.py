@@ -6,7 +6,13 @@ choose_geometry, launch_tall, launch_one / launch_mw and gemm_mixed_f32, knobs r
 independently of gemm_plan.  Each case compares the family, the instantiation, every launch's grid, column base, XCD remap
 and dynamic LDS, the reduction split, rotation, written columns, the slab reduction and its workspace, the tall-Gram
 grouping and the bf16 planes, or the rejection.  (The retired exact variant of the bf16-split skeleton, np = 0 under
-CORRLA_GEMM_WIDE, was off by default and is not part of the table.)"""
+CORRLA_GEMM_WIDE, was off by default and is not part of the table.)
+
+ROUTES / GRAM_ROUTES at the end are the calls of tests/test_gpu_gemm_routes.py, which multiplies each against a reference on
+the GPU: one Context.matmul (or, for the aliased Gram kernels, one power_iter) per instantiation launch_gemm can dispatch and
+per feature of a launch.  Pinned here: every row's plan has the properties the row names, all 90 general and 16 aliased
+instantiations and every feature of FEATURES occur, the knob names are the ones a context reads, and the integer operands
+of the exact check tell neighbouring tiles and columns apart."""
 import itertools
 import os
 import subprocess
@@ -454,3 +460,262 @@ def test_every_family_and_boundary_is_reached(plan):
     assert any(f[10] == "1" for f in general)                      # XCD remap of the first launch
     assert any(f[5 + 7 * int(f[4]) + 4] == "1" for f in general)  # rotate
     assert any(int(f[5]) < int(f[5 + 7 * int(f[4]) + 3]) for f in general)  # persistent: fewer workgroups than tiles
+
+
+# ---- the routes the GPU test runs (tests/test_gpu_gemm_routes.py) ------------------------------------------------------
+# environment variable of each knob (hip_backend.hpp reads them when a context is created)
+KNOB_ENV = {"CORRLA_SPLIT_NN": "split_nn", "CORRLA_SPLIT_TN": "split_tn", "CORRLA_MW": "mw", "CORRLA_GEMM_XCD": "xcd_remap",
+            "CORRLA_TALL_MIN_ROWS": "tall_min_rows", "CORRLA_GEMM_PERSIST_TILES": "persist_max_tiles",
+            "CORRLA_F64_WAVES": "f64_waves", "CORRLA_MIXED_MIN_WORK": "mixed_min_work", "CORRLA_EVEN_BLOCKS": "even_blocks",
+            "CORRLA_NO_GRAM_ALIAS": "no_gram_alias", "CORRLA_GEMM_NO_ROTATE": "no_rotate", "CORRLA_MIXED_SPLIT": "mixed_split"}
+
+
+def matmul_shape(esz, m, n, l, trans, num_cus=256):
+    """The product of Context.matmul(a, x, trans) on a row-major m x n device matrix with l columns (capi_impl.hpp:
+    stage_input, product_body): A is read in place when its rows are whole 16-byte vectors, else from a copy with a
+    64-element leading dimension; the skinny operand and the result are padded work matrices."""
+    a = big(m, n, ld=n if n % (16 // esz) == 0 else round_up(n, 64))
+    xin, xout = (m, n) if trans else (n, m)
+    return shape(trans, esz, a, skinny(xin, l), skinny(xout, l), num_cus=num_cus)
+
+
+def parse(line):
+    """a line of the printer (general / gram_alias) as a dict"""
+    f = line.split()
+    assert f[0] in ("general", "gram_alias"), line
+    p = dict(family=f[0], mw=int(f[1]), nw=int(f[2]), block=int(f[3]), nlaunch=int(f[4]), launches=[])
+    at = 5
+    for _ in range(p["nlaunch"]):
+        g = [int(v) for v in f[at:at + 7]]
+        p["launches"].append(dict(grid=tuple(g[:3]), nt=g[3], col_base=g[4], xcd_remap=g[5], lds=g[6]))
+        at += 7
+    for name in ("tiles_total", "nsplit", "tiles_per_split", "outer_blocks", "rotate", "vec_store", "out_cols", "slab_stride",
+                 "slab_bytes"):
+        p[name] = int(f[at])
+        at += 1
+    p["reduce"] = f[at]
+    return p
+
+
+def reached(p):
+    """what a plan reaches, in the words of the `expect` column of ROUTES"""
+    gw = p["mw"] * p["nw"] // 4  # row tiles per SIMD: the LDS ring is sized for the 64 * gw outer tile
+    ls = p["launches"]
+    r = dict(family=p["family"], mw=p["mw"], nw=p["nw"], nt=tuple(g["nt"] for g in ls), nlaunch=p["nlaunch"], reduce=p["reduce"],
+             persistent=ls[0]["grid"][0] < p["outer_blocks"], rotate=p["rotate"], xcd_remap=tuple(g["xcd_remap"] for g in ls),
+             col_base=tuple(g["col_base"] for g in ls), nsplit=p["nsplit"], tiles_total=p["tiles_total"],
+             tiles_per_split=p["tiles_per_split"], outer_blocks=p["outer_blocks"],
+             empty_slabs=(p["nsplit"] * p["tiles_per_split"] - p["tiles_total"]) // max(1, p["tiles_per_split"]))
+    if p["family"] == "general":
+        r["stages"] = tuple(gemm_stages(gw, g["nt"]) for g in ls)
+        r["short_ring"] = tuple(g["lds"] < gemm_stages(gw, g["nt"]) * stage_bytes(gw, g["nt"]) for g in ls)
+    return r
+
+
+def _expect(mw, nw, nt, reduce="none", persistent=False, rotate=0, xcd_remap=0, stages=None, short_ring=False, **more):
+    """`expect` of a row: the instantiation, the NT / XCD remap / ring depth / shortened ring of each launch, the reduction
+    kind, persistence and rotation; `more` names what a feature row is there for (nsplit, tiles_total, ...)"""
+    nt = nt if isinstance(nt, tuple) else (nt,)
+    per = lambda v: v if isinstance(v, tuple) else (v,) * len(nt)
+    gw = mw * nw // 4
+    return dict(more, family="general", mw=mw, nw=nw, nt=nt, nlaunch=len(nt), reduce=reduce, persistent=persistent, rotate=rotate,
+                xcd_remap=per(xcd_remap), stages=per(stages) if stages else tuple(gemm_stages(gw, t) for t in nt),
+                short_ring=per(short_ring))
+
+
+EXPECT_KEYS = ("family", "mw", "nw", "nt", "nlaunch", "reduce", "persistent", "rotate", "xcd_remap", "stages", "short_ring")
+F64_W4 = {"CORRLA_F64_WAVES": 4}
+
+
+def _routes():
+    """(name, esz, m, n, l, trans, knobs, expect): Context.matmul(a, x, trans) on a row-major m x n matrix, x with l columns.
+    Ragged on purpose: l = 16 NT - 3 leaves 13 of 16 columns in the last column tile, and neither the outer nor the
+    reduction dimension is a multiple of its tile."""
+    rows = []
+    for esz in (4, 8):
+        for trans in (False, True):
+            tag = "f%d-%s" % (8 * esz, "tn" if trans else "nn")
+            for nt in range(1, 10):
+                l = 16 * nt - 3
+                # small: the 64-index tile on four waves, 3 / 4 outer tiles, 3 .. 7 reduction tiles, one slab
+                rows.append(("small-%s-nt%d" % (tag, nt), esz, 150, 200, l, trans, {},
+                             _expect(1, 4, nt, rotate=int(not trans), stages=3)))
+                # mid: the 128-index tile (f32 MW 2; f64 eight waves, or MW 2 under CORRLA_F64_WAVES=4), 5 outer tiles,
+                # the 3-stage ring up to NT = 5 and the 2-stage ring beyond, the plain reduction of 2 (f32) / 4 (f64) slabs
+                wide = dict(reduce="plain", rotate=int(not trans), stages=3 if nt <= 5 else 2, nsplit=2 if esz == 4 else 4)
+                rows.append(("mid-%s-nt%d" % (tag, nt), esz, 520, 520, l, trans, {},
+                             _expect(2 if esz == 4 else 1, 4 if esz == 4 else 8, nt, **wide)))
+                if esz == 8:
+                    rows.append(("mid-w4-%s-nt%d" % (tag, nt), esz, 520, 520, l, trans, F64_W4, _expect(2, 4, nt, **wide)))
+    for trans in (False, True):
+        tag, rot = "tn" if trans else "nn", int(not trans)
+        # uneven column blocking (outer x red x cols_alloc >= 1e10): the second launch runs NT - 1 from column n_wide * NT * 16
+        rows += [
+            ("uneven-f32-%s-9+8" % tag, 4, 6100, 6000, 266, trans, {},
+             _expect(2, 4, (9, 8), reduce="deep", persistent=True, rotate=rot, stages=2, col_base=(0, 144), nsplit=12)),
+            ("uneven-f64-%s-9+8" % tag, 8, 6100, 6000, 266, trans, {},
+             _expect(1, 8, (9, 8), reduce="deep", persistent=True, rotate=rot, stages=2, col_base=(0, 144), nsplit=12)),
+            # one product on a 2-stage and a 3-stage ring
+            ("uneven-f32-%s-6+5" % tag, 4, 8000, 8000, 170, trans, {},
+             _expect(2, 4, (6, 5), reduce="deep", persistent=True, rotate=rot, stages=(2, 3), col_base=(0, 96), nsplit=10)),
+            ("uneven-f64-%s-7+6" % tag, 8, 7000, 7100, 200, trans, {},
+             _expect(1, 8, (7, 6), reduce="deep", persistent=False, rotate=rot, stages=2, col_base=(0, 112), nsplit=10)),
+        ]
+    rows += [
+        # persistent launches: fewer workgroups than outer tiles, the ring runs on across the tile boundaries
+        ("persist-f32-nn", 4, 100037, 72, 13, False, {}, _expect(1, 4, 1, persistent=True, rotate=1, outer_blocks=1564)),
+        ("persist-f64-nn", 8, 100037, 72, 141, False, {}, _expect(1, 4, 9, persistent=True, rotate=1, outer_blocks=1564)),
+        ("persist-f32-nn-wide", 4, 99000, 520, 141, False, {}, _expect(2, 4, 9, persistent=True, rotate=1, outer_blocks=774)),
+        # 100 rows, not 72: on 96 or fewer rows A^T Y with 100037 outer indices belongs to the register-resident kernels
+        ("persist-f32-tn", 4, 100, 100037, 29, True, {}, _expect(1, 4, 2, persistent=True, outer_blocks=1564)),
+        # persistent and deep reduction together: 65 tiles in 64 slabs of 2, so 31 slabs have no tile at all
+        ("persist-deep-f32-nn", 4, 1600, 4100, 61, False, {"CORRLA_SPLIT_NN": 64},
+         _expect(2, 4, 4, reduce="deep", persistent=True, rotate=1, nsplit=64, tiles_total=65, tiles_per_split=2, empty_slabs=31)),
+        # XCD remap: 9 outer tiles x 58 slabs; 3 outer tiles x 11 slabs (neither a multiple of 8)
+        ("xcd-f64-tn", 8, 30000, 1100, 141, True, {},
+         _expect(1, 8, 9, reduce="deep", xcd_remap=1, nsplit=58, outer_blocks=9, empty_slabs=2)),
+        ("xcd-f32-tn", 4, 40000, 190, 77, True, {"CORRLA_SPLIT_TN": 11},
+         _expect(1, 4, 5, reduce="deep", xcd_remap=1, nsplit=11, outer_blocks=3)),
+        # an nn product that does not rotate although its workgroups walk many tiles (more than 32 per split)
+        ("norotate-f32-nn", 4, 300, 2200, 45, False, {"CORRLA_SPLIT_NN": 1}, _expect(2, 4, 3, tiles_per_split=35, nsplit=1)),
+        ("norotate-f64-nn", 8, 300, 1100, 45, False, {"CORRLA_SPLIT_NN": 1}, _expect(1, 8, 3, tiles_per_split=35, nsplit=1)),
+        # a split whose last slabs are empty: 79 tiles in 19 slabs of 5 (3 empty), 157 in 39 of 5 (7 empty)
+        ("emptyslab-f32-tn", 4, 5000, 36, 74, True, {}, _expect(1, 4, 5, reduce="deep", nsplit=19, tiles_per_split=5, empty_slabs=3)),
+        ("emptyslab-f64-tn", 8, 5000, 36, 74, True, {}, _expect(1, 4, 5, reduce="deep", nsplit=39, tiles_per_split=5, empty_slabs=7)),
+        # one reduction tile, unsplit: the launch asks for one slot of the ring
+        ("onetile-f32-nn", 4, 150, 60, 13, False, {}, _expect(1, 4, 1, short_ring=True, tiles_total=1, nsplit=1)),
+        ("onetile-f64-nn", 8, 150, 30, 13, False, {}, _expect(1, 4, 1, short_ring=True, tiles_total=1, nsplit=1)),
+        ("onetile-f32-tn", 4, 60, 150, 13, True, {}, _expect(1, 4, 1, short_ring=True, tiles_total=1, nsplit=1)),
+        ("onetile-f64-tn", 8, 30, 150, 13, True, {}, _expect(1, 4, 1, short_ring=True, tiles_total=1, nsplit=1)),
+        # two reduction tiles: two slots of the 3-stage ring, and the rotation starts half the workgroups on the second
+        ("twotiles-f32-nn", 4, 150, 100, 29, False, {}, _expect(1, 4, 2, rotate=1, short_ring=True, tiles_total=2)),
+        ("twotiles-f64-nn", 8, 150, 50, 29, False, {}, _expect(1, 4, 2, rotate=1, short_ring=True, tiles_total=2)),
+    ]
+    return rows
+
+
+ROUTES = _routes()
+
+# (name, esz, rows, l, knobs, expect): G = Y^T Y of the rows x l sketch of power_iter (the third of products()); the aliased
+# instantiations gemm_nn_kernel<T, 2, NT, true> by default, the general kernels under CORRLA_NO_GRAM_ALIAS=1
+GRAM_ROWS, GRAM_COLS = 700, 150
+GRAM_ROUTES = [("gram-f%d-nt%d-%s" % (8 * esz, nt, "general" if knobs else "alias"), esz, GRAM_ROWS, 16 * nt - 3, knobs,
+                dict(family="general", mw=1, nw=4, nt=(nt,)) if knobs else dict(family="gram_alias", mw=2, nw=4, nt=(nt,)))
+               for esz in (4, 8) for nt in range(1, 9) for knobs in ({}, {"CORRLA_NO_GRAM_ALIAS": 1})]
+
+# what the table must reach besides every instantiation, in the element types named
+FEATURES = {
+    "3-stage ring of the 128-index tile": ((4, 8), lambda row, r: r["mw"] * r["nw"] == 8 and 3 in r["stages"]),
+    "2-stage ring of the 128-index tile": ((4, 8), lambda row, r: r["mw"] * r["nw"] == 8 and 2 in r["stages"]),
+    "a 2-stage and a 3-stage launch in one product": ((4,), lambda row, r: r["stages"] == (2, 3)),
+    "shortened ring": ((4, 8), lambda row, r: any(r["short_ring"])),
+    "uneven blocking, nn": ((4, 8), lambda row, r: not row[5] and r["nlaunch"] == 2 and r["col_base"][1] != 0),
+    "uneven blocking, tn": ((4, 8), lambda row, r: row[5] and r["nlaunch"] == 2 and r["col_base"][1] != 0),
+    "uneven blocking, not persistent": ((8,), lambda row, r: r["nlaunch"] == 2 and not r["persistent"]),
+    "persistent, nn": ((4, 8), lambda row, r: not row[5] and r["persistent"]),
+    "persistent, tn": ((4, 8), lambda row, r: row[5] and r["persistent"]),
+    "persistent on the 128-index tile, one launch": ((4,), lambda row, r: r["persistent"] and r["mw"] == 2 and r["nlaunch"] == 1),
+    "persistent with the deep reduction": ((4, 8), lambda row, r: r["persistent"] and r["reduce"] == "deep"),
+    "no reduction": ((4, 8), lambda row, r: r["reduce"] == "none"),
+    "plain reduction": ((4, 8), lambda row, r: r["reduce"] == "plain"),
+    "deep reduction": ((4, 8), lambda row, r: r["reduce"] == "deep"),
+    "XCD remap": ((4, 8), lambda row, r: any(r["xcd_remap"])),
+    "XCD remap, outer tiles and slabs no multiples of 8": ((4, 8), lambda row, r: any(r["xcd_remap"]) and r["outer_blocks"] % 8 and r["nsplit"] % 8),
+    "rotation": ((4, 8), lambda row, r: r["rotate"] == 1),
+    "nn without rotation on more than one tile per split": ((4, 8), lambda row, r: not row[5] and not r["rotate"] and r["tiles_per_split"] > 1),
+    "empty last slabs": ((4, 8), lambda row, r: r["empty_slabs"] >= 1),
+    "one tile, unsplit": ((4, 8), lambda row, r: r["tiles_total"] == 1 and r["nsplit"] == 1),
+}
+
+
+def route_a(i, j):
+    """Integer test operand A[i, j] in [-3, 3] (i and j: integer index arrays that broadcast, numpy or torch): not
+    symmetric, and row i differs from rows i + 64 and i + 128 -- and column j from columns j + 64 and j + 128 -- in most
+    entries, so a result computed from the neighbouring 64-index tile cannot pass."""
+    return (3 * i + j + (i * j) % 1013 + (i // 64) * (j % 5)) % 7 - 3
+
+
+def route_x(r, c):
+    """Integer skinny operand X[r, c] in [-4, 4]: every column differs from every other within the first 16 rows."""
+    return ((r + 1) * (c + 1) + (r // 3) * (c // 7) + (r // 5) * (c // 63) + c // 9) % 9 - 4
+
+
+def _plans(plan, table, shape_of):
+    cases = [(shape_of(row), dict(DEFAULT_KNOBS, **{KNOB_ENV[k]: v for k, v in row[-2].items()})) for row in table]
+    got = plan(cases)
+    assert len(got) == len(table)
+    return [reached(parse(g)) for g in got]
+
+
+def _route_plans(plan):
+    return _plans(plan, ROUTES, lambda row: matmul_shape(*row[1:6]))
+
+
+def _gram_plans(plan):
+    return _plans(plan, GRAM_ROUTES, lambda row: products(row[1], row[2], GRAM_COLS, row[3], 256)[2])
+
+
+def test_every_route_reaches_what_it_names(plan):
+    for table, plans in ((ROUTES, _route_plans(plan)), (GRAM_ROUTES, _gram_plans(plan))):
+        assert len({row[0] for row in table}) == len(table)
+        for row, r in zip(table, plans):
+            expect = row[-1]
+            if table is ROUTES:
+                assert set(EXPECT_KEYS) <= set(expect), row[0]
+                assert 12 * max(row[2], row[3]) < 1 << 24, row[0]             # the GPU test's integer sums are exact in f32
+                # operand bytes: "about 300 MB", with room for the largest shape first proposed, 7000 x 7100 in f64 (398 MB)
+                assert row[1] * row[2] * row[3] <= 400e6, row[0]
+            assert {k: r[k] for k in expect} == expect, (row[0], r)
+
+
+def test_the_route_table_is_complete(plan):
+    """every instantiation launch_general and the alias launch can dispatch (hip_backend.hpp), every feature in FEATURES"""
+    plans = _route_plans(plan)
+    seen = {(row[1], bool(row[5]), r["mw"], r["nw"], nt) for row, r in zip(ROUTES, plans) for nt in r["nt"]}
+    # launch_general: if constexpr (NW == 4 || (NW == 8 && MW == 1 && T is double)), NT 1 .. kMaxColTiles, nn and tn
+    want = {(esz, tn, mw, nw, nt) for esz in (4, 8) for tn in (False, True) for mw in (1, 2) for nw in (4, 8)
+            if nw == 4 or (nw == 8 and mw == 1 and esz == 8) for nt in range(1, 10)}
+    assert len(want) == 90
+    assert not want - seen, sorted(want - seen)
+    assert not seen - want, sorted(seen - want)
+    for name, (types, hit) in FEATURES.items():
+        for esz in types:
+            assert any(row[1] == esz and hit(row, r) for row, r in zip(ROUTES, plans)), (name, esz)
+    gram = _gram_plans(plan)
+    alias = {(row[1], r["nt"][0]) for row, r in zip(GRAM_ROUTES, gram) if r["family"] == "gram_alias"}
+    assert alias == {(esz, nt) for esz in (4, 8) for nt in range(1, 9)}   # gemm_nn_kernel<T, 2, NT, true>, NT 1 .. 8
+    # ... and each has its twin on the general kernels, which the route table above covers
+    twins = {(row[1], r["mw"], r["nw"], r["nt"][0]) for row, r in zip(GRAM_ROUTES, gram) if r["family"] == "general"}
+    assert {(e, nt) for e, _, _, nt in twins} == alias
+    assert {(e, False, mw, nw, nt) for e, mw, nw, nt in twins} <= seen
+
+
+def test_route_knobs_are_the_ones_a_context_reads():
+    import re
+    src = open(os.path.join(ROOT, "corrla_rs_amd", "csrc", "hip_backend.hpp")).read()
+    # a statement that assigns a knob names the variable it reads, before (getenv) or after (env_int) the assignment
+    read = {}
+    for stmt in src.split(";"):
+        knob, env = re.search(r"gemm_knobs_\.(\w+)\s*=[^=]", stmt), re.findall(r'"(CORRLA_\w+)"', stmt)
+        if knob and len(env) == 1:
+            read[env[0]] = knob.group(1)
+    assert read == KNOB_ENV
+    assert set(KNOB_ENV.values()) == set(KNOB_NAMES)
+
+
+def test_route_operands_tell_tiles_and_columns_apart():
+    """the integer operands of the GPU test: value ranges, distinct columns of X within the shortest reduction, rows and
+    columns of A 64 and 128 apart that differ in most of the entries the shortest reduction of the table reads"""
+    import numpy as np
+    red = min(row[2] if row[5] else row[3] for row in ROUTES)
+    lmax = max(row[4] for row in ROUTES)
+    assert red >= 16  # route_x tells its columns apart within 16 rows
+    i, j = np.arange(1100)[:, None], np.arange(1100)[None, :]
+    a = route_a(i, j)
+    assert a.min() == -3 and a.max() == 3 and np.mean(a != a.T) > 0.8
+    for d in (64, 128):
+        assert np.mean(a[:-d, :red] != a[d:, :red], axis=1).min() > 0.5
+        assert np.mean(a[:red, :-d] != a[:red, d:], axis=0).min() > 0.5
+    x = route_x(np.arange(16)[:, None], np.arange(lmax)[None, :])
+    assert x.min() == -4 and x.max() == 4
+    assert len({tuple(col) for col in x.T}) == lmax
