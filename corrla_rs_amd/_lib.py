@@ -20,11 +20,13 @@ POWER_FUSED = 0x20
 SHARD_COLS = 0x40
 SKETCH_BF16X3 = 0x80
 SKETCH_BF16X6 = 0x100
+PCA_STANDARDIZE = 0x200
 UNIQUE_ID_BYTES = 128
 
 
 class Opts(C.Structure):
-    _fields_ = [("struct_size", u32), ("flags", u32), ("seed", u64), ("omega", vp), ("omega_ld", i64)]
+    _fields_ = [("struct_size", u32), ("flags", u32), ("seed", u64), ("omega", vp), ("omega_ld", i64),
+                ("scales_out", vp)]
 
 
 class Timings(C.Structure):

@@ -143,6 +143,13 @@ def _f32_like(a):
     return np.empty(0, dtype=np.float32)
 
 
+def _check_standardize(v):
+    """standardize is a switch: anything but a bool (a tolerance, a vector of scales, "yes") is a mistake, not a truth value"""
+    if not isinstance(v, (bool, np.bool_)):
+        raise TypeError(f"standardize must be True or False, got {type(v).__name__}")
+    return bool(v)
+
+
 def _ptr(t):
     return t.data_ptr() if _is_torch(t) else t.ctypes.data
 
@@ -350,22 +357,26 @@ class Context:
         del keep
         return u, s, vt
 
-    def _run_pca(self, stem, operand, m, n, nt, like, on_device, rank, n_iter, n_oversamples, seed, omega, flags, in_dtype=None):
+    def _run_pca(self, stem, operand, m, n, nt, like, on_device, rank, n_iter, n_oversamples, seed, omega, flags, in_dtype=None,
+                 standardize=False):
         """The same for the PCA entries.  -> (means (1, n), S (k, 1), components (k, n)); n_iter / n_oversamples default as
-        in pca_rsvd.rs:65-66."""
+        in pca_rsvd.rs:65-66.  standardize: CORRLA_PCA_STANDARDIZE, and a fourth item, scales (1, n) of the kind of means."""
         q = 20 if n_iter is None else int(n_iter)
         p = min(n, 10) if n_oversamples is None else int(n_oversamples)
         l = min(rank + max(p, 0), nt)
-        o, keep = self._opts(seed, omega, nt, l, like.dtype, on_device, flags)
+        o, keep = self._opts(seed, omega, nt, l, like.dtype, on_device, flags | (L.PCA_STANDARDIZE if standardize else 0))
         kk = max(rank, 1)
         means, s, comps = (_empty_colmajor(like, *shape) for shape in ((1, n), (kk, 1), (kk, n)))
+        if standardize:
+            scales = _empty_colmajor(like, 1, n)
+            o.scales_out = _ptr(scales)
         if on_device:
             _sync_stream(like)  # after _opts, as in _run_rsvd
         L.check(self._entry(stem, on_device, in_dtype or like.dtype)(self._h, *_c_args(operand), rank, q, p,
                                                                      C.byref(o) if o is not None else None,
                                                                      _ptr(means), _ptr(s), _ptr(comps), kk))
         del keep
-        return means, s, comps
+        return (means, s, comps, scales) if standardize else (means, s, comps)
 
     # ---- random_svd ----------------------------------------------------------------------
     def rsvd(self, a_mat, n_rank, n_iters, n_oversamples, *, seed=None, omega=None, qr=None, fused=False, mixed=None):
@@ -412,7 +423,7 @@ class Context:
                                 shard_cols=(shard == "cols"), qr=qr, mixed=mixed)
 
     # ---- PCA caller (pca_rsvd.rs:56-82) ---------------------------------------------------
-    def _pca_dense(self, x_mat, rank, n_iter, n_oversamples, seed, omega, center, sharded):
+    def _pca_dense(self, x_mat, rank, n_iter, n_oversamples, seed, omega, center, sharded, standardize=False):
         cflags = {None: 0, "fused": L.PCA_CENTER_FUSED, "copy": L.PCA_CENTER_COPY}[center]
         if sharded:
             _reject_bf16(x_mat, "pca_sharded")
@@ -422,33 +433,42 @@ class Context:
             if on_dev:
                 self._on_my_device(x)
             return self._run_pca("corrla_pca_", (x, m, n, *_strides(x)), m, n, min(m, n), _f32_like(x), on_dev, int(rank), n_iter,
-                                 n_oversamples, seed, omega, cflags, in_dtype=x.dtype)
+                                 n_oversamples, seed, omega, cflags, in_dtype=x.dtype, standardize=standardize)
         return self._run_pca("corrla_pca_sharded_" if sharded else "corrla_pca_", (x, m, n, *_strides(x)), m, n,
-                             n if sharded else min(m, n), x, on_dev, int(rank), n_iter, n_oversamples, seed, omega, cflags)
+                             n if sharded else min(m, n), x, on_dev, int(rank), n_iter, n_oversamples, seed, omega, cflags,
+                             standardize=standardize)
 
-    def pca_sharded(self, x_local, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None):
+    def pca_sharded(self, x_local, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None, standardize=False):
         """PcaRsvd::new on SAMPLE-sharded data (one process per GPU, `comm_init` done): `x_local` = this rank's samples
-        (CUDA tensor m_local x n_dim).  Returns (means, S, components), replicated on every rank."""
+        (CUDA tensor m_local x n_dim).  Returns (means, S, components), replicated on every rank; with standardize=True
+        (see pca) also the scales, from one more all-reduce of n_dim values."""
         _reject_bf16(x_local, "pca_sharded")
         if not (_is_torch(x_local) and x_local.is_cuda):
             raise ValueError("pca_sharded takes torch CUDA tensors")
-        return self._pca_dense(x_local, rank, n_iter, n_oversamples, seed, omega, center, sharded=True)
+        return self._pca_dense(x_local, rank, n_iter, n_oversamples, seed, omega, center, sharded=True,
+                               standardize=_check_standardize(standardize))
 
-    def pca(self, x_mat, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None):
+    def pca(self, x_mat, rank, n_iter=None, n_oversamples=None, *, seed=None, omega=None, center=None, standardize=False):
         """PcaRsvd::new(x, rank): returns (means (1, n), singular values (k, 1), components (k, n)).
         n_iter / n_oversamples default to the reference's hard-coded 20 / min(n_dim, 10) (pca_rsvd.rs:65-66).
         center: None (library default: implicit rank-1 corrections for f64 and bfloat16, a centred copy for f32), "fused"
-        or "copy" (CORRLA_PCA_CENTER_* in include/corrla_rsvd.h; "copy" on a bfloat16 tensor centres a widened f32 copy).  Sparse x_mat (see _as_csr): always "fused"; "copy" raises."""
+        or "copy" (CORRLA_PCA_CENTER_* in include/corrla_rsvd.h; "copy" on a bfloat16 tensor centres a widened f32 copy).  Sparse x_mat (see _as_csr): always "fused"; "copy" raises.
+        standardize=True: PCA on standardised columns (CORRLA_PCA_STANDARDIZE) -- every column is also divided by its sample
+        standard deviation (n_samples - 1 divisor; 1 for a constant column), i.e. PCA of the correlation matrix, what
+        StandardScaler -> PCA gives.  x_mat is not rewritten, widened or densified for it.  Returns
+        (means, S, components, scales) with scales (1, n) of the kind and dtype of means; the components are directions in
+        STANDARDISED coordinates (project (x - means) / scales onto them).  False: today's call and today's three items."""
         rank = int(rank)
+        standardize = _check_standardize(standardize)
         if center not in (None, "fused", "copy"):
             raise ValueError("center must be None, 'fused' or 'copy'")
         if not _is_sparse(x_mat):
-            return self._pca_dense(x_mat, rank, n_iter, n_oversamples, seed, omega, center, sharded=False)
+            return self._pca_dense(x_mat, rank, n_iter, n_oversamples, seed, omega, center, sharded=False, standardize=standardize)
         if center == "copy":  # always the fused centring: the matrix stays sparse
             raise ValueError("center='copy' on sparse input: a centred copy would densify the matrix")
         operand, m, n, like, on_dev = self._csr_operand(x_mat)
         return self._run_pca("corrla_pca_csr_", operand, m, n, min(m, n), like, on_dev, rank, n_iter, n_oversamples, seed, omega,
-                             L.PCA_CENTER_FUSED)
+                             L.PCA_CENTER_FUSED, standardize=standardize)
 
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
@@ -601,12 +621,16 @@ def power_iter(a_mat, omega_rank, n_iter, *, seed=None, omega=None, ctx=None, qr
     return (ctx or default_context()).power_iter(a_mat, omega_rank, n_iter, seed=seed, omega=omega, qr=qr)
 
 
-def rpca(a_mat, n_rank, n_iters=None, n_oversamples=None, *, seed=None, omega=None, ctx=None):
+def rpca(a_mat, n_rank, n_iters=None, n_oversamples=None, *, seed=None, omega=None, ctx=None, standardize=False):
     """pyo3 ``rpca(a_mat, n_rank, n_iters, n_oversamples) -> (singular_values (k, 1), components (k, n))``,
     src/lib_math_utils_py.rs:38-55.  Like the reference, the last two positional arguments are accepted and
-    IGNORED: PcaRsvd::new hard-codes n_iter = 20 and n_oversamples = min(n_dim, 10) (pca_rsvd.rs:65-66)."""
+    IGNORED: PcaRsvd::new hard-codes n_iter = 20 and n_oversamples = min(n_dim, 10) (pca_rsvd.rs:65-66).
+    standardize=True (additive, keyword-only): PCA on standardised columns, see Context.pca; same two results."""
     del n_iters, n_oversamples
-    _means, s, comps = (ctx or default_context()).pca(a_mat, n_rank, seed=seed, omega=omega)
+    if not _check_standardize(standardize):
+        _means, s, comps = (ctx or default_context()).pca(a_mat, n_rank, seed=seed, omega=omega)
+    else:
+        _means, s, comps, _scales = (ctx or default_context()).pca(a_mat, n_rank, seed=seed, omega=omega, standardize=True)
     return s, comps
 
 
@@ -615,11 +639,19 @@ class PcaRsvd:
     singular values (k, 1) and ``components_`` (k, n_dim).  The fit (means, centring, RSVD) runs on the GPU; the
     two k-wide projections below are plain numpy on the stored k x n_dim factors."""
 
-    def __init__(self, x_mat, rank, *, seed=None, omega=None, ctx=None):
+    def __init__(self, x_mat, rank, *, seed=None, omega=None, ctx=None, standardize=False):
+        """standardize=True: the fit is on standardised columns (see Context.pca); ``scales_`` (1, n_dim) keeps the column
+        standard deviations (None otherwise), ``components_`` are directions in standardised coordinates, and apply_tr /
+        apply_inv_tr divide / multiply by ``scales_`` accordingly."""
         self.pca_rank = int(rank)
         x = x_mat if _is_sparse(x_mat) else np.asarray(x_mat)
         self.n_samples = int(x[3][0] if isinstance(x, tuple) else x.shape[0])
-        self.means, self.pca_s, self.components_ = (ctx or default_context()).pca(x, rank, seed=seed, omega=omega)
+        self.scales_ = None
+        if not _check_standardize(standardize):
+            self.means, self.pca_s, self.components_ = (ctx or default_context()).pca(x, rank, seed=seed, omega=omega)
+        else:
+            self.means, self.pca_s, self.components_, self.scales_ = (ctx or default_context()).pca(x, rank, seed=seed, omega=omega,
+                                                                                                    standardize=True)
 
     def fit(self, x_mat, rank, **kw):  # pca_rsvd.rs:85-88
         self.__init__(x_mat, rank, **kw)
@@ -635,10 +667,16 @@ class PcaRsvd:
 
     def apply_tr(self, targ_mat):  # pca_rsvd.rs:43-46: centres the TARGET by its own column means
         t = np.asarray(targ_mat, dtype=self.components_.dtype)
-        return (t - t.mean(axis=0, keepdims=True)) @ self.components_.T
+        tc = t - t.mean(axis=0, keepdims=True)
+        if self.scales_ is not None:
+            tc = tc / self.scales_
+        return tc @ self.components_.T
 
     def apply_inv_tr(self, red_mat):  # pca_rsvd.rs:49-52
-        return np.asarray(red_mat, dtype=self.components_.dtype) @ self.components_ + self.means
+        back = np.asarray(red_mat, dtype=self.components_.dtype) @ self.components_
+        if self.scales_ is not None:
+            back = back * self.scales_
+        return back + self.means
 
 
 def algorithmic_flops(m, n, k, q, p):

@@ -2,6 +2,7 @@
 // argument validation, fat/tall + stride classification, staging of A, output orientation
 // (random_svd.rs:69-74, 96-109).  Templated on the backend; contains no m-/n-sized arithmetic.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -34,7 +35,13 @@ inline corrla_status guarded(F&& f) {
   }
 }
 
-inline RunOpts parse_opts(const corrla_opts* o, bool dev_ptrs) {
+// The first 32 bytes of corrla_opts (through omega_ld) are the layout of the first release: a caller built against that
+// header passes struct_size == 32 and the later fields read as zero.
+constexpr uint32_t kOptsSizeV1 = 32;
+static_assert(offsetof(corrla_opts, scales_out) == kOptsSizeV1, "corrla_opts grows at the end only");
+
+// pca: the call is a corrla_pca_* entry (the only ones CORRLA_PCA_STANDARDIZE is valid on)
+inline RunOpts parse_opts(const corrla_opts* o, bool dev_ptrs, bool pca = false) {
   RunOpts r;
   const char* qr_env = std::getenv("CORRLA_QR");
   r.qr_householder = qr_env && std::strcmp(qr_env, "householder") == 0;
@@ -45,7 +52,7 @@ inline RunOpts parse_opts(const corrla_opts* o, bool dev_ptrs) {
     r.mixed_planes = std::strcmp(mx, "bf16x3") == 0 ? 2 : (std::strcmp(mx, "bf16x6") == 0 ? 3 : 0);
   if (const char* mp = std::getenv("CORRLA_MIXED_PROJECT")) r.mixed_project = std::atoi(mp) != 0;
   if (!o) return r;
-  if (o->struct_size != sizeof(corrla_opts)) throw Error(ST_EINVAL, "corrla_opts.struct_size mismatch");
+  if (o->struct_size != sizeof(corrla_opts) && o->struct_size != kOptsSizeV1) throw Error(ST_EINVAL, "corrla_opts.struct_size mismatch");
   // seed: used as given when it is non-zero or CORRLA_SEED_EXPLICIT is set (so 0 is a usable seed); otherwise every
   // call draws a fresh sketch like the reference's unseeded thread_rng (mat_utils.rs:161-175) -- see fresh_seed()
   r.seed_explicit = o->seed != 0 || (o->flags & CORRLA_SEED_EXPLICIT) != 0;
@@ -57,6 +64,8 @@ inline RunOpts parse_opts(const corrla_opts* o, bool dev_ptrs) {
   if ((o->flags & CORRLA_PCA_CENTER_FUSED) && (o->flags & CORRLA_PCA_CENTER_COPY))
     throw Error(ST_EINVAL, "CORRLA_PCA_CENTER_FUSED and CORRLA_PCA_CENTER_COPY are mutually exclusive");
   r.pca_center = (o->flags & CORRLA_PCA_CENTER_FUSED) ? 1 : ((o->flags & CORRLA_PCA_CENTER_COPY) ? 2 : 0);
+  r.pca_standardize = (o->flags & CORRLA_PCA_STANDARDIZE) != 0;
+  if (r.pca_standardize && !pca) throw Error(ST_EINVAL, "CORRLA_PCA_STANDARDIZE is only valid for corrla_pca_* entry points");
   r.qr_householder = r.qr_householder || (o->flags & CORRLA_QR_HOUSEHOLDER) != 0;
   r.power_fused = r.power_fused || (o->flags & CORRLA_POWER_FUSED) != 0;
   if ((o->flags & CORRLA_SKETCH_BF16X3) && (o->flags & CORRLA_SKETCH_BF16X6))
@@ -146,8 +155,8 @@ inline TallA<T> stage_input(Dev& dev, bool host_ptrs, const T* a, int64_t m, int
 
 // The options of one rsvd / PCA call.  Sparse and bf16-stored operands (not_dense_f32): CORRLA_POWER_FUSED and
 // CORRLA_SKETCH_BF16X3 / X6 only have dense f32 kernels and are ignored, as documented for every operand outside their domain.
-inline RunOpts call_opts(const corrla_opts* o, bool host_ptrs, bool sharded, bool not_dense_f32) {
-  RunOpts ro = parse_opts(o, !host_ptrs);
+inline RunOpts call_opts(const corrla_opts* o, bool host_ptrs, bool sharded, bool not_dense_f32, bool pca = false) {
+  RunOpts ro = parse_opts(o, !host_ptrs, pca);
   if (not_dense_f32) {
     ro.power_fused = false;
     ro.mixed_planes = 0;
@@ -345,12 +354,18 @@ struct PcaCall {
 // column means and every product with the centred matrix are linear in the rows, so they are all-reduced partial sums.
 // An empty shard is not supported here (the centring has no zero-contribution stand-in): it fails validation, on every
 // rank alike.
+// CORRLA_PCA_STANDARDIZE: the columns are divided by their standard deviation as well (PCA of the correlation matrix).
+// One more pass over the operand, next to the one for the means, gives the column sums of squares (Dev::col_ss, read in
+// place; row-sharded: partial sums, all-reduced); the fused form then carries the diagonal 1 / sd on the skinny side of
+// every product (TallA::inv_sd_*), the copy form scales the centred copy.  Needs a backend with those kernels
+// (dev_has_colvar); without them the call ends with ST_EINVAL.
 // sparse: always the fused centring -- the centred operator is A X - 1 (mu^T X), A itself is never
 // rewritten, so the matrix stays sparse; the means are A^T 1 / m through the same SpMM as every other product.
 template <class Dev, class T, class Validate, class Stage>
 inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&& stage) {
   RunOpts ro;
   TallA<T> ta;
+  T* scales_out = nullptr;  // corrla_opts.scales_out: n_dim values, host or device memory as `means`
   prepare_call(
       dev, c.sharded,
       [&] {
@@ -358,7 +373,11 @@ inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&&
         validate();
         if (c.ldc < c.rank) throw Error(ST_EINVAL, "ldc < rank");
         if (c.sparse) need_two_samples(c.m);  // never sharded: the sample count is known before anything is staged
-        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse || c.bf16);
+        ro = call_opts(c.opts, c.host_ptrs, c.sharded, c.sparse || c.bf16, /*pca=*/true);
+        if (ro.pca_standardize && !dev_has_colvar<Dev>::value)
+          throw Error(ST_EINVAL, "CORRLA_PCA_STANDARDIZE: this backend has no column-variance kernels");
+        // (a caller of the 32-byte layout has no scales_out field: read it only when the struct holds it)
+        if (ro.pca_standardize && c.opts->struct_size >= sizeof(corrla_opts)) scales_out = (T*)c.opts->scales_out;
         if (c.sparse && ro.pca_center == 2)
           throw Error(ST_EINVAL, "CORRLA_PCA_CENTER_COPY on CSR input: a centred copy would densify the matrix (use the fused centring)");
         draw_seed(dev, ro);
@@ -380,25 +399,45 @@ inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&&
     drv.at_times(ta, ones, mu, inv_m, c.sharded);  // mu (n) = x^T 1 / m (all-reduced partial sums when sharded)
   else
     drv.a_times(ta, ones, mu, inv_m);            // tall view = x^T (n x m): mu (n) = x^T 1 / m
+  // data columns run along the memory columns iff (tall & row-major) or (fat & column-major): tall view element (i, j)
+  // is memory (i, j) when row-major, else memory (j, i); the data column index of x is j for tall input, i for fat
+  const bool data_cols_along_mem_cols = (ta.row_major != fat);
+  Skinny<T> sd, inv_sd;  // column standard deviations (1 for a constant column) and their reciprocals
+  if (ro.pca_standardize) {
+    if constexpr (dev_has_colvar<Dev>::value) {
+      double* ss = dev.alloc_f64((int)c.n);
+      if (ta.sparse)
+        dev.col_ss_csr(fat ? ta.csr : ta.csr_t, (const T*)mu.p, c.m, ss);  // the CSR whose rows are the data columns
+      else if (ta.bf16)
+        dev.col_ss(ta.mem16, data_cols_along_mem_cols, (const T*)mu.p, ss);
+      else
+        dev.col_ss(ta.mem, data_cols_along_mem_cols, (const T*)mu.p, ss);
+      // with the global means ss is linear in the rows: every rank's partial sums, one all-reduce of n_dim values
+      if (c.sharded) dev.allreduce(ss, (size_t)c.n);
+      sd = dev.template alloc_skinny<T>(c.n, 1);
+      inv_sd = dev.template alloc_skinny<T>(c.n, 1);
+      dev.sd_from_ss((const double*)ss, (const T*)mu.p, c.n, m_global, sd.p, inv_sd.p);
+    }
+  }
   TallA<T> tc = ta;
   const bool fused = c.sparse || ro.pca_center == 1 || (ro.pca_center == 0 && (sizeof(T) == 8 || c.bf16));
   if (fused) {
     // the centred matrix is never formed.  Tall view (i, j) = x(i, j) for tall inputs (means run
     // along the SHORT side), = x(j, i) for fat inputs (means run along the TALL side).
     if (!fat)
-      tc.mu_short = mu.p;
+      tc.mu_short = mu.p, tc.inv_sd_short = inv_sd.p;
     else
-      tc.mu_tall = mu.p;
+      tc.mu_tall = mu.p, tc.inv_sd_tall = inv_sd.p;
   } else {
     // centred copy (center_mat_col clones too, mat_utils.rs:484): memory rows/cols of the staged operand
     const int64_t ldp = round_up(ta.mem.cols, kLdPad);
     T* cbuf = (T*)dev.alloc_bytes((size_t)ta.mem.rows * (size_t)ldp * sizeof(T));
     dev.memset_zero(cbuf, (size_t)ta.mem.rows * (size_t)ldp * sizeof(T));
-    // data columns run along the memory columns iff (tall & row-major) or (fat & column-major-as-rows ...):
-    // tall view element (i, j): row-major memory (i, j), else memory (j, i).  Data column index of x is j for
-    // the tall case and i for the fat case.
-    const bool mean_along_mem_cols = (ta.row_major != fat);
-    dev.center_rows_cols(ta.mem.p, ta.mem.rows, ta.mem.cols, ta.mem.ld, mu.p, mean_along_mem_cols, cbuf, ldp);
+    if constexpr (dev_has_colvar<Dev>::value) {
+      dev.center_rows_cols(ta.mem.p, ta.mem.rows, ta.mem.cols, ta.mem.ld, mu.p, data_cols_along_mem_cols, cbuf, ldp, (const T*)inv_sd.p);
+    } else {
+      dev.center_rows_cols(ta.mem.p, ta.mem.rows, ta.mem.cols, ta.mem.ld, mu.p, data_cols_along_mem_cols, cbuf, ldp);
+    }
     tc.mem.p = cbuf;
     tc.mem.ld = ldp;
     tc.mem.cols_readable = ldp;
@@ -409,11 +448,14 @@ inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&&
   Skinny<T> ut = dev.template alloc_skinny<T>(tc.mt, k);
   Skinny<T> vtall = dev.template alloc_skinny<T>(tc.nt, k);
   T* s_dev = dev.template alloc_scalar<T>((int)k);
+  // the skinny that carries D^-1 into the products (n_dim x l; allocated here, outside the attempts of random_svd_tall)
+  if (tc.inv_sd_short || tc.inv_sd_tall) drv.set_scale_workspace(dev.template alloc_skinny<T>(c.n, l));
   drv.random_svd_tall(tc, k, l, c.n_iter, ro, ut, s_dev, vtall, [&] {
     // components_ = vr = V^T (k x n_dim)   pca_rsvd.rs:70-71
     dev.copy_out(fat ? ut : vtall, k, c.comps, c.ldc, /*transpose=*/true, c.host_ptrs);
     dev.copy_values_out(s_dev, k, c.s, c.host_ptrs);
     dev.copy_values_out(mu.p, c.n, c.means, c.host_ptrs);
+    if (scales_out) dev.copy_values_out(sd.p, c.n, scales_out, c.host_ptrs);
   });
   finish_call(drv, dev, c.tm_out, /*with_sketch_kernel_ms=*/false);
 }

@@ -96,6 +96,13 @@ struct dev_has_bf16in : std::false_type {};
 template <class D>
 struct dev_has_bf16in<D, std::void_t<decltype(D::kHasBf16In)>> : std::true_type {};
 
+// ... and those that carry the column second-moment kernels and the row scaling of PCA on standardised columns with
+// kHasColVar.
+template <class D, class = void>
+struct dev_has_colvar : std::false_type {};
+template <class D>
+struct dev_has_colvar<D, std::void_t<decltype(D::kHasColVar)>> : std::true_type {};
+
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).
 template <class T>
@@ -107,6 +114,11 @@ struct TallA {
   // A - mu_tall 1^T (mu_tall: mt values); A itself is never rewritten.  At most one of them is set.
   const T* mu_short = nullptr;
   const T* mu_tall = nullptr;
+  // Implicit standardisation (CORRLA_PCA_STANDARDIZE): the operator is (A - 1 mu_short^T) D^-1 with D^-1 = diag(inv_sd_short)
+  // (nt values, device) or D^-1 (A - mu_tall 1^T) with D^-1 = diag(inv_sd_tall) (mt values).  At most one of them is set,
+  // and only together with the mu_* of the same side.
+  const T* inv_sd_short = nullptr;
+  const T* inv_sd_tall = nullptr;
   // Sparse operand: `mem` is unused; csr is the tall view (mt x nt) and csr_t its transpose (nt x mt), so both
   // products of the range finder are row gathers.  For a fat input the caller's CSR is csr_t (no copy).
   bool sparse = false;
@@ -125,6 +137,7 @@ struct RunOpts {
   bool omega_on_device = false;
   bool sharded = false;  // rows of A are sharded over the communicator
   int pca_center = 0;    // 0 default, 1 fused, 2 centred copy (corrla_pca_* only)
+  bool pca_standardize = false;  // columns divided by their standard deviation after centring (CORRLA_PCA_STANDARDIZE)
   bool qr_householder = false;  // thin-Q by Householder TSQR instead of CholeskyQR2 (CORRLA_QR_HOUSEHOLDER)
   bool power_fused = false;     // one-sweep Z' = A^T (A Z) where it applies (CORRLA_POWER_FUSED)
   int mixed_planes = 0;         // 0: exact f32 / f64 products; 2 / 3: the tall products of the range finder on the bf16 matrix
@@ -192,7 +205,33 @@ struct RsvdDriver {
     else
       throw Error(ST_EINVAL, "this backend has no bf16-input kernels: bf16 operands are not supported");
   }
-  void a_times(const TallA<T>& a, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev) {
+  // The diagonal D^-1 of the standardised operator where it multiplies the INPUT of a product: d[i] * x(i, :) into the
+  // workspace skinny the entry layer set aside with set_scale_workspace (every product of a call has the same skinny
+  // shape; the caller's operand is never scaled in place).  A shape that does not fit is an error, never a fresh allocation.
+  Skinny<T> scale_ws_;  // set through set_scale_workspace only
+  void set_scale_workspace(const Skinny<T>& ws) { scale_ws_ = ws; }
+  Skinny<T> scaled_input(const Skinny<T>& x, int64_t rows, const T* d) {
+    if constexpr (dev_has_colvar<Dev>::value) {
+      if (!scale_ws_.p || scale_ws_.rows != x.rows || scale_ws_.ld != x.ld || scale_ws_.cols_alloc < x.cols_alloc)
+        throw Error(ST_EINVAL, "internal: the row-scale workspace does not fit the skinny operand of a standardised product");
+      Skinny<T> xs = scale_ws_;
+      xs.cols = x.cols;
+      xs.cols_alloc = x.cols_alloc;
+      dev.row_scale(x, xs, rows, d);
+      return xs;
+    } else {
+      throw Error(ST_EINVAL, "this backend has no row-scale kernel: standardised operands are not supported");
+    }
+  }
+  void scale_output(Skinny<T>& y, int64_t rows, const T* d) {
+    if constexpr (dev_has_colvar<Dev>::value)
+      dev.row_scale(y, y, rows, d);
+    else
+      throw Error(ST_EINVAL, "this backend has no row-scale kernel: standardised operands are not supported");
+  }
+  void a_times(const TallA<T>& a, const Skinny<T>& x_in, Skinny<T>& y, const T* scale_dev) {
+    // ((A - 1 mu^T) D^-1) X = A (D^-1 X) - 1 (mu^T D^-1 X): the diagonal goes onto the skinny input first
+    const Skinny<T> x = a.inv_sd_short ? scaled_input(x_in, a.nt, a.inv_sd_short) : x_in;
     if (a.sparse)
       sparse_times(a.csr, x, y, scale_dev);
     else if (a.bf16)
@@ -209,9 +248,13 @@ struct RsvdDriver {
       dev.weighted_colsum(x, a.nt, a.mu_short, v);
       dev.rank1_sub(y, a.mt, a.mu_tall, v, scale_dev);
     }
+    // D^-1 (A - mu 1^T) X = D^-1 (A X - mu (1^T X)): the diagonal scales the corrected product
+    if (a.inv_sd_tall) scale_output(y, a.mt, a.inv_sd_tall);
   }
   // Z (nt x L) = scale * A^T * Y (mt x L); all-reduced when rows are sharded   random_svd.rs:42-46,80
-  void at_times(const TallA<T>& a, const Skinny<T>& y, Skinny<T>& z, const T* scale_dev, bool sharded) {
+  void at_times(const TallA<T>& a, const Skinny<T>& y_in, Skinny<T>& z, const T* scale_dev, bool sharded) {
+    // (D^-1 (A - mu 1^T))^T Y = A^T (D^-1 Y) - 1 (mu^T D^-1 Y)
+    const Skinny<T> y = a.inv_sd_tall ? scaled_input(y_in, a.mt, a.inv_sd_tall) : y_in;
     if (a.sparse)
       sparse_times(a.csr_t, y, z, scale_dev);
     else if (a.bf16)
@@ -229,6 +272,9 @@ struct RsvdDriver {
       dev.weighted_colsum(y, a.mt, a.mu_tall, v);
       dev.rank1_sub(z, a.nt, a.mu_short, v, scale_dev);
     }
+    // ((A - 1 mu^T) D^-1)^T Y = D^-1 (A^T Y - mu (1^T Y)); before the all-reduce: scaling by a replicated diagonal commutes
+    // with the sum over the ranks
+    if (a.inv_sd_short) scale_output(z, a.nt, a.inv_sd_short);
     // (only the l columns that exist: the padding columns up to cols_alloc are zero on every rank and stay zero)
     if (sharded) dev.allreduce(z.p, (size_t)z.ld * (size_t)z.cols);
   }

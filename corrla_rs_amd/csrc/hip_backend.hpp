@@ -30,6 +30,7 @@
 #include "knn2_kernels.hpp"
 #include "grad_wide_kernels.hpp"
 #include "spmm_kernels.hpp"
+#include "colvar_kernels.hpp"
 
 namespace corrla {
 
@@ -1082,12 +1083,89 @@ class HipDev {
     hipLaunchKernelGGL((k::fill_const_kernel<T>), dim3(blocks), dim3(256), 0, stream, p, n, v);
     CORRLA_HIP(hipGetLastError());
   }
+  // inv_sd (optional, indexed like mu): the copy is standardised as well as centred
   template <class T>
   void center_rows_cols(const T* in, int64_t rows, int64_t cols, int64_t ldi, const T* mu, bool along_cols, T* out,
-                        int64_t ldo) {
+                        int64_t ldo, const T* inv_sd = nullptr) {
     dim3 grid((unsigned)((cols + 255) / 256), (unsigned)std::min<int64_t>(rows, 4096));
     hipLaunchKernelGGL((k::center_kernel<T>), grid, dim3(256), 0, stream, in, rows, cols, ldi, mu, along_cols ? 1 : 0, out,
-                       ldo);
+                       ldo, inv_sd);
+    CORRLA_HIP(hipGetLastError());
+  }
+
+  // ---- PCA on standardised columns (colvar_kernels.hpp) ----------------------------------------------------------
+  static constexpr bool kHasColVar = true;  // driver.hpp: dev_has_colvar
+  // ss[j] (f64) = sum_i (x_ij - mu_j)^2 per data column j of the staged operand `a` (f32, f64 or bf16 bit patterns, read
+  // in place).  along_cols: the data columns run along the memory columns (reduce down the rows), else they are the
+  // memory rows (reduce along them).  Per-slab partial sums, then a final sum in index order.
+  template <class TI, class T>
+  void col_ss(const Big<TI>& a, bool along_cols, const T* mu, double* ss) {
+    constexpr int VEC = k::CvIn<TI>::kVec;
+    const int aligned = ((uintptr_t)a.p % 16 == 0 && a.ld % VEC == 0) ? 1 : 0;
+    const int64_t n = along_cols ? a.cols : a.rows;
+    const int64_t target = (int64_t)num_cus * 8;  // workgroups that fill the device
+    int64_t nslab;
+    double* partial;
+    if (along_cols) {
+      const int64_t ngroups = (a.cols + VEC - 1) / VEC;
+      int groups = 1;
+      while (groups < k::kCvThreads && groups < ngroups) groups *= 2;
+      const int ny = k::kCvThreads / groups;
+      const int64_t col_blocks = (ngroups + groups - 1) / groups;
+      // every row lane gets at least eight rows
+      const int64_t want = std::max<int64_t>(1, std::min<int64_t>((target + col_blocks - 1) / col_blocks, (a.rows + 8 * ny - 1) / (8 * ny)));
+      const int64_t rows_per_slab = (a.rows + want - 1) / want;
+      nslab = (a.rows + rows_per_slab - 1) / rows_per_slab;
+      dim3 grid((unsigned)col_blocks, (unsigned)nslab);
+      check_grid(grid);
+      partial = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
+      hipLaunchKernelGGL((k::colss_down_kernel<TI, T>), grid, dim3(k::kCvThreads), 0, stream, a.p, a.rows, a.cols, a.ld, a.cols_readable,
+                         aligned, mu, groups, rows_per_slab, partial);
+    } else {
+      const int64_t quantum = 64 * VEC;  // what one wave reads per step
+      const int64_t max_segs = (a.cols + 4 * quantum - 1) / (4 * quantum);
+      const int64_t want = std::max<int64_t>(1, std::min<int64_t>((4 * target + a.rows - 1) / a.rows, max_segs));
+      const int64_t seg_len = round_up((a.cols + want - 1) / want, quantum);
+      nslab = (a.cols + seg_len - 1) / seg_len;
+      const int64_t units = a.rows * nslab;
+      const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 2 * target));
+      partial = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
+      hipLaunchKernelGGL((k::colss_along_kernel<TI, T>), dim3((unsigned)blocks), dim3(k::kCvThreads), 0, stream, a.p, a.rows, a.cols,
+                         a.ld, a.cols_readable, aligned, mu, (int)nslab, seg_len, partial);
+    }
+    hipLaunchKernelGGL(k::colss_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)partial, nslab, n, ss);
+    CORRLA_HIP(hipGetLastError());
+  }
+  // the same over a CSR whose ROWS are the data columns (a transpose built by csr_transpose: entries ordered by sample),
+  // the implicit zeros of the n_samples long columns included
+  template <class T>
+  void col_ss_csr(const CsrView<T>& s, const T* mu, int64_t n_samples, double* ss) {
+    const int64_t target = (int64_t)num_cus * 8;
+    const int64_t segs = std::max<int64_t>(1, std::min<int64_t>((4 * target + s.rows - 1) / s.rows, 64));
+    const int64_t units = s.rows * segs;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 2 * target));
+    double* psum = (double*)alloc_bytes(sizeof(double) * (size_t)units);
+    double* pcnt = (double*)alloc_bytes(sizeof(double) * (size_t)units);
+    hipLaunchKernelGGL((k::csr_colss_kernel<T>), dim3((unsigned)blocks), dim3(k::kCvThreads), 0, stream, s.val, s.ci, s.rp, s.rows, mu,
+                       (int)segs, psum, pcnt);
+    hipLaunchKernelGGL((k::csr_colss_final_kernel<T>), dim3((unsigned)((s.rows + 255) / 256)), dim3(256), 0, stream, (const double*)psum,
+                       (const double*)pcnt, segs, s.rows, mu, (double)n_samples, ss);
+    CORRLA_HIP(hipGetLastError());
+  }
+  // sd[j] = sqrt(ss[j] / (m - 1)) -- 1 for a constant column -- and its reciprocal, on the device
+  template <class T>
+  void sd_from_ss(const double* ss, const T* mu, int64_t n, int64_t m_samples, T* sd, T* inv_sd) {
+    hipLaunchKernelGGL((k::sd_from_ss_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ss, mu, n, (double)m_samples, sd,
+                       inv_sd);
+    CORRLA_HIP(hipGetLastError());
+  }
+  // out(i, c) = d[i] * in(i, c) over every allocated column (the padding columns are zero and stay zero); out may be in
+  template <class T>
+  void row_scale(const Skinny<T>& in, Skinny<T>& out, int64_t rows, const T* d) {
+    if (in.ld != out.ld || in.cols_alloc > out.cols_alloc) throw Error(ST_EINVAL, "internal: row_scale operands must share the padded layout");
+    dim3 grid((unsigned)((rows + 255) / 256), (unsigned)in.cols_alloc);
+    check_grid(grid);
+    hipLaunchKernelGGL((k::row_scale_kernel<T>), grid, dim3(256), 0, stream, (const T*)in.p, out.p, in.ld, rows, d);
     CORRLA_HIP(hipGetLastError());
   }
 

@@ -2098,16 +2098,19 @@ template <class T>
 __global__ void fill_const_kernel(T* p, int64_t n, T v) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
-// out[r][c] = in[r][c] - (along_cols ? mu[c] : mu[r]); row-major in/out with leading dimensions ldi / ldo
+// out[r][c] = in[r][c] - (along_cols ? mu[c] : mu[r]); row-major in/out with leading dimensions ldi / ldo.
+// inv_sd (optional, indexed like mu): the centred value is scaled by it (the centred AND standardised copy)
 template <class T>
 __global__ void center_kernel(const T* in, int64_t rows, int64_t cols, int64_t ldi, const T* mu, int along_cols, T* out,
-                              int64_t ldo) {
+                              int64_t ldo, const T* inv_sd) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cols) return;
   const T mc = along_cols ? mu[c] : (T)0;
+  const T ic = (inv_sd && along_cols) ? inv_sd[c] : (T)1;
   for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
     const T m_ = along_cols ? mc : mu[r];
-    out[r * ldo + c] = in[r * ldi + c] - m_;
+    const T d = in[r * ldi + c] - m_;
+    out[r * ldo + c] = inv_sd ? d * (along_cols ? ic : inv_sd[r]) : d;
   }
 }
 
@@ -2146,6 +2149,15 @@ __global__ void rank1_sub_kernel(T* out, int64_t ld, int64_t rows, const T* __re
   if (i >= rows) return;
   const T sc = scale ? *scale : (T)1;
   out[(int64_t)blockIdx.y * ld + i] -= sc * (u ? u[i] : (T)1) * v[blockIdx.y];
+}
+// out(i, c) = d[i] * in(i, c): the diagonal of the standardised operator on the skinny side (in and out share ld; out may
+// be in)
+template <class T>
+__global__ void row_scale_kernel(const T* in, T* out, int64_t ld, int64_t rows, const T* __restrict__ d) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  const int64_t o = (int64_t)blockIdx.y * ld + i;
+  out[o] = d[i] * in[o];
 }
 
 // ---- sign convention of the singular triplets ---------------------------------------------------

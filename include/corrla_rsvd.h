@@ -99,6 +99,20 @@ typedef enum corrla_status {
  * variable CORRLA_SKETCH_MIXED=bf16x3|bf16x6 sets it for every call.  Mutually exclusive. */
 #define CORRLA_SKETCH_BF16X3 0x80u
 #define CORRLA_SKETCH_BF16X6 0x100u
+/* corrla_pca_* (every entry: dense host / device, sharded, bf16, CSR): PCA on STANDARDISED columns -- every column is
+ * divided by its sample standard deviation after centring, i.e. PCA of the correlation matrix (scikit-learn's
+ * StandardScaler -> PCA, R's prcomp(scale. = TRUE)).  x is never rewritten: one more pass over it, next to the one for the
+ * means, gives ss_j = sum_i (x_ij - mu_j)^2 (centred two-pass form, f64 accumulation, fixed summation order), then
+ *   sd_j = sqrt(ss_j / (n_samples - 1))          (the divisor of explained_var, pca_rsvd.rs:91-99),
+ * and the fused centring carries the diagonal D^-1 = diag(1 / sd) on the skinny side of every product,
+ *   ((A - 1 mu^T) D^-1) X = A (D^-1 X) - 1 (mu^T D^-1 X),   ((A - 1 mu^T) D^-1)^T Y = D^-1 (A^T Y - mu (1^T Y)),
+ * (fat input: the mirrored pair); CORRLA_PCA_CENTER_COPY forms the centred and scaled copy instead.  The
+ * CORRLA_PCA_CENTER_* flags and their defaults keep their meaning.  A column that cannot be told from a constant one
+ * (ss_j / m <= m eps ss_j / m + (m mu_j eps)^2, eps of the output type: scikit-learn's rule) gets sd_j = 1 and contributes
+ * exact zeros.  The components are directions in standardised coordinates; corrla_opts.scales_out receives sd.
+ * A bf16 operand that is read in place stays in place; CSR input is never densified (the implicit zeros are counted);
+ * the sample-sharded entries add one all-reduce of n_dim doubles.  On any other entry point: CORRLA_EINVAL. */
+#define CORRLA_PCA_STANDARDIZE 0x200u
 
 /*
  * Options block.  Zero-initialise, set struct_size = sizeof(corrla_opts).  NULL opts == defaults.
@@ -109,6 +123,11 @@ typedef enum corrla_status {
  *   omega  : optional sketch matrix that replaces the draw at random_svd.rs:24 -- column-major
  *            n_t x l, n_t = min(m, n), leading dimension omega_ld (>= n_t), dtype of A.
  *            This is the test hook that lets the CPU oracle and the GPU share one Omega.
+ *   scales_out : optional (may be NULL); written only with CORRLA_PCA_STANDARDIZE: the n_dim column standard
+ *            deviations the columns were divided by (1 for a constant column), dtype of the outputs, host or device
+ *            memory exactly as `means` is for that entry.
+ * The struct grows at the end only.  struct_size == 32 (the layout through omega_ld, the first release of this header) is
+ * accepted as well: the later fields then read as zero, so a caller built against that header keeps working.
  */
 typedef struct corrla_opts {
   uint32_t struct_size;
@@ -116,6 +135,7 @@ typedef struct corrla_opts {
   uint64_t seed;
   const void* omega;
   int64_t omega_ld;
+  void* scales_out;
 } corrla_opts;
 
 /* Phase timings of the last rsvd / pca call on a context, milliseconds of DEVICE time: hipEvents are recorded on the

@@ -23,6 +23,7 @@ pub struct CorrlaOpts {
     pub seed: u64,
     pub omega: *const c_void,
     pub omega_ld: i64,
+    pub scales_out: *mut c_void, // written only with CORRLA_PCA_STANDARDIZE: n_dim column standard deviations (nullable)
 }
 pub const CORRLA_OMEGA_ON_DEVICE: u32 = 0x1;
 pub const CORRLA_PCA_CENTER_FUSED: u32 = 0x2;
@@ -33,6 +34,7 @@ pub const CORRLA_POWER_FUSED: u32 = 0x20;
 pub const CORRLA_SHARD_COLS: u32 = 0x40;
 pub const CORRLA_SKETCH_BF16X3: u32 = 0x80; // opt-in: range finder on the bf16-split kernels (f32 inputs only)
 pub const CORRLA_SKETCH_BF16X6: u32 = 0x100;
+pub const CORRLA_PCA_STANDARDIZE: u32 = 0x200; // corrla_pca_* only: PCA on standardised columns (correlation PCA)
 
 extern "C" {
     fn corrla_ctx_create(device: c_int, out: *mut *mut c_void) -> c_int;
