@@ -3,15 +3,18 @@ hrl.rsvd(A, 4, 8, 10)`, examples/benchmark_rsvd.py:13,101; `from corrla_rs impor
 The RSVD hot path and its callers are provided -- rpca (PCA), PyDMDc, PyPodI (with the PyRbfInterp its mode weights
 are interpolated by) -- and everything m- or n-sized is forwarded to corrla_rs_amd (HIP, gfx950).  active_ss
 (gradient stage on the GPU) is provided too; the samplers (cs_*_sample) of the pyo3 module are outside this build's
-scope."""
+scope.  mat_cov_centered, pearson_corr and rsquared_sens (stats_corr.rs) are ADDITIVE: the pyo3
+module does not expose them; here they run on the symmetric MFMA kernel behind ``Context.cov``."""
 import numpy as _np
 
 from corrla_rs_amd.api import PcaRsvd, power_iter, random_svd, rpca, rsvd  # noqa: F401
 from corrla_rs_amd.callers import DMDc as _DMDc
 from corrla_rs_amd.callers import PodI as _PodI
 from corrla_rs_amd.callers import RbfInterp as _RbfInterp
+from corrla_rs_amd.callers import mat_cov_centered, pearson_corr, rsquared_sens  # noqa: F401
 
-__all__ = ["rsvd", "rpca", "random_svd", "power_iter", "PcaRsvd", "PyDMDc", "PyPodI", "PyRbfInterp", "active_ss"]
+__all__ = ["rsvd", "rpca", "random_svd", "power_iter", "PcaRsvd", "PyDMDc", "PyPodI", "PyRbfInterp", "active_ss",
+           "mat_cov_centered", "pearson_corr", "rsquared_sens"]
 
 
 def active_ss(a_mat, y, order, n_nbr, n_comps):

@@ -21,6 +21,11 @@ SHARD_COLS = 0x40
 SKETCH_BF16X3 = 0x80
 SKETCH_BF16X6 = 0x100
 PCA_STANDARDIZE = 0x200
+# corrla_cov_*: the entry's own flag word and the routes it reports
+COV_CORRELATION = 0x1
+COV_NO_CENTER = 0x2
+COV_ROUTE_INPLACE, COV_ROUTE_INPLACE_CHECKED, COV_ROUTE_REPACKED = 1, 2, 3
+COV_ROUTES = {COV_ROUTE_INPLACE: "inplace", COV_ROUTE_INPLACE_CHECKED: "inplace_checked", COV_ROUTE_REPACKED: "repacked"}
 UNIQUE_ID_BYTES = 128
 
 
@@ -72,6 +77,9 @@ def _sigs():
         s["corrla_pca_csr_" + suf] = (C.c_int, pca_csr)
         s["corrla_pca_csr_dev_" + suf] = (C.c_int, pca_csr)
         s["corrla_spmm_csr_dev_" + suf] = (C.c_int, [vp, C.c_int, vp, vp, vp, i64, i64, i64, vp, i64, i64, sc, vp, i64])
+        cov = [vp, vp, i64, i64, i64, i64, u64, C.c_int, vp, vp, vp, i64, C.POINTER(C.c_int)]
+        s["corrla_cov_" + suf] = (C.c_int, cov)
+        s["corrla_cov_dev_" + suf] = (C.c_int, cov)
         s["corrla_fill_normal_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])

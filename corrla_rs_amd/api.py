@@ -143,11 +143,15 @@ def _f32_like(a):
     return np.empty(0, dtype=np.float32)
 
 
-def _check_standardize(v):
-    """standardize is a switch: anything but a bool (a tolerance, a vector of scales, "yes") is a mistake, not a truth value"""
+def _check_bool(name, v, exc):
+    """a switch is a switch: anything but a bool (a tolerance, a vector of scales, "yes") is a mistake, not a truth value"""
     if not isinstance(v, (bool, np.bool_)):
-        raise TypeError(f"standardize must be True or False, got {type(v).__name__}")
+        raise exc(f"{name} must be True or False, got {type(v).__name__}")
     return bool(v)
+
+
+def _check_standardize(v):
+    return _check_bool("standardize", v, TypeError)
 
 
 def _ptr(t):
@@ -469,6 +473,59 @@ class Context:
         operand, m, n, like, on_dev = self._csr_operand(x_mat)
         return self._run_pca("corrla_pca_csr_", operand, m, n, min(m, n), like, on_dev, rank, n_iter, n_oversamples, seed, omega,
                              L.PCA_CENTER_FUSED, standardize=standardize)
+
+    # ---- covariance / correlation matrices (stats_corr.rs:14-43) --------------------------------
+    def cov(self, x, *, correlation=False, center=True, ddof=1):
+        """Covariance matrix of the columns of x (n_samples x n_dim), ``mat_cov_centered`` (stats_corr.rs:32-43), or with
+        correlation=True their Pearson correlation matrix, ``pearson_corr`` (:14-28) -> (C (n, n), means (1, n), scales (1, n)).
+
+        One symmetric MFMA kernel (corrla_cov_*): only the tile pairs on and above the diagonal are computed, x is centred
+        in registers -- never rewritten, and never copied when its features have unit stride -- and C is bitwise symmetric.
+        center=False: the second-moment matrix x^T x / (n_samples - ddof); means is then None.  scales is None without
+        correlation; with it, the column standard deviations (divisor n_samples - ddof; 1 for a constant column, whose row,
+        column and diagonal entry of C are 0).  ddof: 0 or 1.
+        numpy in -> numpy out; a CUDA tensor in -> tensors on its device.  float32 stays float32, anything else becomes
+        float64.  bfloat16 and sparse inputs raise ValueError.  ``last_cov_route()`` names the route that served the call."""
+        correlation, center = _check_bool("correlation", correlation, ValueError), _check_bool("center", center, ValueError)
+        if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or ddof not in (0, 1):
+            raise ValueError("ddof must be 0 or 1")
+        if correlation and not center:
+            raise ValueError("correlation=True needs center=True: a correlation matrix is one of centred columns")
+        if _is_sparse(x):
+            raise ValueError("cov has no sparse entry: a covariance matrix is dense; pass a dense matrix (.toarray() / .to_dense())")
+        _reject_bf16(x, "cov")
+        a, on_dev = _as_dense(x, "x")
+        if on_dev:
+            self._on_my_device(a)
+        m, n = a.shape
+        if m == 0 or n == 0:
+            raise ValueError("x must be non-empty")
+        flags = (L.COV_CORRELATION if correlation else 0) | (0 if center else L.COV_NO_CENTER)
+        if on_dev:
+            import torch
+            c = torch.empty((n, n), dtype=a.dtype, device=a.device)
+            means = torch.empty((1, n), dtype=a.dtype, device=a.device) if center else None
+            scales = torch.empty((1, n), dtype=a.dtype, device=a.device) if correlation else None
+        else:
+            c = np.empty((n, n), dtype=a.dtype)
+            means = np.empty((1, n), dtype=a.dtype) if center else None
+            scales = np.empty((1, n), dtype=a.dtype) if correlation else None
+        route = C.c_int(0)
+        if on_dev:
+            _sync_stream(a)
+        L.check(self._entry("corrla_cov_", on_dev, a.dtype)(self._h, _ptr(a), m, n, *_strides(a), flags, int(ddof),
+                                                            None if means is None else _ptr(means),
+                                                            None if scales is None else _ptr(scales), _ptr(c), n, C.byref(route)))
+        if on_dev:  # the device entry only enqueues: torch's streams see the results after this
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        self._cov_route = L.COV_ROUTES.get(route.value)
+        return c, means, scales
+
+    def last_cov_route(self):
+        """The route of this context's last ``cov`` call: "inplace" (x read where it lies with 16-byte loads),
+        "inplace_checked" (in place through bounds-checked element loads: base or row stride not 16-byte aligned) or
+        "repacked" (feature-strided x, transposed once into workspace); None before the first call."""
+        return getattr(self, "_cov_route", None)
 
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):

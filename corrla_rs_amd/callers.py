@@ -12,6 +12,9 @@ reference also does after its random_svd calls (k = n_modes, a few tens), writte
   PolyGradientEstimator / ActiveSsRsvd / FittedActiveSsRsvd
                                               <- src/lib_math_utils/active_subspaces.rs:21-277 (the
                                                  neighbour search and the local fits run on the GPU)
+  mat_cov_centered(x) / pearson_corr(x) / rsquared_sens(x, y, cor_dof)
+                                              <- src/lib_math_utils/stats_corr.rs:14-43, 75-107 (the n x n matrix from
+                                                 the symmetric MFMA kernel, ``Context.cov``)
 Every product with an n_x- or N-sized dimension goes through the library's HIP GEMMs (``Context.matmul``); only
 snapshot-count- and n_modes-sized matrices are touched by numpy."""
 import numpy as np
@@ -19,7 +22,7 @@ import numpy as np
 from .api import _is_torch, default_context, rsvd
 
 __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyGradientEstimator", "ActiveSsRsvd",
-           "FittedActiveSsRsvd"]
+           "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens"]
 
 
 def _on_gpu(x):
@@ -40,6 +43,30 @@ def active_ss_fit_svd(grad_mat, n_comps, n_iter=8, n_oversamples=10, *, seed=Non
     u, s, _vt = (ctx or default_context()).rsvd(g * (1.0 / np.sqrt(float(n_samples))), min(k_features, n_comps), n_iter,
                                                 n_oversamples, seed=seed, omega=omega)
     return u, np.diag(s.ravel())
+
+
+def mat_cov_centered(x, *, ctx=None):
+    """``mat_cov_centered(x)`` (stats_corr.rs:32-43): covariance matrix (n, n) of the columns of x, divisor n_samples - 1."""
+    return (ctx or default_context()).cov(x)[0]
+
+
+def pearson_corr(x, *, ctx=None):
+    """``pearson_corr(x)`` (stats_corr.rs:14-28): Pearson correlation matrix (n, n) of the columns of x (the standard
+    deviations with the divisor n_samples - 1, as ``mat_std``)."""
+    return (ctx or default_context()).cov(x, correlation=True)[0]
+
+
+def rsquared_sens(x, y, cor_dof, *, ctx=None):
+    """``rsquared_sens(x, y, cor_dof)`` (stats_corr.rs:75-107): R^2 = r_y^T pinv(r_xx) r_y from the correlation matrix of
+    [x | y] (GPU); cor_dof applies 1 - (1 - R^2) (n - 1) / (n - k - 1).  Returns a (1, 1) array."""
+    xa, ya = np.asarray(x, np.float64), np.asarray(y, np.float64).reshape(len(y), -1)
+    n_samples, k_features = xa.shape
+    r_xy = np.asarray((ctx or default_context()).cov(np.hstack([xa, ya]), correlation=True)[0])
+    r_xx, r_y = r_xy[:-1, :-1], r_xy[:-1, -1:]
+    r_sqr = r_y.T @ _pinv_reg(r_xx) @ r_y
+    if cor_dof:
+        r_sqr = 1.0 - (1.0 - r_sqr) * ((n_samples - 1.0) / (n_samples - k_features - 1.0))
+    return r_sqr
 
 
 class PolyGradientEstimator:

@@ -742,4 +742,37 @@ inline void matmul_bf16_entry(Dev& dev, int trans, const uint16_t* a, int64_t m,
       [&] { return stage_bf16(dev, false, a, m, n, rs, cs, true, l, false); });
 }
 
+// ---- covariance / correlation matrices (corrla_cov_*) -------------------------------------------------------------------
+// Argument checks of every corrla_cov_* entry, then `run` -- on a backend that carries the symmetric rank-k kernel
+// (dev_has_syrk); any other backend ends the call with EINVAL, never with another way of computing the matrix.
+inline bool cov_ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  if (!a || !b) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+template <class Dev, class T, class Run>
+inline void cov_entry(Dev&, const T* x, int64_t m, int64_t n, int64_t rs, int64_t cs, uint64_t flags, int ddof, T* means_out,
+                      T* scales_out, T* c, int64_t ldc, int* route_out, Run&& run) {
+  if (route_out) *route_out = 0;
+  if (flags & ~(uint64_t)(CORRLA_COV_CORRELATION | CORRLA_COV_NO_CENTER)) throw Error(ST_EINVAL, "cov: unknown flag");
+  if ((flags & CORRLA_COV_CORRELATION) && (flags & CORRLA_COV_NO_CENTER))
+    throw Error(ST_EINVAL, "CORRLA_COV_CORRELATION and CORRLA_COV_NO_CENTER are mutually exclusive");
+  if (ddof != 0 && ddof != 1) throw Error(ST_EINVAL, "cov: ddof must be 0 or 1");
+  if (!x || !c) throw Error(ST_EINVAL, "cov: x or c is NULL");
+  if (n < 1 || m < 1) throw Error(ST_EINVAL, "cov: empty matrix");
+  if (m - ddof < 1) throw Error(ST_EINVAL, "cov: n_samples - ddof < 1");
+  if (ldc < n) throw Error(ST_EINVAL, "cov: ldc < n");
+  if (rs < 0 || cs < 0) throw Error(ST_EINVAL, "cov: negative strides are not supported");
+  const size_t xb = (size_t)((m - 1) * rs + (n - 1) * cs + 1) * sizeof(T), cb = (size_t)((n - 1) * ldc + n) * sizeof(T),
+               vb = (size_t)n * sizeof(T);
+  if (cov_ranges_overlap(x, xb, c, cb) || cov_ranges_overlap(x, xb, means_out, vb) || cov_ranges_overlap(x, xb, scales_out, vb) ||
+      cov_ranges_overlap(c, cb, means_out, vb) || cov_ranges_overlap(c, cb, scales_out, vb) ||
+      cov_ranges_overlap(means_out, vb, scales_out, vb))
+    throw Error(ST_EINVAL, "cov: buffers overlap");
+  if constexpr (dev_has_syrk<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no symmetric rank-k kernel: corrla_cov_* is not supported");
+}
+
 }  // namespace corrla

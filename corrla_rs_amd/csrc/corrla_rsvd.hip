@@ -6,6 +6,7 @@
 
 #include "capi_impl.hpp"
 #include "core_svd_stage.hpp"
+#include "cov_stage.hpp"
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 
@@ -266,6 +267,21 @@ CORRLA_API corrla_status corrla_matmul_dev_bf16(corrla_ctx* ctx, int trans, CORR
     matmul_bf16_entry<HipDev>(c.dev, trans, a, m, n, rs, cs, x, ldx, l, beta, res, ldres, &c.last);
   });
 }
+
+// ---- covariance / correlation matrices (stats_corr.rs:14-43) -------------------------------------------------------------
+#define CORRLA_DEFINE_COV(NAME, T, HOST)                                                                                \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(T, x), uint64_t flags, int ddof, T* means_out, T* scales_out, \
+                                T* c, int64_t ldc, int* route_out) {                                                    \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cov_entry<HipDev, T>(cx.dev, x, m, n, rs, cs, flags, ddof, means_out, scales_out, c, ldc, route_out, [&] {        \
+        cov_stage::run<T>(cx.dev, HOST, x, m, n, rs, cs, flags, ddof, means_out, scales_out, c, ldc, route_out);        \
+      });                                                                                                               \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_COV(corrla_cov_f32, float, true)
+CORRLA_DEFINE_COV(corrla_cov_f64, double, true)
+CORRLA_DEFINE_COV(corrla_cov_dev_f32, float, false)
+CORRLA_DEFINE_COV(corrla_cov_dev_f64, double, false)
 
 // ---- active-subspace gradient stage ------------------------------------------------------
 static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,

@@ -103,6 +103,12 @@ struct dev_has_colvar : std::false_type {};
 template <class D>
 struct dev_has_colvar<D, std::void_t<decltype(D::kHasColVar)>> : std::true_type {};
 
+// ... and those that carry the symmetric rank-k kernel of corrla_cov_* (syrk_kernels.hpp) with kHasSyrk.
+template <class D, class = void>
+struct dev_has_syrk : std::false_type {};
+template <class D>
+struct dev_has_syrk<D, std::void_t<decltype(D::kHasSyrk)>> : std::true_type {};
+
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).
 template <class T>

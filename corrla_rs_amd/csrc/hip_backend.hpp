@@ -31,6 +31,7 @@
 #include "grad_wide_kernels.hpp"
 #include "spmm_kernels.hpp"
 #include "colvar_kernels.hpp"
+#include "syrk_kernels.hpp"
 
 namespace corrla {
 
@@ -152,6 +153,7 @@ class HipDev {
     gemm_knobs_.no_gram_alias = env_int("CORRLA_NO_GRAM_ALIAS", 0) != 0;
     gemm_knobs_.no_rotate = env_int("CORRLA_GEMM_NO_ROTATE", 0) != 0;
     gemm_knobs_.mixed_split = env_int("CORRLA_MIXED_SPLIT", 0);
+    syrk_knobs_.slab_rows = env_int("CORRLA_SYRK_SLAB_ROWS", 0);  // syrk_plan.hpp
   }
   ~HipDev() {
     (void)hipSetDevice(device);
@@ -1159,6 +1161,61 @@ class HipDev {
                        inv_sd);
     CORRLA_HIP(hipGetLastError());
   }
+  // ---- covariance / correlation matrices (syrk_plan.hpp, syrk_kernels.hpp) -----------------------------------------------
+  static constexpr bool kHasSyrk = true;  // driver.hpp: dev_has_syrk
+  const SyrkKnobs& syrk_knobs() const { return syrk_knobs_; }
+  // C (n x n, ldc) = covariance (or, corr, Pearson correlation) of the columns of x: m x n row-major with leading dimension
+  // p.ld on the device, read in place.  center: the column moments first (one pass, f64 accumulation), means_out / scales_out
+  // (device, optional) receive the means and -- corr only -- the standard deviations.  Enqueues only: no synchronisation.
+  template <class T>
+  void syrk(const SyrkPlan& p, const T* x, int64_t m, int64_t n, bool center, bool corr, int ddof, T* means_out, T* scales_out,
+            T* c, int64_t ldc) {
+    const int aligned = p.route == SyrkRoute::kInPlaceChecked ? 0 : 1;
+    const double denom = (double)(m - ddof);
+    double *mu64 = nullptr, *sd64 = nullptr;
+    T *mu_t = nullptr, *sd_t = nullptr;
+    int* is_const = nullptr;
+    if (center) {
+      constexpr int VEC = k::CvIn<T>::kVec;
+      const int64_t ngroups = (n + VEC - 1) / VEC;
+      int groups = 1;
+      while (groups < k::kCvThreads && groups < ngroups) groups *= 2;
+      const int ny = k::kCvThreads / groups;
+      const int64_t col_blocks = (ngroups + groups - 1) / groups;
+      const int64_t target = (int64_t)num_cus * 8;
+      const int64_t want = std::max<int64_t>(1, std::min<int64_t>((target + col_blocks - 1) / col_blocks, (m + 8 * ny - 1) / (8 * ny)));
+      const int64_t rows_per_slab = (m + want - 1) / want;
+      const int64_t nslab = (m + rows_per_slab - 1) / rows_per_slab;
+      dim3 grid((unsigned)col_blocks, (unsigned)nslab);
+      check_grid(grid);
+      double* psum = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
+      double* psq = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
+      mu64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
+      sd64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
+      mu_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
+      sd_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
+      is_const = (int*)alloc_bytes(sizeof(int) * (size_t)n);
+      hipLaunchKernelGGL((k::colmom_down_kernel<T>), grid, dim3(k::kCvThreads), 0, stream, x, m, n, p.ld, aligned, groups, rows_per_slab,
+                         psum, psq);
+      hipLaunchKernelGGL((k::colmom_final_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)psum,
+                         (const double*)psq, nslab, n, x, (double)m, denom, mu64, mu_t, sd64, sd_t, is_const);
+      CORRLA_HIP(hipGetLastError());
+      if (means_out) CORRLA_HIP(hipMemcpyAsync(means_out, mu_t, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+      if (corr && scales_out) CORRLA_HIP(hipMemcpyAsync(scales_out, sd_t, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+    }
+    T* ws = (T*)alloc_bytes(p.ws_bytes);
+    k::SyrkArgs<T> a{x, m, n, p.ld, aligned, mu_t, p.slab_rows, p.npairs, ws};
+    dim3 grid(p.grid_x, p.grid_y);
+    check_grid(grid);
+    if (center)
+      hipLaunchKernelGGL((k::syrk_kernel<T, true>), grid, dim3(p.block), p.lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((k::syrk_kernel<T, false>), grid, dim3(p.block), p.lds_bytes, stream, a);
+    CORRLA_HIP(hipGetLastError());
+    k::SyrkFinishArgs<T> f{ws, p.nsplit, p.npairs, n, (double)m, denom, mu64, mu_t, corr ? sd64 : nullptr, is_const, c, ldc};
+    hipLaunchKernelGGL((k::syrk_finish_kernel<T>), dim3(p.finish_grid_x, p.finish_grid_y), dim3(p.finish_block), 0, stream, f);
+    CORRLA_HIP(hipGetLastError());
+  }
   // out(i, c) = d[i] * in(i, c) over every allocated column (the padding columns are zero and stay zero); out may be in
   template <class T>
   void row_scale(const Skinny<T>& in, Skinny<T>& out, int64_t rows, const T* d) {
@@ -1316,6 +1373,7 @@ class HipDev {
   static constexpr size_t kPinnedBytes = (size_t)8 << 20;
   int gemm_debug_flags_ = 0;
   GemmKnobs gemm_knobs_;
+  SyrkKnobs syrk_knobs_;
   uint64_t entropy_ = 0, calls_ = 0, calls_sharded_ = 0;
   bool no_device_chol_ = false;
   const int* run_if_ = nullptr;
@@ -1369,6 +1427,8 @@ class HipDev {
     for_each_nt<sizeof(T) == 4 ? 6 : 4>([](auto nct) {
       lds_limit((const void*)k::tall_gram_kernel<T, decltype(nct)::value>, k::gram_lds_bytes(nct, (int)sizeof(T)));
     });
+    lds_limit((const void*)k::syrk_kernel<T, true>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
+    lds_limit((const void*)k::syrk_kernel<T, false>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::hh_leaf_factor_kernel<T, false>, kMax);
     lds_limit((const void*)k::hh_tree_factor_kernel<T, false>, kMax);
     lds_limit((const void*)k::hh_tree_apply_kernel<T, false>, kMax);

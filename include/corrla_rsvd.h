@@ -374,6 +374,55 @@ CORRLA_API corrla_status corrla_spmm_csr_dev_f64(corrla_ctx* ctx, int trans, con
                                     const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, const double* x,
                                     int64_t ldx, int64_t l, double beta, double* res, int64_t ldres);
 
+/* ---- covariance and Pearson correlation matrices -----------------------------------------------
+ * Replaces  mat_cov_centered(x)                                src/lib_math_utils/stats_corr.rs:32-43
+ *           pearson_corr(x)                                    src/lib_math_utils/stats_corr.rs:14-28
+ * and serves rsquared_sens (stats_corr.rs:75-107), whose correlation of [x | y] is this call.
+ * x: n_samples (m) x n_dim (n), strided like a MatRef, never modified and never copied when its features have unit stride
+ * (col_stride == 1, any row_stride >= n): one symmetric rank-k kernel on the exact f32 / f64 MFMAs computes only the tile
+ * pairs on and above the diagonal, takes both operands from the same staged rows of x and centres them in registers
+ *   C = (x - 1 mu^T)^T (x - 1 mu^T) / (m - ddof),            mu = column means (f64 accumulation, rounded once to T),
+ * then both triangles are written from the same value: C(i, j) and C(j, i) are bitwise equal.  The effect of rounding mu
+ * to T is removed exactly (a rank-1 term in f64).  No floating-point atomics: a fixed input gives a bitwise fixed result.
+ * A base or row_stride that is not 16-byte aligned is read in place through bounds-checked element loads
+ * (CORRLA_COV_ROUTE_INPLACE_CHECKED); a feature-strided x (column-major) is repacked once into workspace by a transposing
+ * copy (CORRLA_COV_ROUTE_REPACKED).
+ *   flags      : this entry's own flag word (NOT corrla_opts.flags), CORRLA_COV_* below
+ *   ddof       : 0 or 1, the divisor is m - ddof (>= 1)
+ *   means_out  : optional (may be NULL), n values; not written with CORRLA_COV_NO_CENTER
+ *   scales_out : optional (may be NULL), n values, written only with CORRLA_COV_CORRELATION: sd_j = sqrt(ss_j / (m - ddof)),
+ *                1 for a column that the rule of CORRLA_PCA_STANDARDIZE calls constant
+ *   c          : n x n, leading dimension ldc >= n (symmetric: row- and column-major read the same); entries of the padding
+ *                [n, ldc) are left as they were
+ *   route_out  : optional (may be NULL), receives the CORRLA_COV_ROUTE_* that served the call (0 when it failed)
+ * CORRLA_COV_CORRELATION: C(i, j) / (sd_i sd_j) clipped to [-1, 1], exactly 1 on the diagonal; a constant column gives a
+ * zero row and column and a zero diagonal.  CORRLA_COV_NO_CENTER: the second-moment matrix x^T x / (m - ddof).
+ * CORRLA_EINVAL: both flags, an unknown flag, ddof outside {0, 1}, m - ddof < 1, n < 1, NULL x or c, overlapping buffers,
+ * ldc < n, negative strides.  Host-pointer entries copy x to the device as it lies (same strides, same alignment, so the
+ * same route serves) and the results back; the *_dev entries take HIP device pointers, enqueue on the context's stream and
+ * return WITHOUT synchronising: corrla_ctx_synchronize (or any later call on the context) orders the results.
+ * (One exception: the first call that needs more workspace than the context's arena holds grows it with hipMalloc, which
+ * synchronises the device implicitly; later calls of that size do not.)  The host-pointer entries copy the whole strided
+ * span of x, first to last element with the gaps between rows: a narrow column view of a wide array stages the wide rows.
+ * The environment variable CORRLA_SYRK_SLAB_ROWS (read when the context is created) forces the rows per slab. */
+#define CORRLA_COV_CORRELATION 0x1ull /* 64-bit, as the flags parameter */
+#define CORRLA_COV_NO_CENTER 0x2ull
+#define CORRLA_COV_ROUTE_INPLACE 1
+#define CORRLA_COV_ROUTE_INPLACE_CHECKED 2
+#define CORRLA_COV_ROUTE_REPACKED 3
+CORRLA_API corrla_status corrla_cov_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t n, int64_t row_stride,
+                                        int64_t col_stride, uint64_t flags, int ddof, float* means_out, float* scales_out,
+                                        float* c, int64_t ldc, int* route_out);
+CORRLA_API corrla_status corrla_cov_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t n, int64_t row_stride,
+                                        int64_t col_stride, uint64_t flags, int ddof, double* means_out, double* scales_out,
+                                        double* c, int64_t ldc, int* route_out);
+CORRLA_API corrla_status corrla_cov_dev_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t n, int64_t row_stride,
+                                            int64_t col_stride, uint64_t flags, int ddof, float* means_out, float* scales_out,
+                                            float* c, int64_t ldc, int* route_out);
+CORRLA_API corrla_status corrla_cov_dev_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t n, int64_t row_stride,
+                                            int64_t col_stride, uint64_t flags, int ddof, double* means_out, double* scales_out,
+                                            double* c, int64_t ldc, int* route_out);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller

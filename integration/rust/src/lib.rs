@@ -35,6 +35,12 @@ pub const CORRLA_SHARD_COLS: u32 = 0x40;
 pub const CORRLA_SKETCH_BF16X3: u32 = 0x80; // opt-in: range finder on the bf16-split kernels (f32 inputs only)
 pub const CORRLA_SKETCH_BF16X6: u32 = 0x100;
 pub const CORRLA_PCA_STANDARDIZE: u32 = 0x200; // corrla_pca_* only: PCA on standardised columns (correlation PCA)
+// corrla_cov_*: the entry's own 64-bit flag word and the routes it reports through route_out
+pub const CORRLA_COV_CORRELATION: u64 = 0x1;
+pub const CORRLA_COV_NO_CENTER: u64 = 0x2;
+pub const CORRLA_COV_ROUTE_INPLACE: c_int = 1;
+pub const CORRLA_COV_ROUTE_INPLACE_CHECKED: c_int = 2;
+pub const CORRLA_COV_ROUTE_REPACKED: c_int = 3;
 
 extern "C" {
     fn corrla_ctx_create(device: c_int, out: *mut *mut c_void) -> c_int;
@@ -87,6 +93,16 @@ extern "C" {
     pub fn corrla_spmm_csr_dev_f64(ctx: *mut c_void, trans: c_int, values: *const f64, col_idx: *const i32,
                                    row_ptr: *const i64, m: i64, n: i64, nnz: i64, x: *const f64, ldx: i64, l: i64,
                                    beta: f64, res: *mut f64, ldres: i64) -> c_int;
+    // covariance / Pearson correlation matrix (stats_corr.rs:14-43); host pointers, c is n x n with leading dimension ldc
+    pub fn corrla_cov_f64(ctx: *mut c_void, x: *const f64, m: i64, n: i64, rs: i64, cs: i64, flags: u64, ddof: c_int,
+                          means_out: *mut f64, scales_out: *mut f64, c: *mut f64, ldc: i64, route_out: *mut c_int) -> c_int;
+    pub fn corrla_cov_f32(ctx: *mut c_void, x: *const f32, m: i64, n: i64, rs: i64, cs: i64, flags: u64, ddof: c_int,
+                          means_out: *mut f32, scales_out: *mut f32, c: *mut f32, ldc: i64, route_out: *mut c_int) -> c_int;
+    // ... device pointers; enqueues on the context's stream and returns without synchronising
+    pub fn corrla_cov_dev_f64(ctx: *mut c_void, x: *const f64, m: i64, n: i64, rs: i64, cs: i64, flags: u64, ddof: c_int,
+                              means_out: *mut f64, scales_out: *mut f64, c: *mut f64, ldc: i64, route_out: *mut c_int) -> c_int;
+    pub fn corrla_cov_dev_f32(ctx: *mut c_void, x: *const f32, m: i64, n: i64, rs: i64, cs: i64, flags: u64, ddof: c_int,
+                              means_out: *mut f32, scales_out: *mut f32, c: *mut f32, ldc: i64, route_out: *mut c_int) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
