@@ -125,6 +125,21 @@ __global__ __launch_bounds__(64 * kKnnWaves) void knn_kernel(const double* __res
   }
 }
 
+// the power of two nearest below 1 / sqrt(d) (d * s * s in [1, 4)); 1 for a zero, negative or non-finite d
+__device__ __forceinline__ double grad_pow2_rsqrt(double d) {
+  if (!(d > 0.0) || !(d < __builtin_huge_val())) return 1.0;
+  int e = ilogb(d);
+  if (e < -1000) e = -1000;  // (a denormal: the scale and its square stay finite)
+  return ldexp(1.0, -(e >> 1));
+}
+// 1 / grad_pow2_rsqrt(d)^2: the even power of two p with d / p in [1, 4)
+__device__ __forceinline__ double grad_pow2_unit(double d) {
+  if (!(d > 0.0) || !(d < __builtin_huge_val())) return 1.0;
+  int e = ilogb(d);
+  if (e < -1000) e = -1000;
+  return ldexp(1.0, 2 * (e >> 1));
+}
+
 // ---- k-NN with the distance tile on the f64 MFMA ---------------------------------------------------------
 // d^2(q, p) = |q|^2 + |p|^2 - 2 q.p: each wave owns 16 queries whose MFMA A-fragments (16 x 4 slices of the query
 // block, f32) stay in registers for the whole scan; per chunk of 64 points it issues 4 x k/4 v_mfma_f32_16x16x4_f32
@@ -133,6 +148,13 @@ __global__ __launch_bounds__(64 * kKnnWaves) void knn_kernel(const double* __res
 // only a FILTER (margin 1e-5 (|q|^2 + |p|^2) covers the f32 rounding); a candidate that passes gets its exact
 // distance sum_d (p_d - q_d)^2 recomputed across the lanes before it may enter the sorted list, so the neighbour sets
 // and their order are those of the exact search.
+// The f32 operands are the coordinates times an exact power of two that brings the cloud's largest |p|^2 to 2^100 .. 2^102
+// (point_norms_kernel finds it): f32 holds 2^-126 .. 2^128, so unscaled products vanish below |x| ~ 1e-19 -- the filter then
+// saw d^2 = |q|^2 + |p|^2 and dropped true neighbours -- and overflow above 1.8e19.  The TOP of f32's range, so that points
+// far smaller than the largest one (a cloud with an outlier) keep their products: 2^-100 of the largest |p|^2 and less is
+// where they would leave the normal range, and such a point goes to the exact re-check with every query (`tiny` in the kernel).
+// The norms and the re-check are f64 on the caller's coordinates.
+constexpr int kKnnScaleLog2 = 50;  // the largest |p| lands in [2^50, 2^51)
 typedef float knn_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ double wave_max_f64(double x) {
   auto dpp = [](double v, auto ctrl) {
@@ -173,6 +195,12 @@ __global__ __launch_bounds__(64 * W) void knn_mfma_kernel(const double* __restri
                                                           const double* __restrict__ pnorm, int64_t n_pts, int k,
                                                           const double* __restrict__ xq, int64_t n_q, int n_nbrs,
                                                           int* __restrict__ nbr) {
+  // pnorm[n_pts]: the largest finite |p|^2 (bit pattern); sc = 2^-m with sc^2 max |p|^2 in [1, 4), isc2 = 1 / sc^2
+  const double pmax = __longlong_as_double(*(const long long*)(pnorm + n_pts));
+  int sce = pmax > 0.0 ? kKnnScaleLog2 - (ilogb(pmax) >> 1) : 0;
+  sce = max(-500, min(500, sce));  // (sc^2 and 1 / sc^2 stay finite, normal numbers)
+  const double sc = ldexp(1.0, sce), isc2 = ldexp(1.0, -2 * sce);
+  const double tiny = ldexp(1.0, -100) * isc2;  // |p|^2 below it: products with it may leave f32's normal range
   constexpr int QT = 16 * W;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int k4 = (k + 3) & ~3;
@@ -212,7 +240,7 @@ __global__ __launch_bounds__(64 * W) void knn_mfma_kernel(const double* __restri
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     const int d = 4 * ks + (lane >> 4);
-    afr[ks] = d < k4 ? (float)qv[(wave * 16 + (lane & 15)) * k4 + d] : 0.0f;
+    afr[ks] = d < k4 ? (float)(qv[(wave * 16 + (lane & 15)) * k4 + d] * sc) : 0.0f;
   }
   // D layout of v_mfma_f32_16x16x4_f32: column (point) = lane & 15, row (query) = 4 (lane >> 4) + r
   double qn_r[4], tau_r[4];
@@ -243,7 +271,7 @@ __global__ __launch_bounds__(64 * W) void knn_mfma_kernel(const double* __restri
       const int d = idx >> 6, j = idx & 63;
       if (d < KD) {
         pts[d * kKnnPitch + j] = pre[i];
-        ptsf[d * kKnnPitch + j] = (float)pre[i];
+        ptsf[d * kKnnPitch + j] = (float)(pre[i] * sc);
       }
     }
     if (tid < 64) pn[tid] = pre_n;
@@ -271,13 +299,14 @@ __global__ __launch_bounds__(64 * W) void knn_mfma_kernel(const double* __restri
       const int pl = 16 * t + (lane & 15);
       const double pnv = pn[pl];
       const bool pvalid = base + pl < n_pts;
+      const bool psmall = pnv < tiny && pnv > 0.0;  // (an exact zero has exact products)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const double nsum = qn_r[r] + pnv;
-        const double dm = nsum - 2.0 * (double)acc[t][r];
+        const double dm = nsum - (2.0 * isc2) * (double)acc[t][r];
         // f32 products and sums over <= 64 dimensions: |error of 2 q.p| < 4e-6 (|q|^2 + |p|^2); the negated comparison
         // lets a non-finite value (f32 overflow) through to the exact re-check as well
-        if (pvalid && !(dm - 1e-5 * nsum >= tau_r[r])) hits |= 1u << (4 * t + r);
+        if (pvalid && (psmall || !(dm - 1e-5 * nsum >= tau_r[r]))) hits |= 1u << (4 * t + r);
       }
     }
     if (__any(hits != 0)) {
@@ -356,13 +385,17 @@ __global__ __launch_bounds__(64 * W) void knn_mfma_kernel(const double* __restri
     nbr[(q0 + qq) * n_nbrs + rank] = ix;
   }
 }
-// |p|^2 of every support point (from the dimension-major copy)
+// |p|^2 of every support point (from the dimension-major copy); pn[n] (zeroed by the launcher) <- the largest finite one, as
+// its bit pattern (non-negative doubles order like their bit patterns)
 __global__ void point_norms_kernel(const double* __restrict__ xt, int64_t ldt, int64_t n, int k, double* pn) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
   double s = 0.0;
-  for (int d = 0; d < k; ++d) s += xt[(int64_t)d * ldt + i] * xt[(int64_t)d * ldt + i];
-  pn[i] = s;
+  if (i < n) {
+    for (int d = 0; d < k; ++d) s += xt[(int64_t)d * ldt + i] * xt[(int64_t)d * ldt + i];
+    pn[i] = s;
+  }
+  const double m = wave_max_f64(s < __builtin_huge_val() ? s : 0.0);  // (a NaN compares false)
+  if ((threadIdx.x & 63) == 0 && m > 0.0) atomicMax((unsigned long long*)(pn + n), (unsigned long long)__double_as_longlong(m));
 }
 
 // g[q * ldg + m] = out_scale * d(fit)/dx_m at query q.  status[q]: 0 ok, 1 ridge-regularised (rank-deficient design).
@@ -478,8 +511,22 @@ __global__ __launch_bounds__(64) void grad_fit_kernel(const double* __restrict__
   // i >= j -- every lane runs the same j-long dot product over its own row (odd pitch: conflict-free) against the
   // broadcast row j, one barrier per column and no read-modify-write of the trailing matrix.  (Round 2's right-looking
   // form spent ~1.5 us per pivot on its unbalanced rank-1 update and two more barriers: ~100 us of a 460-us query.)
+  // The pivot test and the ridge are those of the EQUILIBRATED system (as grad_fit_wide_kernel): column i scaled by the power
+  // of two s_i next to 1 / sqrt(M(i, i)), diagonal in [1, 4) whatever the units of the features.  The raw diagonal spans
+  // (spread of a feature)^2 (^4 for the quadratic columns) against n_nbrs for the constant, and a test against ITS maximum
+  // called full-rank designs with small, large or mixed feature scales singular.  Scaling by powers of two commutes with every
+  // rounding of the factorisation, so the matrix stays as it is and only the test moves: pivot j is compared with
+  // 1e-13 dmax u_j and the ridge of column j is 1e-10 dmax u_j, u_j = 1 / s_j^2 (kept in beta, free until the solves) and
+  // dmax the largest scaled diagonal.  A zero column (a constant feature) has u_j = 1 and still fails its pivot.
+  for (int i = lane; i < P; i += 64) {
+    const double mii = M[i * LM + i], sc = grad_pow2_rsqrt(mii);
+    beta[i] = grad_pow2_unit(mii);
+    dinv[i] = mii * sc * sc;
+  }
+  __syncthreads();
   double dmax = 0.0;
-  for (int i = 0; i < P; ++i) dmax = fmax(dmax, M[i * LM + i]);
+  for (int i = 0; i < P; ++i) dmax = fmax(dmax, dinv[i]);
+  __syncthreads();  // (dinv is written again by the factorisation)
   double ridge = 0.0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     bool ok = true;
@@ -494,9 +541,9 @@ __global__ __launch_bounds__(64) void grad_fit_kernel(const double* __restrict__
           t1 += rj[p2 + 1] * rj[p2 + 1];
         }
         if (p2 < j) t0 += rj[p2] * rj[p2];
-        sjj = rj[j] + ridge - (t0 + t1);
+        sjj = rj[j] + ridge * beta[j] - (t0 + t1);
       }
-      if (!(sjj > 1e-13 * dmax)) {
+      if (!(sjj > 1e-13 * dmax * beta[j])) {
         ok = false;
         break;  // uniform
       }
@@ -638,6 +685,7 @@ __global__ __launch_bounds__(64, 2) void grad_fit_lin_kernel(const double* __res
   __syncthreads();
   int fl = 0;
   double ridge = 0.0, dmax = 0.0;
+  double thr0 = 0.0, thr1 = 0.0;  // pivot thresholds of this lane's rows (lane, 64 + lane), see below
   // optional (CORRLA_KNN2_PROF): 100 MHz ticks per phase, summed over the queries: [0] gather + normal equations,
   // [1] Cholesky, [2] triangular solves, [3] queries
   unsigned long long tp0 = prof ? wall_clock64() : 0, tp1 = 0, tp2 = 0;
@@ -707,17 +755,31 @@ __global__ __launch_bounds__(64, 2) void grad_fit_lin_kernel(const double* __res
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
           const int i = 16 * a + fg + 4 * rg, j = 16 * b + fr;
-          const double v = acc[a][b][rg];
-          if (i < P && j <= i) row(i)[j] = v + ((i == j) ? ridge : 0.0);
+          double v = acc[a][b][rg];
+          if (attempt == 1 && i == j) v += ridge * grad_pow2_unit(v);  // (uniform branch: the second attempt is rare)
+          if (i < P && j <= i) row(i)[j] = v;
           if (i == P && j < P) row(P)[j] = v;  // row k + 1 of G = D^T y
         }
     __syncthreads();
+    // The pivot test and the ridge are those of the EQUILIBRATED system (as grad_fit_wide_kernel): column i scaled by the
+    // power of two s_i next to 1 / sqrt(G(i, i)), diagonal in [1, 4) whatever the units of the features.  The raw diagonal
+    // spans (spread of a feature)^2 against n_nbrs for the constant, and a test against ITS maximum called full-rank designs
+    // with small, large or mixed feature scales singular.  Scaling by powers of two commutes with every rounding of the
+    // factorisation, so the matrix stays as it is and only the test moves: pivot j is compared with thr_j = 1e-13 dmax u_j,
+    // and the ridge of column j is 1e-10 dmax u_j, with u_j = 1 / s_j^2 and dmax the largest scaled diagonal.  The owner of row
+    // j holds thr_j and tests its own pivot; the verdict is collected after the factorisation (a failed pivot only makes
+    // the rest of it not-a-number arithmetic that the retry discards).  A zero column (a constant feature) has u_j = 1 and
+    // still fails.
     if (attempt == 0) {
-      double dm = 0.0;
-      for (int i = lane; i < P; i += 64) dm = fmax(dm, row(i)[i]);
+      const double g0 = lane < P ? M[myoff0 + lane] : 0.0, g1 = 64 + lane < P ? M[myoff1 + 64 + lane] : 0.0;
+      const double u0 = grad_pow2_unit(g0), u1 = grad_pow2_unit(g1), s0 = grad_pow2_rsqrt(g0), s1 = grad_pow2_rsqrt(g1);
+      double dm = fmax(g0 * s0 * s0, g1 * s1 * s1);
       for (int off = 32; off > 0; off >>= 1) dm = fmax(dm, __shfl_xor(dm, off, 64));
       dmax = dm;
+      thr0 = 1e-13 * dm * u0;
+      thr1 = 1e-13 * dm * u1;
     }
+    bool bad = false;
     // ---- Cholesky of the augmented system, BLOCKED left-looking, fixed row ownership: lane r keeps rows r and 64 + r of
     // the P + 1 <= 66 rows (row P is the right-hand side: its factor row is the forward-solved z = L^-1 b, only the back
     // substitution is left afterwards).
@@ -772,10 +834,6 @@ __global__ __launch_bounds__(64, 2) void grad_fit_lin_kernel(const double* __res
       if (r1 >= c0 && r1 < c1) dg1 = row1[r1];
       for (int j = c0; j < c1; ++j) {
         const double sjj = j < 64 ? bcast(dg0, j) : bcast(dg1, j - 64);
-        if (!(sjj > 1e-13 * dmax)) {
-          ok = false;
-          break;  // uniform
-        }
         double rinv = __builtin_amdgcn_rsq(sjj);
         rinv = rinv * (1.5 - 0.5 * sjj * rinv * rinv);
         rinv = rinv * (1.5 - 0.5 * sjj * rinv * rinv);
@@ -807,10 +865,12 @@ __global__ __launch_bounds__(64, 2) void grad_fit_lin_kernel(const double* __res
         if (lane == (j & 63)) {  // the owner of row j
           rj[j] = sjj * rinv;
           dinv[j] = rinv;
+          bad = bad || !(sjj > (j < 64 ? thr0 : thr1));
         }
         __syncthreads();  // column j of the factor is in LDS before pivot j + 1 reads row j + 1 up to it
       }
     }
+    ok = !__any(bad);
     if (ok) break;
     if (attempt == 1) {
       fl = 2;  // still singular: zero gradient

@@ -150,7 +150,8 @@ struct GradPlan {
   int64_t scan_wgs = 0;         // workgroups (kKnn2, kWide: persistent, each takes query tiles in turn)
   int64_t scan_tiles = 0;       // kKnn2, kWide: query tiles
   size_t scan_lds = 0;          // dynamic LDS of the scan kernel
-  size_t scan_ws = 0;           // every workspace of the scan and of the kernels that prepare it
+  size_t scan_ws = 0;           // every workspace of the scan and of the kernels that prepare it, but for scale_ws
+  size_t scale_ws = 0;          // kKnn2, kMfma: the block that holds the filter's power-of-two scale (zeroed before the scan)
   int64_t ldt = 0;              // limited scans: pitch of the transposed cloud (k x ldt doubles)
   int64_t pts_wgs = 0;          // limited scans: 256-thread blocks over the points (grad_transpose_kernel, point_norms_kernel)
   struct Knn2 {                 // kKnn2: the prepared cloud and the per-workgroup lists
@@ -228,6 +229,7 @@ inline GradPlan grad_plan(int64_t n_pts, int64_t kf, int64_t n_q, int order, int
       g.list_i = lists * k::kK2List * sizeof(int);
       // + the column sums of the g.nb blocks and the mean, 64 doubles each
       p.scan_ws += g.pb + g.pn + (size_t)(g.nb + 1) * 64 * sizeof(double) + g.cand + g.list_d + g.list_i;
+      p.scale_ws = 64 * sizeof(double);
     } else if (knn_mode == 1 || (knn_mode == 0 && n_pts < 131072) || k::knn_mfma_lds_bytes(kk, nn, 2) > kMax) {
       // (also when the MFMA scan's per-query lists outgrow LDS: n_nbrs > ~400 at k = 64)
       p.scan = GradScan::kValu;
@@ -244,6 +246,7 @@ inline GradPlan grad_plan(int64_t n_pts, int64_t kf, int64_t n_q, int order, int
       p.scan_lds = k::knn_mfma_lds_bytes(kk, nn, p.scan_w);
       p.scan_wgs = ceil_div(n_q, 16 * p.scan_w);
       p.scan_ws += (size_t)n_pts * sizeof(double);  // the points' squared norms
+      p.scale_ws = sizeof(double);                  // the largest of them
     }
   }
   // ---- fit ----

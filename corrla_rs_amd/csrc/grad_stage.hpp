@@ -60,9 +60,11 @@ inline void scan_knn2(HipDev& dev, const GradCall& c, const GradPlan& p) {
   const int kk = (int)c.k;
   __bf16* pb = ws<__bf16>(dev, g.pb);
   float* pn = ws<float>(dev, g.pn);
-  double* mean = ws<double>(dev, 64 * sizeof(double));
+  double* mean = ws<double>(dev, 64 * sizeof(double) + p.scale_ws);  // the centre, then the filter's scale (Knn2Args::mean)
   double* partial = ws<double>(dev, (size_t)g.nb * 64 * sizeof(double));
-  hipLaunchKernelGGL(k::knn2_colsum_kernel, dim3((unsigned)g.nb), dim3(256), 0, dev.stream, c.x, c.n_pts, kk, g.rpb, partial);
+  CORRLA_HIP(hipMemsetAsync(mean + 64, 0, p.scale_ws, dev.stream));
+  hipLaunchKernelGGL(k::knn2_colsum_kernel, dim3((unsigned)g.nb), dim3(256), 0, dev.stream, c.x, c.n_pts, kk, g.rpb, partial,
+                     (unsigned long long*)(mean + 66));
   hipLaunchKernelGGL(k::knn2_mean_kernel, dim3(1), dim3(64), 0, dev.stream, (const double*)partial, g.nb, c.n_pts, kk, mean);
   hipLaunchKernelGGL(k::knn2_prep_kernel, dim3((unsigned)g.nchunks), dim3(256), 0, dev.stream, c.x, c.n_pts, kk, (const double*)mean,
                      p.scan_s, pb, pn);
@@ -89,7 +91,8 @@ inline void scan_valu(HipDev& dev, const GradCall& c, const GradPlan& p) {  // g
 
 inline void scan_mfma(HipDev& dev, const GradCall& c, const GradPlan& p) {  // grad_kernels.hpp: f32-MFMA distance tiles
   const double* xt = transposed(dev, c, p);
-  double* pnorm = ws<double>(dev, sizeof(double) * (size_t)c.n_pts);
+  double* pnorm = ws<double>(dev, sizeof(double) * (size_t)c.n_pts + p.scale_ws);  // + the largest of them (the filter's scale)
+  CORRLA_HIP(hipMemsetAsync(pnorm + c.n_pts, 0, p.scale_ws, dev.stream));
   hipLaunchKernelGGL(k::point_norms_kernel, dim3((unsigned)p.pts_wgs), dim3(256), 0, dev.stream, xt, p.ldt, c.n_pts, (int)c.k, pnorm);
   with_one_of<4, 2>(p.scan_w, [&](auto w) {
     with_one_of<4, 8, 16>(p.scan_nks, [&](auto s) {

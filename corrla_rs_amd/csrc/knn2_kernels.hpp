@@ -14,6 +14,12 @@
 //    read is one conflict-free ds_read_b128.  A pair passes when  d^2_filter - margin (|q|^2 + |p|^2) < tau_q  (tau_q = the
 //    query's current n-th exact distance; margin 2e-4 bounds every rounding of the filter) -- conservative, never exact;
 //    the point's share of that test rides in as the MFMA's C operand, so the test is one compare per pair.
+//    Everything the filter sees -- the centred points and queries, the norms, tau_q -- is multiplied by an exact power of
+//    two (its square for norms and tau_q) that brings the cloud's largest |coordinate| into [2^50, 2^51): f32 holds
+//    2^-126 .. 2^128, so unscaled squares vanish below ~1e-19 and overflow above 1.8e19 (a point whose -c_p became -inf was
+//    taken for padding and could never be a neighbour); at the top of the range points 2^-100 of the largest in norm keep
+//    normal products, and smaller ones are sent to the re-check (knn2_prep_kernel).  knn2_colsum_kernel finds the maximum,
+//    knn2_mean_kernel the power of two.
 //  * SURVIVORS are only appended (4-byte index, ballot + popcount, no sorting) to a per-query candidate buffer.
 //  * FLUSHES are batched and ALIGNED: after chunks 1, 2, 4, 8, ... (the expected number of survivors per query between
 //    chunk c and 2c is n ln 2) every wave empties the buffers of its 32 queries at the same time -- the waves of a
@@ -39,14 +45,16 @@ namespace corrla {
 namespace k {
 
 constexpr float kK2Margin = 2.0e-4f;    // bound on |d^2_filter - d^2| / (|q|^2 + |p|^2), see the header
+constexpr int kK2ScaleLog2 = 50;        // the filter's images: the largest |x| of the cloud times the scale lies in [2^50, 2^51)
 
 struct Knn2Args {
   const __bf16* pb;   // [chunk][s][plane (hi, lo)][tile t of 16 points][lane][8]: B fragments of the centred points
   const float* pn;    // [chunk][64][4]: -c_p = -(1 - margin) |x_p - mean|^2 / 2 in f32, four copies (one 16-byte MFMA C operand
-                      // per point column); -inf for the padding points of the last chunk
+                      // per point column); -inf for the padding points of the last chunk, the largest float for a point
+                      // every query has to re-check (knn2_prep_kernel)
   const double* x;    // support points, row-major n_pts x k
   const double* xq;   // queries, row-major n_q x k
-  const double* mean; // [k]
+  const double* mean; // [64] the centre; [64] sc = the filter's power-of-two scale, [65] sc^2; [66] the largest finite |x|
   int64_t n_pts, n_q, nchunks, ntiles;
   int k, n_nbrs;
   int* cand;          // [gridDim.x][kK2Q][kK2Cap]
@@ -57,10 +65,13 @@ struct Knn2Args {
                              // [0] in flushes, [1] waiting for the chunk (DMA + barrier), [2] in all, [3] list merges (batches)
 };
 
-// column means of x (n x k row-major), two stages in fixed order: partial[b][d] = sum over the rows of block b
+// column means of x (n x k row-major), two stages in fixed order: partial[b][d] = sum over the rows of block b;
+// *amax (zeroed by the launcher) <- the largest |x| of the coordinates that enter the mean, as its bit pattern
+// (non-negative doubles order like their bit patterns)
 __global__ __launch_bounds__(256) void knn2_colsum_kernel(const double* __restrict__ x, int64_t n, int k, int64_t rows_per_block,
-                                                          double* partial) {
+                                                          double* partial, unsigned long long* amax) {
   __shared__ double red[256];
+  double am = 0.0;
   const int d = threadIdx.x & 63, sub = threadIdx.x >> 6;  // 4 row phases x 64 dimensions
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = min(n, r0 + rows_per_block);
   double s = 0.0;
@@ -70,11 +81,16 @@ __global__ __launch_bounds__(256) void knn2_colsum_kernel(const double* __restri
       // every pair would pass the filter, and the scan would degenerate into the exact re-check of all N x N_q pairs
       // (the centre only has to be near the cloud; a non-finite point itself still goes through the re-check and sorts last)
       const double v = x[r * k + d];
-      if (fabs(v) < 1.0e300) s += v;
+      if (fabs(v) < 1.0e300) {
+        s += v;
+        am = fmax(am, fabs(v));
+      }
     }
   red[threadIdx.x] = s;
   __syncthreads();
   if (sub == 0 && d < k) partial[(int64_t)blockIdx.x * 64 + d] = (red[d] + red[64 + d]) + (red[128 + d] + red[192 + d]);
+  for (int off = 32; off > 0; off >>= 1) am = fmax(am, __shfl_xor(am, off, 64));
+  if ((threadIdx.x & 63) == 0 && am > 0.0) atomicMax(amax, (unsigned long long)__double_as_longlong(am));
 }
 __global__ void knn2_mean_kernel(const double* partial, int nblocks, int64_t n, int k, double* mean) {
   const int d = threadIdx.x;
@@ -83,6 +99,14 @@ __global__ void knn2_mean_kernel(const double* partial, int nblocks, int64_t n, 
   if (d < k)
     for (int b = 0; b < nblocks; ++b) s += partial[(int64_t)b * 64 + d];
   mean[d] = d < k ? s / (double)n : 0.0;
+  if (d == 0) {
+    const double a = mean[66];
+    // max |x| lands in [2^50, 2^51), near the TOP of what f32 can square and sum over 64 dimensions (|x - mean| <= 2 max |x|:
+    // norms below 2^110): points far smaller than the largest one (a cloud with outliers) keep normal products
+    const double sc = a > 0.0 ? ldexp(1.0, max(-500, min(500, kK2ScaleLog2 - ilogb(a)))) : 1.0;  // (sc^2 stays finite, normal)
+    mean[64] = sc;
+    mean[65] = sc * sc;
+  }
 }
 
 // one 256-thread block per chunk of 64 points: centred coordinates -> two bf16 pieces in B-fragment order, + norms.
@@ -91,34 +115,51 @@ __global__ __launch_bounds__(256) void knn2_prep_kernel(const double* __restrict
                                                         int nsteps, __bf16* pb, float* pn) {
   const int64_t c = blockIdx.x;
   const int tid = threadIdx.x;
+  const double sc = mean[64];
+  // -c_p first.  Two kinds of points go to the exact re-check with every query instead of through the filter: they get the
+  // largest float as -c_p, which passes every real query's test (c_q is finite or -inf there) and fails that of a padding
+  // query of the last tile (c_q = +inf; a NaN would pass it, and the flush would read the row of a query that does not exist).
+  //  * A point whose scaled norm is below 2^-100 (2^-200 of the largest coordinate's square: a cloud with a far outlier)
+  //    may lose products to f32's denormal range, more than the margin allows when the query is as small.  An exact zero
+  //    has exact products.
+  //  * A point whose norm is not finite (a NaN or infinite coordinate, or one so large that it stayed out of the mean and the
+  //    maximum): its fragments are zeros, its distances are whatever the re-check finds (not-a-numbers sort last).
+  // -inf is left to the padding points of the last chunk.
+  __shared__ int recheck[kK2Chunk];
+  if (tid < kK2Chunk) {
+    const int64_t p = c * kK2Chunk + tid;
+    float out = -__builtin_huge_valf();
+    bool nonfinite = false;
+    if (p < n_pts) {
+      double s2 = 0.0;
+      for (int d = 0; d < k; ++d) {
+        const double df = (x[p * k + d] - mean[d]) * sc;
+        s2 += df * df;
+      }
+      out = -(0.5f * (1.0f - kK2Margin)) * (float)s2;
+      nonfinite = !(s2 < __builtin_huge_val());
+      if (nonfinite || ((float)s2 < 0x1p-100f && s2 > 0.0)) out = 3.0e38f;
+    }
+    recheck[tid] = nonfinite;
+    *(f32x4*)(pn + (c * kK2Chunk + tid) * 4) = (f32x4){out, out, out, out};
+  }
+  __syncthreads();
   __bf16* dst = pb + c * (int64_t)(nsteps * 8192 / 2);
   for (int item = tid; item < nsteps * 4 * 64; item += 256) {  // (s, t, lane)
     const int lane = item & 63, t = (item >> 6) & 3, s = item >> 8;
     const int64_t p = c * kK2Chunk + 16 * t + (lane & 15);
+    const bool use = p < n_pts && !recheck[16 * t + (lane & 15)];
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int d = 32 * s + 8 * (lane >> 4) + j;
-      v[j] = (p < n_pts && d < k) ? (float)(x[p * k + d] - mean[d]) : 0.0f;
+      v[j] = (use && d < k) ? (float)((x[p * k + d] - mean[d]) * sc) : 0.0f;
     }
     // (the f32 rounding of the centred coordinate, 2^-24 relative, is part of the margin)
     bf16x8 fr[2];
     mx_split8<2>(v, fr);
     *(bf16x8*)(dst + ((s * 2 + 0) * 4 + t) * 512 + lane * 8) = fr[0];
     *(bf16x8*)(dst + ((s * 2 + 1) * 4 + t) * 512 + lane * 8) = fr[1];
-  }
-  if (tid < kK2Chunk) {
-    const int64_t p = c * kK2Chunk + tid;
-    float out = -__builtin_huge_valf();
-    if (p < n_pts) {
-      double s2 = 0.0;
-      for (int d = 0; d < k; ++d) {
-        const double df = x[p * k + d] - mean[d];
-        s2 += df * df;
-      }
-      out = -(0.5f * (1.0f - kK2Margin)) * (float)s2;
-    }
-    *(f32x4*)(pn + (c * kK2Chunk + tid) * 4) = (f32x4){out, out, out, out};
   }
 }
 
@@ -224,7 +265,7 @@ struct K2WaveState {
 // (the kernel's argument block is passed field by field: taking its address moves the whole block to scratch)
 __device__ __forceinline__ void k2_flush_wave(const double* __restrict__ x, const double* __restrict__ xq, int kdim, int n_nbrs,
                                                        K2WaveState* st, int least, int64_t q0, int* cand_w, double* ld_w,
-                                                       int* li_w, double* qs, unsigned long long* n_batches) {
+                                                       int* li_w, double* qs, unsigned long long* n_batches, double sc2) {
   const int lane = threadIdx.x & 63, fg = lane >> 4;
   const double inf = __builtin_huge_val();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's candidate stores have left it
@@ -318,7 +359,8 @@ __device__ __forceinline__ void k2_flush_wave(const double* __restrict__ x, cons
     const int nn = n_nbrs;
     const double tsel = nn <= 64 ? l0.d : l1.d;  // (nn is uniform: readlane)
     const int tl = nn <= 64 ? nn - 1 : nn - 65;
-    const double tau = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(tsel), tl), __builtin_amdgcn_readlane(__double2loint(tsel), tl));
+    double tau = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(tsel), tl), __builtin_amdgcn_readlane(__double2loint(tsel), tl));
+    if (tau < inf) tau *= sc2;  // in the filter's units
     // the filter compares in f32: round the threshold UP (never below the exact n-th distance); the few ulps the f32
     // evaluation of cq loses are part of the margin
     float tf = (float)tau;
@@ -339,6 +381,9 @@ __global__ __launch_bounds__(64 * kK2Waves, kK2Waves / 4) void knn2_kernel(Knn2A
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int kdim = g.k;
+  // the filter's power-of-two scale and its square, read once at the start as uniform (scalar) values: read anywhere in or
+  // near the flush they cost the scan loop its register allocation (tests/test_abi.py guards that loop)
+  const double sc = g.mean[64], sc2 = g.mean[65];
   int* const cand_w = g.cand + ((int64_t)blockIdx.x * kK2Q + wave * kK2WQ) * kK2Cap;
   double* const ld_w = g.list_d + ((int64_t)blockIdx.x * kK2Q + wave * kK2WQ) * kK2List;
   int* const li_w = g.list_i + ((int64_t)blockIdx.x * kK2Q + wave * kK2WQ) * kK2List;
@@ -381,7 +426,7 @@ __global__ __launch_bounds__(64 * kK2Waves, kK2Waves / 4) void knn2_kernel(Knn2A
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int d = 32 * s + 8 * fg + j;
-          v[j] = (qv && d < kdim) ? (float)(g.xq[q * kdim + d] - g.mean[d]) : 0.0f;
+          v[j] = (qv && d < kdim) ? (float)((g.xq[q * kdim + d] - g.mean[d]) * sc) : 0.0f;
           qn += v[j] * v[j];
         }
         bf16x8 f2[2];
@@ -491,7 +536,7 @@ __global__ __launch_bounds__(64 * kK2Waves, kK2Waves / 4) void knn2_kernel(Knn2A
         for (int t = 0; t < 4; ++t) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            // negated comparison: a NaN (a non-finite point or query) goes through to the exact re-check
+            // negated comparison: a NaN (a non-finite query) goes through to the exact re-check
             hm[t][r] = __ballot(!(acc[mw][t][r] <= cq_r[4 * mw + r]));
           at[t] = (hm[t][0] | hm[t][1]) | (hm[t][2] | hm[t][3]);
         }
@@ -532,7 +577,7 @@ __global__ __launch_bounds__(64 * kK2Waves, kK2Waves / 4) void knn2_kernel(Knn2A
           stv.cnt[u] = cnt_r[u];
         }
         k2_flush_wave(g.x, g.xq, kdim, g.n_nbrs, &stv, least, q0, cand_w, ld_w, li_w,
-                      (double*)(smem + kK2Stages * STG) + wave * 64, g.prof ? &n_batches : nullptr);
+                      (double*)(smem + kK2Stages * STG) + wave * 64, g.prof ? &n_batches : nullptr, sc2);
 #pragma unroll
         for (int u = 0; u < 4 * kK2RowTiles; ++u) {
           cq_r[u] = stv.cq[u];

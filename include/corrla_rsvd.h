@@ -450,9 +450,15 @@ CORRLA_API corrla_status corrla_fill_normal_dev_f64(corrla_ctx* ctx, double* p, 
  * g  : out_scale * gradients in the reference's k x n_q column-major layout: n_q rows of k contiguous values, row
  *      stride ldg >= k.  fit_svd (active_subspaces.rs:233-250) passes out_scale = 1 / sqrt(n_q) and hands g to
  *      corrla_rsvd_dev_f64 as the k x n_q matrix (row_stride 1, col_stride ldg).
- * n_regularised (optional): queries whose normal equations were numerically singular (the reference's pinv returns
- *      the minimum-norm fit there; this build retries with a 1e-10 relative ridge, and writes a zero gradient if that
- *      fails too).  Nearest neighbours are exact (brute force); equal distances are ordered by index. */
+ * n_regularised (optional): queries whose design is numerically rank deficient -- a Cholesky pivot of the normal equations
+ *      below 1e-13 once every column is scaled to unit size, so a feature's units do not enter: a constant feature or too
+ *      few distinct neighbours are counted, a full-rank design whose features are small, large or differ in scale is not
+ *      (the reference's pinv returns the minimum-norm fit there; this build retries with a ridge of 1e-10 on the scaled
+ *      diagonal, and writes a zero gradient if that fails too).
+ *      Nearest neighbours are exact (brute force); equal distances are ordered by index.
+ *      Scale: any coordinates whose squares and pairwise squared distances are finite, normal f64 numbers; features may
+ *      differ in scale (micrometres beside pascals), points may differ in size (outliers), and nothing needs to be
+ *      normalised.  The neighbours are those of the coordinates as passed. */
 CORRLA_API corrla_status corrla_grad_mat_f64(corrla_ctx* ctx, const double* x, int64_t n_pts, int64_t k, const double* y,
                                              const double* xq, int64_t n_q, int est_order, int64_t n_nbrs, double out_scale,
                                              double* g, int64_t ldg, int* n_regularised);

@@ -1003,6 +1003,14 @@ def test_grad_mat_device_tensors_and_duplicate_points(ctx, torch):
     xd = x[:40].repeat_interleave(25, dim=0)
     gd, nreg = ctx.grad_mat(xd, xd @ w, 1, 20)
     assert nreg > 0 and torch.isfinite(gd).all()
+    # every point twice, y drawn independently of x, 41 neighbours: the query's two copies, 19 pairs and ONE copy of the
+    # next pair -- the lower index, as in the reference (with y = f(x) either copy gives the same gradient);
+    # tests/test_grad_reference.py asserts that every query's cut separates a pair and that the other copy would show
+    from tests import grad_reference as gr
+    xp, yp, xqp = (torch.tensor(a, device="cuda") for a in gr.paired_cloud(16))
+    g2, nreg = ctx.grad_mat(xp, yp, 1, gr.PAIRED_CLOUDS[16][1], xqp)
+    go, _, _ = gr.reference("paired", 16, 1, gr.PAIRED_CLOUDS[16][1], gr.N_QUERIES)
+    assert nreg == 0 and gr.feature_unit_error(g2.cpu().numpy(), go) <= 1e-9
 
 
 def test_randomised_parity_sweep(ctx):

@@ -259,6 +259,18 @@ def test_knn2_neighbour_sets_are_exact(ctx, monkeypatch, n, k, n_nbrs, nq, kind)
     if kind in ("gauss", "offset"):
         go = _ref_gradients(x, y, xq[:60], n_nbrs)
         assert np.max(np.abs(g3[:, :60] - go)) <= 1e-8 * np.abs(go).max()
+    if kind == "dups":
+        # y = f(x) gives two copies of a point the same value: whichever copy a scan keeps, the gradient is the same.  With
+        # y drawn independently of x the choice shows: 8200 points, every one twice, 81 neighbours -- the cut separates the
+        # two copies of one point for EVERY query (tests/test_grad_reference.py), and the lower index must be kept
+        from tests import grad_reference as gr
+        xp, yp, xqp = gr.paired_cloud(k)
+        go, _, _ = gr.reference("paired", k, 1, gr.PAIRED_CLOUDS[k][1], gr.N_QUERIES)
+        for knn in ("3", "1"):
+            monkeypatch.setenv("CORRLA_KNN", knn)
+            gi, nregi = ctx.grad_mat(xp, yp, 1, gr.PAIRED_CLOUDS[k][1], xqp)
+            assert nregi == 0 and gr.feature_unit_error(gi, go) <= 1e-9, knn
+        monkeypatch.delenv("CORRLA_KNN")
 
 
 def test_knn2_is_the_default_scan_and_handles_few_queries_many_points(ctx, torch):

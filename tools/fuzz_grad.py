@@ -4,6 +4,9 @@ cloud sizes, neighbour counts, both orders, the three k-NN kernels (CORRLA_KNN =
 (CORRLA_FIT), and now and then an order-2 design too large for LDS (k up to 30: normal equations in global memory).
 --wide draws the wide kernels' ground instead: k up to 256 and n_nbrs up to 2048 (order 1), order 2 up to k = 48, and
 the switches that force the wide scan and fit (CORRLA_KNN=4, CORRLA_FIT=2) next to the others.
+Every case is multiplied by a power-of-two scale, one for the cloud or one per feature (2^-40 .. 2^40), and checked in
+feature units against the scale-free reference of tests/grad_reference.py (exact least squares; the oracle's pseudo-inverse
+adds 1e-14 to the singular values and is only accurate for O(1) features).
 usage: fuzz_grad.py [n_cases] [seed] [--wide]"""
 import os
 import sys
@@ -11,11 +14,12 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import corrla_rs_amd as cr  # noqa: E402
-from oracle import active_ss_oracle as aso  # noqa: E402
+from tests import grad_reference as gr  # noqa: E402
 
 
 def run(n_cases=60, seed=0, ctx=None, verbose=True, wide=False):
     rng = np.random.default_rng(seed)
+    rng_scale = np.random.default_rng([seed, 1])   # a stream of its own: the shapes of a seed stay what they were
     ctx = ctx or cr.Context(0)
     bad = 0
     worst = 0.0
@@ -35,6 +39,9 @@ def run(n_cases=60, seed=0, ctx=None, verbose=True, wide=False):
         if not wide:
             nq = int(rng.integers(1, 8 if big2 else 60))
         xq = x[rng.choice(n, size=nq, replace=False)] if rng.random() < 0.5 else rng.standard_normal((nq, k))
+        # units: one power of two for the whole cloud, or one per feature
+        d = np.exp2(rng_scale.integers(-40, 41, size=k if rng_scale.random() < 0.5 else 1).astype(np.float64)) * np.ones(k)
+        x, xq = x * d, xq * d
         if wide:
             os.environ["CORRLA_KNN"] = str(int(rng.integers(0, 5)))   # 4 = the wide scan on any call
             os.environ["CORRLA_FIT"] = str(int(rng.integers(0, 3)))   # 2 = the wide fit on any call
@@ -48,15 +55,15 @@ def run(n_cases=60, seed=0, ctx=None, verbose=True, wide=False):
                 print("EXCEPTION", case, order, k, n, n_nbrs, repr(e)[:160])
             bad += 1
             continue
-        est = aso.PolyGradientEstimator(x, y, order, n_nbrs)
-        go = aso.create_grad_mat(est, xq)
-        dev = float(np.max(np.abs(g - go)) / max(np.abs(go).max(), 1e-300))
-        # ill-conditioned local designs amplify the forward-difference / rounding differences of the two solvers
+        go, _ = gr.gradients(x, y, xq, order, n_nbrs)
+        dev = gr.feature_unit_error(g, go, d)
+        # ill-conditioned local designs amplify the rounding differences of the two solvers (normal equations here)
         tol = 1e-7 if order == 1 else 1e-3
         worst = max(worst, dev)
         if nreg == 0 and not (dev <= tol):
             if verbose:
-                print("VIOLATION", case, "order", order, "k", k, "n", n, "nbrs", n_nbrs, "nq", nq, "dev %.2e" % dev)
+                print("VIOLATION", case, "order", order, "k", k, "n", n, "nbrs", n_nbrs, "nq", nq, "log2 scales %d..%d" %
+                      (np.log2(d.min()), np.log2(d.max())), "dev %.2e" % dev)
             bad += 1
     os.environ.pop("CORRLA_KNN", None)
     os.environ.pop("CORRLA_FIT", None)
