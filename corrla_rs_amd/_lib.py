@@ -26,6 +26,13 @@ COV_CORRELATION = 0x1
 COV_NO_CENTER = 0x2
 COV_ROUTE_INPLACE, COV_ROUTE_INPLACE_CHECKED, COV_ROUTE_REPACKED = 1, 2, 3
 COV_ROUTES = {COV_ROUTE_INPLACE: "inplace", COV_ROUTE_INPLACE_CHECKED: "inplace_checked", COV_ROUTE_REPACKED: "repacked"}
+# corrla_pca_transform_*: the entry's own flag word (the centre flags keep their corrla_opts values) and what
+# corrla_ctx_last_pca_apply reports
+PCA_APPLY_OWN_MEANS = 0x400
+PCA_APPLY_ROUTE_INPLACE, PCA_APPLY_ROUTE_INPLACE_CHECKED, PCA_APPLY_ROUTE_REPACKED = 1, 2, 3
+PCA_APPLY_ROUTES = {PCA_APPLY_ROUTE_INPLACE: "inplace", PCA_APPLY_ROUTE_INPLACE_CHECKED: "inplace_checked",
+                    PCA_APPLY_ROUTE_REPACKED: "repacked"}
+PCA_APPLY_CENTRINGS = {1: "fused", 2: "copy"}
 UNIQUE_ID_BYTES = 128
 
 
@@ -55,6 +62,7 @@ def _sigs():
         "corrla_ctx_comm_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "corrla_comm_unique_id": (C.c_int, [vp]),
         "corrla_ctx_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+        "corrla_ctx_last_pca_apply": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     }
     for suf, sc in (("f32", flt), ("f64", dbl)):
         rsvd = [vp, vp, i64, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
@@ -80,6 +88,12 @@ def _sigs():
         cov = [vp, vp, i64, i64, i64, i64, u64, C.c_int, vp, vp, vp, i64, C.POINTER(C.c_int)]
         s["corrla_cov_" + suf] = (C.c_int, cov)
         s["corrla_cov_dev_" + suf] = (C.c_int, cov)
+        # fitted PCA model: (x | CSR operand), means, scales, components, ldc, k, flags, scores, ld_scores, resid_out, means_out
+        model = [vp, vp, vp, i64, i64, u64, vp, i64, vp, vp]
+        s["corrla_pca_transform_" + suf] = s["corrla_pca_transform_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64] + model)
+        s["corrla_pca_transform_csr_" + suf] = s["corrla_pca_transform_csr_dev_" + suf] = (C.c_int, [vp, vp, vp, vp, i64, i64, i64] + model)
+        inverse = [vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64]
+        s["corrla_pca_inverse_" + suf] = s["corrla_pca_inverse_dev_" + suf] = (C.c_int, inverse)
         s["corrla_fill_normal_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])

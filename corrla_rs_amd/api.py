@@ -527,6 +527,147 @@ class Context:
         "repacked" (feature-strided x, transposed once into workspace); None before the first call."""
         return getattr(self, "_cov_route", None)
 
+    # ---- the fitted PCA model on the device (pca_rsvd.rs:43-52) ----------------------------------
+    def _model_array(self, v, like, on_device):
+        """A small array of the model (means, scales, components, scores) as the dtype, kind and device of `like`."""
+        if on_device:
+            import torch
+            t = v if _is_torch(v) else torch.tensor(np.asarray(v))  # (a copy: the model arrays are small, and may be read-only)
+            return t.detach().to(device=like.device, dtype=like.dtype)
+        return np.asarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=like.dtype)
+
+    def _model(self, means, components, scales, n, like, on_device):
+        """-> (means (n,) or None, scales (n,) or None, components as k x n column-major with ldc = k, k); ValueError on
+        any shape that does not fit n features (n None: the components say how many there are)."""
+        if components is None:
+            raise ValueError("components must be given")
+        comps = self._model_array(components, like, on_device)
+        if comps.ndim != 2 or (n is not None and comps.shape[1] != n):
+            raise ValueError(f"components must have shape (k, {'n' if n is None else n}), got {tuple(comps.shape)}")
+        n = int(comps.shape[1])
+        k = int(comps.shape[0])
+        if k < 1 or k > n:
+            raise ValueError(f"components must have between 1 and n = {n} rows, got {k}")
+        # (k, n) column-major: numpy F order; torch: the (n, k) row-major transpose
+        comps = comps.t().contiguous() if on_device else np.asfortranarray(comps)
+        vecs = []
+        for name, v in (("means", means), ("scales", scales)):
+            if v is None:
+                vecs.append(None)
+                continue
+            a = self._model_array(v, like, on_device).reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError(f"{name} must have {n} entries, got {a.shape[0]}")
+            vecs.append(a.contiguous() if on_device else np.ascontiguousarray(a))
+        return vecs[0], vecs[1], comps, k
+
+    def _pca_apply_done(self, on_device):
+        """After a transform / inverse call: the device entries only enqueue, so torch's streams see the results after
+        this; then how the call ran (corrla_ctx_last_pca_apply)."""
+        if on_device:
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        centring, route = C.c_int(0), C.c_int(0)
+        L.check(self._lib.corrla_ctx_last_pca_apply(self._h, C.byref(centring), C.byref(route)))
+        self._pca_apply_centring = L.PCA_APPLY_CENTRINGS.get(centring.value)
+        self._pca_apply_route = L.PCA_APPLY_ROUTES.get(route.value)
+
+    def pca_transform(self, x, means, components, scales=None, *, own_means=False, residuals=False, center=None):
+        """A fitted PCA model applied to x (m x n) on the device (corrla_pca_transform_*): the scores
+        t = ((x - means) / scales) @ components.T, shape (m, k), column-major like U.  `means` (n values), `components`
+        (k, n) and `scales` (n values, None: 1) are what ``pca`` returned; they are converted to x's dtype and device.
+        means=None: no centring.
+
+        own_means=True: x is centred by its OWN column means (the reference's ``apply_tr``, pca_rsvd.rs:43-46); `means` is
+        ignored and the means of x, (1, n), are appended to the result.
+        residuals=True: also q (m,), the Q / SPE statistic q_i = ||z_i - t_i V||^2 of every sample, formed directly from
+        z - t V by the back-projection kernel (never as a difference of norms, never through an m x n temporary) from the
+        scores as stored.  -> scores | (scores, q) [+ (means,)].
+        center: None (library default: fused for float64, a centred and scaled copy in workspace for float32), "fused" or
+        "copy", as for ``pca``.  x: dense numpy, a CUDA tensor, or any sparse form ``_as_csr`` takes (always "fused", never
+        densified; residuals=True raises ValueError).  numpy in -> numpy out, a tensor in -> tensors on its device; float32
+        stays float32, anything else becomes float64; bfloat16 raises.
+        Row-sharded data needs nothing more: every rank calls this on its own rows with the replicated model.
+        ``last_pca_apply_route()`` / ``last_pca_apply_centring()`` say how the call ran."""
+        own_means = _check_bool("own_means", own_means, ValueError)
+        residuals = _check_bool("residuals", residuals, ValueError)
+        if center not in (None, "fused", "copy"):
+            raise ValueError("center must be None, 'fused' or 'copy'")
+        flags = {None: 0, "fused": L.PCA_CENTER_FUSED, "copy": L.PCA_CENTER_COPY}[center] | (L.PCA_APPLY_OWN_MEANS if own_means else 0)
+        _reject_bf16(x, "pca_transform")
+        if _is_sparse(x):
+            if residuals:
+                raise ValueError("residuals=True on sparse input: the residual over a sparse row's implicit zeros is a dense computation")
+            if center == "copy":
+                raise ValueError("center='copy' on sparse input: a centred copy would densify the matrix")
+            operand, m, n, like, on_dev = self._csr_operand(x)
+            stem = "corrla_pca_transform_csr_"
+        else:
+            a, on_dev = _as_dense(x, "x")
+            if on_dev:
+                self._on_my_device(a)
+            m, n = a.shape
+            if m == 0 or n == 0:
+                raise ValueError("x must be non-empty")
+            operand, like, stem = (a, m, n, *_strides(a)), a, "corrla_pca_transform_"
+        mu, sd, comps, k = self._model(None if own_means else means, components, scales, n, like, on_dev)
+        scores = _empty_colmajor(like, m, k)
+        if on_dev:
+            import torch
+            q = torch.empty((m,), dtype=like.dtype, device=like.device) if residuals else None
+            mu_out = torch.empty((1, n), dtype=like.dtype, device=like.device) if own_means else None
+            _sync_stream(like)
+        else:
+            q = np.empty((m,), dtype=like.dtype) if residuals else None
+            mu_out = np.empty((1, n), dtype=like.dtype) if own_means else None
+        opt = lambda v: None if v is None else _ptr(v)  # noqa: E731
+        L.check(self._entry(stem, on_dev, like.dtype)(self._h, *_c_args(operand), opt(mu), opt(sd), _ptr(comps), k, k, flags,
+                                                      _ptr(scores), m, opt(q), opt(mu_out)))
+        self._pca_apply_done(on_dev)
+        out = (scores,) + ((q,) if residuals else ()) + ((mu_out,) if own_means else ())
+        return out[0] if len(out) == 1 else out
+
+    def pca_inverse_transform(self, scores, means, components, scales=None):
+        """The reconstruction (scores @ components) * scales + means, (m, n) row-major, in one kernel and one write of m x n
+        (corrla_pca_inverse_*; ``apply_inv_tr``, pca_rsvd.rs:49-52).  means / scales None: 0 / 1.  numpy in -> numpy out, a
+        CUDA tensor in -> a tensor on its device; float32 stays float32, anything else becomes float64."""
+        _reject_bf16(scores, "pca_inverse_transform")
+        if _is_sparse(scores):
+            raise ValueError("pca_inverse_transform takes dense scores")
+        t, on_dev = _as_dense(scores, "scores")
+        if on_dev:
+            self._on_my_device(t)
+        m, k_in = t.shape
+        if m == 0 or k_in == 0:
+            raise ValueError("scores must be non-empty")
+        mu, sd, comps, k = self._model(means, components, scales, None, t, on_dev)
+        n = int(comps.shape[0] if on_dev else comps.shape[1])
+        if k != k_in:
+            raise ValueError(f"scores have {k_in} columns, components {k} rows")
+        # (m, k) column-major with ld = m: no copy for what pca_transform returned
+        tc = t.t().contiguous() if on_dev else np.asfortranarray(t)
+        if on_dev:
+            import torch
+            out = torch.empty((m, n), dtype=t.dtype, device=t.device)
+            _sync_stream(t)
+        else:
+            out = np.empty((m, n), dtype=t.dtype)
+        opt = lambda v: None if v is None else _ptr(v)  # noqa: E731
+        L.check(self._entry("corrla_pca_inverse_", on_dev, t.dtype)(self._h, _ptr(tc), m, k, m, opt(mu), opt(sd), _ptr(comps), k, n,
+                                                                    _ptr(out), n))
+        self._pca_apply_done(on_dev)
+        return out
+
+    def last_pca_apply_route(self):
+        """How the back-projection kernel of this context's last ``pca_transform`` / ``pca_inverse_transform`` call touched
+        its m x n operand (x of the residuals, the output of the inverse): "inplace" (16-byte accesses), "inplace_checked"
+        (element accesses: base or row stride not 16-byte aligned) or "repacked" (feature-strided x, transposed once into
+        workspace); None when the call ran no such kernel, and before the first call."""
+        return getattr(self, "_pca_apply_route", None)
+
+    def last_pca_apply_centring(self):
+        """The centring of the last ``pca_transform`` call: "fused", "copy", or None (no centring, or no such call yet)."""
+        return getattr(self, "_pca_apply_centring", None)
+
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
         """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that
@@ -693,15 +834,19 @@ def rpca(a_mat, n_rank, n_iters=None, n_oversamples=None, *, seed=None, omega=No
 
 class PcaRsvd:
     """Mirror of ``PcaRsvd`` (src/lib_math_utils/pca_rsvd.rs:13-112): fit on construction, keeps the means, the
-    singular values (k, 1) and ``components_`` (k, n_dim).  The fit (means, centring, RSVD) runs on the GPU; the
-    two k-wide projections below are plain numpy on the stored k x n_dim factors."""
+    singular values (k, 1) and ``components_`` (k, n_dim).  The fit (means, centring, RSVD) runs on the GPU.  A host input
+    gives a host-fitted model (numpy arrays) whose apply_tr / apply_inv_tr on numpy arguments are plain numpy on the
+    stored k x n_dim factors; a CUDA tensor gives a device-fitted model (``means``, ``pca_s``, ``components_``, ``scales_``
+    are tensors on its device).  transform / inverse_transform / residuals / fit_transform, and apply_tr / apply_inv_tr on
+    CUDA tensors or on a device-fitted model, run on the GPU (Context.pca_transform / pca_inverse_transform)."""
 
     def __init__(self, x_mat, rank, *, seed=None, omega=None, ctx=None, standardize=False):
         """standardize=True: the fit is on standardised columns (see Context.pca); ``scales_`` (1, n_dim) keeps the column
         standard deviations (None otherwise), ``components_`` are directions in standardised coordinates, and apply_tr /
         apply_inv_tr divide / multiply by ``scales_`` accordingly."""
         self.pca_rank = int(rank)
-        x = x_mat if _is_sparse(x_mat) else np.asarray(x_mat)
+        x = x_mat if _is_sparse(x_mat) or (_is_torch(x_mat) and x_mat.is_cuda) else np.asarray(x_mat)
+        self._ctx = ctx
         self.n_samples = int(x[3][0] if isinstance(x, tuple) else x.shape[0])
         self.scales_ = None
         if not _check_standardize(standardize):
@@ -722,7 +867,34 @@ class PcaRsvd:
     def singular_values(self):
         return self.pca_s
 
+    # ---- the model applied on the device ----------------------------------------------------------------------------
+    def _context(self):
+        return self._ctx or default_context()
+
+    def _on_device(self, arg):
+        """the device path serves CUDA arguments and every argument of a device-fitted model"""
+        return (_is_torch(arg) and arg.is_cuda) or _is_torch(self.components_)
+
+    def transform(self, x_mat):
+        """Scores of x_mat under the fitted model, centred by the MODEL's means (scikit-learn's transform): (m, k)."""
+        return self._context().pca_transform(x_mat, self.means, self.components_, self.scales_)
+
+    def inverse_transform(self, red_mat):
+        """(m, k) scores back to (m, n_dim): (red_mat @ components_) * scales_ + means."""
+        return self._context().pca_inverse_transform(red_mat, self.means, self.components_, self.scales_)
+
+    def residuals(self, x_mat):
+        """Q / SPE statistic of every sample of x_mat under the fitted model: (m,), see Context.pca_transform."""
+        return self._context().pca_transform(x_mat, self.means, self.components_, self.scales_, residuals=True)[1]
+
+    def fit_transform(self, x_mat, rank, **kw):
+        """fit(x_mat, rank, **kw), then the scores of x_mat."""
+        self.fit(x_mat, rank, **kw)
+        return self.transform(x_mat)
+
     def apply_tr(self, targ_mat):  # pca_rsvd.rs:43-46: centres the TARGET by its own column means
+        if self._on_device(targ_mat):
+            return self._context().pca_transform(targ_mat, None, self.components_, self.scales_, own_means=True)[0]
         t = np.asarray(targ_mat, dtype=self.components_.dtype)
         tc = t - t.mean(axis=0, keepdims=True)
         if self.scales_ is not None:
@@ -730,6 +902,8 @@ class PcaRsvd:
         return tc @ self.components_.T
 
     def apply_inv_tr(self, red_mat):  # pca_rsvd.rs:49-52
+        if self._on_device(red_mat):
+            return self.inverse_transform(red_mat)
         back = np.asarray(red_mat, dtype=self.components_.dtype) @ self.components_
         if self.scales_ is not None:
             back = back * self.scales_

@@ -775,4 +775,102 @@ inline void cov_entry(Dev&, const T* x, int64_t m, int64_t n, int64_t rs, int64_
     throw Error(ST_EINVAL, "this backend has no symmetric rank-k kernel: corrla_cov_* is not supported");
 }
 
+// ---- the fitted PCA model on the device (corrla_pca_transform_* / corrla_pca_inverse_*, pca_rsvd.rs:43-52) ---------------
+// Argument checks of every entry, then `run` -- on a backend that carries the back-projection kernel (dev_has_pca_apply);
+// any other backend ends the call with EINVAL, never with another way of computing the result.
+struct PcaApplyRange {
+  const void* p;
+  size_t bytes;
+  const char* name;
+};
+// every output against every input and every other output
+inline void pca_apply_no_overlap(const PcaApplyRange* in, int n_in, const PcaApplyRange* out, int n_out, const char* who) {
+  for (int o = 0; o < n_out; ++o) {
+    for (int i = 0; i < n_in; ++i)
+      if (cov_ranges_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes))
+        throw Error(ST_EINVAL, std::string(who) + ": " + out[o].name + " overlaps " + in[i].name);
+    for (int q = o + 1; q < n_out; ++q)
+      if (cov_ranges_overlap(out[o].p, out[o].bytes, out[q].p, out[q].bytes))
+        throw Error(ST_EINVAL, std::string(who) + ": " + out[o].name + " overlaps " + out[q].name);
+  }
+}
+
+// What a transform call is, apart from its operand: the arguments of the prototype after the operand, in its order.
+template <class T>
+struct PcaTransformCall {
+  int64_t m, n;
+  const T* means;
+  const T* scales;
+  const T* comps;
+  int64_t ldc, k;
+  uint64_t flags;
+  T* scores;
+  int64_t ld_scores;
+  T* resid_out;
+  T* means_out;
+  bool own_means() const { return (flags & CORRLA_PCA_APPLY_OWN_MEANS) != 0; }
+  // 1 fused, 2 centred-and-scaled copy; the defaults of corrla_pca_*: fused for f64, the copy for f32
+  int centring() const {
+    return (flags & CORRLA_PCA_CENTER_FUSED) ? 1 : ((flags & CORRLA_PCA_CENTER_COPY) ? 2 : (sizeof(T) == 8 ? 1 : 2));
+  }
+};
+
+// `operand`: the ranges of the target (x, or the three CSR arrays), checked for overlap with the outputs
+template <class Dev, class T, class Run>
+inline void pca_transform_entry(Dev&, const PcaTransformCall<T>& c, bool sparse, const PcaApplyRange* operand, int n_operand,
+                                Run&& run) {
+  const char* who = sparse ? "pca_transform_csr" : "pca_transform";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (c.flags & ~(uint64_t)(CORRLA_PCA_CENTER_FUSED | CORRLA_PCA_CENTER_COPY | CORRLA_PCA_APPLY_OWN_MEANS)) bad("unknown flag");
+  if ((c.flags & CORRLA_PCA_CENTER_FUSED) && (c.flags & CORRLA_PCA_CENTER_COPY))
+    bad("CORRLA_PCA_CENTER_FUSED and CORRLA_PCA_CENTER_COPY are mutually exclusive");
+  if (sparse && (c.flags & CORRLA_PCA_CENTER_COPY)) bad("CORRLA_PCA_CENTER_COPY on CSR input: a centred copy would densify the matrix");
+  if (c.m < 1 || c.n < 1) bad("m and n must be >= 1");
+  if (c.k < 1 || c.k > c.n) bad("k must be in [1, n]");
+  if (!c.comps) bad("components is NULL");
+  if (!c.scores) bad("scores is NULL");
+  if (c.ldc < c.k) bad("ldc < k");
+  if (c.ld_scores < c.m) bad("ld_scores < m");
+  if (sparse && c.resid_out) bad("resid_out must be NULL: the residual over a sparse row's implicit zeros is a dense computation");
+  const size_t vb = (size_t)c.n * sizeof(T);
+  PcaApplyRange in[6] = {{c.own_means() ? nullptr : c.means, vb, "means"},
+                         {c.scales, vb, "scales"},
+                         {c.comps, (size_t)((c.n - 1) * c.ldc + c.k) * sizeof(T), "components"}};
+  int n_in = 3;
+  for (int i = 0; i < n_operand && n_in < 6; ++i) in[n_in++] = operand[i];
+  const PcaApplyRange out[3] = {{c.scores, (size_t)((c.k - 1) * c.ld_scores + c.m) * sizeof(T), "scores"},
+                                {c.resid_out, (size_t)c.m * sizeof(T), "resid_out"},
+                                {c.own_means() ? c.means_out : nullptr, vb, "means_out"}};
+  pca_apply_no_overlap(in, n_in, out, 3, who);
+  if constexpr (dev_has_pca_apply<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no PCA back-projection kernel: corrla_pca_transform_* is not supported");
+}
+
+template <class Dev, class T, class Run>
+inline void pca_inverse_entry(Dev&, const T* scores, int64_t m, int64_t k, int64_t ld_scores, const T* means, const T* scales,
+                              const T* comps, int64_t ldc, int64_t n, T* out, int64_t row_stride_out, Run&& run) {
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string("pca_inverse: ") + what); };
+  if (m < 1 || n < 1) bad("m and n must be >= 1");
+  if (k < 1 || k > n) bad("k must be in [1, n]");
+  if (!scores) bad("scores is NULL");
+  if (!comps) bad("components is NULL");
+  if (!out) bad("out is NULL");
+  if (ldc < k) bad("ldc < k");
+  if (ld_scores < m) bad("ld_scores < m");
+  if (row_stride_out < n && m > 1) bad("row_stride_out < n");
+  const size_t vb = (size_t)n * sizeof(T);
+  const PcaApplyRange in[4] = {{scores, (size_t)((k - 1) * ld_scores + m) * sizeof(T), "scores"},
+                               {means, vb, "means"},
+                               {scales, vb, "scales"},
+                               {comps, (size_t)((n - 1) * ldc + k) * sizeof(T), "components"}};
+  const PcaApplyRange o[1] = {{out, (size_t)((m - 1) * row_stride_out + n) * sizeof(T), "out"}};
+  pca_apply_no_overlap(in, 4, o, 1, "pca_inverse");
+  if constexpr (dev_has_pca_apply<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no PCA back-projection kernel: corrla_pca_inverse_* is not supported");
+}
+
 }  // namespace corrla

@@ -9,6 +9,7 @@
 #include "cov_stage.hpp"
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
+#include "pca_apply_stage.hpp"
 
 using namespace corrla;
 
@@ -17,6 +18,7 @@ struct corrla_ctx {
   Timings last;
   std::mutex mu;
   bool profile;
+  pca_apply_stage::Ran pca_apply;  // how the last corrla_pca_transform_* / corrla_pca_inverse_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -282,6 +284,66 @@ CORRLA_DEFINE_COV(corrla_cov_f32, float, true)
 CORRLA_DEFINE_COV(corrla_cov_f64, double, true)
 CORRLA_DEFINE_COV(corrla_cov_dev_f32, float, false)
 CORRLA_DEFINE_COV(corrla_cov_dev_f64, double, false)
+
+// ---- the fitted PCA model: transform, inverse transform, Q-residuals (pca_rsvd.rs:43-52) -----------------------------------
+#define CORRLA_PCA_MODEL(T) const T *means, const T *scales, const T *components, int64_t ldc, int64_t k, uint64_t flags, T *scores, \
+                            int64_t ld_scores, T *resid_out, T *means_out
+#define CORRLA_PCA_MODEL_CALL(T) PcaTransformCall<T>{m, n, means, scales, components, ldc, k, flags, scores, ld_scores, resid_out, means_out}
+#define CORRLA_DEFINE_PCA_TRANSFORM(NAME, T, HOST)                                                                      \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(T, x), CORRLA_PCA_MODEL(T)) {                             \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cx.pca_apply = pca_apply_stage::Ran();                                                                            \
+      const PcaTransformCall<T> c = CORRLA_PCA_MODEL_CALL(T);                                                           \
+      if (!x) throw Error(ST_EINVAL, "pca_transform: x is NULL");                                                       \
+      if (m < 1 || n < 1) throw Error(ST_EINVAL, "pca_transform: m and n must be >= 1");                                \
+      if (rs < 0 || cs < 0) throw Error(ST_EINVAL, "pca_transform: negative strides are not supported");                \
+      const PcaApplyRange xr{x, (size_t)((m - 1) * rs + (n - 1) * cs + 1) * sizeof(T), "x"};                            \
+      pca_transform_entry<HipDev, T>(cx.dev, c, false, &xr, 1,                                                          \
+                                     [&] { pca_apply_stage::run_dense<T>(cx.dev, HOST, x, rs, cs, c, &cx.pca_apply); }); \
+    });                                                                                                                 \
+  }
+#define CORRLA_DEFINE_PCA_TRANSFORM_CSR(NAME, T, HOST)                                                                  \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_CSR_A(T), CORRLA_PCA_MODEL(T)) {                                \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cx.pca_apply = pca_apply_stage::Ran();                                                                            \
+      const PcaTransformCall<T> c = CORRLA_PCA_MODEL_CALL(T);                                                           \
+      validate_csr_args(values, col_idx, row_ptr, m, n, nnz);                                                           \
+      const PcaApplyRange op[3] = {{values, (size_t)nnz * sizeof(T), "values"},                                         \
+                                   {col_idx, (size_t)nnz * sizeof(int32_t), "col_idx"},                                 \
+                                   {row_ptr, (size_t)(m + 1) * sizeof(int64_t), "row_ptr"}};                            \
+      pca_transform_entry<HipDev, T>(cx.dev, c, true, op, 3, [&] {                                                      \
+        pca_apply_stage::run_csr<T>(cx.dev, HOST, values, col_idx, row_ptr, nnz, c, &cx.pca_apply);                     \
+      });                                                                                                               \
+    });                                                                                                                 \
+  }
+#define CORRLA_DEFINE_PCA_INVERSE(NAME, T, HOST)                                                                        \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, const T* scores, int64_t m, int64_t k, int64_t ld_scores, const T* means, \
+                                const T* scales, const T* components, int64_t ldc, int64_t n, T* out, int64_t row_stride_out) { \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cx.pca_apply = pca_apply_stage::Ran();                                                                            \
+      pca_inverse_entry<HipDev, T>(cx.dev, scores, m, k, ld_scores, means, scales, components, ldc, n, out, row_stride_out, [&] { \
+        pca_apply_stage::run_inverse<T>(cx.dev, HOST, scores, m, k, ld_scores, means, scales, components, ldc, n, out,   \
+                                        row_stride_out, &cx.pca_apply);                                                 \
+      });                                                                                                               \
+    });                                                                                                                 \
+  }
+#define CORRLA_DEFINE_PCA_APPLY(SUF, T)                                  \
+  CORRLA_DEFINE_PCA_TRANSFORM(corrla_pca_transform_##SUF, T, true)       \
+  CORRLA_DEFINE_PCA_TRANSFORM(corrla_pca_transform_dev_##SUF, T, false)  \
+  CORRLA_DEFINE_PCA_TRANSFORM_CSR(corrla_pca_transform_csr_##SUF, T, true)      \
+  CORRLA_DEFINE_PCA_TRANSFORM_CSR(corrla_pca_transform_csr_dev_##SUF, T, false) \
+  CORRLA_DEFINE_PCA_INVERSE(corrla_pca_inverse_##SUF, T, true)           \
+  CORRLA_DEFINE_PCA_INVERSE(corrla_pca_inverse_dev_##SUF, T, false)
+CORRLA_DEFINE_PCA_APPLY(f32, float)
+CORRLA_DEFINE_PCA_APPLY(f64, double)
+CORRLA_API corrla_status corrla_ctx_last_pca_apply(corrla_ctx* ctx, int* centring_out, int* route_out) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (centring_out) *centring_out = c->pca_apply.centring;
+    if (route_out) *route_out = c->pca_apply.route;
+  });
+}
 
 // ---- active-subspace gradient stage ------------------------------------------------------
 static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,

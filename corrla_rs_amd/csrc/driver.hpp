@@ -109,6 +109,13 @@ struct dev_has_syrk : std::false_type {};
 template <class D>
 struct dev_has_syrk<D, std::void_t<decltype(D::kHasSyrk)>> : std::true_type {};
 
+// ... and those that carry the back-projection kernel of corrla_pca_transform_* / corrla_pca_inverse_* (pca_apply_kernels.hpp)
+// with kHasPcaApply.
+template <class D, class = void>
+struct dev_has_pca_apply : std::false_type {};
+template <class D>
+struct dev_has_pca_apply<D, std::void_t<decltype(D::kHasPcaApply)>> : std::true_type {};
+
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).
 template <class T>

@@ -32,6 +32,7 @@
 #include "spmm_kernels.hpp"
 #include "colvar_kernels.hpp"
 #include "syrk_kernels.hpp"
+#include "pca_apply_kernels.hpp"
 
 namespace corrla {
 
@@ -1216,6 +1217,8 @@ class HipDev {
     hipLaunchKernelGGL((k::syrk_finish_kernel<T>), dim3(p.finish_grid_x, p.finish_grid_y), dim3(p.finish_block), 0, stream, f);
     CORRLA_HIP(hipGetLastError());
   }
+  // ---- fitted PCA model on the device: pca_apply_plan.hpp plans, pca_apply_stage.hpp launches pca_apply_kernels.hpp ---------
+  static constexpr bool kHasPcaApply = true;  // driver.hpp: dev_has_pca_apply
   // out(i, c) = d[i] * in(i, c) over every allocated column (the padding columns are zero and stay zero); out may be in
   template <class T>
   void row_scale(const Skinny<T>& in, Skinny<T>& out, int64_t rows, const T* d) {

@@ -1,0 +1,233 @@
+// The fitted-model stage of the C ABI (corrla_pca_transform_* / corrla_pca_inverse_*, pca_rsvd.rs:43-52): the forward product
+// on the tall kernels as pca_body drives them (RsvdDriver::a_times over a TallA with mu_short / inv_sd_short, or over a centred
+// and scaled copy), the back-projection kernel by the plan of pca_apply_plan.hpp, and for host pointers the copies around
+// them.  The arguments were checked by pca_transform_entry / pca_inverse_entry (capi_impl.hpp).
+// The device path enqueues and returns, as cov_stage does: begin_call has no end_call there, every constant goes to the
+// device through a kernel (fill_const), never through a synchronising copy, and a throw after begin_call is drained by the
+// entry's locked_call.  What can still synchronise: hipMalloc inside alloc_bytes the first time a call needs more workspace
+// than the arena holds, and the validation of a CSR operand (csr_plan), as in every CSR entry.  The host path copies the
+// whole strided SPAN of x to the device as it lies, so the device path's routes serve it unchanged.
+#pragma once
+#include "capi_impl.hpp"
+#include "hip_backend.hpp"
+
+namespace corrla {
+namespace pca_apply_stage {
+
+// how the context's last call ran (corrla_ctx_last_pca_apply)
+struct Ran {
+  int centring = 0;  // 0 none, 1 fused, 2 copy
+  int route = 0;     // PcaApplyRoute of the back-projection kernel, 0: none ran
+};
+
+template <class T>
+const T* to_device(HipDev& dev, const T* host, size_t count) {
+  if (!host) return nullptr;
+  T* d = (T*)dev.alloc_bytes(count * sizeof(T));
+  dev.h2d_bytes(d, host, count * sizeof(T));
+  return d;
+}
+
+// One launch of pca_back_kernel<T, MODE> (and, RESID, of the finishing kernel).  t: m x k column-major (ldt); v: k rows of n
+// contiguous features (ldv); big: out (STORE) or x (RESID) with the plan's row stride.
+template <class T>
+void back(HipDev& dev, const PcaApplyPlan& p, PcaApplyMode mode, const T* t, int64_t ldt, const T* v, int64_t ldv, const T* mu,
+          const T* sd, int64_t m, int64_t n, int64_t k, T* big, T* q) {
+  k::PcaBackArgs<T> a{t, ldt, v, ldv, mu, sd, m, n, k, p.nbn, big, p.ld, p.wide, nullptr};
+  const dim3 grid(p.grid_x);  // one-dimensional: the plan keeps it below 2^31
+  if (mode == PcaApplyMode::kStore) {
+    hipLaunchKernelGGL((k::pca_back_kernel<T, k::kPcaStore>), grid, dim3(p.block), p.lds_bytes, dev.stream, a);
+    CORRLA_HIP(hipGetLastError());
+    return;
+  }
+  a.ws = (T*)dev.alloc_bytes(p.ws_bytes);
+  hipLaunchKernelGGL((k::pca_back_kernel<T, k::kPcaResid>), grid, dim3(p.block), p.lds_bytes, dev.stream, a);
+  CORRLA_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k::pca_resid_finish_kernel<T>), dim3(p.finish_grid_x), dim3(p.finish_block), 0, dev.stream, (const T*)a.ws, p.nbn, m,
+                     q);
+  CORRLA_HIP(hipGetLastError());
+}
+
+// The dense target as the caller describes it (device memory by now).
+template <class T>
+struct DenseX {
+  const T* x = nullptr;
+  int64_t rs = 0, cs = 0;
+};
+
+// Everything on device pointers.  `stage`: the target as the tall operand (never transposed).
+template <class T, class Stage>
+void transform_dev(HipDev& dev, const PcaTransformCall<T>& c, const DenseX<T>& dx, Stage&& stage, Ran* ran) {
+  const int64_t m = c.m, n = c.n, k = c.k;
+  const bool sparse = dx.x == nullptr;
+  PcaApplyPlan rp;
+  if (c.resid_out) {
+    PcaApplyShape s;
+    s.m = m, s.n = n, s.k = k;
+    s.row_stride = dx.rs, s.col_stride = dx.cs;
+    s.esz = (int)sizeof(T);
+    s.base_aligned = (uintptr_t)dx.x % 16 == 0;
+    s.mode = PcaApplyMode::kResid;
+    rp = pca_apply_plan(s);
+    if (rp.route == PcaApplyRoute::kReject) throw Error(ST_EINVAL, rp.error);
+  }
+  TallA<T> ta = stage();
+  RsvdDriver<HipDev, T> drv(dev, false);
+  // V^T as the n x k skinny operand of the forward product; read row-wise it is V with unit stride along the features, which
+  // is how the back-projection kernel stages it
+  Skinny<T> vt = dev.template alloc_skinny<T>(n, k);
+  dev.pack_strided(c.comps, k, n, (int64_t)1, c.ldc, vt.p, vt.ld);
+  const T* mu = c.means;
+  if (c.own_means()) {
+    // the target's own column means, by the routine pca_body uses: x^T 1 / m through the transposed product
+    Skinny<T> ones = dev.template alloc_skinny<T>(m, 1);
+    dev.fill_const(ones.p, m, (T)1);
+    Skinny<T> mus = dev.template alloc_skinny<T>(n, 1);
+    T* inv_m = dev.template alloc_scalar<T>(1);
+    dev.fill_const(inv_m, (int64_t)1, (T)(1.0 / (double)m));
+    drv.at_times(ta, ones, mus, inv_m, false);
+    mu = mus.p;
+    if (c.means_out) dev.copy_values_out(mus.p, n, c.means_out, /*dst_is_host=*/false);
+  }
+  const T* inv_sd = nullptr;
+  if (c.scales) {
+    T* inv = (T*)dev.alloc_bytes((size_t)n * sizeof(T));
+    hipLaunchKernelGGL((k::pca_reciprocal_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dev.stream, c.scales, n, inv);
+    CORRLA_HIP(hipGetLastError());
+    inv_sd = inv;
+    if (!mu) mu = dev.template alloc_scalar<T>((int)n);  // scaling without centring: zero means
+  }
+  TallA<T> tc = ta;
+  const int centring = !mu ? 0 : (sparse ? 1 : c.centring());
+  if (centring == 1) {
+    tc.mu_short = mu, tc.inv_sd_short = inv_sd;
+    if (inv_sd) drv.set_scale_workspace(dev.template alloc_skinny<T>(n, k));
+  } else if (centring == 2) {
+    // centred and scaled copy of the staged operand (its memory rows are the samples iff it is row-major)
+    const int64_t ldp = round_up(ta.mem.cols, kLdPad);
+    T* cbuf = (T*)dev.alloc_bytes((size_t)ta.mem.rows * (size_t)ldp * sizeof(T));
+    // only the padding columns need zeros (the copy kernel writes every other element): no pass over m x n for them
+    if (ldp > ta.mem.cols)
+      CORRLA_HIP(hipMemset2DAsync(cbuf + ta.mem.cols, (size_t)ldp * sizeof(T), 0, (size_t)(ldp - ta.mem.cols) * sizeof(T),
+                                  (size_t)ta.mem.rows, dev.stream));
+    dev.center_rows_cols(ta.mem.p, ta.mem.rows, ta.mem.cols, ta.mem.ld, mu, ta.row_major, cbuf, ldp, inv_sd);
+    tc.mem.p = cbuf;
+    tc.mem.ld = ldp;
+    tc.mem.cols_readable = ldp;
+  }
+  Skinny<T> y = caller_skinny(c.scores, m, k, c.ld_scores);  // the scores land in the caller's buffer
+  drv.a_times(tc, vt, y, nullptr);
+  ran->centring = centring;
+  ran->route = 0;
+  if (!c.resid_out) return;
+  const T* xr = dx.x;
+  if (rp.route == PcaApplyRoute::kRepacked) {
+    T* packed = (T*)dev.alloc_bytes(rp.repack_bytes);
+    dev.pack_strided(dx.x, m, n, dx.rs, dx.cs, packed, rp.ld);
+    xr = packed;
+  }
+  back<T>(dev, rp, PcaApplyMode::kResid, c.scores, c.ld_scores, vt.p, vt.ld, mu, c.scales, m, n, k, const_cast<T*>(xr), c.resid_out);
+  ran->route = (int)rp.route;
+}
+
+// Host pointers: the model and the target to the device, the device path, the results back.
+template <class T, class StageHost>
+void transform_host(HipDev& dev, const PcaTransformCall<T>& c, const DenseX<T>& hx, StageHost&& stage_host, Ran* ran) {
+  const int64_t m = c.m, n = c.n, k = c.k;
+  PcaTransformCall<T> d = c;
+  d.means = c.own_means() ? nullptr : to_device(dev, c.means, (size_t)n);
+  d.scales = to_device(dev, c.scales, (size_t)n);
+  d.comps = to_device(dev, c.comps, (size_t)((n - 1) * c.ldc + k));
+  d.scores = (T*)dev.alloc_bytes((size_t)m * (size_t)k * sizeof(T));
+  d.ld_scores = m;
+  d.resid_out = c.resid_out ? (T*)dev.alloc_bytes((size_t)m * sizeof(T)) : nullptr;
+  d.means_out = (c.own_means() && c.means_out) ? (T*)dev.alloc_bytes((size_t)n * sizeof(T)) : nullptr;
+  DenseX<T> dx;
+  if (hx.x) {
+    // x to the device as it lies: the same strides and the same offset from a 16-byte boundary
+    const size_t span = (size_t)((m - 1) * hx.rs + (n - 1) * hx.cs + 1);
+    char* buf = (char*)dev.alloc_bytes(span * sizeof(T) + 16);
+    T* xs = (T*)(buf + (uintptr_t)hx.x % 16);
+    dev.h2d_bytes(xs, hx.x, span * sizeof(T));
+    dx.x = xs, dx.rs = hx.rs, dx.cs = hx.cs;
+  }
+  transform_dev<T>(dev, d, dx, [&] { return stage_host(dx); }, ran);
+  CORRLA_HIP(hipMemcpy2DAsync(c.scores, (size_t)c.ld_scores * sizeof(T), d.scores, (size_t)m * sizeof(T), (size_t)m * sizeof(T), (size_t)k,
+                              hipMemcpyDeviceToHost, dev.stream));
+  if (d.resid_out) CORRLA_HIP(hipMemcpyAsync(c.resid_out, d.resid_out, (size_t)m * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
+  if (d.means_out) CORRLA_HIP(hipMemcpyAsync(c.means_out, d.means_out, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
+  dev.end_call();
+}
+
+template <class T>
+void run_dense(HipDev& dev, bool host_ptrs, const T* x, int64_t rs, int64_t cs, const PcaTransformCall<T>& c, Ran* ran) {
+  validate_matrix(x, c.m, c.n, rs, cs);
+  dev.begin_call();
+  const DenseX<T> dx{x, rs, cs};
+  auto stage = [&](const DenseX<T>& on_dev) {
+    return stage_input<HipDev, T>(dev, false, on_dev.x, c.m, c.n, on_dev.rs, on_dev.cs, /*force_tall=*/true);
+  };
+  if (host_ptrs)
+    transform_host<T>(dev, c, dx, stage, ran);
+  else
+    transform_dev<T>(dev, c, dx, [&] { return stage(dx); }, ran);
+}
+
+template <class T>
+void run_csr(HipDev& dev, bool host_ptrs, const T* values, const int32_t* ci, const int64_t* rp, int64_t nnz,
+             const PcaTransformCall<T>& c, Ran* ran) {
+  validate_csr_args(values, ci, rp, c.m, c.n, nnz);
+  dev.begin_call();
+  auto stage = [&](const DenseX<T>&) {
+    return stage_csr<HipDev, T>(dev, host_ptrs, values, ci, rp, c.m, c.n, nnz, /*keep_orientation=*/true);
+  };
+  if (host_ptrs)
+    transform_host<T>(dev, c, DenseX<T>{}, stage, ran);
+  else
+    transform_dev<T>(dev, c, DenseX<T>{}, [&] { return stage(DenseX<T>{}); }, ran);
+}
+
+template <class T>
+void run_inverse(HipDev& dev, bool host_ptrs, const T* scores, int64_t m, int64_t k, int64_t ld_scores, const T* means,
+                 const T* scales, const T* comps, int64_t ldc, int64_t n, T* out, int64_t row_stride_out, Ran* ran) {
+  PcaApplyShape s;
+  s.m = m, s.n = n, s.k = k;
+  s.row_stride = row_stride_out;
+  s.col_stride = 1;
+  s.esz = (int)sizeof(T);
+  s.base_aligned = (uintptr_t)out % 16 == 0;
+  s.mode = PcaApplyMode::kStore;
+  const PcaApplyPlan p = pca_apply_plan(s);
+  if (p.route == PcaApplyRoute::kReject) throw Error(ST_EINVAL, p.error);
+  dev.begin_call();
+  const T *td = scores, *md = means, *sd = scales, *cd = comps;
+  int64_t ldt = ld_scores;
+  T* od = out;
+  if (host_ptrs) {
+    T* ts = (T*)dev.alloc_bytes((size_t)m * (size_t)k * sizeof(T));
+    CORRLA_HIP(hipMemcpy2DAsync(ts, (size_t)m * sizeof(T), scores, (size_t)ld_scores * sizeof(T), (size_t)m * sizeof(T), (size_t)k,
+                                hipMemcpyHostToDevice, dev.stream));
+    td = ts, ldt = m;
+    md = to_device(dev, means, (size_t)n);
+    sd = to_device(dev, scales, (size_t)n);
+    cd = to_device(dev, comps, (size_t)((n - 1) * ldc + k));
+    // out on the device as it lies on the host: the same row stride and the same offset from a 16-byte boundary, so the
+    // route is the one a device pointer of this layout takes
+    char* buf = (char*)dev.alloc_bytes((size_t)((m - 1) * p.ld + n) * sizeof(T) + 16);
+    od = (T*)(buf + (uintptr_t)out % 16);
+  }
+  // V with unit stride along the features (k rows, padded row stride): one small transposing copy
+  const int64_t ldv = round_up(n, kLdPad);
+  T* v = (T*)dev.alloc_bytes((size_t)k * (size_t)ldv * sizeof(T));
+  dev.pack_strided(cd, k, n, (int64_t)1, ldc, v, ldv);
+  back<T>(dev, p, PcaApplyMode::kStore, td, ldt, (const T*)v, ldv, md, sd, m, n, k, od, (T*)nullptr);
+  ran->centring = 0;
+  ran->route = (int)p.route;
+  if (!host_ptrs) return;  // enqueued on the context's stream; the workspace is reused by later calls in stream order
+  CORRLA_HIP(hipMemcpy2DAsync(out, (size_t)p.ld * sizeof(T), od, (size_t)p.ld * sizeof(T), (size_t)n * sizeof(T), (size_t)m,
+                              hipMemcpyDeviceToHost, dev.stream));
+  dev.end_call();
+}
+
+}  // namespace pca_apply_stage
+}  // namespace corrla

@@ -423,6 +423,87 @@ CORRLA_API corrla_status corrla_cov_dev_f64(corrla_ctx* ctx, const double* x, in
                                             int64_t col_stride, uint64_t flags, int ddof, double* means_out, double* scales_out,
                                             double* c, int64_t ldc, int* route_out);
 
+/* ---- the fitted PCA model on the device: transform, inverse transform, Q-residuals -------------------
+ * Replaces  PcaRsvd::apply_tr(targ_mat)                        src/lib_math_utils/pca_rsvd.rs:43-46
+ *           PcaRsvd::apply_inv_tr(red_mat)                     src/lib_math_utils/pca_rsvd.rs:49-52
+ * The model: means mu (n values), components V (k x n, column-major with leading dimension ldc, as corrla_pca_* writes
+ * it) and optional scales sigma (n values, CORRLA_PCA_STANDARDIZE; NULL: sigma = 1).  With z = (x - 1 mu^T) D^-1,
+ * D = diag(sigma):
+ *   scores         t = z V^T                       (m x k, column-major with leading dimension ld_scores >= m, like U)
+ *   reconstruction xh = (t V) D + 1 mu^T           (m x n, unit stride along the features, row stride row_stride_out)
+ *   Q-residual     q_i = || z_i - t_i V ||_2^2     (m values; the SPE statistic of PCA-based outlier detection)
+ * corrla_pca_transform_*: the forward product runs on the tall kernels of corrla_pca_* with the centring of that entry:
+ * CORRLA_PCA_CENTER_FUSED (x read in place, rank-1 corrections; the f64 default) or CORRLA_PCA_CENTER_COPY (a centred and
+ * scaled m x n copy in workspace; the f32 default) -- the numeric values and defaults of corrla_opts.flags, passed in this
+ * entry's own 64-bit word.  CORRLA_PCA_APPLY_OWN_MEANS: the target is centred by its OWN column means, which is what the
+ * reference's apply_tr does; `means` is then ignored and the means go to means_out when it is given.  means == NULL
+ * without that flag: no centring.  scales, resid_out, means_out may be NULL.
+ * resid_out: q from the scores AS STORED (rounded to T), formed directly from z_i - t_i V in registers by the
+ * back-projection kernel -- never as ||z_i||^2 - ||t_i||^2, which cancels where the model explains the data, and never
+ * through an m x n temporary.  x is read in place with 16-byte loads, in place with checked element loads (base or row
+ * stride not 16-byte aligned), or from one repacked copy (feature-strided x).  No atomics: q is bitwise reproducible.
+ * corrla_pca_transform_csr_*: the same for a CSR target (operand description of corrla_pca_csr_*): always the fused
+ * centring, the matrix is never densified; resid_out must be NULL (a residual over the implicit zeros is a dense
+ * computation).  The CSR validation synchronises once, as in every CSR entry.
+ * corrla_pca_inverse_*: out = (scores V) D + 1 mu^T in one kernel and one write of m x n; means / scales may be NULL.
+ * CORRLA_EINVAL (the message names the argument): m, n < 1; k < 1 or k > n; NULL x, components, scores or out; ldc < k;
+ * ld_scores < m; row_stride_out < n; both centre flags; an unknown flag; an output overlapping an input or another output.
+ * Host-pointer entries copy x to the device as it lies (the whole strided span, as corrla_cov_*) and the results back;
+ * the *_dev entries enqueue on the context's stream and return WITHOUT synchronising (but for a first-time growth of the
+ * workspace arena): corrla_ctx_synchronize orders the results.  Row-sharded data needs no entry of its own: every rank
+ * transforms its rows with the replicated model.
+ * corrla_ctx_last_pca_apply: how the context's last transform / inverse call ran: centring_out 0 none, 1 fused, 2 copy;
+ * route_out the CORRLA_PCA_APPLY_ROUTE_* of the back-projection kernel (0: the call ran none).  Either may be NULL. */
+#define CORRLA_PCA_APPLY_OWN_MEANS 0x400ull /* 64-bit, as the flags parameter */
+#define CORRLA_PCA_APPLY_ROUTE_INPLACE 1
+#define CORRLA_PCA_APPLY_ROUTE_INPLACE_CHECKED 2
+#define CORRLA_PCA_APPLY_ROUTE_REPACKED 3
+CORRLA_API corrla_status corrla_pca_transform_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t n, int64_t row_stride,
+                                                  int64_t col_stride, const float* means, const float* scales, const float* components,
+                                                  int64_t ldc, int64_t k, uint64_t flags, float* scores, int64_t ld_scores, float* resid_out,
+                                                  float* means_out);
+CORRLA_API corrla_status corrla_pca_transform_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t n, int64_t row_stride,
+                                                  int64_t col_stride, const double* means, const double* scales, const double* components,
+                                                  int64_t ldc, int64_t k, uint64_t flags, double* scores, int64_t ld_scores, double* resid_out,
+                                                  double* means_out);
+CORRLA_API corrla_status corrla_pca_transform_dev_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t n, int64_t row_stride,
+                                                      int64_t col_stride, const float* means, const float* scales, const float* components,
+                                                      int64_t ldc, int64_t k, uint64_t flags, float* scores, int64_t ld_scores, float* resid_out,
+                                                      float* means_out);
+CORRLA_API corrla_status corrla_pca_transform_dev_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t n, int64_t row_stride,
+                                                      int64_t col_stride, const double* means, const double* scales, const double* components,
+                                                      int64_t ldc, int64_t k, uint64_t flags, double* scores, int64_t ld_scores, double* resid_out,
+                                                      double* means_out);
+CORRLA_API corrla_status corrla_pca_transform_csr_f32(corrla_ctx* ctx, const float* values, const int32_t* col_idx,
+                                                      const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, const float* means,
+                                                      const float* scales, const float* components, int64_t ldc, int64_t k, uint64_t flags,
+                                                      float* scores, int64_t ld_scores, float* resid_out, float* means_out);
+CORRLA_API corrla_status corrla_pca_transform_csr_f64(corrla_ctx* ctx, const double* values, const int32_t* col_idx,
+                                                      const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, const double* means,
+                                                      const double* scales, const double* components, int64_t ldc, int64_t k, uint64_t flags,
+                                                      double* scores, int64_t ld_scores, double* resid_out, double* means_out);
+CORRLA_API corrla_status corrla_pca_transform_csr_dev_f32(corrla_ctx* ctx, const float* values, const int32_t* col_idx,
+                                                          const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, const float* means,
+                                                          const float* scales, const float* components, int64_t ldc, int64_t k, uint64_t flags,
+                                                          float* scores, int64_t ld_scores, float* resid_out, float* means_out);
+CORRLA_API corrla_status corrla_pca_transform_csr_dev_f64(corrla_ctx* ctx, const double* values, const int32_t* col_idx,
+                                                          const int64_t* row_ptr, int64_t m, int64_t n, int64_t nnz, const double* means,
+                                                          const double* scales, const double* components, int64_t ldc, int64_t k, uint64_t flags,
+                                                          double* scores, int64_t ld_scores, double* resid_out, double* means_out);
+CORRLA_API corrla_status corrla_pca_inverse_f32(corrla_ctx* ctx, const float* scores, int64_t m, int64_t k, int64_t ld_scores,
+                                                const float* means, const float* scales, const float* components, int64_t ldc, int64_t n,
+                                                float* out, int64_t row_stride_out);
+CORRLA_API corrla_status corrla_pca_inverse_f64(corrla_ctx* ctx, const double* scores, int64_t m, int64_t k, int64_t ld_scores,
+                                                const double* means, const double* scales, const double* components, int64_t ldc, int64_t n,
+                                                double* out, int64_t row_stride_out);
+CORRLA_API corrla_status corrla_pca_inverse_dev_f32(corrla_ctx* ctx, const float* scores, int64_t m, int64_t k, int64_t ld_scores,
+                                                    const float* means, const float* scales, const float* components, int64_t ldc, int64_t n,
+                                                    float* out, int64_t row_stride_out);
+CORRLA_API corrla_status corrla_pca_inverse_dev_f64(corrla_ctx* ctx, const double* scores, int64_t m, int64_t k, int64_t ld_scores,
+                                                    const double* means, const double* scales, const double* components, int64_t ldc, int64_t n,
+                                                    double* out, int64_t row_stride_out);
+CORRLA_API corrla_status corrla_ctx_last_pca_apply(corrla_ctx* ctx, int* centring_out, int* route_out);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller

@@ -41,6 +41,11 @@ pub const CORRLA_COV_NO_CENTER: u64 = 0x2;
 pub const CORRLA_COV_ROUTE_INPLACE: c_int = 1;
 pub const CORRLA_COV_ROUTE_INPLACE_CHECKED: c_int = 2;
 pub const CORRLA_COV_ROUTE_REPACKED: c_int = 3;
+// corrla_pca_transform_*: the entry's own 64-bit flag word takes CORRLA_PCA_CENTER_FUSED / _COPY (values above) and
+pub const CORRLA_PCA_APPLY_OWN_MEANS: u64 = 0x400; // centre the target by its own column means (pca_rsvd.rs:43-46)
+pub const CORRLA_PCA_APPLY_ROUTE_INPLACE: c_int = 1;
+pub const CORRLA_PCA_APPLY_ROUTE_INPLACE_CHECKED: c_int = 2;
+pub const CORRLA_PCA_APPLY_ROUTE_REPACKED: c_int = 3;
 
 extern "C" {
     fn corrla_ctx_create(device: c_int, out: *mut *mut c_void) -> c_int;
@@ -103,6 +108,49 @@ extern "C" {
                               means_out: *mut f64, scales_out: *mut f64, c: *mut f64, ldc: i64, route_out: *mut c_int) -> c_int;
     pub fn corrla_cov_dev_f32(ctx: *mut c_void, x: *const f32, m: i64, n: i64, rs: i64, cs: i64, flags: u64, ddof: c_int,
                               means_out: *mut f32, scales_out: *mut f32, c: *mut f32, ldc: i64, route_out: *mut c_int) -> c_int;
+    // the fitted PCA model (pca_rsvd.rs:43-52): scores (m x k, column-major ld_scores), optional Q-residuals and own means
+    pub fn corrla_pca_transform_f64(ctx: *mut c_void, x: *const f64, m: i64, n: i64, rs: i64, cs: i64, means: *const f64,
+                                     scales: *const f64, components: *const f64, ldc: i64, k: i64, flags: u64,
+                                     scores: *mut f64, ld_scores: i64, resid_out: *mut f64, means_out: *mut f64) -> c_int;
+    pub fn corrla_pca_transform_f32(ctx: *mut c_void, x: *const f32, m: i64, n: i64, rs: i64, cs: i64, means: *const f32,
+                                     scales: *const f32, components: *const f32, ldc: i64, k: i64, flags: u64,
+                                     scores: *mut f32, ld_scores: i64, resid_out: *mut f32, means_out: *mut f32) -> c_int;
+    pub fn corrla_pca_transform_dev_f64(ctx: *mut c_void, x: *const f64, m: i64, n: i64, rs: i64, cs: i64, means: *const f64,
+                                     scales: *const f64, components: *const f64, ldc: i64, k: i64, flags: u64,
+                                     scores: *mut f64, ld_scores: i64, resid_out: *mut f64, means_out: *mut f64) -> c_int;
+    pub fn corrla_pca_transform_dev_f32(ctx: *mut c_void, x: *const f32, m: i64, n: i64, rs: i64, cs: i64, means: *const f32,
+                                     scales: *const f32, components: *const f32, ldc: i64, k: i64, flags: u64,
+                                     scores: *mut f32, ld_scores: i64, resid_out: *mut f32, means_out: *mut f32) -> c_int;
+    pub fn corrla_pca_transform_csr_f64(ctx: *mut c_void, values: *const f64, col_idx: *const i32, row_ptr: *const i64,
+                                         m: i64, n: i64, nnz: i64, means: *const f64, scales: *const f64,
+                                         components: *const f64, ldc: i64, k: i64, flags: u64, scores: *mut f64,
+                                         ld_scores: i64, resid_out: *mut f64, means_out: *mut f64) -> c_int;
+    pub fn corrla_pca_transform_csr_f32(ctx: *mut c_void, values: *const f32, col_idx: *const i32, row_ptr: *const i64,
+                                         m: i64, n: i64, nnz: i64, means: *const f32, scales: *const f32,
+                                         components: *const f32, ldc: i64, k: i64, flags: u64, scores: *mut f32,
+                                         ld_scores: i64, resid_out: *mut f32, means_out: *mut f32) -> c_int;
+    pub fn corrla_pca_transform_csr_dev_f64(ctx: *mut c_void, values: *const f64, col_idx: *const i32, row_ptr: *const i64,
+                                         m: i64, n: i64, nnz: i64, means: *const f64, scales: *const f64,
+                                         components: *const f64, ldc: i64, k: i64, flags: u64, scores: *mut f64,
+                                         ld_scores: i64, resid_out: *mut f64, means_out: *mut f64) -> c_int;
+    pub fn corrla_pca_transform_csr_dev_f32(ctx: *mut c_void, values: *const f32, col_idx: *const i32, row_ptr: *const i64,
+                                         m: i64, n: i64, nnz: i64, means: *const f32, scales: *const f32,
+                                         components: *const f32, ldc: i64, k: i64, flags: u64, scores: *mut f32,
+                                         ld_scores: i64, resid_out: *mut f32, means_out: *mut f32) -> c_int;
+    // out (m x n, unit stride along the features) = (scores V) D + 1 mu^T
+    pub fn corrla_pca_inverse_f64(ctx: *mut c_void, scores: *const f64, m: i64, k: i64, ld_scores: i64, means: *const f64,
+                                   scales: *const f64, components: *const f64, ldc: i64, n: i64, out: *mut f64,
+                                   row_stride_out: i64) -> c_int;
+    pub fn corrla_pca_inverse_f32(ctx: *mut c_void, scores: *const f32, m: i64, k: i64, ld_scores: i64, means: *const f32,
+                                   scales: *const f32, components: *const f32, ldc: i64, n: i64, out: *mut f32,
+                                   row_stride_out: i64) -> c_int;
+    pub fn corrla_pca_inverse_dev_f64(ctx: *mut c_void, scores: *const f64, m: i64, k: i64, ld_scores: i64, means: *const f64,
+                                   scales: *const f64, components: *const f64, ldc: i64, n: i64, out: *mut f64,
+                                   row_stride_out: i64) -> c_int;
+    pub fn corrla_pca_inverse_dev_f32(ctx: *mut c_void, scores: *const f32, m: i64, k: i64, ld_scores: i64, means: *const f32,
+                                   scales: *const f32, components: *const f32, ldc: i64, n: i64, out: *mut f32,
+                                   row_stride_out: i64) -> c_int;
+    pub fn corrla_ctx_last_pca_apply(ctx: *mut c_void, centring_out: *mut c_int, route_out: *mut c_int) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
