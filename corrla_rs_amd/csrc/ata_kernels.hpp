@@ -31,8 +31,8 @@
 namespace corrla {
 namespace k {
 
-constexpr int kAtaRows = 16;  // rows of A per LDS tile
-
+// kAtaRows (rows of A per LDS tile) and the LDS layout ata_tile_bytes / ata_tpart_bytes / ata_stages / ata_lds_bytes:
+// gemm_plan.hpp, with the plan of the launch (ata_plan)
 struct AtaArgs {
   const float* a;       // row-major m x n
   int64_t m, n, lda, n_readable;
@@ -44,16 +44,6 @@ struct AtaArgs {
   int nrowgroups;
   const float* zero;       // >= 16 bytes of zeros
 };
-
-__host__ __device__ constexpr int ata_tile_bytes(int nk) { return kAtaRows * nk * 256; }
-__host__ __device__ constexpr int ata_tpart_bytes(int nct) { return 2 * 4 * nct * 1024; }  // [parity][wave][ct][16 x 16]
-__host__ __device__ constexpr int ata_stages(int nk, int nct) {
-  const int s = (160 * 1024 - ata_tpart_bytes(nct)) / ata_tile_bytes(nk);
-  return s > 4 ? 4 : s;
-}
-__host__ __device__ constexpr int ata_lds_bytes(int nk, int nct) {
-  return ata_stages(nk, nct) * ata_tile_bytes(nk) + ata_tpart_bytes(nct);
-}
 
 // NK = reduction segments of 256 bytes per tile row (n padded to 64 NK), NCT = 16-column tiles of Z
 template <int NK, int NCT>

@@ -10,6 +10,7 @@
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "pca_apply_stage.hpp"
+#include "tall_stage.hpp"
 
 using namespace corrla;
 

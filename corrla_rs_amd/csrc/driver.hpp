@@ -33,8 +33,7 @@ inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 // Skinny matrices (Omega, Y, Z, Q, B^T, small l x l operands) are column-major device
 // buffers with a leading dimension padded to 64 elements and a column count padded to the
 // kernel's column blocking (col_blocking, gemm_plan.hpp); ALL padding is kept zero so the GEMM
-// kernels never bounds-check them.
-constexpr int kLdPad = 64;
+// kernels never bounds-check them.  kLdPad and the layout rule (skinny_layout) are in gemm_plan.hpp.
 
 template <class T>
 struct Skinny {

@@ -1,9 +1,12 @@
-// The tall products' plan (gemm_nn / gemm_tn / gemm_mixed, hip_backend.hpp): which kernel family and instantiation serves a
-// product, its launches (grid, column base, XCD remap, dynamic LDS), the reduction split and the slab reduction that sums
-// it -- or why the call is rejected -- and the LDS and geometry arithmetic those choices rest on.
-// Host code only, no HIP call: tests/test_gemm_plan.py compiles this header with the host compiler and pins the plan.
-// The kernels that use the size helpers on the device include it through hip_kernels.hpp (which tall_kernels.hpp and
-// mixed_kernels.hpp include); driver.hpp takes the column blocking from it.
+// The tall products' plans (tall_stage.hpp launches what they say and computes none of it again).  gemm_plan: which
+// kernel family and instantiation serves a product (gemm_nn / gemm_tn / gemm_mixed / gemm_bf16a), its launches (grid, column
+// base, XCD remap, dynamic LDS), the reduction split and the slab reduction that sums it -- or why the call is rejected.
+// ata_plan: the one-sweep A^T (A Z).  spmm_plan: the CSR product.  With them the LDS and geometry arithmetic those choices
+// rest on, the layout of a padded skinny matrix, and the list of instantiations each kernel family has.
+// Host code only, no HIP call: tests/test_gemm_plan.py, tests/test_gemm_plan_bf16.py and tests/test_tall_stage_plan.py
+// compile this header with the host compiler and pin the plans.  The kernels that use the size helpers on the device include
+// it through hip_kernels.hpp (which tall_kernels.hpp, mixed_kernels.hpp and ata_kernels.hpp include) or directly
+// (spmm_kernels.hpp); driver.hpp takes the column blocking and kLdPad from it.
 //
 // Families.  GENERAL: gemm_nn_kernel / gemm_tn_kernel<T, MW, NT, NW> (hip_kernels.hpp), any shape.  GRAM ALIAS: the
 // aliased gemm_nn_kernel<T, 2, NT, true> for G = Y^T Y with l <= 128.  TALL APPLY / TALL GRAM: the register-resident
@@ -14,6 +17,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 
 #include "core_svd_plan.hpp"  // kLdsMaxBytes, CORRLA_HD
 
@@ -35,6 +39,29 @@ inline ColBlocking col_blocking(int64_t cols) {
   b.cols_alloc = (int64_t)b.nblk * b.nt * 16;
   return b;
 }
+
+// A skinny matrix (driver.hpp: Skinny) of rows x cols as the backend allocates it: the leading dimension padded to kLdPad
+// elements, the column count to the column blocking.
+constexpr int kLdPad = 64;
+struct SkinnyLayout {
+  int64_t ld, cols_alloc;
+};
+inline SkinnyLayout skinny_layout(int64_t rows, int64_t cols) {
+  return {(std::max<int64_t>(rows, 1) + kLdPad - 1) / kLdPad * kLdPad, col_blocking(cols).cols_alloc};
+}
+
+// ---- the instantiations of each kernel family.  tall_stage.hpp dispatches on these and registers the dynamic LDS of every
+// kernel from these: a kernel that can be launched is one whose limit was set. ----
+// gemm_nn_kernel<T, MW, NT, false, NW> / gemm_tn_kernel<T, MW, NT, NW>: four MFMA waves, or the f64 MW = 2 tile on eight
+constexpr bool gemm_general_exists(int esz, int mw, int nt, int nw) {
+  return (mw == 1 || mw == 2) && nt >= 1 && nt <= kMaxColTiles && (nw == 4 || (nw == 8 && mw == 1 && esz == 8));
+}
+using GeneralNWs = std::integer_sequence<int, 4, 8>;
+constexpr int kAliasMaxTiles = 8;                    // gemm_nn_kernel<T, 2, NT, true>: NT 1 .. 8
+constexpr int tall_max_tiles(int esz) { return esz == 4 ? 6 : 4; }  // tall_apply_kernel<T, K, K>, tall_gram_kernel<T, NCT>
+constexpr int kMxMinPlanes = 2, kMxMaxPlanes = 3;    // gemm_bf16s_kernel<NT, NP, TN>: NT 1 .. kMaxColTiles, NP 2 .. 3
+using AtaNKs = std::integer_sequence<int, 2, 4, 8>;  // ata_fused_kernel<NK, NCT>: NK of the list, NCT 1 .. 5
+constexpr int kAtaMaxColTiles = 5;                   // (gemm_bf16a_kernel<NT, TN>: NT 1 .. kMaxColTiles)
 
 namespace k {
 
@@ -92,6 +119,19 @@ constexpr int kBaBigBytes = kMxOuter * kMxKT * 2;       // 16 KiB: one 32-deep t
 constexpr int kBaASlots = 4, kBaBSlots = 3;
 CORRLA_HD constexpr int ba_bslot_bytes(int nt) { return kBaPlanes * mx_plane_bytes(nt); }
 CORRLA_HD constexpr int ba_lds_bytes(int nt) { return kBaASlots * kBaBigBytes + kBaBSlots * ba_bslot_bytes(nt) + 1024; }
+
+// ---- one-sweep A^T (A Z) (ata_kernels.hpp): a ring of up to 4 tiles of kAtaRows rows of A, then the partial T tiles ----
+constexpr int kAtaRows = 16;  // rows of A per LDS tile
+CORRLA_HD constexpr int ata_tile_bytes(int nk) { return kAtaRows * nk * 256; }
+CORRLA_HD constexpr int ata_tpart_bytes(int nct) { return 2 * 4 * nct * 1024; }  // [parity][wave][ct][16 x 16]
+CORRLA_HD constexpr int ata_stages(int nk, int nct) {
+  const int s = (160 * 1024 - ata_tpart_bytes(nct)) / ata_tile_bytes(nk);
+  return s > 4 ? 4 : s;
+}
+CORRLA_HD constexpr int ata_lds_bytes(int nk, int nct) { return ata_stages(nk, nct) * ata_tile_bytes(nk) + ata_tpart_bytes(nct); }
+
+// ---- CSR product (spmm_kernels.hpp) ----
+constexpr int kSpTile = 64;  // rows and sketch columns of one output tile
 
 }  // namespace k
 
@@ -210,7 +250,7 @@ inline bool plan_reduce(GemmPlan& p, int64_t outer_n, int64_t cols_alloc) {
 
 // Y M (tn) and Y^T Y (nn) of a very tall sketch on the register-resident kernels; false: not theirs
 inline bool plan_tall(const GemmShape& s, const GemmKnobs& kn, int64_t outer_n, int64_t red_n, GemmPlan& p) {
-  const int kMaxL = s.esz == 4 ? 96 : 64;  // register budget of the B fragments
+  const int kMaxL = 16 * tall_max_tiles(s.esz);  // 96 / 64: register budget of the B fragments
   const int vec = k::gemm_vec(s.esz);
   if (kn.tall_min_rows <= 0) return false;
   if (s.tn) {
@@ -333,7 +373,7 @@ inline GemmPlan gemm_plan(const GemmShape& s, const GemmKnobs& kn) {
                       (double)outer_n * (double)red_n * (double)cb.cols_alloc >= 1.0e10;
   // Gram matrix G = Y^T Y: both operands are the same memory and one outer tile (MW = 2: 128 indices) holds every
   // column -> the aliased instantiation stages Y once per tile
-  const bool alias = !s.tn && s.same && s.r.ld == s.x.ld && cb.nblk == 1 && outer_n <= 128 && cb.nt <= 8 &&
+  const bool alias = !s.tn && s.same && s.r.ld == s.x.ld && cb.nblk == 1 && outer_n <= 128 && cb.nt <= kAliasMaxTiles &&
                      outer_n == s.x.cols && !kn.no_gram_alias;
 
   // MW (16-wide outer tiles per wave) and nsplit (split of the reduction into slabs).  One workgroup is resident per CU
@@ -420,6 +460,92 @@ inline GemmPlan gemm_plan(const GemmShape& s, const GemmKnobs& kn) {
     }
   }
   if (!plan_reduce(p, outer_n, cb.cols_alloc)) p.error = "problem too large for the launch grid";
+  return p;
+}
+
+// Both tall products of a call on the bf16-stored operand r with an l-column sketch, the skinny operands as the backend
+// allocates them, are in the bf16-stored kernels' domain.
+inline bool gemm_bf16a_call_domain(const GemmOperand& r, int64_t l, int num_cus) {
+  for (int tn = 0; tn < 2; ++tn) {
+    const int64_t xr = tn ? r.rows : r.cols, outr = tn ? r.cols : r.rows;
+    const SkinnyLayout lx = skinny_layout(xr, l), lo = skinny_layout(outr, l);
+    GemmShape s;
+    s.tn = tn != 0;
+    s.r = r;
+    s.x = {xr, l, lx.ld, 0, lx.cols_alloc, false, true};
+    s.out = {outr, l, lo.ld, 0, lo.cols_alloc, false, true};
+    s.r_bf16 = true;
+    s.num_cus = num_cus;
+    if (!gemm_bf16a_domain(s)) return false;
+  }
+  return true;
+}
+
+// ---- one-sweep Z' = A^T (A Z) (ata_kernels.hpp): row-major f32 A (rows x n), Z and Z' n x l in the padded layout ----------
+struct AtaPlan {
+  bool in_domain = false;       // what the driver asks before it takes this route: f32, 16 <= n <= 512, l <= 80, rows >= 4096
+  const char* error = nullptr;  // the call is rejected (thrown as ST_EINVAL)
+  int nk = 0, nct = 0;          // ata_fused_kernel<NK, NCT>: n padded to 64 NK, 16 NCT columns
+  int nrg = 0;                  // row groups = workgroups, one partial Z' each
+  int block = 256, lds = 0;
+  int64_t rows_per_group = 0, slab_stride = 0;
+  size_t slab_bytes = 0;        // zero-filled: empty groups contribute zeros
+  SlabReducePlan reduce;
+};
+inline bool ata_domain(int esz, int64_t rows, int64_t n, int64_t l) {
+  return esz == 4 && n <= 512 && n >= 16 && l <= 16 * kAtaMaxColTiles && rows >= 4096;
+}
+// a: the big operand; x, z: the skinny operand and the result
+inline AtaPlan ata_plan(int esz, const GemmOperand& a, const GemmOperand& x, const GemmOperand& z, int num_cus) {
+  AtaPlan p;
+  auto rejected = [&p](const char* why) {
+    p.error = why;
+    return p;
+  };
+  p.in_domain = ata_domain(esz, a.rows, a.cols, x.cols);
+  if (esz != 4) return rejected("internal: the one-sweep power iteration is f32 only");
+  if (x.rows != a.cols || z.rows != a.cols) return rejected("ata_fused: shapes");
+  const ColBlocking cb = col_blocking(x.cols);
+  if (cb.cols_alloc > x.cols_alloc || cb.cols_alloc > z.cols_alloc || x.ld != z.ld || cb.cols_alloc > 16 * kAtaMaxColTiles)
+    return rejected("internal: ata_fused operands must share the padded layout (<= 80 columns)");
+  if (!a.aligned || (a.ld % 4) || (a.cols_readable % 4)) return rejected("internal: operand not vector aligned");
+  // reduction segments: n padded to 128 / 256 / 512 (three instantiation families)
+  p.nk = a.cols <= 128 ? 2 : (a.cols <= 256 ? 4 : 8);
+  p.nct = (int)(cb.cols_alloc / 16);
+  // one workgroup per CU; every workgroup gets at least a few tiles
+  const int64_t blocks = (a.rows + k::kAtaRows - 1) / k::kAtaRows;
+  p.nrg = (int)std::max<int64_t>(1, std::min<int64_t>(num_cus, blocks / 8));
+  p.rows_per_group = ((blocks + p.nrg - 1) / p.nrg) * k::kAtaRows;
+  p.lds = k::ata_lds_bytes(p.nk, p.nct);
+  p.slab_stride = z.ld * cb.cols_alloc;
+  p.slab_bytes = (size_t)p.nrg * (size_t)p.slab_stride * 4;
+  p.reduce = {SlabReduce::deep, {(unsigned)((a.cols + 63) / 64), (unsigned)cb.cols_alloc}, p.nrg, a.cols, cb.cols_alloc};
+  if (!gemm_plan_detail::grid_fits(p.reduce.grid[1], 1)) return rejected("problem too large for the launch grid");
+  return p;
+}
+
+// ---- CSR product Y (rows x L) = S X (spmm_kernels.hpp): X goes through a row-major scratch XT (cols x Lp), the long rows
+// (n_long of them, in n_chunks chunks) through partial sums of Lpart values per chunk ----
+struct SpmmPlan {
+  const char* error = nullptr;  // the call is rejected (thrown as ST_EINVAL)
+  int64_t Lp = 0, jt = 0, Lpart = 0;
+  size_t xt_bytes = 0, scratch_bytes = 0;  // XT, and XT + the partial sums
+  unsigned grid_xt[2] = {0, 0}, grid_rows[2] = {0, 0};
+  unsigned grid_long_partial[2] = {0, 0}, grid_long_reduce[2] = {0, 0};  // launched when n_long > 0
+};
+inline SpmmPlan spmm_plan(int esz, int64_t rows, int64_t cols, int64_t L, int64_t n_long, int64_t n_chunks) {
+  SpmmPlan p;
+  const int64_t tile = k::kSpTile;
+  p.Lp = (L + 15) / 16 * 16;
+  p.jt = (L + tile - 1) / tile;
+  p.Lpart = p.jt * 64;
+  p.xt_bytes = ((size_t)cols * (size_t)p.Lp * (size_t)esz + 255) / 256 * 256;
+  p.scratch_bytes = p.xt_bytes + (size_t)n_chunks * (size_t)p.Lpart * (size_t)esz;
+  p.grid_xt[0] = (unsigned)((cols + tile - 1) / tile), p.grid_xt[1] = (unsigned)((p.Lp + tile - 1) / tile);
+  p.grid_rows[0] = (unsigned)((rows + tile - 1) / tile), p.grid_rows[1] = (unsigned)p.jt;
+  p.grid_long_partial[0] = (unsigned)n_chunks, p.grid_long_partial[1] = (unsigned)p.jt;
+  p.grid_long_reduce[0] = (unsigned)n_long, p.grid_long_reduce[1] = (unsigned)p.jt;
+  if (!gemm_plan_detail::grid_fits(p.grid_xt[1], p.grid_rows[1])) p.error = "problem too large for the launch grid";
   return p;
 }
 

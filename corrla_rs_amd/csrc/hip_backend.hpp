@@ -105,6 +105,12 @@ namespace core_svd_stage {
 template <class T>
 void set_lds_limits();  // core_svd_stage.hpp: the core SVD's kernels
 }
+namespace tall_stage {
+struct Call;            // tall_stage.hpp: what a launcher of the tall products needs of a context
+template <class T>
+void set_lds_limits();  // the tall products' kernels of element type T ...
+inline void set_lds_limits();  // ... and the f32-only ones (bf16 split, bf16 stored, one-sweep)
+}
 
 class HipDev {
  public:
@@ -283,13 +289,20 @@ class HipDev {
     return p;
   }
 
+  // rows x cols in the padded layout (gemm_plan.hpp: skinny_layout), not yet backed by memory
   template <class T>
-  Skinny<T> alloc_skinny(int64_t rows, int64_t cols) {
+  static Skinny<T> skinny_of(int64_t rows, int64_t cols) {
+    const SkinnyLayout lay = skinny_layout(rows, cols);
     Skinny<T> s;
     s.rows = rows;
     s.cols = cols;
-    s.ld = round_up(std::max<int64_t>(rows, 1), kLdPad);
-    s.cols_alloc = col_blocking(cols).cols_alloc;
+    s.ld = lay.ld;
+    s.cols_alloc = lay.cols_alloc;
+    return s;
+  }
+  template <class T>
+  Skinny<T> alloc_skinny(int64_t rows, int64_t cols) {
+    Skinny<T> s = skinny_of<T>(rows, cols);
     const size_t bytes = (size_t)s.ld * (size_t)s.cols_alloc * sizeof(T);
     s.p = (T*)alloc_zeroed(bytes);
     return s;
@@ -299,11 +312,7 @@ class HipDev {
   // are 12.8 GB of memset otherwise)
   template <class T>
   Skinny<T> alloc_skinny_out(int64_t rows, int64_t cols) {
-    Skinny<T> s;
-    s.rows = rows;
-    s.cols = cols;
-    s.ld = round_up(std::max<int64_t>(rows, 1), kLdPad);
-    s.cols_alloc = col_blocking(cols).cols_alloc;
+    Skinny<T> s = skinny_of<T>(rows, cols);
     const size_t bytes = (size_t)s.ld * (size_t)s.cols_alloc * sizeof(T);
     if (bytes < ((size_t)4 << 20)) {
       s.p = (T*)alloc_zeroed(bytes);
@@ -335,17 +344,11 @@ class HipDev {
     h2d_2d((void*)dst, dpitch_e, (const void*)src, spitch_e, width_e, rows, sizeof(T));
   }
 
-  // ---- tall products: gemm_plan (gemm_plan.hpp) decides, the functions below launch what it says ----------------
+  // ---- tall products: gemm_plan.hpp decides, tall_stage.hpp launches what it says and defines these members -----------
   template <class T>
-  void gemm_nn(const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev) {
-    if (x.rows != r.cols) throw Error(ST_EINVAL, "gemm_nn: inner dimensions differ");
-    launch_gemm<T>(false, r, x, out, scale_dev);
-  }
+  void gemm_nn(const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev);
   template <class T>
-  void gemm_tn(const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev) {
-    if (x.rows != r.rows) throw Error(ST_EINVAL, "gemm_tn: inner dimensions differ");
-    launch_gemm<T>(true, r, x, out, scale_dev);
-  }
+  void gemm_tn(const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev);
 
   // ---- CSR sparse operand (spmm_kernels.hpp) ---------------------------------------------------------------------
   static constexpr bool kHasSpmm = true;  // driver.hpp: dev_has_spmm
@@ -353,105 +356,21 @@ class HipDev {
   // violation -- before anything is gathered through these arrays -- and builds the lists of long rows and their chunks.
   // One host synchronisation (the verdict and the two list sizes come back in one 40-byte copy).
   template <class T>
-  void csr_plan(CsrView<T>& v, bool check_idx) {
-    k::CsrCounts* cnt = (k::CsrCounts*)alloc_zeroed(sizeof(k::CsrCounts));
-    const int64_t top = std::max(v.rows, v.nnz);
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((top + 255) / 256, (int64_t)num_cus * 16));
-    hipLaunchKernelGGL(k::csr_validate_kernel, dim3(blocks), dim3(256), 0, stream, v.rp, v.ci, v.rows, v.cols, v.nnz, check_idx ? 1 : 0, cnt);
-    CORRLA_HIP(hipGetLastError());
-    k::CsrCounts h;
-    read_bytes(cnt, sizeof(h), &h);
-    if (h.bad) {
-      std::string why;
-      if (h.bad & 1) why += " row_ptr[0] != 0;";
-      if (h.bad & 2) why += " row_ptr is not monotone within [0, nnz];";
-      if (h.bad & 4) why += " row_ptr[m] != nnz;";
-      if (h.bad & 8) why += " a column index lies outside [0, n);";
-      throw Error(ST_EINVAL, "invalid CSR matrix:" + why);
-    }
-    v.n_long = (int64_t)h.n_long;
-    v.n_chunks = (int64_t)h.n_chunks;
-    if (v.n_long == 0) return;
-    if (v.n_chunks > 0x7fffffff) throw Error(ST_EINVAL, "problem too large for the launch grid");
-    int64_t* lr = (int64_t*)alloc_bytes(sizeof(int64_t) * (size_t)v.n_long);
-    int64_t* lb = (int64_t*)alloc_bytes(sizeof(int64_t) * (size_t)v.n_long);
-    int32_t* cl = (int32_t*)alloc_bytes(sizeof(int32_t) * (size_t)v.n_chunks);
-    const unsigned b2 = (unsigned)std::max<int64_t>(1, std::min<int64_t>((v.rows + 255) / 256, (int64_t)num_cus * 16));
-    hipLaunchKernelGGL(k::csr_long_build_kernel, dim3(b2), dim3(256), 0, stream, v.rp, v.rows, cnt, lr, lb, cl);
-    CORRLA_HIP(hipGetLastError());
-    v.long_row = lr;
-    v.long_base = lb;
-    v.chunk_long = cl;
-  }
+  void csr_plan(CsrView<T>& v, bool check_idx);
   // CSR of the transpose of a VALIDATED matrix, in arena memory (released with the call).  Entries of a row of the
   // transpose keep the order (original row, original position): a stable radix sort by column index.
   template <class T>
-  CsrView<T> csr_transpose(const CsrView<T>& a) {
-    const int64_t nnz = a.nnz;
-    if (nnz < 1 || nnz > 0x7fffffff) throw Error(ST_EINVAL, "csr_transpose: nnz must be in [1, 2^31)");
-    const int64_t nb = (nnz + k::kSortTile - 1) / k::kSortTile;
-    uint32_t* key[2] = {(uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz), (uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz)};
-    uint32_t* pay[2] = {(uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz), (uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nnz)};
-    uint32_t* hist = (uint32_t*)alloc_bytes(sizeof(uint32_t) * (size_t)nb * 256);
-    int bits = 1;
-    while (((int64_t)1 << bits) < a.cols) ++bits;
-    const int passes = (bits + 7) / 8;
-    const uint32_t* kin = (const uint32_t*)a.ci;  // validated: every index is in [0, cols), so the bit patterns agree
-    const uint32_t* pin = nullptr;
-    for (int ps = 0; ps < passes; ++ps) {
-      uint32_t* kout = key[ps & 1];
-      uint32_t* pout = pay[ps & 1];
-      hipLaunchKernelGGL(k::csr_radix_hist_kernel, dim3((unsigned)nb), dim3(64), 0, stream, kin, nnz, 8 * ps, hist, nb);
-      hipLaunchKernelGGL(k::csr_scan_kernel, dim3(1), dim3(1024), 0, stream, hist, nb * 256);
-      hipLaunchKernelGGL(k::csr_radix_scatter_kernel, dim3((unsigned)nb), dim3(64), 0, stream, kin, pin, nnz, 8 * ps, (const uint32_t*)hist, nb,
-                         kout, pout);
-      CORRLA_HIP(hipGetLastError());
-      kin = kout;
-      pin = pout;
-    }
-    CsrView<T> t;
-    t.rows = a.cols;
-    t.cols = a.rows;
-    t.nnz = nnz;
-    int64_t* trp = (int64_t*)alloc_bytes(sizeof(int64_t) * (size_t)(a.cols + 1));
-    int32_t* tci = (int32_t*)alloc_bytes(sizeof(int32_t) * (size_t)nnz);
-    T* tval = (T*)alloc_bytes(sizeof(T) * (size_t)nnz);
-    hipLaunchKernelGGL((k::csr_transpose_finish_kernel<T>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, kin, pin, a.rp, a.rows,
-                       a.val, nnz, a.cols, trp, tci, tval);
-    CORRLA_HIP(hipGetLastError());
-    t.rp = trp;
-    t.ci = tci;
-    t.val = tval;
-    return t;
-  }
+  CsrView<T> csr_transpose(const CsrView<T>& a);
   // y (s.rows x L) = scale * S * x (s.cols x L); writes rows [0, s.rows) x columns [0, x.cols) of y and nothing else
   template <class T>
-  void spmm(const CsrView<T>& s, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev) {
-    if (x.rows != s.cols || y.rows != s.rows) throw Error(ST_EINVAL, "spmm: dimensions differ");
-    const int64_t L = x.cols;
-    if (L < 1 || y.cols < L) throw Error(ST_EINVAL, "spmm: destination has fewer columns than the operand");
-    const int64_t Lp = round_up(L, 16), jt = (L + k::kSpTile - 1) / k::kSpTile, Lpart = jt * 64;
-    const size_t xt_bytes = ((size_t)s.cols * (size_t)Lp * sizeof(T) + 255) / 256 * 256;
-    const size_t need = xt_bytes + (size_t)s.n_chunks * (size_t)Lpart * sizeof(T);
-    if (need > sp_scratch_bytes_) {  // one scratch per call, grown on demand (the arena is released at end_call)
-      sp_scratch_ = alloc_bytes(need);
-      sp_scratch_bytes_ = need;
+  void spmm(const CsrView<T>& s, const Skinny<T>& x, Skinny<T>& y, const T* scale_dev);
+  // XT + long-row partial sums of the SpMM: one scratch per call, grown on demand (the arena is released at end_call)
+  void* spmm_scratch(size_t bytes) {
+    if (bytes > sp_scratch_bytes_) {
+      sp_scratch_ = alloc_bytes(bytes);
+      sp_scratch_bytes_ = bytes;
     }
-    T* xt = (T*)sp_scratch_;
-    T* part = (T*)((char*)sp_scratch_ + xt_bytes);
-    dim3 gx((unsigned)((s.cols + k::kSpTile - 1) / k::kSpTile), (unsigned)((Lp + k::kSpTile - 1) / k::kSpTile));
-    dim3 gr((unsigned)((s.rows + k::kSpTile - 1) / k::kSpTile), (unsigned)jt);
-    check_grid(gx);
-    check_grid(gr);
-    hipLaunchKernelGGL((k::spmm_xt_kernel<T>), gx, dim3(256), 0, stream, (const T*)x.p, x.ld, s.cols, L, xt, Lp);
-    hipLaunchKernelGGL((k::spmm_rows_kernel<T>), gr, dim3(256), 0, stream, s.rp, s.ci, s.val, (const T*)xt, Lp, s.rows, L, y.p, y.ld, scale_dev);
-    if (s.n_long > 0) {
-      hipLaunchKernelGGL((k::spmm_long_partial_kernel<T>), dim3((unsigned)s.n_chunks, (unsigned)jt), dim3(256), 0, stream, s.rp, s.ci, s.val,
-                         (const T*)xt, Lp, L, s.long_row, s.long_base, s.chunk_long, part, Lpart);
-      hipLaunchKernelGGL((k::spmm_long_reduce_kernel<T>), dim3((unsigned)s.n_long, (unsigned)jt), dim3(64), 0, stream, s.rp, s.long_row,
-                         s.long_base, (const T*)part, Lpart, L, y.p, y.ld, scale_dev);
-    }
-    CORRLA_HIP(hipGetLastError());
+    return sp_scratch_;
   }
   void h2d_bytes(void* dst, const void* src, size_t bytes) {
     CORRLA_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
@@ -462,97 +381,17 @@ class HipDev {
   // ("bf16x3": hi hi + hi lo + lo hi) or 3 ("bf16x6").  The caller asks mixed_fits first and keeps the exact kernels
   // for everything outside the split kernels' domain (gemm_mixed_domain).
   template <class T>
-  bool mixed_fits(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out) const {
-    return gemm_mixed_domain(gemm_shape(tn, r, x, out, 2), gemm_knobs_);
-  }
+  bool mixed_fits(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out) const;
   template <class T>
-  void gemm_mixed(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev, int np) {
-    if constexpr (std::is_same<T, float>::value)
-      gemm_mixed_f32(tn, r, x, out, scale_dev, np);
-    else
-      throw Error(ST_EINVAL, "internal: the bf16-split products are f32 only");
-  }
-  void gemm_mixed_f32(bool tn, const Big<float>& r, const Skinny<float>& x, Skinny<float>& out, const float* scale_dev, int np) {
-    const GemmPlan p = plan_gemm(tn, r, x, out, np);
-    // the skinny operand in np bf16 planes, reduction index in MFMA fragment order
-    __bf16* planes = (__bf16*)alloc_bytes(p.plane_bytes);
-    with_nt<3, 2>(p.np, [&](auto np_c) {
-      hipLaunchKernelGGL((k::split_planes_kernel<decltype(np_c)::value>), dim3(p.split_grid), dim3(256), 0, stream, (const float*)x.p,
-                         x.ld, p.plane_cols, planes, p.plane_stride, run_if_);
-    });
-    CORRLA_HIP(hipGetLastError());
-    float* slab = p.reduce.kind != SlabReduce::none ? (float*)alloc_bytes(p.slab_bytes) : nullptr;
-    const k::MxArgs a{r.p, r.rows, r.cols, r.ld, r.cols_readable,  // big operand
-                      planes, x.ld, p.plane_stride,                // skinny operand
-                      out.p, out.ld, p.out_cols,                   // output
-                      slab, p.slab_stride, scale_dev, (const float*)zero_page_,
-                      p.tiles_total, p.tiles_per_split, p.nsplit, run_if_, p.vec_store, gemm_debug_flags_};
-    const GemmLaunch& L = p.launch[0];
-    with_nt<kMaxColTiles>(L.nt, [&](auto nt) {
-      with_nt<3, 2>(p.np, [&](auto np_c) {
-        constexpr int NT = decltype(nt)::value, NP = decltype(np_c)::value;
-        const dim3 grid(L.grid[0], L.grid[1], L.grid[2]), block(p.block);
-        if (tn)
-          hipLaunchKernelGGL((k::gemm_bf16s_kernel<NT, NP, true>), grid, block, L.lds, stream, a);
-        else
-          hipLaunchKernelGGL((k::gemm_bf16s_kernel<NT, NP, false>), grid, block, L.lds, stream, a);
-      });
-    });
-    CORRLA_HIP(hipGetLastError());
-    slab_reduce<float>(p.reduce, slab, p.slab_stride, out.p, out.ld, scale_dev, run_if_);
-  }
+  void gemm_mixed(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev, int np);
 
   // ---- dense bf16 input (bf16in_kernels.hpp): R stored in bfloat16, f32 skinny operands, f32 accumulate ---------------
   static constexpr bool kHasBf16In = true;  // driver.hpp: dev_has_bf16in
-  // both products of a call with this operand and an l-column sketch are in the kernel's domain (gemm_bf16a_domain):
+  // both products of a call with this operand and an l-column sketch are in the kernel's domain (gemm_bf16a_call_domain):
   // asked ONCE per call by the entry layer, which widens the matrix otherwise
-  bool bf16a_fits(const Big<uint16_t>& r, int64_t l) const {
-    for (int tn = 0; tn < 2; ++tn) {
-      const int64_t xr = tn ? r.rows : r.cols, outr = tn ? r.cols : r.rows;
-      GemmShape s;
-      s.tn = tn != 0;
-      s.r = {r.rows, r.cols, r.ld, r.cols_readable, 0, false, (uintptr_t)r.p % 16 == 0};
-      s.x = {xr, l, round_up(std::max<int64_t>(xr, 1), kLdPad), 0, col_blocking(l).cols_alloc, false, true};
-      s.out = {outr, l, round_up(std::max<int64_t>(outr, 1), kLdPad), 0, col_blocking(l).cols_alloc, false, true};
-      s.r_bf16 = true;
-      s.num_cus = num_cus;
-      if (!gemm_bf16a_domain(s)) return false;
-    }
-    return true;
-  }
+  bool bf16a_fits(const Big<uint16_t>& r, int64_t l) const;
   // out = scale * op(R) * X on gemm_bf16a_kernel; a product outside its domain is an error (no fallback here)
-  void gemm_bf16a(bool tn, const Big<uint16_t>& r, const Skinny<float>& x, Skinny<float>& out, const float* scale_dev) {
-    if (x.rows != (tn ? r.rows : r.cols)) throw Error(ST_EINVAL, "gemm_bf16a: inner dimensions differ");
-    Big<float> shape_only;  // the plan reads sizes and alignment, never the element type
-    shape_only.p = (const float*)(const void*)r.p;
-    shape_only.rows = r.rows, shape_only.cols = r.cols, shape_only.ld = r.ld, shape_only.cols_readable = r.cols_readable;
-    GemmShape s = gemm_shape(tn, shape_only, x, out, 0);
-    s.r_bf16 = true;
-    const GemmPlan p = gemm_plan(s, gemm_knobs_);
-    if (p.error) throw Error(ST_EINVAL, p.error);
-    // the skinny operand in three bf16 planes, reduction index in memory order
-    __bf16* planes = (__bf16*)alloc_bytes(p.plane_bytes);
-    hipLaunchKernelGGL((k::split_planes_kernel<k::kBaPlanes, false>), dim3(p.split_grid), dim3(256), 0, stream, (const float*)x.p, x.ld,
-                       p.plane_cols, planes, p.plane_stride, run_if_);
-    CORRLA_HIP(hipGetLastError());
-    float* slab = p.reduce.kind != SlabReduce::none ? (float*)alloc_bytes(p.slab_bytes) : nullptr;
-    const k::BaArgs a{r.p, r.rows, r.cols, r.ld, r.cols_readable,  // big operand
-                      planes, x.ld, p.plane_stride,                // skinny operand
-                      out.p, out.ld, p.out_cols,                   // output
-                      slab, p.slab_stride, scale_dev, (const float*)zero_page_,
-                      p.tiles_total, p.tiles_per_split, p.nsplit, run_if_, p.vec_store, 0};
-    const GemmLaunch& L = p.launch[0];
-    with_nt<kMaxColTiles>(L.nt, [&](auto nt) {
-      constexpr int NT = decltype(nt)::value;
-      const dim3 grid(L.grid[0], L.grid[1], L.grid[2]), block(p.block);
-      if (tn)
-        hipLaunchKernelGGL((k::gemm_bf16a_kernel<NT, true>), grid, block, L.lds, stream, a);
-      else
-        hipLaunchKernelGGL((k::gemm_bf16a_kernel<NT, false>), grid, block, L.lds, stream, a);
-    });
-    CORRLA_HIP(hipGetLastError());
-    slab_reduce<float>(p.reduce, slab, p.slab_stride, out.p, out.ld, scale_dev, run_if_);
-  }
+  void gemm_bf16a(bool tn, const Big<uint16_t>& r, const Skinny<float>& x, Skinny<float>& out, const float* scale_dev);
   // strided bf16 view -> zero-padded row-major f32 (dst already cleared): the widened route of the entry layer
   void widen_bf16(const uint16_t* src, int64_t rows, int64_t cols, int64_t rs, int64_t cs, float* dst, int64_t ldd) {
     const int64_t tiles_c = (cols + 31) / 32, tiles_r = (rows + 31) / 32;
@@ -562,55 +401,11 @@ class HipDev {
     CORRLA_HIP(hipGetLastError());
   }
 
-  // ---- one-sweep Z' = A^T (A Z) (ata_kernels.hpp): row-major f32 A with n <= 512, l <= 80 -----------
+  // ---- one-sweep Z' = A^T (A Z) (ata_kernels.hpp): row-major f32 A with n <= 512, l <= 80 (ata_plan) -----
   template <class T>
-  bool ata_fused_fits(const Big<T>& a, int64_t l) const {
-    return std::is_same<T, float>::value && a.cols <= 512 && a.cols >= 16 && l <= 80 && a.rows >= 4096;
-  }
+  bool ata_fused_fits(const Big<T>& a, int64_t l) const;
   template <class T>
-  void ata_fused(const Big<T>& a, const Skinny<T>& x, Skinny<T>& z) {
-    if constexpr (!std::is_same<T, float>::value) {
-      throw Error(ST_EINVAL, "internal: the one-sweep power iteration is f32 only");
-    } else {
-      if (x.rows != a.cols || z.rows != a.cols) throw Error(ST_EINVAL, "ata_fused: shapes");
-      const ColBlocking cb = col_blocking(x.cols);
-      if (cb.cols_alloc > x.cols_alloc || cb.cols_alloc > z.cols_alloc || x.ld != z.ld || cb.cols_alloc > 80)
-        throw Error(ST_EINVAL, "internal: ata_fused operands must share the padded layout (<= 80 columns)");
-      if (((uintptr_t)a.p % 16) || (a.ld % 4) || (a.cols_readable % 4)) throw Error(ST_EINVAL, "internal: operand not vector aligned");
-      // reduction segments: n padded to 128 / 256 / 512 (three instantiation families)
-      const int nk = a.cols <= 128 ? 2 : (a.cols <= 256 ? 4 : 8);
-      const int nct = (int)(cb.cols_alloc / 16);
-      // one workgroup per CU; every workgroup gets at least a few tiles
-      const int64_t blocks = (a.rows + k::kAtaRows - 1) / k::kAtaRows;
-      const int nrg = (int)std::max<int64_t>(1, std::min<int64_t>(num_cus, blocks / 8));
-      const int64_t rows_per_group = ((blocks + nrg - 1) / nrg) * k::kAtaRows;
-      k::AtaArgs g;
-      g.a = a.p;
-      g.m = a.rows;
-      g.n = a.cols;
-      g.lda = a.ld;
-      g.n_readable = a.cols_readable;
-      g.z = x.p;
-      g.z_ld = x.ld;
-      g.out_ld = z.ld;
-      g.slab_stride = (int64_t)z.ld * cb.cols_alloc;
-      g.slab = (float*)alloc_zeroed((size_t)nrg * (size_t)g.slab_stride * sizeof(float));  // empty groups contribute zeros
-      g.rows_per_group = rows_per_group;
-      g.nrowgroups = nrg;
-      g.zero = (const float*)zero_page_;
-      with_nt<8, 2>(nk, [&](auto nk_c) {  // nk is 2, 4 or 8
-        with_nt<5>(nct, [&](auto nct_c) {
-          constexpr int NK = decltype(nk_c)::value, NCT = decltype(nct_c)::value;
-          if constexpr (NK == 2 || NK == 4 || NK == 8)
-            hipLaunchKernelGGL((k::ata_fused_kernel<NK, NCT>), dim3((unsigned)nrg), dim3(256), k::ata_lds_bytes(NK, NCT), stream, g);
-        });
-      });
-      CORRLA_HIP(hipGetLastError());
-      const SlabReducePlan rp{SlabReduce::deep, {(unsigned)((a.cols + 63) / 64), (unsigned)cb.cols_alloc}, nrg, a.cols, cb.cols_alloc};
-      check_grid(dim3(rp.grid[0], rp.grid[1]));
-      slab_reduce<float>(rp, g.slab, g.slab_stride, z.p, z.ld, nullptr, nullptr);
-    }
-  }
+  void ata_fused(const Big<T>& a, const Skinny<T>& x, Skinny<T>& z);
 
   // ---- collectives (RCCL over xGMI, on the compute stream) ---------------------------------
   template <class T>
@@ -1396,14 +1191,7 @@ class HipDev {
     set_lds_limits_typed<double>();
     core_svd_stage::set_lds_limits<float>();
     core_svd_stage::set_lds_limits<double>();
-    set_ata_limits<2>();
-    set_ata_limits<4>();
-    set_ata_limits<8>();
-    set_mixed_limits<2, false>();
-    set_mixed_limits<2, true>();
-    set_mixed_limits<3, false>();
-    set_mixed_limits<3, true>();
-    set_bf16a_limits();
+    tall_stage::set_lds_limits();
     // nearest neighbours and local fits of the gradient stage (grad_stage.hpp)
     lds_limit((const void*)k::knn_kernel, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);
@@ -1426,10 +1214,7 @@ class HipDev {
   template <class T>
   static void set_lds_limits_typed() {
     constexpr size_t kMax = k::kLdsMaxBytes;
-    for_each_nt<kMaxColTiles>([](auto nt) { set_gemm_limits<T, decltype(nt)::value>(); });
-    for_each_nt<sizeof(T) == 4 ? 6 : 4>([](auto nct) {
-      lds_limit((const void*)k::tall_gram_kernel<T, decltype(nct)::value>, k::gram_lds_bytes(nct, (int)sizeof(T)));
-    });
+    tall_stage::set_lds_limits<T>();
     lds_limit((const void*)k::syrk_kernel<T, true>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::syrk_kernel<T, false>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::hh_leaf_factor_kernel<T, false>, kMax);
@@ -1441,127 +1226,12 @@ class HipDev {
     lds_limit((const void*)k::hh_tree_apply_kernel<T, true>, kMax);
     lds_limit((const void*)k::hh_leaf_apply_kernel<T, true>, kMax);
   }
-  template <class T, int NT>
-  static void set_gemm_limits() {
-    lds_limit((const void*)k::gemm_nn_kernel<T, 1, NT>, k::gemm_lds_bytes(1, NT));
-    lds_limit((const void*)k::gemm_tn_kernel<T, 1, NT>, k::gemm_lds_bytes(1, NT));
-    lds_limit((const void*)k::gemm_nn_kernel<T, 2, NT>, k::gemm_lds_bytes(2, NT));
-    lds_limit((const void*)k::gemm_tn_kernel<T, 2, NT>, k::gemm_lds_bytes(2, NT));
-    if constexpr (NT <= 8) lds_limit((const void*)k::gemm_nn_kernel<T, 2, NT, true>, 3 * k::big_tile_bytes(2));
-    if constexpr (std::is_same<T, double>::value) {  // two MFMA waves per SIMD on the MW = 2 tile (launch_general)
-      lds_limit((const void*)k::gemm_nn_kernel<T, 1, NT, false, 8>, k::gemm_lds_bytes(2, NT));
-      lds_limit((const void*)k::gemm_tn_kernel<T, 1, NT, 8>, k::gemm_lds_bytes(2, NT));
-    }
-  }
-  template <int NK>
-  static void set_ata_limits() {
-    for_each_nt<5>([](auto nct) { lds_limit((const void*)k::ata_fused_kernel<NK, decltype(nct)::value>, k::ata_lds_bytes(NK, nct)); });
-  }
-  template <int NP, bool TN>
-  static void set_mixed_limits() {
-    for_each_nt<kMaxColTiles>([](auto nt) {
-      lds_limit((const void*)k::gemm_bf16s_kernel<decltype(nt)::value, NP, TN>, k::mx_lds_bytes(nt, NP));
-    });
-  }
-  static void set_bf16a_limits() {
-    for_each_nt<kMaxColTiles>([](auto nt) {
-      lds_limit((const void*)k::gemm_bf16a_kernel<decltype(nt)::value, false>, k::ba_lds_bytes(nt));
-      lds_limit((const void*)k::gemm_bf16a_kernel<decltype(nt)::value, true>, k::ba_lds_bytes(nt));
-    });
-  }
-  // ---- launchers of the tall products (gemm_plan.hpp) ----
-  template <class T>
-  GemmShape gemm_shape(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out, int np) const {
-    auto aligned = [](const void* p) { return (uintptr_t)p % 16 == 0; };
-    GemmShape s;
-    s.tn = tn;
-    s.esz = (int)sizeof(T);
-    s.r = {r.rows, r.cols, r.ld, r.cols_readable, 0, false, aligned(r.p)};
-    s.x = {x.rows, x.cols, x.ld, 0, x.cols_alloc, x.external, aligned(x.p)};
-    s.out = {out.rows, out.cols, out.ld, 0, out.cols_alloc, out.external, aligned(out.p)};
-    s.same = (const void*)r.p == (const void*)x.p;
-    s.np = np;
-    s.num_cus = num_cus;
-    return s;
-  }
-  template <class T>
-  GemmPlan plan_gemm(bool tn, const Big<T>& r, const Skinny<T>& x, const Skinny<T>& out, int np) const {
-    const GemmPlan p = gemm_plan(gemm_shape(tn, r, x, out, np), gemm_knobs_);
-    if (p.error) throw Error(ST_EINVAL, p.error);
-    return p;
-  }
-  // sum of the partial results of a split reduction (slab_reduce_kernel / slab_reduce_deep_kernel)
-  template <class T>
-  void slab_reduce(const SlabReducePlan& rp, const T* slab, int64_t stride, T* out, int64_t ld, const T* scale, const int* run_if) {
-    if (rp.kind == SlabReduce::none) return;
-    const dim3 grid(rp.grid[0], rp.grid[1]);
-    if (rp.kind == SlabReduce::deep)
-      hipLaunchKernelGGL((k::slab_reduce_deep_kernel<T>), grid, dim3(256), 0, stream, slab, stride, rp.slabs, out, ld, rp.rows,
-                         rp.cols, scale, run_if);
-    else
-      hipLaunchKernelGGL((k::slab_reduce_kernel<T>), grid, dim3(256), 0, stream, slab, stride, rp.slabs, out, ld, rp.rows, rp.cols,
-                         scale, run_if);
-    CORRLA_HIP(hipGetLastError());
-  }
-
-  // gemm_nn_kernel / gemm_tn_kernel<T, MW, NT, NW> with the plan's MW and NW (NW = 8: the f64 MW = 2 tile on eight waves)
-  template <class T, int NT>
-  void launch_general(bool tn, const GemmPlan& p, dim3 grid, dim3 block, int lds, const k::GemmArgs<T>& a) {
-    with_nt<2>(p.mw, [&](auto mw) {
-      with_nt<8, 4>(p.nw, [&](auto nw) {
-        constexpr int MW = decltype(mw)::value, NW = decltype(nw)::value;
-        if constexpr (NW == 4 || (NW == 8 && MW == 1 && std::is_same<T, double>::value)) {
-          if (tn)
-            hipLaunchKernelGGL((k::gemm_tn_kernel<T, MW, NT, NW>), grid, block, lds, stream, a);
-          else
-            hipLaunchKernelGGL((k::gemm_nn_kernel<T, MW, NT, false, NW>), grid, block, lds, stream, a);
-        }
-      });
-    });
-  }
-
+  // ---- the tall products' launch (tall_stage.hpp) ----
+  // what a launcher of the stage needs of this context beyond the plan
+  tall_stage::Call tall_call();
   // out (outer_n x L) = scale * op(R) * X: op(R) = R (tn false, outer_n = R's rows) or R^T (outer_n = R's columns)
   template <class T>
-  void launch_gemm(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev) {
-    const GemmPlan p = plan_gemm(tn, r, x, out, 0);
-    const GemmLaunch& L0 = p.launch[0];
-    T* slab = p.reduce.kind != SlabReduce::none ? (T*)alloc_bytes(p.slab_bytes) : nullptr;
-    if (p.family == GemmFamily::tall_apply) {  // tall_kernels.hpp: out (m x n2) = Y M with Y^T stored row-major kdim x m
-      const k::TallApplyArgs<T> g{r.p, r.cols, r.ld, (int)r.rows, x.p, x.ld, (int)x.cols, out.p, out.ld, (int)p.out_cols,
-                                  scale_dev, p.vec_store, run_if_};
-      with_nt<sizeof(T) == 4 ? 6 : 4>(L0.nt, [&](auto kt) {
-        constexpr int K = decltype(kt)::value;
-        hipLaunchKernelGGL((k::tall_apply_kernel<T, K, K>), dim3(L0.grid[0]), dim3(p.block), L0.lds, stream, g);
-      });
-    } else if (p.family == GemmFamily::tall_gram) {  // G (l x l) = Y^T Y: both operands are the same m x l memory
-      const k::TallGramArgs<T> g{x.p, r.cols, x.ld, (int)out.rows, slab, p.slab_stride, out.ld, p.rows_per_group,
-                                 (const T*)zero_page_, run_if_};
-      with_nt<sizeof(T) == 4 ? 6 : 4>(L0.nt, [&](auto nct) {
-        hipLaunchKernelGGL((k::tall_gram_kernel<T, decltype(nct)::value>), dim3(L0.grid[0]), dim3(p.block), L0.lds, stream, g);
-      });
-    } else {
-      k::GemmArgs<T> a{r.p, r.rows, r.cols, r.ld, r.cols_readable,  // big operand
-                       x.p, x.ld,                                     // skinny operand
-                       out.p, out.ld, p.out_cols, 0,                  // output; col_base per launch
-                       slab, p.slab_stride, scale_dev, (const T*)zero_page_,
-                       p.tiles_total, p.tiles_per_split, p.nsplit, gemm_debug_flags_, run_if_,
-                       p.vec_store, p.rotate, p.outer_blocks, 0};     // xcd_remap per launch
-      for (int i = 0; i < p.nlaunch; ++i) {
-        const GemmLaunch& L = p.launch[i];
-        const dim3 grid(L.grid[0], L.grid[1], L.grid[2]), block(p.block);
-        a.col_base = L.col_base;
-        a.xcd_remap = L.xcd_remap;
-        if (p.family == GemmFamily::gram_alias)
-          with_nt<8>(L.nt, [&](auto nt) {
-            hipLaunchKernelGGL((k::gemm_nn_kernel<T, 2, decltype(nt)::value, true>), grid, block, L.lds, stream, a);
-          });
-        else
-          with_nt<kMaxColTiles>(L.nt, [&](auto nt) { launch_general<T, decltype(nt)::value>(tn, p, grid, block, L.lds, a); });
-      }
-    }
-    CORRLA_HIP(hipGetLastError());
-    slab_reduce<T>(p.reduce, slab, p.slab_stride, out.p, out.ld, scale_dev, run_if_);
-  }
+  void launch_gemm(bool tn, const Big<T>& r, const Skinny<T>& x, Skinny<T>& out, const T* scale_dev);
 
   template <class T>
   void launch_copy_out(const T* src, int64_t lds_, int64_t rows, int64_t cols, T* dst, int64_t ldd, bool transpose) {

@@ -20,7 +20,7 @@
 //   * Only rows [0, rows) x columns [0, L) of Y are written: the zero padding of a Skinny stays zero and nothing is
 //     written past the columns of an external destination.
 //   * Unsorted and duplicate column indices are legal (duplicates add).  No index is dereferenced before
-//     csr_validate_kernel has checked it (hip_backend.hpp: csr_plan runs first and ends the call on a violation).
+//     csr_validate_kernel has checked it (tall_stage.hpp: csr_plan runs first and ends the call on a violation).
 //
 // Transposition: a stable LSD radix sort (8-bit digits) of the nonzero positions keyed by column index; stability keeps
 // the entries of a column ordered by original row, then original position, which fixes the summation order of A^T Y.
@@ -29,11 +29,12 @@
 
 #include <cstdint>
 
+#include "gemm_plan.hpp"  // kSpTile (rows and sketch columns of one output tile), with the plan of the launches (spmm_plan)
+
 namespace corrla {
 namespace k {
 
 constexpr int kSpLong = 2048;      // a row with more nonzeros is split into chunks of this many
-constexpr int kSpTile = 64;        // rows and sketch columns of one output tile
 constexpr int kSortTile = 4096;    // keys per (single-wave) workgroup of the radix sort
 
 // written by csr_validate_kernel, read back by the host before anything is gathered

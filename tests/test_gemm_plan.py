@@ -9,8 +9,9 @@ grouping and the bf16 planes, or the rejection.  (The retired exact variant of t
 CORRLA_GEMM_WIDE, was off by default and is not part of the table.)
 
 ROUTES / GRAM_ROUTES at the end are the calls of tests/test_gpu_gemm_routes.py, which multiplies each against a reference on
-the GPU: one Context.matmul (or, for the aliased Gram kernels, one power_iter) per instantiation launch_gemm can dispatch and
-per feature of a launch.  Pinned here: every row's plan has the properties the row names, all 90 general and 16 aliased
+the GPU: one Context.matmul (or, for the aliased Gram kernels, one power_iter) per instantiation launch_gemm (tall_stage.hpp)
+can dispatch and per feature of a launch.  PLANE_ROUTES / ATA_ROUTES next to them are the calls of
+tests/test_gpu_tall_routes.py for the bf16-split, bf16-stored and one-sweep kernels; tests/test_tall_stage_plan.py pins them.  Pinned here: every row's plan has the properties the row names, all 90 general and 16 aliased
 instantiations and every feature of FEATURES occur, the knob names are the ones a context reads, and the integer operands
 of the exact check tell neighbouring tiles and columns apart."""
 import itertools
@@ -322,7 +323,7 @@ def plan(tmp_path_factory):
     return run
 
 
-# ---- operands as the backend builds them (hip_backend.hpp: alloc_skinny, driver.hpp: as_rowmajor_transposed) ----
+# ---- operands as the backend builds them (gemm_plan.hpp: skinny_layout, driver.hpp: as_rowmajor_transposed) ----
 def skinny(rows, cols, external=False, aligned=True, ld=None):
     return dict(rows=rows, cols=cols, ld=ld if ld is not None else round_up(max(rows, 1), 64),
                 cols_alloc=cols if external else col_blocking(cols)[3], external=external, aligned=aligned)
@@ -603,6 +604,26 @@ GRAM_ROUTES = [("gram-f%d-nt%d-%s" % (8 * esz, nt, "general" if knobs else "alia
                 dict(family="general", mw=1, nw=4, nt=(nt,)) if knobs else dict(family="gram_alias", mw=2, nw=4, nt=(nt,)))
                for esz in (4, 8) for nt in range(1, 9) for knobs in ({}, {"CORRLA_NO_GRAM_ALIAS": 1})]
 
+# (name, family, m, n, l, trans, np, knobs, expect): Context.matmul(a, x, trans) on a row-major m x n matrix -- f32 under
+# CORRLA_SKETCH_MIXED=bf16x3 / bf16x6 (np 2 / 3) for the bf16 split, a bfloat16 tensor for the bf16-stored kernel -- x with
+# l = 16 NT - 3 columns.  300 x 72: outer and reduction tails in both orientations, and a row of 72 elements is whole 16-byte
+# vectors in either type, so both kernels read the matrix in place.
+PLANE_M, PLANE_N = 300, 72
+PLANE_MODES = {2: "bf16x3", 3: "bf16x6"}
+PLANE_ROUTES = (
+    [("split-np%d-%s-nt%d" % (np_, "tn" if trans else "nn", nt), "bf16_split", PLANE_M, PLANE_N, 16 * nt - 3, trans, np_,
+      {"CORRLA_MIXED_MIN_WORK": 1}, dict(family="bf16_split", nt=nt, np=np_, tn=trans))
+     for np_ in (2, 3) for trans in (False, True) for nt in range(1, 10)] +
+    [("stored-%s-nt%d" % ("tn" if trans else "nn", nt), "bf16_stored", PLANE_M, PLANE_N, 16 * nt - 3, trans, 0, {},
+      dict(family="bf16_stored", nt=nt, np=3, tn=trans))
+     for trans in (False, True) for nt in range(1, 10)])
+
+# (name, m, n, k, p, q, expect): rsvd(a, k, q, p, fused=True) on a row-major f32 m x n matrix; the sketch has l = k + p =
+# 16 NCT - 3 columns and the one-sweep kernel runs on ata_fused_kernel<NK, NCT>, NK by n: 2 (<= 128), 4 (<= 256), 8
+ATA_M = 4100
+ATA_ROUTES = [("ata-nk%d-nct%d" % (nk, nct), ATA_M, n, 16 * nct - 3 - 5, 5, 1, dict(nk=nk, nct=nct))
+              for nk, n in ((2, 100), (4, 200), (8, 300)) for nct in range(1, 6)]
+
 # what the table must reach besides every instantiation, in the element types named
 FEATURES = {
     "3-stage ring of the 128-index tile": ((4, 8), lambda row, r: r["mw"] * r["nw"] == 8 and 3 in r["stages"]),
@@ -669,10 +690,11 @@ def test_every_route_reaches_what_it_names(plan):
 
 
 def test_the_route_table_is_complete(plan):
-    """every instantiation launch_general and the alias launch can dispatch (hip_backend.hpp), every feature in FEATURES"""
+    """every instantiation the `general` launcher can dispatch, alias included (tall_stage.hpp), every feature in FEATURES"""
     plans = _route_plans(plan)
     seen = {(row[1], bool(row[5]), r["mw"], r["nw"], nt) for row, r in zip(ROUTES, plans) for nt in r["nt"]}
-    # launch_general: if constexpr (NW == 4 || (NW == 8 && MW == 1 && T is double)), NT 1 .. kMaxColTiles, nn and tn
+    # gemm_general_exists (gemm_plan.hpp): NW == 4 || (NW == 8 && MW == 1 && T is double), NT 1 .. kMaxColTiles, nn and tn;
+    # tests/test_tall_stage_plan.py counts the same 90 from the predicate itself
     want = {(esz, tn, mw, nw, nt) for esz in (4, 8) for tn in (False, True) for mw in (1, 2) for nw in (4, 8)
             if nw == 4 or (nw == 8 and mw == 1 and esz == 8) for nt in range(1, 10)}
     assert len(want) == 90

@@ -1,5 +1,6 @@
 """GPU tests of dense bfloat16 input (csrc/bf16in_kernels.hpp, corrla_*_bf16): the product kernel bit for bit on small
-integers for every column-tile count and both orientations, its accuracy against f64, and random_svd / PCA on a bf16
+integers in both orientations on shapes with row and reduction tails (the one-row-per-instantiation check of
+gemm_bf16a_kernel<NT, TN> is tests/test_gpu_tall_routes.py), its accuracy against f64, and random_svd / PCA on a bf16
 tensor against the f32 oracle on the SAME values (the tensor's .float() widening) with the gates of the exact f32 path.
 Run with -m gpu.
 
@@ -39,9 +40,10 @@ def _bf16(a32):
 # ---- the product kernel ------------------------------------------------------------------------------------------------
 # (rows of A, columns of A, columns of the skinny operand).  First the list of tests/test_gpu_mixed.py; a bf16 row must be a
 # multiple of 8 elements (16 bytes) long to be read in place, so those of its shapes with n % 8 != 0 go the widened way --
-# each is followed here by a twin with n rounded up to 8, so that every column-tile count 1..9 and the row / reduction
-# tails run on the kernel as well (plus NT = 5, which that list lacks); the last shape is the odd row length the widened
-# route is asserted on.
+# each is followed here by a twin with n rounded up to 8, so that the column-tile counts of that list (1 .. 4, 6 .. 9) and
+# the row / reduction tails run on the kernel as well, and (520, 136, 70) adds NT = 5 in the nn and the tn orientation
+# (tests/test_gpu_tall_routes.py has one row per instantiation); the last shape is the odd row length the widened route is
+# asserted on.
 _SHAPES = [(256, 32, 16), (300, 70, 5), (1000, 600, 138), (257, 33, 144), (513, 1030, 17), (2048, 96, 40), (700, 257, 49),
            (64, 4100, 64), (4100, 64, 81), (1500, 520, 100), (1024, 1024, 113), (33, 8, 128),
            (300, 72, 5), (257, 40, 144), (513, 1032, 17), (700, 264, 49), (64, 4104, 64), (520, 136, 70),

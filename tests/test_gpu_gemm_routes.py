@@ -1,4 +1,4 @@
-"""GPU test of the tall products' dispatch (gemm_plan.hpp, launch_gemm in hip_backend.hpp; run with -m gpu on an MI355X): one
+"""GPU test of the tall products' dispatch (gemm_plan.hpp, launch_gemm in tall_stage.hpp; run with -m gpu on an MI355X): one
 small Context.matmul per instantiation and per feature of the plan -- every gemm_nn_kernel / gemm_tn_kernel<T, MW, NT, NW>,
 both ring depths of the wide tile, the uneven two-launch column blocking, persistent launches, both slab reductions, empty
 slabs, the XCD remap, rotation and its absence -- on integer operands whose product is exact in either element type, and on

@@ -1,5 +1,6 @@
 """GPU tests of the bf16-split tall products (csrc/mixed_kernels.hpp; off by default): exact-integer layout
-checks of both kernels for every column-tile count and both piece counts, accuracy against f64 on Gaussian data, and the
+checks of both kernels and both piece counts on shapes with row and reduction tails (column-tile counts 1 .. 4 and 6 .. 9;
+tests/test_gpu_tall_routes.py launches every instantiation, NT = 5 included), accuracy against f64 on Gaussian data, and the
 whole random_svd with the option on against the oracle with the SAME gates as the exact-f32 path.  Run with -m gpu."""
 import os
 
@@ -47,7 +48,8 @@ def _matmul(ctx, torch, a, x, trans, mode, monkeypatch):
     return res.cpu().numpy()
 
 
-# (rows of A, columns of A, columns of the skinny operand): every column-tile count 1..9, row / reduction tails
+# (rows of A, columns of A, columns of the skinny operand): column-tile counts 1 .. 4 and 6 .. 9 (no l in 65 .. 80: NT = 5 is
+# launched by tests/test_gpu_tall_routes.py, which has one row per instantiation), row / reduction tails
 _SHAPES = [(256, 32, 16), (300, 70, 5), (1000, 600, 138), (257, 33, 144), (513, 1030, 17), (2048, 96, 40), (700, 257, 49),
            (64, 4100, 64), (4100, 64, 81), (1500, 520, 100), (1024, 1024, 113), (33, 8, 128)]
 
