@@ -94,7 +94,11 @@ def _sigs():
         s["corrla_pca_transform_csr_" + suf] = s["corrla_pca_transform_csr_dev_" + suf] = (C.c_int, [vp, vp, vp, vp, i64, i64, i64] + model)
         inverse = [vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64]
         s["corrla_pca_inverse_" + suf] = s["corrla_pca_inverse_dev_" + suf] = (C.c_int, inverse)
-        s["corrla_fill_normal_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
+        # RBF kernel matrices: xq, n_q, ldq, xs, n_s, lds, dim, kernel, eps [, poly_degree, coeffs, ldw, n_rhs], out, ld_out
+        points = [vp, vp, i64, i64, vp, i64, i64, i64, C.c_int, dbl]
+        s["corrla_rbf_matrix_" + suf] = s["corrla_rbf_matrix_dev_" + suf] = (C.c_int, points + [vp, i64])
+        s["corrla_rbf_apply_" + suf] = s["corrla_rbf_apply_dev_" + suf] = (C.c_int, points + [C.c_int, vp, i64, i64, vp, i64])
+        s["corrla_fill_normal_dev_" + suf] =(C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])
     # dense bf16 input: A is uint16 bit patterns, every other array f32; argument lists of the f32 twins

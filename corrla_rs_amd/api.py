@@ -668,6 +668,111 @@ class Context:
         """The centring of the last ``pca_transform`` call: "fused", "copy", or None (no centring, or no such call yet)."""
         return getattr(self, "_pca_apply_centring", None)
 
+    # ---- radial-basis-function kernel matrices (interp_utils.rs:96-129, 146-153) -------------------
+    @staticmethod
+    def _rbf_kernel_id(kernel_type):
+        """``PyRbfInterp::new``: 1 linear, 2 multiquadric, 3 cubic, anything else Gaussian (4)."""
+        k = int(kernel_type)
+        return k if k in (1, 2, 3) else 4
+
+    def _rbf_points(self, x_query, x_support, what):
+        """-> (queries, supports, on_device): both row-major with unit stride along the coordinates, the supports in the
+        kind, dtype and device of the queries."""
+        for v in (x_query, x_support):
+            _reject_bf16(v, what)
+            if _is_sparse(v):
+                raise ValueError(f"{what} takes dense points")
+        xq, on_dev = _as_dense(x_query, "x_query")
+        if on_dev:
+            self._on_my_device(xq)
+        xs = self._model_array(x_support, xq, on_dev)
+        if xs.ndim != 2:
+            raise ValueError("x_support must be 2-D")
+        if xq.shape[0] == 0 or xs.shape[0] == 0 or xq.shape[1] == 0:
+            raise ValueError("x_query and x_support must be non-empty")
+        if xs.shape[1] != xq.shape[1]:
+            raise ValueError(f"x_query has {xq.shape[1]} coordinates, x_support {xs.shape[1]}")
+        return self._rbf_rowmajor(xq, on_dev), self._rbf_rowmajor(xs, on_dev), on_dev
+
+    @staticmethod
+    def _rbf_rowmajor(a, on_device):
+        """`a` as the entries read it: unit stride along the columns, rows that do not overlap; a view with a padded row
+        stride stays the view it is."""
+        rs, cs = _strides(a)
+        if (cs != 1 and a.shape[1] > 1) or (rs < a.shape[1] and a.shape[0] > 1):
+            return a.contiguous() if on_device else np.ascontiguousarray(a)
+        return a
+
+    @staticmethod
+    def _row_stride(a):
+        """the row stride of what _rbf_rowmajor returned (a single row has none: its length serves)"""
+        return int(_strides(a)[0]) if a.shape[0] > 1 else int(a.shape[1])
+
+    def rbf_matrix(self, x_query, x_support, kernel_type, kernel_param=0.0):
+        """The kernel matrix Phi[i, j] = phi(||x_query_i - x_support_j||_2), (n_q, n_s) row-major, on the device
+        (corrla_rbf_matrix_*): 1 linear r, 2 multiquadric sqrt(1 + (eps r)^2), 3 cubic r^3, anything else the Gaussian
+        exp(-(eps r)^2), eps = kernel_param -- the ids of ``PyRbfInterp``.  Distances are the direct sum of squared
+        differences, so ``rbf_matrix(x, x)`` equals its transpose bitwise and has the exact diagonal phi(0).  dim <= 128.
+        numpy in -> numpy out, a CUDA tensor as x_query -> a tensor on its device; float32 stays float32, anything else
+        becomes float64; bfloat16 and sparse inputs raise ValueError."""
+        xq, xs, on_dev = self._rbf_points(x_query, x_support, "rbf_matrix")
+        n_q, dim = (int(v) for v in xq.shape)
+        n_s = int(xs.shape[0])
+        if on_dev:
+            import torch
+            out = torch.empty((n_q, n_s), dtype=xq.dtype, device=xq.device)
+            _sync_stream(xq)
+        else:
+            out = np.empty((n_q, n_s), dtype=xq.dtype)
+        L.check(self._entry("corrla_rbf_matrix_", on_dev, xq.dtype)(self._h, _ptr(xq), n_q, self._row_stride(xq), _ptr(xs), n_s,
+                                                                   self._row_stride(xs), dim, self._rbf_kernel_id(kernel_type),
+                                                                   float(kernel_param), _ptr(out), n_s))
+        if on_dev:  # the device entry only enqueues: torch's streams see the results after this
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        return out
+
+    def rbf_apply(self, x_query, x_support, coeffs, kernel_type, kernel_param=0.0, *, poly_degree=None):
+        """Phi(x_query, x_support) @ W_rbf + P(x_query) @ W_poly, (n_q, n_rhs) row-major, on the device (corrla_rbf_apply_*)
+        without ever storing the (n_q, n_s) kernel matrix: what ``RbfInterp.predict`` computes (interp_utils.rs:146-153).
+        `coeffs` is (n_s + n_poly, n_rhs) as ``RbfInterp.fit`` lays it out: the first n_s rows weight the kernel columns,
+        the rest the polynomial tail [x, 1] (poly_degree 0 or 1: dim + 1 rows) or [x, x_a x_b (a <= b), 1] (poly_degree >= 2:
+        dim + dim (dim + 1) / 2 + 1 rows); poly_degree=None: no tail, n_s rows.  Kernel ids and kernel_param as for
+        ``rbf_matrix``.  x_support and coeffs are converted to the kind, dtype and device of x_query.  numpy in -> numpy out,
+        a CUDA tensor as x_query -> a tensor on its device; float32 stays float32, anything else becomes float64; bfloat16
+        and sparse inputs raise ValueError."""
+        xq, xs, on_dev = self._rbf_points(x_query, x_support, "rbf_apply")
+        n_q, dim = (int(v) for v in xq.shape)
+        n_s = int(xs.shape[0])
+        if poly_degree is not None and (isinstance(poly_degree, (bool, np.bool_)) or not isinstance(poly_degree, (int, np.integer))):
+            raise ValueError("poly_degree must be None or an integer")
+        degree = -1 if poly_degree is None or poly_degree < 0 else int(poly_degree)
+        n_poly = 0 if degree < 0 else (dim + 1 if degree < 2 else dim + dim * (dim + 1) // 2 + 1)
+        _reject_bf16(coeffs, "rbf_apply")
+        if _is_sparse(coeffs):
+            raise ValueError("rbf_apply takes dense coefficients")
+        w = self._model_array(coeffs, xq, on_dev)
+        if w.ndim == 1:
+            w = w.reshape(-1, 1)
+        if w.ndim != 2 or w.shape[1] == 0:
+            raise ValueError("coeffs must be a non-empty matrix")
+        if w.shape[0] != n_s + n_poly:
+            raise ValueError(f"coeffs must have n_s + n_poly = {n_s} + {n_poly} rows, got {w.shape[0]}")
+        w = self._rbf_rowmajor(w, on_dev)
+        n_rhs = int(w.shape[1])
+        if on_dev:
+            import torch
+            out = torch.empty((n_q, n_rhs), dtype=xq.dtype, device=xq.device)
+            _sync_stream(xq)
+        else:
+            out = np.empty((n_q, n_rhs), dtype=xq.dtype)
+        L.check(self._entry("corrla_rbf_apply_", on_dev, xq.dtype)(self._h, _ptr(xq), n_q, self._row_stride(xq), _ptr(xs), n_s,
+                                                                  self._row_stride(xs), dim, self._rbf_kernel_id(kernel_type),
+                                                                  float(kernel_param), degree, _ptr(w), self._row_stride(w), n_rhs,
+                                                                  _ptr(out), n_rhs))
+        if on_dev:
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        return out
+
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
         """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that

@@ -22,7 +22,7 @@ import numpy as np
 from .api import _is_torch, default_context, rsvd
 
 __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyGradientEstimator", "ActiveSsRsvd",
-           "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens"]
+           "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply"]
 
 
 def _on_gpu(x):
@@ -330,15 +330,34 @@ def _pinv_reg(m):  # mat_pinv, mat_utils.rs:37-53: every singular value inverted
     return (vt.T * (1.0 / (sv + 1.0e-14))) @ u.T
 
 
+def rbf_matrix(x_query, x_support, kernel_type, kernel_param=0.0, *, ctx=None):
+    """The kernel matrix phi(||x_query_i - x_support_j||), (n_q, n_s), on the device: ``Context.rbf_matrix``."""
+    return (ctx or default_context()).rbf_matrix(x_query, x_support, kernel_type, kernel_param)
+
+
+def rbf_apply(x_query, x_support, coeffs, kernel_type, kernel_param=0.0, *, poly_degree=None, ctx=None):
+    """Phi(x_query, x_support) @ W_rbf + P(x_query) @ W_poly without the (n_q, n_s) matrix: ``Context.rbf_apply``."""
+    return (ctx or default_context()).rbf_apply(x_query, x_support, coeffs, kernel_type, kernel_param, poly_degree=poly_degree)
+
+
 class RbfInterp:
     """Radial-basis-function interpolant with a polynomial tail (interp_utils.rs:11-160; pyo3 ``PyRbfInterp(kernel_type,
     kernel_param, dim, poly_degree)``: 1 linear r, 2 multiquadric sqrt(1 + (eps r)^2), 3 cubic r^3, otherwise Gaussian
-    exp(-(eps r)^2)).  Sized by the number of support points (snapshots), so it stays on the host; ``fit`` accepts several
-    right-hand-side columns at once (PodI fits one interpolant per mode weight over the same support points)."""
+    exp(-(eps r)^2)).  ``fit`` accepts several right-hand-side columns at once (PodI fits one interpolant per mode weight
+    over the same support points).
 
-    def __init__(self, kernel_type, kernel_param, dim, poly_degree):
+    device=False and numpy arguments: the numpy code, sized by the number of support points (snapshots), on the host.
+    device=True, or whenever ``fit`` / ``predict`` is handed a CUDA tensor: the kernel matrix of the fit comes from
+    ``Context.rbf_matrix(x, x)`` and ``predict`` is one ``Context.rbf_apply`` -- the (n_q, n_s) kernel matrix of the
+    queries is never stored, so 10^5 queries against 10^4 supports need no 8 GB temporary.  The solve of the
+    (n_s + n_poly)-sized block system stays on the host in float64: its SVD pseudo-inverse with every singular value
+    inverted as 1 / (s + 1e-14) (``mat_pinv``) is what parity with the reference means.  numpy in -> numpy out, a tensor
+    in -> a tensor out; ``predict`` with a CUDA query on a host-fitted model uploads the small model per call."""
+
+    def __init__(self, kernel_type, kernel_param, dim, poly_degree, *, device=False, ctx=None):
         self.kernel_type, self.eps, self.dim, self.poly_degree = int(kernel_type), float(kernel_param), int(dim), int(poly_degree)
         self.x_known = self.coeffs = None
+        self.device, self._ctx = bool(device), ctx
 
     def _phi(self, r):
         if self.kernel_type == 1:
@@ -353,7 +372,14 @@ class RbfInterp:
         r = np.sqrt(((x[:, None, :] - self.x_known[None, :, :]) ** 2).sum(axis=2))
         return np.hstack([self._phi(r), _poly_block(x, self.poly_degree)])
 
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
     def fit(self, x_in, y_in):
+        if self.device or _on_gpu(x_in) or _on_gpu(y_in):
+            return self._fit_device(x_in, y_in)
         x = np.asarray(x_in, np.float64)
         y = np.asarray(y_in, np.float64).reshape(x.shape[0], -1)
         if x.shape[1] != self.dim:
@@ -364,11 +390,44 @@ class RbfInterp:
         kp = np.vstack([upper, np.hstack([p.T, np.zeros((p.shape[1], p.shape[1]))])])
         self.coeffs = _pinv_reg(kp) @ np.vstack([y, np.zeros((p.shape[1], y.shape[1]))])
 
+    def _fit_device(self, x_in, y_in):
+        """K from the device (float64), the block system [[K, P], [P^T, 0]] and its regularised pseudo-inverse on the host;
+        the model stays where the supports were given: on the device for a CUDA tensor, else on the host."""
+        on_gpu = _on_gpu(x_in)
+        x = x_in.detach().double() if on_gpu else np.asarray(x_in.detach().cpu().numpy() if _is_torch(x_in) else x_in, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError("x_in must have `dim` columns")
+        y = np.asarray(y_in.detach().cpu().numpy() if _is_torch(y_in) else y_in, np.float64).reshape(x.shape[0], -1)
+        k = self._context().rbf_matrix(x, x, self.kernel_type, self.eps)
+        x_host = x.cpu().numpy() if on_gpu else x
+        k = k.cpu().numpy() if on_gpu else k
+        p = _poly_block(x_host, self.poly_degree)
+        kp = np.vstack([np.hstack([k, p]), np.hstack([p.T, np.zeros((p.shape[1], p.shape[1]))])])
+        coeffs = _pinv_reg(kp) @ np.vstack([y, np.zeros((p.shape[1], y.shape[1]))])
+        if on_gpu:
+            import torch
+            self.x_known, self.coeffs = x.clone(), torch.as_tensor(coeffs, device=x.device)
+        else:
+            self.x_known, self.coeffs = x.copy(), coeffs
+
     def predict(self, x_query):
+        if self.device or _on_gpu(x_query) or _on_gpu(self.x_known):
+            return self._predict_device(x_query)
         xq = np.asarray(x_query, np.float64)
         if xq.shape[1] != self.dim:
             raise ValueError("x_query must have `dim` columns")  # assert_eq at interp_utils.rs:149
         return self._upper(xq) @ self.coeffs
+
+    def _predict_device(self, x_query):
+        """one Context.rbf_apply in float64; the result is of the kind of the query"""
+        if self.coeffs is None:
+            raise ValueError("predict before fit")
+        on_gpu = _on_gpu(x_query)
+        xq = x_query.detach().double() if on_gpu else np.asarray(x_query.detach().cpu().numpy() if _is_torch(x_query) else x_query,
+                                                                 np.float64)
+        if xq.ndim != 2 or xq.shape[1] != self.dim:
+            raise ValueError("x_query must have `dim` columns")
+        return self._context().rbf_apply(xq, self.x_known, self.coeffs, self.kernel_type, self.eps, poly_degree=self.poly_degree)
 
 
 class PodI:

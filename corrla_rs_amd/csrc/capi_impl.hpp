@@ -10,6 +10,7 @@
 
 #include "../../include/corrla_rsvd.h"
 #include "driver.hpp"
+#include "rbf_plan.hpp"  // rbf_poly_terms, kRbfMaxDim
 
 namespace corrla {
 
@@ -871,6 +872,67 @@ inline void pca_inverse_entry(Dev&, const T* scores, int64_t m, int64_t k, int64
     run();
   else
     throw Error(ST_EINVAL, "this backend has no PCA back-projection kernel: corrla_pca_inverse_* is not supported");
+}
+
+// ---- radial-basis-function kernel matrices (corrla_rbf_matrix_* / corrla_rbf_apply_*, interp_utils.rs:96-129, 146-153) ------
+// Argument checks of every entry, then `run` -- on a backend that carries the kernels (dev_has_rbf); any other backend ends
+// the call with EINVAL, never with another way of computing the result.
+template <class T>
+struct RbfCall {
+  const T* xq;
+  int64_t n_q, ldq;
+  const T* xs;
+  int64_t n_s, ldxs, dim;
+  int kernel;
+  double eps;
+  int poly_degree;  // APPLY: < 0 no tail
+  const T* coeffs;  // APPLY: (n_s + n_poly) x n_rhs, row stride ldw
+  int64_t ldw, n_rhs;
+  T* out;           // MATRIX: n_q x n_s; APPLY: n_q x n_rhs; row stride ld_out
+  int64_t ld_out;
+  int64_t n_poly() const { return rbf_poly_terms(dim, poly_degree); }
+};
+
+template <class Dev, class T, class Run>
+inline void rbf_entry(Dev&, const RbfCall<T>& c, bool apply, Run&& run) {
+  const char* who = apply ? "rbf_apply" : "rbf_matrix";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.xq) bad("xq is NULL");
+  if (!c.xs) bad("xs is NULL");
+  if (!c.out) bad("out is NULL");
+  if (c.n_q < 1) bad("n_q must be >= 1");
+  if (c.n_s < 1) bad("n_s must be >= 1");
+  if (c.dim < 1 || c.dim > k::kRbfMaxDim) bad("dim must be in [1, 128]");
+  if (c.kernel < 1 || c.kernel > 4) bad("kernel must be in [1, 4]");
+  if (!std::isfinite(c.eps)) bad("eps must be finite");
+  if (c.ldq < c.dim) bad("ldq < dim");
+  if (c.ldxs < c.dim) bad("lds < dim");
+  const int64_t out_cols = apply ? c.n_rhs : c.n_s;
+  if (apply) {
+    if (!c.coeffs) bad("coeffs is NULL");
+    if (c.n_rhs < 1) bad("n_rhs must be >= 1");
+    if (c.ldw < c.n_rhs) bad("ldw < n_rhs");
+    if (c.ld_out < c.n_rhs) bad("ld_out < n_rhs");
+  } else if (c.ld_out < c.n_s) {
+    bad("ld_out < n_s");
+  }
+  const PcaApplyRange in[3] = {{c.xq, (size_t)((c.n_q - 1) * c.ldq + c.dim) * sizeof(T), "xq"},
+                               {c.xs, (size_t)((c.n_s - 1) * c.ldxs + c.dim) * sizeof(T), "xs"},
+                               {apply ? c.coeffs : nullptr, apply ? (size_t)((c.n_s + c.n_poly() - 1) * c.ldw + c.n_rhs) * sizeof(T) : 0, "coeffs"}};
+  const PcaApplyRange o[1] = {{c.out, (size_t)((c.n_q - 1) * c.ld_out + out_cols) * sizeof(T), "out"}};
+  pca_apply_no_overlap(in, 3, o, 1, who);
+  if constexpr (dev_has_rbf<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no radial-basis-function kernels: corrla_rbf_* is not supported");
+}
+template <class Dev, class T, class Run>
+inline void rbf_apply_entry(Dev& dev, const RbfCall<T>& c, Run&& run) {
+  rbf_entry<Dev, T>(dev, c, true, run);
+}
+template <class Dev, class T, class Run>
+inline void rbf_matrix_entry(Dev& dev, const RbfCall<T>& c, Run&& run) {
+  rbf_entry<Dev, T>(dev, c, false, run);
 }
 
 }  // namespace corrla

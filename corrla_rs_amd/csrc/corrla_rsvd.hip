@@ -10,6 +10,7 @@
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "pca_apply_stage.hpp"
+#include "rbf_stage.hpp"
 #include "tall_stage.hpp"
 
 using namespace corrla;
@@ -345,6 +346,27 @@ CORRLA_API corrla_status corrla_ctx_last_pca_apply(corrla_ctx* ctx, int* centrin
     if (route_out) *route_out = c->pca_apply.route;
   });
 }
+
+// ---- radial-basis-function kernel matrices (interp_utils.rs:96-129, 146-153) -----------------------------------------------
+#define CORRLA_RBF_POINTS(T) const T *xq, int64_t n_q, int64_t ldq, const T *xs, int64_t n_s, int64_t lds, int64_t dim, int kernel, double eps
+#define CORRLA_DEFINE_RBF(SUF, DEV, T, HOST)                                                                            \
+  CORRLA_API corrla_status corrla_rbf_matrix_##DEV##SUF(corrla_ctx* ctx, CORRLA_RBF_POINTS(T), T* out, int64_t ld_out) { \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const RbfCall<T> c{xq, n_q, ldq, xs, n_s, lds, dim, kernel, eps, -1, nullptr, 0, 0, out, ld_out};                 \
+      rbf_matrix_entry<HipDev, T>(cx.dev, c, [&] { rbf_stage::run_matrix<T>(cx.dev, HOST, c); });                       \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  CORRLA_API corrla_status corrla_rbf_apply_##DEV##SUF(corrla_ctx* ctx, CORRLA_RBF_POINTS(T), int poly_degree, const T* coeffs, \
+                                                       int64_t ldw, int64_t n_rhs, T* out, int64_t ld_out) {            \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const RbfCall<T> c{xq, n_q, ldq, xs, n_s, lds, dim, kernel, eps, poly_degree, coeffs, ldw, n_rhs, out, ld_out};   \
+      rbf_apply_entry<HipDev, T>(cx.dev, c, [&] { rbf_stage::run_apply<T>(cx.dev, HOST, c); });                         \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_RBF(f32, , float, true)
+CORRLA_DEFINE_RBF(f64, , double, true)
+CORRLA_DEFINE_RBF(f32, dev_, float, false)
+CORRLA_DEFINE_RBF(f64, dev_, double, false)
 
 // ---- active-subspace gradient stage ------------------------------------------------------
 static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,

@@ -115,6 +115,12 @@ struct dev_has_pca_apply : std::false_type {};
 template <class D>
 struct dev_has_pca_apply<D, std::void_t<decltype(D::kHasPcaApply)>> : std::true_type {};
 
+// ... and those that carry the radial-basis-function kernels of corrla_rbf_* (rbf_kernels.hpp) with kHasRbf.
+template <class D, class = void>
+struct dev_has_rbf : std::false_type {};
+template <class D>
+struct dev_has_rbf<D, std::void_t<decltype(D::kHasRbf)>> : std::true_type {};
+
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).
 template <class T>

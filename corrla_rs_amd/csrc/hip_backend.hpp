@@ -33,6 +33,7 @@
 #include "colvar_kernels.hpp"
 #include "syrk_kernels.hpp"
 #include "pca_apply_kernels.hpp"
+#include "rbf_kernels.hpp"
 
 namespace corrla {
 
@@ -110,6 +111,10 @@ struct Call;            // tall_stage.hpp: what a launcher of the tall products 
 template <class T>
 void set_lds_limits();  // the tall products' kernels of element type T ...
 inline void set_lds_limits();  // ... and the f32-only ones (bf16 split, bf16 stored, one-sweep)
+}
+namespace rbf_stage {
+template <class T>
+void set_lds_limits();  // rbf_stage.hpp: the radial-basis-function kernels
 }
 
 class HipDev {
@@ -1014,6 +1019,8 @@ class HipDev {
   }
   // ---- fitted PCA model on the device: pca_apply_plan.hpp plans, pca_apply_stage.hpp launches pca_apply_kernels.hpp ---------
   static constexpr bool kHasPcaApply = true;  // driver.hpp: dev_has_pca_apply
+  // ---- radial-basis-function kernel matrices: rbf_plan.hpp plans, rbf_stage.hpp launches rbf_kernels.hpp ---------------------
+  static constexpr bool kHasRbf = true;  // driver.hpp: dev_has_rbf
   // out(i, c) = d[i] * in(i, c) over every allocated column (the padding columns are zero and stay zero); out may be in
   template <class T>
   void row_scale(const Skinny<T>& in, Skinny<T>& out, int64_t rows, const T* d) {
@@ -1215,6 +1222,7 @@ class HipDev {
   static void set_lds_limits_typed() {
     constexpr size_t kMax = k::kLdsMaxBytes;
     tall_stage::set_lds_limits<T>();
+    rbf_stage::set_lds_limits<T>();
     lds_limit((const void*)k::syrk_kernel<T, true>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::syrk_kernel<T, false>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::hh_leaf_factor_kernel<T, false>, kMax);

@@ -504,6 +504,54 @@ CORRLA_API corrla_status corrla_pca_inverse_dev_f64(corrla_ctx* ctx, const doubl
                                                     double* out, int64_t row_stride_out);
 CORRLA_API corrla_status corrla_ctx_last_pca_apply(corrla_ctx* ctx, int* centring_out, int* route_out);
 
+/* ---- radial-basis-function kernel matrices: the kernel block of the fit and the prediction ------------
+ * Replaces  RbfInterp::fit's kernel matrix                      src/lib_math_utils/interp_utils.rs:96-129
+ *           RbfInterp::predict                                  src/lib_math_utils/interp_utils.rs:146-153
+ * With Phi_ij = phi(||xq_i - xs_j||_2) over n_q queries and n_s support points of `dim` coordinates:
+ *   corrla_rbf_matrix_*: out = Phi                              (n_q x n_s, row-major, row stride ld_out >= n_s)
+ *   corrla_rbf_apply_* : out = Phi W_rbf + P(Xq) W_poly         (n_q x n_rhs, row-major, row stride ld_out >= n_rhs)
+ * Phi is never stored by the apply entries: a workgroup forms a tile of it in registers and feeds it to the exact f32 / f64
+ * matrix instructions, so 10^5 queries against 10^4 supports need no n_q x n_s temporary.
+ * kernel: 1 linear r, 2 multiquadric sqrt(1 + (eps r)^2), 3 cubic r^3, 4 Gaussian exp(-(eps r)^2) (interp_utils.rs:37-80),
+ * evaluated from the squared distance with the library sqrt / exp of the type.
+ * Layouts: xq (n_q x dim) and xs (n_s x dim) row-major with unit stride along the coordinates and row strides ldq, lds >= dim;
+ * any base alignment.  coeffs is (n_s + n_poly) x n_rhs, row-major with row stride ldw >= n_rhs: the first n_s rows are
+ * W_rbf, the rest W_poly -- the layout RbfInterp::fit produces.  n_poly follows poly_degree: < 0 no tail (n_s rows),
+ * 0 or 1 the dim + 1 terms [x, 1], >= 2 the dim + dim (dim + 1) / 2 + 1 terms [x, x_a x_b (a <= b, a outer), 1] of
+ * build_full_vandermonde (stats_corr.rs:183-209).  The padding columns of out, [n_rhs, ld_out) or [n_s, ld_out), are left
+ * as they were.
+ * Limits: 1 <= dim <= 128; f32 and f64.
+ * Exactness: distances are always the direct form sum_d (xq_id - xs_jd)^2 summed in index order, never the Gram form
+ * ||a||^2 + ||b||^2 - 2 a.b.  So when xq and xs are the same array, corrla_rbf_matrix_* returns a matrix that equals its
+ * transpose bitwise, with the exact diagonal phi(0) (0, 1, 0, 1 for kernels 1 to 4) and exact zeros where two rows coincide
+ * (kernels 1 and 3).  No atomics: the supports may be split over workgroups, whose partials a finishing kernel adds in index
+ * order together with the tail; a fixed input gives a bitwise fixed output.
+ * CORRLA_EINVAL (the message names the argument): NULL xq, xs, coeffs or out; n_q, n_s, n_rhs < 1; dim outside [1, 128];
+ * kernel outside [1, 4]; ldq, lds < dim; ldw, ld_out < n_rhs (matrix: ld_out < n_s); a non-finite eps; out overlapping an
+ * input.  Host-pointer entries copy the operands to the device as they lie and the result back; the *_dev entries enqueue
+ * on the context's stream and return WITHOUT synchronising (but for a first-time growth of the workspace arena):
+ * corrla_ctx_synchronize orders the results. */
+CORRLA_API corrla_status corrla_rbf_matrix_f32(corrla_ctx* ctx, const float* xq, int64_t n_q, int64_t ldq, const float* xs, int64_t n_s,
+                                               int64_t lds, int64_t dim, int kernel, double eps, float* out, int64_t ld_out);
+CORRLA_API corrla_status corrla_rbf_matrix_f64(corrla_ctx* ctx, const double* xq, int64_t n_q, int64_t ldq, const double* xs, int64_t n_s,
+                                               int64_t lds, int64_t dim, int kernel, double eps, double* out, int64_t ld_out);
+CORRLA_API corrla_status corrla_rbf_matrix_dev_f32(corrla_ctx* ctx, const float* xq, int64_t n_q, int64_t ldq, const float* xs, int64_t n_s,
+                                                   int64_t lds, int64_t dim, int kernel, double eps, float* out, int64_t ld_out);
+CORRLA_API corrla_status corrla_rbf_matrix_dev_f64(corrla_ctx* ctx, const double* xq, int64_t n_q, int64_t ldq, const double* xs, int64_t n_s,
+                                                   int64_t lds, int64_t dim, int kernel, double eps, double* out, int64_t ld_out);
+CORRLA_API corrla_status corrla_rbf_apply_f32(corrla_ctx* ctx, const float* xq, int64_t n_q, int64_t ldq, const float* xs, int64_t n_s,
+                                              int64_t lds, int64_t dim, int kernel, double eps, int poly_degree, const float* coeffs,
+                                              int64_t ldw, int64_t n_rhs, float* out, int64_t ld_out);
+CORRLA_API corrla_status corrla_rbf_apply_f64(corrla_ctx* ctx, const double* xq, int64_t n_q, int64_t ldq, const double* xs, int64_t n_s,
+                                              int64_t lds, int64_t dim, int kernel, double eps, int poly_degree, const double* coeffs,
+                                              int64_t ldw, int64_t n_rhs, double* out, int64_t ld_out);
+CORRLA_API corrla_status corrla_rbf_apply_dev_f32(corrla_ctx* ctx, const float* xq, int64_t n_q, int64_t ldq, const float* xs, int64_t n_s,
+                                                  int64_t lds, int64_t dim, int kernel, double eps, int poly_degree, const float* coeffs,
+                                                  int64_t ldw, int64_t n_rhs, float* out, int64_t ld_out);
+CORRLA_API corrla_status corrla_rbf_apply_dev_f64(corrla_ctx* ctx, const double* xq, int64_t n_q, int64_t ldq, const double* xs, int64_t n_s,
+                                                  int64_t lds, int64_t dim, int kernel, double eps, int poly_degree, const double* coeffs,
+                                                  int64_t ldw, int64_t n_rhs, double* out, int64_t ld_out);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller

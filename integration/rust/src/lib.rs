@@ -151,6 +151,28 @@ extern "C" {
                                    scales: *const f32, components: *const f32, ldc: i64, n: i64, out: *mut f32,
                                    row_stride_out: i64) -> c_int;
     pub fn corrla_ctx_last_pca_apply(ctx: *mut c_void, centring_out: *mut c_int, route_out: *mut c_int) -> c_int;
+    // RBF kernel matrices (interp_utils.rs:96-129, 146-153): out (n_q x n_s, row-major) = phi(||xq_i - xs_j||)
+    pub fn corrla_rbf_matrix_f64(ctx: *mut c_void, xq: *const f64, n_q: i64, ldq: i64, xs: *const f64, n_s: i64, lds: i64,
+                                  dim: i64, kernel: c_int, eps: f64, out: *mut f64, ld_out: i64) -> c_int;
+    pub fn corrla_rbf_matrix_f32(ctx: *mut c_void, xq: *const f32, n_q: i64, ldq: i64, xs: *const f32, n_s: i64, lds: i64,
+                                  dim: i64, kernel: c_int, eps: f64, out: *mut f32, ld_out: i64) -> c_int;
+    pub fn corrla_rbf_matrix_dev_f64(ctx: *mut c_void, xq: *const f64, n_q: i64, ldq: i64, xs: *const f64, n_s: i64, lds: i64,
+                                  dim: i64, kernel: c_int, eps: f64, out: *mut f64, ld_out: i64) -> c_int;
+    pub fn corrla_rbf_matrix_dev_f32(ctx: *mut c_void, xq: *const f32, n_q: i64, ldq: i64, xs: *const f32, n_s: i64, lds: i64,
+                                  dim: i64, kernel: c_int, eps: f64, out: *mut f32, ld_out: i64) -> c_int;
+    // out (n_q x n_rhs, row-major) = Phi W_rbf + P(xq) W_poly; coeffs = [W_rbf; W_poly] as RbfInterp::fit lays them out
+    pub fn corrla_rbf_apply_f64(ctx: *mut c_void, xq: *const f64, n_q: i64, ldq: i64, xs: *const f64, n_s: i64, lds: i64,
+                                 dim: i64, kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *const f64, ldw: i64,
+                                 n_rhs: i64, out: *mut f64, ld_out: i64) -> c_int;
+    pub fn corrla_rbf_apply_f32(ctx: *mut c_void, xq: *const f32, n_q: i64, ldq: i64, xs: *const f32, n_s: i64, lds: i64,
+                                 dim: i64, kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *const f32, ldw: i64,
+                                 n_rhs: i64, out: *mut f32, ld_out: i64) -> c_int;
+    pub fn corrla_rbf_apply_dev_f64(ctx: *mut c_void, xq: *const f64, n_q: i64, ldq: i64, xs: *const f64, n_s: i64, lds: i64,
+                                 dim: i64, kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *const f64, ldw: i64,
+                                 n_rhs: i64, out: *mut f64, ld_out: i64) -> c_int;
+    pub fn corrla_rbf_apply_dev_f32(ctx: *mut c_void, xq: *const f32, n_q: i64, ldq: i64, xs: *const f32, n_s: i64, lds: i64,
+                                 dim: i64, kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *const f32, ldw: i64,
+                                 n_rhs: i64, out: *mut f32, ld_out: i64) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
