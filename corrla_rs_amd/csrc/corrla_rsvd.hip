@@ -12,6 +12,7 @@
 #include "pca_apply_stage.hpp"
 #include "rbf_stage.hpp"
 #include "tall_stage.hpp"
+#include "thinq_stage.hpp"
 
 using namespace corrla;
 

@@ -19,6 +19,7 @@
 
 #include "gemm_plan.hpp"
 #include "small_linalg.hpp"
+#include "thinq_plan.hpp"
 
 namespace corrla {
 
@@ -164,7 +165,7 @@ struct RunOpts {
   int poison_core = 0;          // TEST HOOK (env CORRLA_TEST_POISON_CORE = 1 NaN / 2 inf): one entry of the l x l core of
                                 // random_svd.rs:89 is overwritten before its SVD; the call must end with ST_ENUMERIC
 };
-// bits of the device need_next words besides bit 0 (k::kNeedNonFinite / k::kNeedNullCols in hip_kernels.hpp)
+// bits of the device need_next words besides bit 0 (k::kNeedNonFinite / k::kNeedNullCols in thinq_plan.hpp)
 constexpr int kFlagNonFinite = 2, kFlagNullCols = 4;
 
 struct Timings {
@@ -310,7 +311,7 @@ struct RsvdDriver {
   // `rough`: stop after the first clean Cholesky pass -- enough for the in-loop re-orthonormalisations
   // (random_svd.rs:37-39), whose only role is to keep the sketch well conditioned; the span is unchanged.
   static constexpr size_t kStatusBytes = 32;  // one device status record (CholStatus)
-  static constexpr int kRobustPasses = 8;  // most passes a device-robust thin-Q enqueues (2 always, the rest conditional)
+  static constexpr int kRobustPasses = kRobustMaxPasses;  // most passes a device-robust thin-Q enqueues (2 always, the rest conditional)
   static constexpr T kPivotTol = (T)(4.0 * (double)std::numeric_limits<T>::epsilon());  // of every device Cholesky
   // What a stage of an optimistic run leaves to be judged once the last kernel of the call is enqueued (attempt_verdict)
   struct Pending {
@@ -408,13 +409,11 @@ struct RsvdDriver {
   // the all-reduced t, so row-sharded ranks decide alike.  The projections are tall MFMA products.
   void householder_thin_q_any_width(Skinny<T>& y, Skinny<T>& tmp, bool sharded) {
     const int64_t l = y.cols, m = y.rows;
-    int64_t wmax = dev.template householder_max_width<T>();
-    if (const char* e = std::getenv("CORRLA_HH_BLOCK")) wmax = std::max<int64_t>(1, std::min<int64_t>(wmax, std::atoll(e)));
-    if (l <= wmax) {
+    const int64_t w = hh_column_blocks(l, dev.template householder_max_width<T>()).w;  // (the backend applies CORRLA_HH_BLOCK)
+    if (w == l) {
       householder_panel(y, tmp, sharded);
       return;
     }
-    const int64_t nb = (l + wmax - 1) / wmax, w = (l + nb - 1) / nb;
     std::vector<double> th;
     for (int64_t c0 = 0; c0 < l; c0 += w) {
       const int64_t wb = std::min(w, l - c0);
@@ -510,9 +509,14 @@ struct RsvdDriver {
     int64_t n1 = 0, n2 = 0;
     T* minus_one = nullptr;  // device scalar
   };
+  // status records per pass of the factor the backend has for an l-column sketch (ThinQRoute::records_per_pass as the
+  // backend's knobs give it): 1 = it fits one chol_inv_kernel, 2 = 2 x 2 blocked (blocked_factor_inverse), 0 = neither
+  int records_per_pass(int64_t l) const {
+    return dev.template device_chol_fits<T>(l) ? 1 : (dev.template device_chol_blocked_fits<T>(l) ? 2 : 0);
+  }
   BlockSplit block_split(int64_t l) {
     BlockSplit s;
-    s.n1 = round_up((l + 1) / 2, (int64_t)4);
+    s.n1 = blocked_split_n1(l);
     s.n2 = l - s.n1;
     s.minus_one = dev.template alloc_scalar<T>(1);
     dev.fill_const(s.minus_one, (int64_t)1, (T)-1);
@@ -567,19 +571,16 @@ struct RsvdDriver {
   int64_t orthonormalize_device(Skinny<T>& y, Skinny<T>& tmp, bool sharded, bool rough, bool polish) {
     const int64_t l = y.cols;
     PhaseTimer qt0;
-    const bool inplace = dev.qr_inplace_fits(l);
-    const bool single = dev.template device_chol_fits<T>(l);
+    const bool inplace = dev.qr_inplace_fits(l), single = dev.template device_chol_fits<T>(l);
     // how many passes are enqueued is a property of the CONTEXT: it starts at the two (polish: one) a well-conditioned
     // sketch needs -- no conditional launch at all -- and doubles (2 -> 4 -> 8) whenever a call ends with a thin-Q
-    // still asking for more; the call is then repeated on the device with the higher count (random_svd_tall)
-    const int level = std::max(2, std::min(dev.robust_passes(), kRobustPasses));
+    // still asking for more; the call is then repeated on the device with the higher count (random_svd_tall).
     // in-loop (rough, random_svd.rs:37-39): ONE shifted pass is enough whenever its pivots say the sketch was not too
     // ill-conditioned for it (need_ratio); otherwise the same conditional chain as the final thin-Q lifts what can be
     // lifted and re-seeds the rest (a context at level 2 has none enqueued: it escalates like for the final thin-Q)
-    const bool inloop = rough && !polish;
-    const int npass_even = level;  // 2, 4, 8
-    const int npass = inloop ? (level <= 2 ? 1 : npass_even - 1) : (polish ? (level <= 2 ? 1 : 3) : level);
-    const int always = (polish || inloop) ? 1 : 2;
+    const RobustSchedule sched =
+        robust_schedule(dev.robust_passes(), polish ? RobustMode::kPolish : (rough ? RobustMode::kInLoop : RobustMode::kFinal), inplace);
+    const int npass = sched.npass, always = sched.always;
     int* need = att_.flags_pool + att_.flags_used;
     int* null_mask = dev.alloc_flags((int)l);
     int* need_blk = dev.alloc_flags(2);
@@ -587,7 +588,6 @@ struct RsvdDriver {
     void* insp = single ? nullptr : dev.template alloc_inspect<T>();
     Skinny<T> gd = dev.template alloc_skinny<T>(l, l);
     Skinny<T> md = dev.template alloc_skinny<T>(l, l);
-    const double eps0 = (double)std::numeric_limits<T>::epsilon();
     // shift: as small as the rounding error of the computed Gram allows (~ eps sqrt(m) relative to its largest diagonal
     // entry; never below the 16 eps of the host-controlled path).  A small shift lifts the weak directions further per
     // pass AND keeps them more accurate (16384 x 16384 f32, sigma_i = 0.7^i: the 10th singular value to 1.6e-5 with
@@ -597,7 +597,7 @@ struct RsvdDriver {
     // stays within the 16 eps in practice (thousands of fuzz cases), the Schur complement of the 2 x 2 blocked form is formed
     // by a product and carries ~l eps (tools/fuzz_parity.py seed 22 case 133 lost 2e-4 in a trailing singular value at l = 160 with 16 eps).  (Clamping
     // failed pivots to the shift instead keeps the span too, but the inverse factor of dozens of clamped columns overflows.)
-    double shift_rel = eps0 * std::max({16.0, 0.25 * std::sqrt((double)std::max<int64_t>(y.rows, 1)), single ? 0.0 : 2.0 * (double)l});
+    double shift_rel = robust_shift_rel(sizeof(T), y.rows, l, single);
     if (const char* e = std::getenv("CORRLA_QR_SHIFT_SCALE")) shift_rel *= std::atof(e);  // experiments
     // in-loop: a direction whose residual is below the shift would leave the pass less than half normalised; such
     // half-lifted columns measurably hurt (DMDc snapshots: 7e-7 instead of 1e-14 in the 8th singular vector), so they
@@ -606,43 +606,40 @@ struct RsvdDriver {
     if (const char* e = std::getenv("CORRLA_QR_NULL_EXCESS")) nullx = (float)std::atof(e);  // experiments
     const BlockSplit split = single ? BlockSplit{} : block_split(l);
     for (int pass = 0; pass < npass; ++pass) {
+      const RobustSchedule::Pass& ps = sched.pass[pass];
       // gate: in place, the pass before; in pairs, the pass before the PAIR
-      const int gate = pass < always ? -1 : (inplace ? pass - 1 : always + ((pass - always) / 2) * 2 - 1);
-      dev.set_run_if(gate < 0 ? nullptr : need + gate);
-      const int shift_mode = polish ? 2 : (pass == 0 ? 1 : 0);
+      dev.set_run_if(ps.gate < 0 ? nullptr : need + ps.gate);
       // in-loop (rough): directions below the level one shifted pass can lift are re-seeded at random, like the
       // completion of the host-controlled path -- the next products with A pull the re-seeded columns back into range(A)
       // (final thin-Q: the first two passes only lift; what is still below the shift level in the third has no
       // independent information -- amplified rounding noise is not even linearly independent, it would be lifted and
       // crushed again for ever -- and is re-seeded too)
-      const float nx = (!polish && pass >= 2) ? nullx : 0.f;
-      const float need_ratio = (inloop && pass == 0) ? 1e-2f : 0.f;
+      const float nx = ps.null_excess ? nullx : 0.f;
       // (not in place: conditional passes come in pairs, so a skipped pair swaps y and tmp twice over untouched data)
       cholqr_pass(y, tmp, gd, sharded, inplace, [&](Skinny<T>& g) {
         if (single) {
-          dev.chol_inv_robust(g, l, kPivotTol, (float)shift_rel, shift_mode, nx, md, st_scratch, pass, need + pass, null_mask, nullptr,
-                              need_ratio);
+          dev.chol_inv_robust(g, l, kPivotTol, (float)shift_rel, ps.shift_mode, nx, md, st_scratch, pass, need + pass, null_mask, nullptr,
+                              ps.need_ratio);
           return md;
         }
-        dev.gram_inspect(g, l, (float)shift_rel, shift_mode, insp);
+        dev.gram_inspect(g, l, (float)shift_rel, ps.shift_mode, insp);
         const void* shp = dev.template inspect_shift_ptr<T>(insp);
         blocked_factor_inverse(g, split, md, [&](const Skinny<T>& blk, int64_t n, int which, Skinny<T>& x) {
           dev.chol_inv_robust(blk, n, kPivotTol, 0.f, 2, nx, x, st_scratch, 2 * pass + which, need_blk + which,
-                              null_mask + which * split.n1, shp, need_ratio);
+                              null_mask + which * split.n1, shp, ps.need_ratio);
         });
-        dev.template combine_need<T>(need + pass, need_ratio > 0.f ? nullptr : insp, need_blk, need_blk + 1);
+        dev.template combine_need<T>(need + pass, ps.need_ratio > 0.f ? nullptr : insp, need_blk, need_blk + 1);
         return md;
       });
-      // (a re-seeded column needs a following pass to be orthonormalised: none after the last one; in-loop, the next
-      // products with A and the next thin-Q take care of it)
-      if (pass + 1 < npass || inloop)
+      if (ps.refill)
         dev.refill_null(y, l, null_mask, (uint64_t)(0x9e3779b97f4a7c15ull ^ (uint64_t)(977 * (att_.flags_used + pass) + l)));
       if (pass < always) ++tm.qr_passes;  // the conditional ones are counted when the flags are read (attempt_verdict)
     }
     dev.set_run_if(nullptr);
     // in-loop: only the single pass of a level-2 context is verified (so that the context escalates); with a conditional
     // chain enqueued the in-loop thin-Q is best effort -- it only has to keep the sketch well conditioned
-    att_.pending.push_back(Pending::robust_chol(always, npass, (inloop && npass > 1) ? -1 : att_.flags_used, st_scratch, single ? 1 : 2));
+    att_.pending.push_back(Pending::robust_chol(always, npass, sched.flag_slot < 0 ? -1 : att_.flags_used + sched.flag_slot, st_scratch,
+                                                single ? 1 : 2));
     att_.flags_used += npass;
     subphase(tm.qr_gram_ms, qt0);
     return l;
@@ -656,8 +653,7 @@ struct RsvdDriver {
     if (att_.defer && (sharded || y.rows >= l) && att_.flags_used + kRobustPasses <= att_.flags_cap &&
         dev.template device_qr_robust_fits<T>(l))
       return orthonormalize_device(y, tmp, sharded, rough, polish);
-    // status records per pass: 1 = the factor fits one chol_inv_kernel, 2 = 2 x 2 blocked (blocked_factor_inverse), 0 = neither
-    const int rpp = dev.template device_chol_fits<T>(l) ? 1 : (dev.template device_chol_blocked_fits<T>(l) ? 2 : 0);
+    const int rpp = records_per_pass(l);
     if (rpp > 0) {
       // Optimistic CholeskyQR2 entirely on the device: [Gram, Cholesky + inverse, apply] x2 are enqueued
       // back to back and the two status records (blocked: four) are read once at the end.  Anything unusual (a failed
@@ -903,7 +899,7 @@ struct RsvdDriver {
     // Householder mode has no status records to defer: the body runs with the host in the loop, which also lets it
     // complete the null vectors of an exactly singular core (see random_svd_tall_body)
     const bool hh = qr_householder;
-    if (!hh && (dev.template device_chol_fits<T>(l) || dev.template device_chol_blocked_fits<T>(l))) {
+    if (!hh && records_per_pass(l) > 0) {
       // Optimistic run: every Cholesky-QR status record is checked once, after the last kernel is enqueued
       // (no host synchronisation inside the call).  A record that is not clean (rank deficiency, zero or
       // non-finite input, ...) repeats the computation with the host in the loop.

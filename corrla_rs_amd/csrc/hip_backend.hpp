@@ -2,6 +2,9 @@
 // (optionally) one RCCL communicator per context.  Implements the `Dev` interface that
 // driver.hpp / capi_impl.hpp are written against.  Every operation is enqueued on the context's
 // stream; the only host synchronisations are the small l x l downloads the host factorizations need.
+// The compute stages are planned in their *_plan.hpp and launched from their *_stage.hpp, which define the members declared
+// here (tall products: tall_stage.hpp, core SVD: core_svd_stage.hpp, thin-Q: thinq_stage.hpp); this file keeps the device
+// services -- memory, transfers, collectives, events -- the state of a context and the small elementwise launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -20,7 +23,7 @@
 #include "core_svd_plan.hpp"
 #include "driver.hpp"
 #include "hip_kernels.hpp"
-#include "tsqr_kernels.hpp"
+#include "thinq_plan.hpp"
 #include "jacobi_mc_kernels.hpp"
 #include "ata_kernels.hpp"
 #include "tall_kernels.hpp"
@@ -116,6 +119,10 @@ namespace rbf_stage {
 template <class T>
 void set_lds_limits();  // rbf_stage.hpp: the radial-basis-function kernels
 }
+namespace thinq_stage {
+template <class T>
+void set_lds_limits();  // thinq_stage.hpp: the Householder panels
+}
 
 class HipDev {
  public:
@@ -148,9 +155,11 @@ class HipDev {
       std::random_device rd;
       entropy_ = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
     }
-    no_device_chol_ = env_int("CORRLA_HOST_CHOL", 0) != 0;
+    // the thin-Q's knobs (thinq_plan.hpp)
+    thinq_knobs_.host_chol = env_int("CORRLA_HOST_CHOL", 0) != 0;
+    thinq_knobs_.robust_qr = env_int("CORRLA_DEVICE_ROBUST_QR", 1) != 0;  // 0: the round-1 optimistic CholeskyQR2 + host-controlled repeat
+    if (const char* e = std::getenv("CORRLA_HH_BLOCK")) thinq_knobs_.hh_block = std::atoll(e);
     robust_passes_ = std::max(2, env_int("CORRLA_ROBUST_PASSES", 2));
-    robust_qr_ = env_int("CORRLA_DEVICE_ROBUST_QR", 1) != 0;  // 0: the round-1 optimistic CholeskyQR2 + host-controlled repeat
     gemm_debug_flags_ = env_int("CORRLA_GEMM_DEBUG", 0);  // timing-only ablations, results are wrong
     // the tall products' geometry knobs (gemm_plan.hpp)
     gemm_knobs_.split_nn = env_int("CORRLA_SPLIT_NN", 0);
@@ -521,16 +530,16 @@ class HipDev {
                               stream));
     if (dst_is_host) sync();
   }
-  // ---- device Cholesky + inverse (optimistic CholeskyQR2) ------------------------------------------
+  // ---- thin-Q orthonormalisation: thinq_plan.hpp routes and sizes, thinq_stage.hpp launches what it says and defines the
+  // members declared here ----
   template <class T>
-  bool device_chol_fits(int64_t l) const {
-    return l <= 4096 && k::chol_inv_fits((int)l, sizeof(T)) && !no_device_chol_;
-  }
+  bool device_chol_fits(int64_t l) const { return thinq_route(sizeof(T), l, thinq_knobs_).factor == ThinQFactor::kSingle; }
   template <class T>
-  bool device_chol_blocked_fits(int64_t l) const {
-    const int64_t n1 = round_up((l + 1) / 2, (int64_t)4);
-    return l > 8 && l <= 4096 && k::chol_inv_fits((int)n1, sizeof(T)) && !no_device_chol_;
-  }
+  bool device_chol_blocked_fits(int64_t l) const { return thinq_route(sizeof(T), l, thinq_knobs_).factor == ThinQFactor::kBlocked2x2; }
+  template <class T>
+  bool device_qr_robust_fits(int64_t l) const { return thinq_route(sizeof(T), l, thinq_knobs_).robust; }
+  // one column block: the products of a pass may run in place (see apply_inplace)
+  bool qr_inplace_fits(int64_t l) const { return thinq_route(sizeof(float), l, thinq_knobs_).inplace; }
   // dst(dr0 + i, dc0 + j) <- src(r0 + i, c0 + j), i < rows, j < cols
   template <class T>
   void copy_block(const Skinny<T>& src, int64_t r0, int64_t c0, int64_t rows, int64_t cols, Skinny<T>& dst, int64_t dr0,
@@ -540,14 +549,9 @@ class HipDev {
                                 (size_t)src.ld * sizeof(T), (size_t)rows * sizeof(T), (size_t)cols, hipMemcpyDeviceToDevice,
                                 stream));
   }
+  // optimistic CholeskyQR2: factor-and-invert of the r x r Gram g into m_out, status record `slot` of st_dev
   template <class T>
-  void chol_inv(const Skinny<T>& g, int64_t r, T piv_rel, Skinny<T>& m_out, void* st_dev, int slot) {
-    // m_out comes zero-filled from alloc_skinny and only its upper triangle is ever written
-    hipLaunchKernelGGL((k::chol_inv_kernel<T>), dim3(1), dim3(k::chol_inv_threads((int)r)),
-                       k::chol_inv_lds_bytes((int)r, sizeof(T)), stream, (const T*)g.p, g.ld, (int)r, piv_rel, m_out.p,
-                       m_out.ld, (k::CholStatus*)st_dev + slot);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void chol_inv(const Skinny<T>& g, int64_t r, T piv_rel, Skinny<T>& m_out, void* st_dev, int slot);
   // ---- device-robust Cholesky-QR (driver.hpp: orthonormalize_device) ----
   // every launch enqueued while a run_if word is set does nothing when that device word is 0
   void set_run_if(const int* p) { run_if_ = p; }
@@ -633,40 +637,20 @@ class HipDev {
     CORRLA_HIP(hipMemcpyAsync(host, dev_p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, stream));
     sync();
   }
-  template <class T>
-  bool device_qr_robust_fits(int64_t l) const {
-    return robust_qr_ && (device_chol_fits<T>(l) || device_chol_blocked_fits<T>(l));
-  }
-  // one column block: the products of a pass may run in place (see apply_inplace)
-  bool qr_inplace_fits(int64_t l) const { return col_blocking(l).nblk == 1; }
   // 2 x 2 blocked robust factorisation (l > 176 / 152): the whole Gram is inspected (shift decision, ||G - I||) and shifted
   // once, the two diagonal-block factorisations take the shift from the record, combine_need forms the pass verdict
   template <class T>
-  void* alloc_inspect() { return alloc_zeroed(sizeof(k::GramInspect<T>)); }
+  void* alloc_inspect();
   template <class T>
-  const void* inspect_shift_ptr(const void* insp) const { return &((const k::GramInspect<T>*)insp)->shift; }
+  const void* inspect_shift_ptr(const void* insp) const;
   template <class T>
-  void gram_inspect(Skinny<T>& g, int64_t l, float shift_rel, int shift_mode, void* insp) {
-    hipLaunchKernelGGL((k::gram_inspect_kernel<T>), dim3(1), dim3(1024), 0, stream, g.p, g.ld, (int)l, shift_rel, shift_mode,
-                       (k::GramInspect<T>*)insp, run_if_);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void gram_inspect(Skinny<T>& g, int64_t l, float shift_rel, int shift_mode, void* insp);
   template <class T>
-  void combine_need(int* need, const void* insp, const int* na, const int* nb) {
-    hipLaunchKernelGGL((k::combine_need_kernel<T>), dim3(1), dim3(1), 0, stream, need, (const k::GramInspect<T>*)insp, na, nb,
-                       run_if_);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void combine_need(int* need, const void* insp, const int* na, const int* nb);
   template <class T>
   void chol_inv_robust(const Skinny<T>& g, int64_t r, T piv_rel, float shift_rel, int shift_mode, float null_excess,
                        Skinny<T>& m_out, void* st_dev, int slot, int* need_next, int* null_mask,
-                       const void* abs_shift = nullptr, float need_ratio = 0.f) {
-    k::CholRobust rb{shift_rel, shift_mode, null_excess, need_next, null_mask, run_if_, need_ratio, abs_shift};
-    hipLaunchKernelGGL((k::chol_inv_kernel<T>), dim3(1), dim3(k::chol_inv_threads((int)r)),
-                       k::chol_inv_lds_bytes((int)r, sizeof(T)), stream, (const T*)g.p, g.ld, (int)r, piv_rel, m_out.p,
-                       m_out.ld, (k::CholStatus*)st_dev + slot, rb);
-    CORRLA_HIP(hipGetLastError());
-  }
+                       const void* abs_shift = nullptr, float need_ratio = 0.f);
   // y <- y * m (m: l x l): in place -- a workgroup / wave of the product kernels reads exactly the rows it writes,
   // all of them before its first store (one column block only: device_qr_robust_fits)
   template <class T>
@@ -676,13 +660,9 @@ class HipDev {
     mv.rows = l;
     launch_gemm<T>(true, as_rowmajor_transposed(y, l), mv, out, (const T*)nullptr);
   }
+  // columns of y marked in null_mask <- random columns (refill_null_kernel)
   template <class T>
-  void refill_null(Skinny<T>& y, int64_t l, const int* null_mask, uint64_t seed) {
-    const int bx = (int)std::min<int64_t>(64, (y.rows + 255) / 256);
-    hipLaunchKernelGGL((k::refill_null_kernel<T>), dim3((unsigned)std::max(bx, 1), (unsigned)l), dim3(256), 0, stream, y.p, y.ld,
-                       y.rows, (int)l, null_mask, seed, run_if_);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void refill_null(Skinny<T>& y, int64_t l, const int* null_mask, uint64_t seed);
 
   void read_chol_status(const void* st_dev, int n, int* fail, float* min_ratio, float* dev_i) {
     static_assert(sizeof(k::CholStatus) == 32, "driver.hpp assumes 32-byte status records");
@@ -703,122 +683,37 @@ class HipDev {
 
   // m_out (r x r) = (I + E)^(-1/2) with G = I + E given in g (overwritten by E); everything on the device
   template <class T>
-  void inv_sqrt_series(Skinny<T>& g, int64_t r, Skinny<T>& m_out) {
-    Skinny<T> e2 = alloc_skinny<T>(r, r), e3 = alloc_skinny<T>(r, r);
-    if (e2.ld != g.ld || m_out.ld != g.ld) throw Error(ST_EINVAL, "internal: series operands must share a leading dimension");
-    dim3 grid((unsigned)((r + 63) / 64), (unsigned)r);
-    hipLaunchKernelGGL((k::series_prep_kernel<T>), grid, dim3(64), 0, stream, g.p, g.ld, (int)r);
-    Big<T> eb;  // E is symmetric: its column-major image is also its row-major image
-    eb.p = g.p;
-    eb.rows = r;
-    eb.cols = r;
-    eb.ld = g.ld;
-    eb.cols_readable = g.ld;
-    Skinny<T> gv = g.view_cols(r);
-    gv.rows = r;
-    gemm_nn(eb, gv, e2, (const T*)nullptr);
-    gemm_nn(eb, e2, e3, (const T*)nullptr);
-    memset_zero(m_out.p, (size_t)m_out.ld * m_out.cols_alloc * sizeof(T));
-    hipLaunchKernelGGL((k::series_combine_kernel<T>), grid, dim3(64), 0, stream, (const T*)g.p, (const T*)e2.p,
-                       (const T*)e3.p, g.ld, (int)r, m_out.p, m_out.ld);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void inv_sqrt_series(Skinny<T>& g, int64_t r, Skinny<T>& m_out);
 
   // ---- Householder TSQR with explicit thin Q (tsqr_kernels.hpp) -------------------------------------------
-  // one 2 l x l panel (plus the 16 x 16 T and Gram blocks of the blocked form) must fit in LDS: l <= 142 (f32) / 99 (f64)
-  bool hh_wy_ = env_int("CORRLA_HH_WY", 1) != 0;  // blocked compact-WY panels on the MFMA units (0: the unblocked panels)
+  // one 2 l x l panel (plus the 16 x 16 T and Gram blocks of the compact-WY form) must fit in LDS: l <= 142 (f32) / 99 (f64)
   template <class T>
-  size_t hh_panel_lds(int rows, int l) const {
-    return hh_wy_ ? k::hh_wy_lds_bytes(rows, l, sizeof(T)) : k::hh_lds_bytes(rows, l, sizeof(T));
-  }
+  bool householder_fits(int64_t l) const { return hh_fits(sizeof(T), l); }
+  // widest column block of a Householder thin-Q: the widest panel one workgroup can hold, under the CORRLA_HH_BLOCK cap
   template <class T>
-  bool householder_fits(int64_t l) const {
-    return l >= 1 && l <= 4096 && hh_panel_lds<T>((int)(2 * l), (int)l) <= (size_t)160 * 1024 && 2 * l <= 64 * k::kHhMaxRowsPerLane;
-  }
+  int householder_max_width() const { return (int)hh_capped_width(hh_max_width(sizeof(T)), thinq_knobs_.hh_block); }
   // Up sweep of the TSQR of y (m x l, m >= l): leaf reflectors -> tmp (same shape as y), tree reflectors and the root's
   // R factor (l x l, column-major, ld = l) stay in call-lifetime device buffers named by the returned state.
   template <class T>
   struct HhState {
     int64_t m = 0;
-    int l = 0, nleaf = 0, levels = 0, max_rows = 0;
-    std::vector<int> n_at;
-    std::vector<T*> rbuf, cbuf, taub, vbuf, tbuf;  // tbuf: the T factors of the 16-column blocks (blocked form)
-    T* r_root() const { return rbuf[levels]; }
+    int l = 0;
+    HhTreePlan plan;  // the panel tree, the buffer sizes and the LDS of both sweeps
+    std::vector<T*> rbuf, cbuf, taub, vbuf, tbuf;  // per level; tbuf: the T factors of the 16-column blocks
+    T* r_root() const { return rbuf[plan.levels]; }
   };
   template <class T>
-  HhState<T> householder_up(Skinny<T>& y, Skinny<T>& tmp) {
-    HhState<T> h;
-    const int64_t m = y.rows;
-    const int l = (int)y.cols;
-    if (m < l) throw Error(ST_EINVAL, "householder_thin_q: fewer rows than columns");
-    if (!householder_fits<T>(l)) throw Error(ST_EINVAL, "householder_thin_q: panel does not fit in LDS");
-    const int64_t br = 2 * (int64_t)l;
-    const int64_t nleaf64 = m <= br ? 1 : (m + br - 1) / br;
-    if (nleaf64 > 0x3fffffff) throw Error(ST_EINVAL, "householder_thin_q: too many panels");
-    h.m = m;
-    h.l = l;
-    h.nleaf = (int)nleaf64;
-    h.max_rows = (int)std::min<int64_t>(m, br);
-    const size_t lds = hh_panel_lds<T>(h.max_rows, l);
-    h.n_at = {h.nleaf};
-    while (h.n_at.back() > 1) h.n_at.push_back((h.n_at.back() + 1) / 2);
-    h.levels = (int)h.n_at.size() - 1;
-    const size_t ll = (size_t)l * l;
-    h.rbuf.resize(h.levels + 1);
-    h.cbuf.resize(h.levels + 1);
-    h.taub.resize(h.levels + 1);
-    h.vbuf.assign(h.levels + 1, nullptr);
-    h.tbuf.assign(h.levels + 1, nullptr);
-    const size_t tsz = (size_t)k::hh_wy_panels(l) * k::kWyNb * k::kWyNb;
-    for (int k_ = 0; k_ <= h.levels; ++k_) {
-      if (hh_wy_) h.tbuf[k_] = (T*)alloc_bytes(tsz * h.n_at[k_] * sizeof(T));
-      h.rbuf[k_] = (T*)alloc_bytes(ll * h.n_at[k_] * sizeof(T));
-      h.cbuf[k_] = (T*)alloc_bytes(ll * h.n_at[k_] * sizeof(T));
-      h.taub[k_] = (T*)alloc_bytes((size_t)l * h.n_at[k_] * sizeof(T));
-      if (k_ >= 1) h.vbuf[k_] = (T*)alloc_bytes(2 * ll * h.n_at[k_] * sizeof(T));
-    }
-    auto leaf = hh_wy_ ? k::hh_leaf_factor_kernel<T, true> : k::hh_leaf_factor_kernel<T, false>;
-    auto tree = hh_wy_ ? k::hh_tree_factor_kernel<T, true> : k::hh_tree_factor_kernel<T, false>;
-    hipLaunchKernelGGL(leaf, dim3((unsigned)h.nleaf), dim3(k::kHhThreads), lds, stream, (const T*)y.p, y.ld, m, l, h.nleaf, tmp.p,
-                       tmp.ld, h.taub[0], h.rbuf[0], h.tbuf[0]);
-    const size_t lds_tree = hh_panel_lds<T>(2 * l, l);
-    for (int k_ = 1; k_ <= h.levels; ++k_)
-      hipLaunchKernelGGL(tree, dim3((unsigned)h.n_at[k_]), dim3(k::kHhThreads), lds_tree, stream, (const T*)h.rbuf[k_ - 1],
-                         h.n_at[k_ - 1], l, h.vbuf[k_], h.taub[k_], h.rbuf[k_], h.tbuf[k_]);
-    CORRLA_HIP(hipGetLastError());
-    return h;
-  }
+  HhState<T> householder_up(Skinny<T>& y, Skinny<T>& tmp);
   // Down sweep: y <- Q [C; 0] with Q the orthogonal factor of the up sweep and C = root_coef (l x l, column-major,
   // ld = l; nullptr = the identity, i.e. y <- the explicit thin Q).  A cross-rank TSQR passes its block of the top-level
   // Q here (driver.hpp householder_panel).
   template <class T>
-  void householder_down(HhState<T>& h, Skinny<T>& y, Skinny<T>& tmp, const T* root_coef = nullptr) {
-    const int l = h.l;
-    const size_t lds = k::hh_lds_bytes(h.max_rows, l, sizeof(T));
-    const size_t lds_tree = k::hh_lds_bytes(2 * l, l, sizeof(T));
-    auto tree = hh_wy_ ? k::hh_tree_apply_kernel<T, true> : k::hh_tree_apply_kernel<T, false>;
-    auto leaf = hh_wy_ ? k::hh_leaf_apply_kernel<T, true> : k::hh_leaf_apply_kernel<T, false>;
-    for (int k_ = h.levels; k_ >= 1; --k_)
-      hipLaunchKernelGGL(tree, dim3((unsigned)h.n_at[k_]), dim3(k::kHhThreads), lds_tree, stream,
-                         (const T*)(k_ == h.levels ? root_coef : h.cbuf[k_]), (const T*)h.vbuf[k_], (const T*)h.taub[k_],
-                         h.n_at[k_ - 1], l, h.cbuf[k_ - 1], (const T*)h.tbuf[k_]);
-    hipLaunchKernelGGL(leaf, dim3((unsigned)h.nleaf), dim3(k::kHhThreads), lds, stream,
-                       (const T*)(h.levels == 0 ? root_coef : h.cbuf[0]), (const T*)tmp.p, tmp.ld, (const T*)h.taub[0], h.m, l,
-                       h.nleaf, y.p, y.ld, (const T*)h.tbuf[0]);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void householder_down(HhState<T>& h, Skinny<T>& y, Skinny<T>& tmp, const T* root_coef = nullptr);
   // y (m x l, m >= l) <- thin Q of its Householder QR; tmp (same shape) receives the leaf reflectors
   template <class T>
   void householder_thin_q(Skinny<T>& y, Skinny<T>& tmp) {
     HhState<T> h = householder_up(y, tmp);
     householder_down(h, y, tmp);
-  }
-  // widest panel one workgroup can hold: 142 (f32) / 99 (f64)
-  template <class T>
-  int householder_max_width() const {
-    int w = 1;
-    while (householder_fits<T>(w + 1)) ++w;
-    return w;
   }
   int rank() const { return comm_rank; }
 
@@ -1180,10 +1075,9 @@ class HipDev {
   GemmKnobs gemm_knobs_;
   SyrkKnobs syrk_knobs_;
   uint64_t entropy_ = 0, calls_ = 0, calls_sharded_ = 0;
-  bool no_device_chol_ = false;
+  ThinQKnobs thinq_knobs_;  // thinq_plan.hpp
   const int* run_if_ = nullptr;
   bool phase_events_ = true;
-  bool robust_qr_ = true;
   int robust_passes_ = 2;
   CoreSvdState svd_state_;  // core_svd_plan.hpp
 
@@ -1220,19 +1114,11 @@ class HipDev {
   }
   template <class T>
   static void set_lds_limits_typed() {
-    constexpr size_t kMax = k::kLdsMaxBytes;
     tall_stage::set_lds_limits<T>();
     rbf_stage::set_lds_limits<T>();
     lds_limit((const void*)k::syrk_kernel<T, true>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::syrk_kernel<T, false>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
-    lds_limit((const void*)k::hh_leaf_factor_kernel<T, false>, kMax);
-    lds_limit((const void*)k::hh_tree_factor_kernel<T, false>, kMax);
-    lds_limit((const void*)k::hh_tree_apply_kernel<T, false>, kMax);
-    lds_limit((const void*)k::hh_leaf_apply_kernel<T, false>, kMax);
-    lds_limit((const void*)k::hh_leaf_factor_kernel<T, true>, kMax);
-    lds_limit((const void*)k::hh_tree_factor_kernel<T, true>, kMax);
-    lds_limit((const void*)k::hh_tree_apply_kernel<T, true>, kMax);
-    lds_limit((const void*)k::hh_leaf_apply_kernel<T, true>, kMax);
+    thinq_stage::set_lds_limits<T>();
   }
   // ---- the tall products' launch (tall_stage.hpp) ----
   // what a launcher of the stage needs of this context beyond the plan

@@ -11,12 +11,13 @@
 //          l x l coefficient blocks, every inner node turns its coefficient block into two, every leaf turns its
 //          block into its rows of Q.  In this direction a wave owns its columns for the whole panel, so the
 //          apply loop needs no barriers at all.
-// Two panel codes: the unblocked one (hh_factor_panel / hh_apply_panel: every reflector applied to the whole trailing
-// panel by the VALU) and the blocked compact-WY one (hh_wy_*: reflector steps inside 16-column blocks, trailing update
-// and down sweep on the MFMA units), selected per context (CORRLA_HH_WY, default blocked).
+// One panel code, the blocked compact-WY one (hh_wy_*: reflector steps inside 16-column blocks, trailing update and down
+// sweep on the MFMA units).  (The unblocked panels -- every reflector applied to the whole trailing panel by the VALU --
+// measured 1.6-2.5x slower at every shape and were retired: CHANGELOG.md.)
 // A Householder thin-Q is orthonormal whatever the rank of the sketch (tau = 0 for a column that is already reduced),
 // which is exactly the behaviour of the reference on rank-deficient inputs.  One panel (2 l x l) must fit in the
-// 160 KB LDS of a CU: l <= 142 (f32) / l <= 99 (f64).
+// 160 KB LDS of a CU: l <= 142 (f32) / l <= 99 (f64).  The panel sizes (kHhThreads, kHhMaxRowsPerLane, kWyNb, kWyExtra,
+// hh_pitch, hh_lds_bytes, hh_wy_lds_bytes, hh_wy_panels, hh_leaf_row0) are in thinq_plan.hpp, which plans every launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,14 +26,12 @@
 #include <type_traits>
 
 #include "hip_kernels.hpp"  // MT<T>: the MFMA wrappers and their register layouts
+#include "thinq_plan.hpp"
 
 namespace corrla {
 namespace k {
 
-constexpr int kHhThreads = 1024;  // 16 waves per panel: four per SIMD hide the load -> reduce -> update chain of a column group
 constexpr int kHhWaves = kHhThreads / 64;
-constexpr int kHhGroup = 3;  // columns of one wave in flight together (138 columns = 16 waves x 3 groups of 3)
-constexpr int kHhMaxRowsPerLane = 5;  // ceil(2 * 138 / 64): panel rows a lane may own in one column
 constexpr int kHhTriSlices = 3;       // ceil(138 / 64): rows l .. l + j of a stacked-triangle panel
 
 template <int CTRL, int ROW_MASK = 0xf>
@@ -70,161 +69,6 @@ __device__ __forceinline__ T hh_wave_sum(T x) {
 // (~2 us) per reflector step -- which was the whole cost of a step.
 __device__ __forceinline__ void hh_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__host__ __device__ inline int hh_pitch(int rows) { return (rows + 3) & ~3; }
-__host__ __device__ inline size_t hh_lds_bytes(int max_rows, int l, size_t esz) {
-  return (size_t)hh_pitch(max_rows) * (size_t)l * esz + 64;
-}
-// rows of leaf i when m rows are cut into nleaf panels
-__host__ __device__ inline int64_t hh_leaf_row0(int64_t m, int nleaf, int i) { return (m * (int64_t)i) / nleaf; }
-
-// In-LDS Householder reduction of the rows x l panel P (column pitch RP).  On return the upper triangle holds R and
-// column j holds v_j below the diagonal (v_j(j) = 1 implied); tau[j] is written to global memory by wave 0.
-// TRI: the panel is two stacked upper triangles [R_a; R_b] (rows = 2 l).  Reflector j then only involves row j and rows
-// l .. l + j (everything else of column j below the diagonal is, and stays, zero): NS = 3 row slices instead of 5.
-template <class T, int NS, bool TRI>
-__device__ void hh_factor_panel(T* P, int RP, int rows, int l, T* tau_out) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int j = 0; j < l; ++j) {
-    T* cj = P + (size_t)j * RP;
-    const int lo = TRI ? l : j + 1, hi = TRI ? l + j + 1 : rows;  // rows [lo, hi) carry v below the diagonal
-    // every wave forms the reflector redundantly (identical arithmetic -> identical values): no exchange needed
-    T xr[NS];
-    T part = (T)0;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      const int r = lo + lane + 64 * i;
-      const T val = cj[min(r, hi - 1)];  // unconditional load (clamped), then select: the five loads overlap
-      xr[i] = r < hi ? val : (T)0;
-      part += xr[i] * xr[i];
-    }
-    const T sigma = hh_wave_sum(part);
-    const T alpha = cj[j];
-    T tau = (T)0, beta = alpha, scale = (T)0;
-    if (sigma > (T)0) {  // LAPACK xLARFG
-      beta = -copysign(sqrt(alpha * alpha + sigma), alpha);
-      tau = (beta - alpha) / beta;
-      scale = (T)1 / (alpha - beta);
-    }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) xr[i] *= scale;  // v below the diagonal
-    hh_lds_barrier();  // everyone has read column j
-    if (wave == 0) {
-#pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        const int r = lo + lane + 64 * i;
-        if (r < hi) cj[r] = xr[i];
-      }
-      if (lane == 0) {
-        cj[j] = beta;
-        tau_out[j] = tau;
-      }
-    }
-    // trailing update, kHhGroup columns of this wave at a time: every LDS load is unconditional (clamped row / column
-    // index; v is zero on the rows that do not exist) so that the twenty loads of a group are in flight together,
-    // the four reductions overlap, and the update is made from registers
-    int rr[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) rr[i] = min(lo + lane + 64 * i, hi - 1);
-    // columns are dealt round-robin (column j + 1 + wave + 16 i), kHhGroup of a wave's columns at a time
-    for (int c0 = j + 1 + wave; c0 < l; c0 += kHhGroup * kHhWaves) {
-      T pv[kHhGroup][NS], pj[kHhGroup], d[kHhGroup];
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) {
-        const T* cc = P + (size_t)min(c0 + u * kHhWaves, l - 1) * RP;
-        pj[u] = cc[j];
-#pragma unroll
-        for (int i = 0; i < NS; ++i) pv[u][i] = cc[rr[i]];
-      }
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) {
-        d[u] = (T)0;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) d[u] += xr[i] * pv[u][i];
-      }
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) d[u] = hh_wave_sum(d[u]);
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) {
-        const int c = c0 + u * kHhWaves;
-        if (c < l) {
-          T* cc = P + (size_t)c * RP;
-          const T w = tau * (d[u] + pj[u]);
-#pragma unroll
-          for (int i = 0; i < NS; ++i) {
-            const int r = lo + lane + 64 * i;
-            if (r < hi) cc[r] = pv[u][i] - w * xr[i];
-          }
-          if (lane == 0) cc[j] = pj[u] - w;
-        }
-      }
-    }
-    hh_lds_barrier();  // column j + 1 is complete before the next reflector is formed
-  }
-}
-
-// P <- H_0 H_1 ... H_{l-1} P for the rows x l panel P in LDS; reflectors (V, leading dimension ldv) and tau in global
-// memory.  A wave owns its columns throughout: no barriers.
-template <class T, int NS, bool TRI>
-__device__ void hh_apply_panel(T* P, int RP, int rows, int l, const T* __restrict__ V, int64_t ldv,
-                               const T* __restrict__ tau_in) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  T vn[NS];
-  auto load_v = [&](int j) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      const int lo_ = TRI ? l : j + 1, hi_ = TRI ? l + max(j, 0) + 1 : rows;
-      const int r = lo_ + lane + 64 * i;
-      const T val = V[(int64_t)max(j, 0) * ldv + min(r, hi_ - 1)];  // unconditional, clamped
-      vn[i] = (j >= 0 && r < hi_) ? val : (T)0;
-    }
-  };
-  load_v(l - 1);
-  for (int j = l - 1; j >= 0; --j) {
-    T v[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) v[i] = vn[i];
-    const T tau = tau_in[j];
-    load_v(j - 1);  // the next reflector travels while this one is applied
-    if (tau == (T)0) continue;
-    const int lo = TRI ? l : j + 1, hi = TRI ? l + j + 1 : rows;
-    int rr[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) rr[i] = min(lo + lane + 64 * i, hi - 1);
-    for (int c0 = wave; c0 < l; c0 += kHhGroup * kHhWaves) {
-      T pv[kHhGroup][NS], pj[kHhGroup], d[kHhGroup];
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) {
-        const T* cc = P + (size_t)min(c0 + u * kHhWaves, l - 1) * RP;
-        pj[u] = cc[j];
-#pragma unroll
-        for (int i = 0; i < NS; ++i) pv[u][i] = cc[rr[i]];
-      }
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) {
-        d[u] = (T)0;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) d[u] += v[i] * pv[u][i];
-      }
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) d[u] = hh_wave_sum(d[u]);
-#pragma unroll
-      for (int u = 0; u < kHhGroup; ++u) {
-        const int c = c0 + u * kHhWaves;
-        if (c < l) {
-          T* cc = P + (size_t)c * RP;
-          const T w = tau * (d[u] + pj[u]);
-#pragma unroll
-          for (int i = 0; i < NS; ++i) {
-            const int r = lo + lane + 64 * i;
-            if (r < hi) cc[r] = pv[u][i] - w * v[i];
-          }
-          if (lane == 0) cc[j] = pj[u] - w;
-        }
-      }
-    }
-  }
-}
-
 // ---- blocked (compact WY) panels: reflector steps inside 16-column blocks, everything else on the MFMA units ------------
 // H_0 ... H_{15} of one block = I - V T V^T (V: unit lower trapezoidal, T: 16 x 16 upper triangular, LAPACK xLARFT).
 //   factor : (a) the block's columns live in the registers of one wave each; reflector jj is formed by its owner, written
@@ -236,8 +80,7 @@ __device__ void hh_apply_panel(T* P, int RP, int rows, int l, const T* __restric
 //                the reduction index permuted to the D layout (step i of a 16-deep product takes k = drow(lane, i)).
 //   apply  : P <- (I - V T V^T) P block by block in reverse, V and T streamed from global memory (L1 / L2 resident; the
 //            panel fills the LDS); a wave owns its 16-column tiles for the whole panel: no barriers.
-// tau = 0 (a column that is already reduced) gives a zero column in T: the reflector drops out, as in the unblocked code.
-constexpr int kWyNb = 16;
+// tau = 0 (a column that is already reduced) gives a zero column in T: the reflector drops out.
 // (A variant in which ONE wave owns a whole 16-column block of a tree node in registers -- no barrier between reflector
 // steps -- measured slower, 142 -> 184 us per node in f32 and worse in f64, and was removed in round 3: CHANGELOG.md.)
 constexpr int kWyPipe = 8;      // k-steps whose operand loads are issued before their MFMAs
@@ -247,11 +90,6 @@ constexpr int kWyApplyPipe = 8;   // (16 / 6 measured slower: the masked last tr
 constexpr int kWyApplyRowTiles = 3;
 static_assert(kHhWaves >= kWyNb, "one wave per column of a block");
 static_assert(kHhMaxRowsPerLane * 64 / 2 / 16 + 1 <= kHhWaves - 1, "trailing tiles of a block: one wave each, the last wave builds T");
-constexpr int kWyExtra = 2 * kWyNb * kWyNb + kWyNb;  // Ts, Rs (parked diagonal block), tau_s (elements) in front of the panel
-__host__ __device__ inline size_t hh_wy_lds_bytes(int max_rows, int l, size_t esz) {
-  return hh_lds_bytes(max_rows, l, esz) + (size_t)kWyExtra * esz;
-}
-__host__ __device__ inline int hh_wy_panels(int l) { return (l + kWyNb - 1) / kWyNb; }
 
 // entry (r, c) of the block's V as the MFMA operands need it.  V is stored CLEAN (explicit 1 on the diagonal, 0 above
 // it: the factor kernels park the R entries of the block's 16 x 16 diagonal block in LDS while the block is being applied,
@@ -606,12 +444,12 @@ __device__ void hh_wy_apply_panel(T* P, int RP, int rows, int l, const T* __rest
 // ---- up sweep -----------------------------------------------------------------------------------------------------
 // leaves: panel i = rows [row0(i), row0(i + 1)) of y (column-major, ld ldy).  Reflectors -> v (same layout as y),
 // tau -> tau[i * l ..], R -> rout[i * l * l ..] (l x l column-major, zeros below the diagonal).
-template <class T, bool WY>
+template <class T>
 __global__ __launch_bounds__(kHhThreads) void hh_leaf_factor_kernel(const T* __restrict__ y, int64_t ldy, int64_t m, int l,
                                                                     int nleaf, T* __restrict__ v, int64_t ldv, T* tau,
                                                                     T* rout, T* tbuf) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* P = (T*)smem + (WY ? kWyExtra : 0);
+  T* P = (T*)smem + kWyExtra;
   const int node = blockIdx.x;
   const int64_t r0 = hh_leaf_row0(m, nleaf, node);
   const int rows = (int)(hh_leaf_row0(m, nleaf, node + 1) - r0);
@@ -621,16 +459,13 @@ __global__ __launch_bounds__(kHhThreads) void hh_leaf_factor_kernel(const T* __r
     P[(size_t)c * RP + r] = y[(int64_t)c * ldy + r0 + r];
   }
   __syncthreads();
-  if constexpr (WY)
-    hh_wy_factor_panel<T, kHhMaxRowsPerLane, false>(P, RP, rows, l, tau + (size_t)node * l,
-                                                    tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb, (T*)smem,
-                                                    (T*)smem + kWyNb * kWyNb, (T*)smem + 2 * kWyNb * kWyNb);
-  else
-    hh_factor_panel<T, kHhMaxRowsPerLane, false>(P, RP, rows, l, tau + (size_t)node * l);
+  hh_wy_factor_panel<T, kHhMaxRowsPerLane, false>(P, RP, rows, l, tau + (size_t)node * l,
+                                                  tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb, (T*)smem,
+                                                  (T*)smem + kWyNb * kWyNb, (T*)smem + 2 * kWyNb * kWyNb);
   for (int idx = threadIdx.x; idx < rows * l; idx += kHhThreads) {
     const int c = idx / rows, r = idx - c * rows;
     const T pv = P[(size_t)c * RP + r];
-    v[(int64_t)c * ldv + r0 + r] = WY ? (r > c ? pv : (r == c ? (T)1 : (T)0)) : pv;  // blocked form: clean reflectors
+    v[(int64_t)c * ldv + r0 + r] = r > c ? pv : (r == c ? (T)1 : (T)0);  // clean reflectors
   }
   T* ro = rout + (size_t)node * l * l;
   for (int idx = threadIdx.x; idx < l * l; idx += kHhThreads) {
@@ -641,11 +476,11 @@ __global__ __launch_bounds__(kHhThreads) void hh_leaf_factor_kernel(const T* __r
 
 // inner level: node t combines rin[2 t] and rin[2 t + 1] (an unpaired last R is passed through, tau = 0).
 // Reflectors -> v[t] (2 l x l, ld 2 l), tau -> tau[t * l ..], R -> rout[t].
-template <class T, bool WY>
+template <class T>
 __global__ __launch_bounds__(kHhThreads) void hh_tree_factor_kernel(const T* __restrict__ rin, int n_in, int l, T* __restrict__ v,
                                                                     T* tau, T* rout, T* tbuf) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* P = (T*)smem + (WY ? kWyExtra : 0);
+  T* P = (T*)smem + kWyExtra;
   const int node = blockIdx.x;
   const int a = 2 * node, b = 2 * node + 1;
   T* ro = rout + (size_t)node * l * l;
@@ -661,17 +496,14 @@ __global__ __launch_bounds__(kHhThreads) void hh_tree_factor_kernel(const T* __r
     P[(size_t)c * RP + l + r] = rin[(size_t)b * l * l + idx];
   }
   __syncthreads();
-  if constexpr (WY)
-    hh_wy_factor_panel<T, kHhTriSlices + 1, true>(P, RP, rows, l, tau + (size_t)node * l,
-                                                  tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb, (T*)smem,
-                                                  (T*)smem + kWyNb * kWyNb, (T*)smem + 2 * kWyNb * kWyNb);
-  else
-    hh_factor_panel<T, kHhTriSlices, true>(P, RP, rows, l, tau + (size_t)node * l);
+  hh_wy_factor_panel<T, kHhTriSlices + 1, true>(P, RP, rows, l, tau + (size_t)node * l,
+                                                tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb, (T*)smem,
+                                                (T*)smem + kWyNb * kWyNb, (T*)smem + 2 * kWyNb * kWyNb);
   T* vo = v + (size_t)node * rows * l;
   for (int idx = threadIdx.x; idx < rows * l; idx += kHhThreads) {
     const int c = idx / rows, r = idx - c * rows;
     const T pv = P[(size_t)c * RP + r];
-    vo[idx] = WY ? (r > c ? pv : (r == c ? (T)1 : (T)0)) : pv;
+    vo[idx] = r > c ? pv : (r == c ? (T)1 : (T)0);
   }
   for (int idx = threadIdx.x; idx < l * l; idx += kHhThreads) {
     const int c = idx / l, r = idx - c * l;
@@ -682,7 +514,7 @@ __global__ __launch_bounds__(kHhThreads) void hh_tree_factor_kernel(const T* __r
 // ---- down sweep ---------------------------------------------------------------------------------------------------
 // inner level: node t turns its coefficient block cin[t] (l x l; the identity when cin == nullptr: the root) into
 // the blocks of its children cout[2 t], cout[2 t + 1].
-template <class T, bool WY>
+template <class T>
 __global__ __launch_bounds__(kHhThreads) void hh_tree_apply_kernel(const T* __restrict__ cin, const T* __restrict__ v,
                                                                    const T* __restrict__ tau, int n_children, int l, T* cout,
                                                                    const T* __restrict__ tbuf) {
@@ -704,11 +536,8 @@ __global__ __launch_bounds__(kHhThreads) void hh_tree_apply_kernel(const T* __re
     P[(size_t)c * RP + l + r] = (T)0;
   }
   __syncthreads();
-  if constexpr (WY)
-    hh_wy_apply_panel<T, true>(P, RP, rows, l, v + (size_t)node * rows * l, (int64_t)rows,
-                         tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb);
-  else
-    hh_apply_panel<T, kHhTriSlices, true>(P, RP, rows, l, v + (size_t)node * rows * l, (int64_t)rows, tau + (size_t)node * l);
+  hh_wy_apply_panel<T, true>(P, RP, rows, l, v + (size_t)node * rows * l, (int64_t)rows,
+                             tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb);
   __syncthreads();
   for (int idx = threadIdx.x; idx < l * l; idx += kHhThreads) {
     const int c = idx / l, r = idx - c * l;
@@ -718,7 +547,7 @@ __global__ __launch_bounds__(kHhThreads) void hh_tree_apply_kernel(const T* __re
 }
 
 // leaves: rows of Q = H_0 ... H_{l-1} [cin[i]; 0]  (cin == nullptr: a single leaf, coefficient block = identity)
-template <class T, bool WY>
+template <class T>
 __global__ __launch_bounds__(kHhThreads) void hh_leaf_apply_kernel(const T* __restrict__ cin, const T* __restrict__ v, int64_t ldv,
                                                                    const T* __restrict__ tau, int64_t m, int l, int nleaf,
                                                                    T* __restrict__ q, int64_t ldq, const T* __restrict__ tbuf) {
@@ -735,10 +564,7 @@ __global__ __launch_bounds__(kHhThreads) void hh_leaf_apply_kernel(const T* __re
     P[(size_t)c * RP + r] = val;
   }
   __syncthreads();
-  if constexpr (WY)
-    hh_wy_apply_panel<T, false>(P, RP, rows, l, v + r0, ldv, tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb);
-  else
-    hh_apply_panel<T, kHhMaxRowsPerLane, false>(P, RP, rows, l, v + r0, ldv, tau + (size_t)node * l);
+  hh_wy_apply_panel<T, false>(P, RP, rows, l, v + r0, ldv, tbuf + (size_t)node * hh_wy_panels(l) * kWyNb * kWyNb);
   __syncthreads();
   for (int idx = threadIdx.x; idx < rows * l; idx += kHhThreads) {
     const int c = idx / rows, r = idx - c * rows;

@@ -248,21 +248,23 @@ class EmuDev {
     float min_ratio, dev_i, gmax;
     long long clk, wall;  // same 32-byte record as the device kernel's
   };
-  template <class T>
-  bool device_chol_fits(int64_t l) const {
-    return l <= (sizeof(T) == 8 ? 152 : 176) && !std::getenv("CORRLA_EMU_NO_DEVICE_CHOL");
+  // the device's routes (thinq_plan.hpp, the functions HipDev reads), with the emulation's own switches as knobs; read at
+  // every call: the tests set and clear them around single calls
+  ThinQKnobs thinq_knobs() const {
+    ThinQKnobs kn;
+    kn.host_chol = std::getenv("CORRLA_EMU_NO_DEVICE_CHOL") != nullptr;
+    kn.robust_qr = std::getenv("CORRLA_EMU_NO_ROBUST_QR") == nullptr;
+    if (const char* e = std::getenv("CORRLA_HH_BLOCK")) kn.hh_block = std::atoll(e);
+    return kn;
   }
   template <class T>
-  bool device_chol_blocked_fits(int64_t l) const {
-    return l > 8 && l <= 276 && !std::getenv("CORRLA_EMU_NO_DEVICE_CHOL");
-  }
+  bool device_chol_fits(int64_t l) const { return thinq_route(sizeof(T), l, thinq_knobs()).factor == ThinQFactor::kSingle; }
+  template <class T>
+  bool device_chol_blocked_fits(int64_t l) const { return thinq_route(sizeof(T), l, thinq_knobs()).factor == ThinQFactor::kBlocked2x2; }
   // ---- Householder TSQR with explicit thin Q: the same panel partition, pairwise tree and reverse application as
   // csrc/tsqr_kernels.hpp / HipDev::householder_thin_q, written with plain loops --------------------------------
   template <class T>
-  bool householder_fits(int64_t l) const {
-    // one 2 l x l panel plus the blocked form's 16 x 16 T / parked-R blocks and tau (528 elements) in 160 KB of LDS
-    return l >= 1 && (size_t)((2 * l + 3) / 4 * 4) * (size_t)l * sizeof(T) + 64 + 528 * sizeof(T) <= (size_t)160 * 1024 && 2 * l <= 320;
-  }
+  bool householder_fits(int64_t l) const { return hh_fits(sizeof(T), l); }
   template <class T>
   static void hh_factor_panel(std::vector<T>& P, int rows, int l, T* tau) {  // P column-major rows x l
     for (int j = 0; j < l; ++j) {
@@ -424,11 +426,7 @@ class EmuDev {
     householder_down(h, y, tmp);
   }
   template <class T>
-  int householder_max_width() const {
-    int w = 1;
-    while (householder_fits<T>(w + 1)) ++w;
-    return w;
-  }
+  int householder_max_width() const { return (int)hh_capped_width(hh_max_width(sizeof(T)), thinq_knobs().hh_block); }
   int rank() const { return g_rank; }
 
   template <class T>
@@ -507,10 +505,8 @@ class EmuDev {
   void read_flags(const int* dev_p, int n, int* host) { std::memcpy(host, dev_p, sizeof(int) * (size_t)n); }
   void read_bytes(const void* dev_p, size_t bytes, void* host) { std::memcpy(host, dev_p, bytes); }
   template <class T>
-  bool device_qr_robust_fits(int64_t l) const {
-    return (device_chol_fits<T>(l) || device_chol_blocked_fits<T>(l)) && !std::getenv("CORRLA_EMU_NO_ROBUST_QR");
-  }
-  bool qr_inplace_fits(int64_t l) const { return col_blocking(l).nblk == 1; }
+  bool device_qr_robust_fits(int64_t l) const { return thinq_route(sizeof(T), l, thinq_knobs()).robust; }
+  bool qr_inplace_fits(int64_t l) const { return thinq_route(sizeof(float), l, thinq_knobs()).inplace; }
   template <class T>
   struct EmuInspect {
     T shift;

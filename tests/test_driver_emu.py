@@ -333,7 +333,7 @@ def _thin_q_route_input(dtype, l, spectrum):
 
 # (dtype, l, spectrum, qr_passes).  The widths straddle every switch of the thin-Q: the blocked floor (9), products in place
 # or conditional passes in pairs (144 | 145), one factor kernel or the 2 x 2 blocked form (f32 176 | 177, f64 152 | 153).
-# qr_passes as measured on commit 50e5020 (the parent of the thin-Q refactor), every row.
+# qr_passes as measured on commit 50e5020 (the parent of the thin-Q refactor), every row down to f64 153.
 _THIN_Q_ROUTES = [
     (np.float32, 9, "flat", 5), (np.float32, 9, "decay", 5),
     (np.float32, 144, "flat", 6), (np.float32, 144, "decay", 12),
@@ -342,6 +342,12 @@ _THIN_Q_ROUTES = [
     (np.float32, 177, "flat", 6), (np.float32, 177, "decay", 13),
     (np.float64, 152, "flat", 5), (np.float64, 152, "decay", 9),
     (np.float64, 153, "flat", 5), (np.float64, 153, "decay", 9),
+    # the upper ends of the blocked form and the first width of the host-controlled loop (f32 352 | 353, f64 304 | 305), which
+    # the emulation reaches since it reads the device's limits from thinq_plan.hpp.  qr_passes as measured on commit 5f6dc07
+    # with the emulation's own limit of the blocked form (276) replaced by the device's, nothing else.
+    # (the decay rows at 352 and 304 -- 13 and 10 passes there, and reproduced here -- are left out: 17 s between them)
+    (np.float32, 352, "flat", 7), (np.float32, 353, "flat", 5),
+    (np.float64, 304, "flat", 5), (np.float64, 305, "flat", 5),
 ]
 
 
