@@ -33,6 +33,8 @@ PCA_APPLY_ROUTE_INPLACE, PCA_APPLY_ROUTE_INPLACE_CHECKED, PCA_APPLY_ROUTE_REPACK
 PCA_APPLY_ROUTES = {PCA_APPLY_ROUTE_INPLACE: "inplace", PCA_APPLY_ROUTE_INPLACE_CHECKED: "inplace_checked",
                     PCA_APPLY_ROUTE_REPACKED: "repacked"}
 PCA_APPLY_CENTRINGS = {1: "fused", 2: "copy"}
+# corrla_polyfit_gram_* / corrla_poly_eval_*: what corrla_ctx_last_polyfit reports
+POLYFIT_ROUTES = {1: "inplace", 2: "inplace_checked"}
 UNIQUE_ID_BYTES = 128
 
 
@@ -63,6 +65,7 @@ def _sigs():
         "corrla_comm_unique_id": (C.c_int, [vp]),
         "corrla_ctx_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int]),
         "corrla_ctx_last_pca_apply": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "corrla_ctx_last_polyfit": (C.c_int, [vp, C.POINTER(C.c_int)]),
     }
     for suf, sc in (("f32", flt), ("f64", dbl)):
         rsvd = [vp, vp, i64, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
@@ -98,6 +101,12 @@ def _sigs():
         points = [vp, vp, i64, i64, vp, i64, i64, i64, C.c_int, dbl]
         s["corrla_rbf_matrix_" + suf] = s["corrla_rbf_matrix_dev_" + suf] = (C.c_int, points + [vp, i64])
         s["corrla_rbf_apply_" + suf] = s["corrla_rbf_apply_dev_" + suf] = (C.c_int, points + [C.c_int, vp, i64, i64, vp, i64])
+        # polynomial response surfaces: x, m, k, ldx, y, r, ldy, degree, normalize, G, ldg, means, scales /
+        # x, m, k, ldx, coeffs, ldc, r, degree, out, ld_out, jac, ld_jac
+        gram = [vp, vp, i64, i64, i64, vp, i64, i64, C.c_int, C.c_int, vp, i64, vp, vp]
+        s["corrla_polyfit_gram_" + suf] = s["corrla_polyfit_gram_dev_" + suf] = (C.c_int, gram)
+        peval = [vp, vp, i64, i64, i64, vp, i64, i64, C.c_int, vp, i64, vp, i64]
+        s["corrla_poly_eval_" + suf] = s["corrla_poly_eval_dev_" + suf] = (C.c_int, peval)
         s["corrla_fill_normal_dev_" + suf] =(C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])

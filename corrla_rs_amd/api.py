@@ -773,6 +773,141 @@ class Context:
             L.check(self._lib.corrla_ctx_synchronize(self._h))
         return out
 
+    # ---- polynomial response surfaces (stats_corr.rs:146-249) ---------------------------------------
+    @staticmethod
+    def _poly_degree(degree):
+        if isinstance(degree, (bool, np.bool_)) or not isinstance(degree, (int, np.integer)) or degree not in (1, 2):
+            raise ValueError("degree must be 1 or 2")
+        return int(degree)
+
+    def _poly_x(self, x, what):
+        """-> (x row-major with unit stride along the features, on_device)"""
+        _reject_bf16(x, what)
+        if _is_sparse(x):
+            raise ValueError(f"{what} takes a dense x")
+        a, on_dev = _as_dense(x, "x")
+        if on_dev:
+            self._on_my_device(a)
+        if a.shape[0] == 0 or a.shape[1] == 0:
+            raise ValueError("x must be non-empty")
+        if a.shape[1] > 128:
+            raise ValueError(f"{what}: x has {a.shape[1]} features, the kernels take 1 to 128")
+        return self._rbf_rowmajor(a, on_dev), on_dev
+
+    def _polyfit_done(self, on_device):
+        if on_device:  # the device entry only enqueues: torch's streams see the results after this
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        route = C.c_int(0)
+        L.check(self._lib.corrla_ctx_last_polyfit(self._h, C.byref(route)))
+        self._polyfit_route = L.POLYFIT_ROUTES.get(route.value)
+
+    def polyfit_gram(self, x, y=None, degree=2, *, normalize=True):
+        """The normal equations of a polynomial least-squares fit without the Vandermonde matrix -> (G, means, scales).
+
+        With V = [z, z_a z_b (a <= b, a outer), 1] (degree 2; [z, 1] for degree 1 -- ``build_vandermonde``,
+        stats_corr.rs:201-209) of the samples z = (x - means) * (1 / scales) and W = [V, y], G = W^T W of order p + r
+        (p = k + k (k + 1) / 2 + 1 or k + 1; r the columns of y, 0 without y): ``G[:p, :p]`` is V^T V, ``G[:p, p:]`` is
+        V^T y and ``G[p:, p:]`` is y^T y.  One fused MFMA kernel (corrla_polyfit_gram_*) forms the columns of W in registers;
+        all arithmetic is f64 and float32 input is widened in place.  G, means (1, k) and scales (1, k) are float64 for
+        either input type; G is bitwise symmetric and bitwise reproducible.  normalize=True (the default) centres and scales
+        every feature by its mean and population standard deviation (1 for a constant column) inside the kernel, which is
+        what keeps V^T V solvable for data away from the origin; normalize=False takes x as it is and returns None for
+        means and scales.  1 <= k <= 128, at most 64 columns of y.
+        numpy in -> numpy out; a CUDA tensor in -> tensors on its device.  bfloat16 and sparse inputs raise ValueError.
+        ``last_polyfit_route()`` names the route that served the call."""
+        degree = self._poly_degree(degree)
+        normalize = _check_bool("normalize", normalize, ValueError)
+        a, on_dev = self._poly_x(x, "polyfit_gram")
+        m, kf = (int(v) for v in a.shape)
+        if y is None:
+            yy, r, ldy = None, 0, 0
+        else:
+            _reject_bf16(y, "polyfit_gram")
+            if _is_sparse(y):
+                raise ValueError("polyfit_gram takes a dense y")
+            yy = self._model_array(y, a, on_dev)
+            if yy.ndim == 1:
+                yy = yy.reshape(-1, 1)
+            if yy.ndim != 2 or yy.shape[0] != m:
+                raise ValueError(f"y must have {m} rows, one per sample, got shape {tuple(yy.shape)}")
+            r = int(yy.shape[1])
+            if r > 64:
+                raise ValueError(f"polyfit_gram: y has {r} columns, the kernels take at most 64")
+            if r == 0:
+                yy = None
+            else:
+                yy = self._rbf_rowmajor(yy, on_dev)
+            ldy = self._row_stride(yy) if r else 0
+        order = (kf + 1 if degree == 1 else kf + kf * (kf + 1) // 2 + 1) + r
+        if on_dev:
+            import torch
+            g = torch.empty((order, order), dtype=torch.float64, device=a.device)
+            means = torch.empty((1, kf), dtype=torch.float64, device=a.device) if normalize else None
+            scales = torch.empty((1, kf), dtype=torch.float64, device=a.device) if normalize else None
+            _sync_stream(a)
+        else:
+            g = np.empty((order, order), dtype=np.float64)
+            means = np.empty((1, kf), dtype=np.float64) if normalize else None
+            scales = np.empty((1, kf), dtype=np.float64) if normalize else None
+        L.check(self._entry("corrla_polyfit_gram_", on_dev, a.dtype)(self._h, _ptr(a), m, kf, self._row_stride(a),
+                                                                    None if yy is None else _ptr(yy), r, ldy, degree, int(normalize),
+                                                                    _ptr(g), order, None if means is None else _ptr(means),
+                                                                    None if scales is None else _ptr(scales)))
+        self._polyfit_done(on_dev)
+        return g, means, scales
+
+    def poly_eval(self, x, coeffs, degree=2, *, jac=False):
+        """The polynomial with the coefficients `coeffs` at the rows of x -> values (m, r), or (values, gradients) with jac.
+
+        `coeffs` is (p, r) -- a vector is one column -- in the column order of ``build_vandermonde`` (stats_corr.rs:201-209):
+        [x, x_a x_b (a <= b, a outer), 1] for degree 2, [x, 1] for degree 1, in the coordinates of x; they are taken as
+        float64 whatever the type of x.  What ``quad_eval`` (stats_corr.rs:222-226) computes as V(x) @ coeffs is computed
+        here as xt^T C xt with xt = [x, 1] and C the symmetric (k + 1) x (k + 1) matrix of one coefficient column, on the
+        f64 MFMAs (corrla_poly_eval_*); V is never formed.  jac=True also returns the analytic gradients 2 (C xt)[:k] from
+        the same product: shape (m, k) for r = 1 and (r, m, k) otherwise.  Values and gradients have the dtype of x.
+        numpy in -> numpy out; a CUDA tensor in -> tensors on its device.  bfloat16 and sparse inputs raise ValueError."""
+        degree = self._poly_degree(degree)
+        jac = _check_bool("jac", jac, ValueError)
+        a, on_dev = self._poly_x(x, "poly_eval")
+        m, kf = (int(v) for v in a.shape)
+        _reject_bf16(coeffs, "poly_eval")
+        if _is_sparse(coeffs):
+            raise ValueError("poly_eval takes dense coefficients")
+        if on_dev:
+            import torch
+            c = self._model_array(coeffs, torch.empty(0, dtype=torch.float64, device=a.device), True)
+        else:
+            c = self._model_array(coeffs, np.empty(0, dtype=np.float64), False)
+        if c.ndim == 1:
+            c = c.reshape(-1, 1)
+        p = kf + 1 if degree == 1 else kf + kf * (kf + 1) // 2 + 1
+        if c.ndim != 2 or c.shape[0] != p or c.shape[1] == 0:
+            raise ValueError(f"coeffs must have p = {p} rows for {kf} features at degree {degree}, got shape {tuple(c.shape)}")
+        r = int(c.shape[1])
+        if r > 64:
+            raise ValueError(f"poly_eval: coeffs has {r} columns, the kernels take at most 64")
+        c = self._rbf_rowmajor(c, on_dev)
+        if on_dev:
+            out = torch.empty((m, r), dtype=a.dtype, device=a.device)
+            grad = torch.empty((r, m, kf), dtype=a.dtype, device=a.device) if jac else None
+            _sync_stream(a)
+        else:
+            out = np.empty((m, r), dtype=a.dtype)
+            grad = np.empty((r, m, kf), dtype=a.dtype) if jac else None
+        L.check(self._entry("corrla_poly_eval_", on_dev, a.dtype)(self._h, _ptr(a), m, kf, self._row_stride(a), _ptr(c),
+                                                                 self._row_stride(c), r, degree, _ptr(out), r,
+                                                                 None if grad is None else _ptr(grad), kf))
+        self._polyfit_done(on_dev)
+        if not jac:
+            return out
+        return out, (grad[0] if r == 1 else grad)
+
+    def last_polyfit_route(self):
+        """The route of this context's last ``polyfit_gram`` / ``poly_eval`` call: "inplace" (x read where it lies with 16-byte
+        loads) or "inplace_checked" (element loads: the base or the row stride of x not 16-byte aligned); None before the
+        first call.  y, the narrow operand, is read by its own alignment and does not change the route."""
+        return getattr(self, "_polyfit_route", None)
+
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
         """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that

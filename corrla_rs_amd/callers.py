@@ -15,6 +15,10 @@ reference also does after its random_svd calls (k = n_modes, a few tens), writte
   mat_cov_centered(x) / pearson_corr(x) / rsquared_sens(x, y, cor_dof)
                                               <- src/lib_math_utils/stats_corr.rs:14-43, 75-107 (the n x n matrix from
                                                  the symmetric MFMA kernel, ``Context.cov``)
+  linear_fit / quad_fit / quad_eval / jac_from_lin / jac_from_quad
+                                              <- src/lib_math_utils/stats_corr.rs:146-249 (the normal equations and the
+                                                 evaluation from the fused kernels, ``Context.polyfit_gram`` /
+                                                 ``poly_eval``; the p-sized solve on the host)
 Every product with an n_x- or N-sized dimension goes through the library's HIP GEMMs (``Context.matmul``); only
 snapshot-count- and n_modes-sized matrices are touched by numpy."""
 import numpy as np
@@ -22,7 +26,8 @@ import numpy as np
 from .api import _is_torch, default_context, rsvd
 
 __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyGradientEstimator", "ActiveSsRsvd",
-           "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply"]
+           "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply",
+           "linear_fit", "quad_fit", "quad_eval", "jac_from_lin", "jac_from_quad", "polyfit_solve"]
 
 
 def _on_gpu(x):
@@ -67,6 +72,115 @@ def rsquared_sens(x, y, cor_dof, *, ctx=None):
     if cor_dof:
         r_sqr = 1.0 - (1.0 - r_sqr) * ((n_samples - 1.0) / (n_samples - k_features - 1.0))
     return r_sqr
+
+
+# ---- global polynomial response surfaces (stats_corr.rs:146-249) -----------------------------------------------------------
+def _poly_sym(c, k, degree):
+    """The coefficient columns c (p, r) in the column order [x, x_a x_b (a <= b, a outer), 1] (degree 1: [x, 1]) as r
+    symmetric matrices C (r, k + 1, k + 1) with V(x) c = xt^T C xt, xt = [x, 1]: C(a, a) = c_aa, C(a, b) = c_ab / 2,
+    C(a, k) = c_a / 2, C(k, k) = c_0."""
+    r = c.shape[1]
+    out = np.zeros((r, k + 1, k + 1))
+    out[:, :k, k] = out[:, k, :k] = 0.5 * c[:k].T
+    out[:, k, k] = c[-1]
+    if degree >= 2:
+        ia, ib = np.triu_indices(k)  # a-major, b >= a: the order of mat_col_interactions
+        q = c[k:-1].T
+        out[:, ia, ib] = 0.5 * q
+        out[:, ib, ia] += 0.5 * q    # the diagonal gets both halves
+    return out
+
+
+def _poly_unsym(cm, k, degree):
+    """the inverse of _poly_sym: (r, k + 1, k + 1) -> (p, r)"""
+    rows = [2.0 * cm[:, :k, k].T]
+    if degree >= 2:
+        ia, ib = np.triu_indices(k)
+        rows.append((cm[:, ia, ib] * np.where(ia == ib, 1.0, 2.0)).T)
+    rows.append(cm[:, k, k][None, :])
+    return np.vstack(rows)
+
+
+def polyfit_solve(g, k, degree, means=None, scales=None):
+    """Coefficients (p, r) of the least-squares polynomial from the Gram matrix G of ``Context.polyfit_gram`` (order p + r),
+    in the coordinates of the raw x.  p-sized host work:
+      1. V^T V = G[:p, :p] is equilibrated by its diagonal (D^-1/2 A D^-1/2, unit diagonal);
+      2. its symmetric eigendecomposition is taken;
+      3. only eigenvalues above p 2^-52 lambda_max are inverted -- the minimum-norm solution of the equilibrated system.
+         This is the one deliberate difference from the reference: ``mat_pinv`` (mat_utils.rs:37-53) divides by s + 1e-14,
+         which turns an exactly rank-deficient V into coefficients of order 1e14 times rounding noise; here the null
+         directions are dropped;
+      4. the coefficients of the normalised samples z = (x - means) / scales are mapped back to x by the congruence
+         C_x = M^T C_z M, M = [[diag(1 / scales), -means / scales], [0, 1]], on the symmetric form of every column."""
+    g = np.asarray(g, dtype=np.float64)
+    p = k + 1 if degree < 2 else k + k * (k + 1) // 2 + 1
+    a, b = g[:p, :p], g[:p, p:]
+    d = np.sqrt(np.diag(a))
+    d = np.where(d > 0.0, d, 1.0)
+    w, q = np.linalg.eigh(a / np.outer(d, d))
+    keep = w > p * 2.0 ** -52 * w[-1]
+    qk = q[:, keep]
+    cz = (qk @ ((qk.T @ (b / d[:, None])) / w[keep][:, None])) / d[:, None]
+    if means is None and scales is None:
+        return cz
+    mu = np.zeros(k) if means is None else np.asarray(means, dtype=np.float64).reshape(-1)
+    sg = np.ones(k) if scales is None else np.asarray(scales, dtype=np.float64).reshape(-1)
+    # In extended precision, rounded once: for data far from the origin the intercept of the raw coordinates is a sum of
+    # terms (mean / scale)^2 times larger than itself, and (k + 1)^2 numbers per column cost nothing.
+    mm = np.zeros((k + 1, k + 1), dtype=np.longdouble)
+    inv = (1.0 / sg).astype(np.longdouble)          # the kernel's z = (x - means) * fl(1 / scales)
+    mm[np.arange(k), np.arange(k)] = inv
+    mm[:k, k] = -mu.astype(np.longdouble) * inv
+    mm[k, k] = 1.0
+    return _poly_unsym(mm.T @ _poly_sym(cz, k, degree).astype(np.longdouble) @ mm, k, degree).astype(np.float64)
+
+
+def _poly_fit(x, y, degree, normalize, ctx):
+    c = ctx or default_context()
+    g, means, scales = c.polyfit_gram(x, y, degree, normalize=normalize)
+    k = int(x.shape[1])
+    on_gpu = _is_torch(g)
+    host = (lambda v: None if v is None else v.cpu().numpy()) if on_gpu else (lambda v: v)
+    coeffs = polyfit_solve(host(g), k, degree, host(means), host(scales))
+    if on_gpu:
+        import torch
+        return torch.from_numpy(coeffs).to(g.device)
+    return coeffs
+
+
+def linear_fit(x, y, *, normalize=True, ctx=None):
+    """``linear_fit(x, y)`` (stats_corr.rs:146-160): least-squares coefficients (k + 1, r) of y = [x, 1] c -- slopes, then
+    the intercept -- from the fused normal-equation kernel (``Context.polyfit_gram``) and the host solve of
+    ``polyfit_solve``; the (m, k + 1) Vandermonde matrix is never stored.  The coefficients are in the coordinates of the
+    raw x whether or not the kernel normalises.  numpy in -> numpy out, CUDA tensors in -> a tensor on their device."""
+    return _poly_fit(x, y, 1, normalize, ctx)
+
+
+def quad_fit(x, y, *, normalize=True, ctx=None):
+    """``quad_fit(x, y)`` (stats_corr.rs:213-219): least-squares coefficients (p, r), p = k + k (k + 1) / 2 + 1, of
+    y = [x, x_a x_b (a <= b, a outer), 1] c, as ``linear_fit``.  Where V is rank-deficient the reference's
+    ``pinv`` with 1 / (s + 1e-14) returns noise along the null directions; this returns the minimum-norm solution of the
+    equilibrated system (``polyfit_solve``), so compare predictions there, not coefficients."""
+    return _poly_fit(x, y, 2, normalize, ctx)
+
+
+def quad_eval(x, coeffs, *, ctx=None):
+    """``quad_eval(x, coeffs)`` (stats_corr.rs:222-226): the quadratic at the rows of x, (m, r), on the device
+    (``Context.poly_eval``)."""
+    return (ctx or default_context()).poly_eval(x, coeffs, 2)
+
+
+def jac_from_lin(x, y, *, normalize=True, ctx=None):
+    """``jac_from_lin(x, y)`` (stats_corr.rs:164-169): the slopes of ``linear_fit`` as a row per column of y, (r, k)."""
+    c = linear_fit(x, y, normalize=normalize, ctx=ctx)
+    return c[:x.shape[1]].T
+
+
+def jac_from_quad(x0, coeffs, *, ctx=None):
+    """``jac_from_quad(x0, coeffs)`` (stats_corr.rs:230-249): the gradient of the quadratic at the rows of x0, (m, k) for one
+    coefficient column and (r, m, k) for r of them.  This is the ANALYTIC gradient 2 (C xt)[:k] from the evaluation kernel;
+    the reference differences forward with eps = 1e-10 and so carries a rounding error of about 4 * 2^-52 max|y| / 1e-10."""
+    return (ctx or default_context()).poly_eval(x0, coeffs, 2, jac=True)[1]
 
 
 class PolyGradientEstimator:

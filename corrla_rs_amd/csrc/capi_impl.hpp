@@ -11,6 +11,7 @@
 #include "../../include/corrla_rsvd.h"
 #include "driver.hpp"
 #include "rbf_plan.hpp"  // rbf_poly_terms, kRbfMaxDim
+#include "polyfit_plan.hpp"  // poly_terms, kPolyMaxK, kPolyMaxRhs
 
 namespace corrla {
 
@@ -933,6 +934,91 @@ inline void rbf_apply_entry(Dev& dev, const RbfCall<T>& c, Run&& run) {
 template <class Dev, class T, class Run>
 inline void rbf_matrix_entry(Dev& dev, const RbfCall<T>& c, Run&& run) {
   rbf_entry<Dev, T>(dev, c, false, run);
+}
+
+// ---- polynomial response surfaces (corrla_polyfit_gram_* / corrla_poly_eval_*, stats_corr.rs:146-249) ------------------------
+// Argument checks of every entry, then `run` -- on a backend that carries the kernels (dev_has_polyfit); any other backend
+// ends the call with EINVAL, never with another way of computing the result.
+template <class T>
+struct PolyGramCall {
+  const T* x;
+  int64_t m, kf, ldx;
+  const T* y;       // m x r, row stride ldy; ignored when r == 0
+  int64_t r, ldy;
+  int degree, normalize;
+  double* g;        // (p + r) x (p + r), row stride ldg
+  int64_t ldg;
+  double* means;    // kf each, written when normalize is set; nullable
+  double* scales;
+  int64_t order() const { return poly_terms(kf, degree) + r; }
+};
+
+template <class Dev, class T, class Run>
+inline void polyfit_gram_entry(Dev&, const PolyGramCall<T>& c, Run&& run) {
+  const char* who = "polyfit_gram";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.x) bad("x is NULL");
+  if (!c.g) bad("G is NULL");
+  if (c.m < 1) bad("m must be >= 1");
+  if (c.kf < 1 || c.kf > k::kPolyMaxK) bad("k must be in [1, 128]");
+  if (c.degree != 1 && c.degree != 2) bad("degree must be 1 or 2");
+  if (c.r < 0 || c.r > k::kPolyMaxRhs) bad("r must be in [0, 64]");
+  if (c.normalize != 0 && c.normalize != 1) bad("normalize must be 0 or 1");
+  if (c.ldx < c.kf) bad("ldx < k");
+  if (c.r > 0 && !c.y) bad("y is NULL");
+  if (c.r > 0 && c.ldy < c.r) bad("ldy < r");
+  if (c.ldg < c.order()) bad("ldg < p + r");
+  const bool norm = c.normalize != 0;
+  const PcaApplyRange in[2] = {{c.x, (size_t)((c.m - 1) * c.ldx + c.kf) * sizeof(T), "x"},
+                               {c.r > 0 ? c.y : nullptr, c.r > 0 ? (size_t)((c.m - 1) * c.ldy + c.r) * sizeof(T) : 0, "y"}};
+  const PcaApplyRange o[3] = {{c.g, (size_t)((c.order() - 1) * c.ldg + c.order()) * sizeof(double), "G"},
+                              {norm ? c.means : nullptr, (size_t)c.kf * sizeof(double), "means"},
+                              {norm ? c.scales : nullptr, (size_t)c.kf * sizeof(double), "scales"}};
+  pca_apply_no_overlap(in, 2, o, 3, who);
+  if constexpr (dev_has_polyfit<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no polynomial response-surface kernels: corrla_polyfit_gram_* is not supported");
+}
+
+template <class T>
+struct PolyEvalCall {
+  const T* x;
+  int64_t m, kf, ldx;
+  const double* coeffs;  // p x r, row stride ldc
+  int64_t ldc, r;
+  int degree;
+  T* out;                // m x r, row stride ld_out
+  int64_t ld_out;
+  T* jac;                // nullable: r slabs of m x kf, row stride ld_jac
+  int64_t ld_jac;
+  int64_t p() const { return poly_terms(kf, degree); }
+};
+
+template <class Dev, class T, class Run>
+inline void poly_eval_entry(Dev&, const PolyEvalCall<T>& c, Run&& run) {
+  const char* who = "poly_eval";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.x) bad("x is NULL");
+  if (!c.coeffs) bad("coeffs is NULL");
+  if (!c.out) bad("out is NULL");
+  if (c.m < 1) bad("m must be >= 1");
+  if (c.kf < 1 || c.kf > k::kPolyMaxK) bad("k must be in [1, 128]");
+  if (c.degree != 1 && c.degree != 2) bad("degree must be 1 or 2");
+  if (c.r < 1 || c.r > k::kPolyMaxRhs) bad("r must be in [1, 64]");
+  if (c.ldx < c.kf) bad("ldx < k");
+  if (c.ldc < c.r) bad("ldc < r");
+  if (c.ld_out < c.r) bad("ld_out < r");
+  if (c.jac && c.ld_jac < c.kf) bad("ld_jac < k");
+  const PcaApplyRange in[2] = {{c.x, (size_t)((c.m - 1) * c.ldx + c.kf) * sizeof(T), "x"},
+                               {c.coeffs, (size_t)((c.p() - 1) * c.ldc + c.r) * sizeof(double), "coeffs"}};
+  const PcaApplyRange o[2] = {{c.out, (size_t)((c.m - 1) * c.ld_out + c.r) * sizeof(T), "out"},
+                              {c.jac, c.jac ? (size_t)((c.r * c.m - 1) * c.ld_jac + c.kf) * sizeof(T) : 0, "jac"}};
+  pca_apply_no_overlap(in, 2, o, 2, who);
+  if constexpr (dev_has_polyfit<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no polynomial response-surface kernels: corrla_poly_eval_* is not supported");
 }
 
 }  // namespace corrla

@@ -10,6 +10,7 @@
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "pca_apply_stage.hpp"
+#include "polyfit_stage.hpp"
 #include "rbf_stage.hpp"
 #include "tall_stage.hpp"
 #include "thinq_stage.hpp"
@@ -22,6 +23,7 @@ struct corrla_ctx {
   std::mutex mu;
   bool profile;
   pca_apply_stage::Ran pca_apply;  // how the last corrla_pca_transform_* / corrla_pca_inverse_* call ran
+  polyfit_stage::Ran polyfit;      // how the last corrla_polyfit_gram_* / corrla_poly_eval_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -368,6 +370,38 @@ CORRLA_DEFINE_RBF(f32, , float, true)
 CORRLA_DEFINE_RBF(f64, , double, true)
 CORRLA_DEFINE_RBF(f32, dev_, float, false)
 CORRLA_DEFINE_RBF(f64, dev_, double, false)
+
+// ---- polynomial response surfaces (linear_fit / quad_fit / quad_eval / jac_from_quad, stats_corr.rs:146-249) ---------------
+#define CORRLA_DEFINE_POLYFIT(SUF, DEV, T, HOST)                                                                        \
+  CORRLA_API corrla_status corrla_polyfit_gram_##DEV##SUF(corrla_ctx* ctx, const T* x, int64_t m, int64_t k, int64_t ldx, const T* y, \
+                                                          int64_t r, int64_t ldy, int degree, int normalize, double* G, int64_t ldg, \
+                                                          double* means, double* scales) {                               \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cx.polyfit = polyfit_stage::Ran();                                                                                \
+      const PolyGramCall<T> c{x, m, k, ldx, y, r, ldy, degree, normalize, G, ldg, means, scales};                       \
+      polyfit_gram_entry<HipDev, T>(cx.dev, c, [&] { polyfit_stage::run_gram<T>(cx.dev, HOST, c, &cx.polyfit); });      \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  CORRLA_API corrla_status corrla_poly_eval_##DEV##SUF(corrla_ctx* ctx, const T* x, int64_t m, int64_t k, int64_t ldx,   \
+                                                       const double* coeffs, int64_t ldc, int64_t r, int degree, T* out, \
+                                                       int64_t ld_out, T* jac, int64_t ld_jac) {                         \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cx.polyfit = polyfit_stage::Ran();                                                                                \
+      const PolyEvalCall<T> c{x, m, k, ldx, coeffs, ldc, r, degree, out, ld_out, jac, ld_jac};                          \
+      poly_eval_entry<HipDev, T>(cx.dev, c, [&] { polyfit_stage::run_eval<T>(cx.dev, HOST, c, &cx.polyfit); });         \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_POLYFIT(f32, , float, true)
+CORRLA_DEFINE_POLYFIT(f64, , double, true)
+CORRLA_DEFINE_POLYFIT(f32, dev_, float, false)
+CORRLA_DEFINE_POLYFIT(f64, dev_, double, false)
+CORRLA_API corrla_status corrla_ctx_last_polyfit(corrla_ctx* ctx, int* route_out) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (route_out) *route_out = c->polyfit.route;
+  });
+}
 
 // ---- active-subspace gradient stage ------------------------------------------------------
 static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,

@@ -122,6 +122,13 @@ struct dev_has_rbf : std::false_type {};
 template <class D>
 struct dev_has_rbf<D, std::void_t<decltype(D::kHasRbf)>> : std::true_type {};
 
+// ... and those that carry the response-surface kernels of corrla_polyfit_gram_* / corrla_poly_eval_* (polyfit_kernels.hpp)
+// with kHasPolyfit.
+template <class D, class = void>
+struct dev_has_polyfit : std::false_type {};
+template <class D>
+struct dev_has_polyfit<D, std::void_t<decltype(D::kHasPolyfit)>> : std::true_type {};
+
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).
 template <class T>

@@ -37,6 +37,7 @@
 #include "syrk_kernels.hpp"
 #include "pca_apply_kernels.hpp"
 #include "rbf_kernels.hpp"
+#include "polyfit_kernels.hpp"
 
 namespace corrla {
 
@@ -119,6 +120,9 @@ namespace rbf_stage {
 template <class T>
 void set_lds_limits();  // rbf_stage.hpp: the radial-basis-function kernels
 }
+namespace polyfit_stage {
+inline void set_lds_limits();  // polyfit_stage.hpp: the polynomial response-surface kernels
+}
 namespace thinq_stage {
 template <class T>
 void set_lds_limits();  // thinq_stage.hpp: the Householder panels
@@ -175,6 +179,7 @@ class HipDev {
     gemm_knobs_.no_rotate = env_int("CORRLA_GEMM_NO_ROTATE", 0) != 0;
     gemm_knobs_.mixed_split = env_int("CORRLA_MIXED_SPLIT", 0);
     syrk_knobs_.slab_rows = env_int("CORRLA_SYRK_SLAB_ROWS", 0);  // syrk_plan.hpp
+    poly_knobs_.slab_rows = env_int("CORRLA_POLYFIT_SLAB_ROWS", 0);  // polyfit_plan.hpp
   }
   ~HipDev() {
     (void)hipSetDevice(device);
@@ -183,6 +188,7 @@ class HipDev {
     for (auto& c : chunks_) (void)hipFree(c.p);
     for (auto& c : zchunks_) (void)hipFree(c.p);
     if (zero_page_) (void)hipFree(zero_page_);
+    if (poly_table_) (void)hipFree(poly_table_);
     if (pinned_) (void)hipHostFree(pinned_);
     for (auto& e : events_)
       if (e) (void)hipEventDestroy(e);
@@ -860,6 +866,44 @@ class HipDev {
   // ---- covariance / correlation matrices (syrk_plan.hpp, syrk_kernels.hpp) -----------------------------------------------
   static constexpr bool kHasSyrk = true;  // driver.hpp: dev_has_syrk
   const SyrkKnobs& syrk_knobs() const { return syrk_knobs_; }
+  // The column moments of x (m x n row-major, ld) in one pass with f64 accumulation (colmom_down_kernel, colmom_final_kernel):
+  // the f64 means and standard deviations (divisor denom; 1 for a constant column), both rounded to T, and the verdict.
+  // Workspace of the arena; enqueues only.
+  template <class T>
+  struct ColMoments {
+    double *mu64, *sd64;
+    T *mu_t, *sd_t;
+    int* is_const;
+  };
+  template <class T>
+  ColMoments<T> col_moments(const T* x, int64_t m, int64_t n, int64_t ld, int aligned, double denom) {
+    constexpr int VEC = k::CvIn<T>::kVec;
+    const int64_t ngroups = (n + VEC - 1) / VEC;
+    int groups = 1;
+    while (groups < k::kCvThreads && groups < ngroups) groups *= 2;
+    const int ny = k::kCvThreads / groups;
+    const int64_t col_blocks = (ngroups + groups - 1) / groups;
+    const int64_t target = (int64_t)num_cus * 8;
+    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((target + col_blocks - 1) / col_blocks, (m + 8 * ny - 1) / (8 * ny)));
+    const int64_t rows_per_slab = (m + want - 1) / want;
+    const int64_t nslab = (m + rows_per_slab - 1) / rows_per_slab;
+    dim3 grid((unsigned)col_blocks, (unsigned)nslab);
+    check_grid(grid);
+    double* psum = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
+    double* psq = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
+    ColMoments<T> cm;
+    cm.mu64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
+    cm.sd64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
+    cm.mu_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
+    cm.sd_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
+    cm.is_const = (int*)alloc_bytes(sizeof(int) * (size_t)n);
+    hipLaunchKernelGGL((k::colmom_down_kernel<T>), grid, dim3(k::kCvThreads), 0, stream, x, m, n, ld, aligned, groups, rows_per_slab,
+                       psum, psq);
+    hipLaunchKernelGGL((k::colmom_final_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)psum,
+                       (const double*)psq, nslab, n, x, (double)m, denom, cm.mu64, cm.mu_t, cm.sd64, cm.sd_t, cm.is_const);
+    CORRLA_HIP(hipGetLastError());
+    return cm;
+  }
   // C (n x n, ldc) = covariance (or, corr, Pearson correlation) of the columns of x: m x n row-major with leading dimension
   // p.ld on the device, read in place.  center: the column moments first (one pass, f64 accumulation), means_out / scales_out
   // (device, optional) receive the means and -- corr only -- the standard deviations.  Enqueues only: no synchronisation.
@@ -872,30 +916,8 @@ class HipDev {
     T *mu_t = nullptr, *sd_t = nullptr;
     int* is_const = nullptr;
     if (center) {
-      constexpr int VEC = k::CvIn<T>::kVec;
-      const int64_t ngroups = (n + VEC - 1) / VEC;
-      int groups = 1;
-      while (groups < k::kCvThreads && groups < ngroups) groups *= 2;
-      const int ny = k::kCvThreads / groups;
-      const int64_t col_blocks = (ngroups + groups - 1) / groups;
-      const int64_t target = (int64_t)num_cus * 8;
-      const int64_t want = std::max<int64_t>(1, std::min<int64_t>((target + col_blocks - 1) / col_blocks, (m + 8 * ny - 1) / (8 * ny)));
-      const int64_t rows_per_slab = (m + want - 1) / want;
-      const int64_t nslab = (m + rows_per_slab - 1) / rows_per_slab;
-      dim3 grid((unsigned)col_blocks, (unsigned)nslab);
-      check_grid(grid);
-      double* psum = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
-      double* psq = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
-      mu64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
-      sd64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
-      mu_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
-      sd_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
-      is_const = (int*)alloc_bytes(sizeof(int) * (size_t)n);
-      hipLaunchKernelGGL((k::colmom_down_kernel<T>), grid, dim3(k::kCvThreads), 0, stream, x, m, n, p.ld, aligned, groups, rows_per_slab,
-                         psum, psq);
-      hipLaunchKernelGGL((k::colmom_final_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)psum,
-                         (const double*)psq, nslab, n, x, (double)m, denom, mu64, mu_t, sd64, sd_t, is_const);
-      CORRLA_HIP(hipGetLastError());
+      const ColMoments<T> cm = col_moments<T>(x, m, n, p.ld, aligned, denom);
+      mu64 = cm.mu64, sd64 = cm.sd64, mu_t = cm.mu_t, sd_t = cm.sd_t, is_const = cm.is_const;
       if (means_out) CORRLA_HIP(hipMemcpyAsync(means_out, mu_t, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
       if (corr && scales_out) CORRLA_HIP(hipMemcpyAsync(scales_out, sd_t, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
     }
@@ -916,6 +938,23 @@ class HipDev {
   static constexpr bool kHasPcaApply = true;  // driver.hpp: dev_has_pca_apply
   // ---- radial-basis-function kernel matrices: rbf_plan.hpp plans, rbf_stage.hpp launches rbf_kernels.hpp ---------------------
   static constexpr bool kHasRbf = true;  // driver.hpp: dev_has_rbf
+  // ---- polynomial response surfaces: polyfit_plan.hpp plans, polyfit_stage.hpp launches polyfit_kernels.hpp ------------------
+  static constexpr bool kHasPolyfit = true;  // driver.hpp: dev_has_polyfit
+  const PolyKnobs& poly_knobs() const { return poly_knobs_; }
+  // The plan's pair table on the device.  It depends on (k, r, degree) alone, so it is uploaded when those change and kept
+  // between calls: a repeated fit enqueues without a synchronising copy.
+  const int32_t* poly_table(int64_t kf, int64_t r, int degree) {
+    const int64_t key = (kf * 128 + r) * 4 + degree;
+    if (key != poly_table_key_) {
+      constexpr size_t kMaxBytes = ((size_t)poly_terms(k::kPolyMaxK, 2) + k::kPolyMaxRhs + k::kPolyBT) * sizeof(int32_t);
+      if (!poly_table_) CORRLA_HIP(hipMalloc((void**)&poly_table_, kMaxBytes));
+      const std::vector<int32_t> t = poly_pair_table(kf, r, degree);
+      sync();  // a queued launch may still read the previous table
+      h2d_bytes(poly_table_, t.data(), t.size() * sizeof(int32_t));
+      poly_table_key_ = key;
+    }
+    return poly_table_;
+  }
   // out(i, c) = d[i] * in(i, c) over every allocated column (the padding columns are zero and stay zero); out may be in
   template <class T>
   void row_scale(const Skinny<T>& in, Skinny<T>& out, int64_t rows, const T* d) {
@@ -1074,6 +1113,9 @@ class HipDev {
   int gemm_debug_flags_ = 0;
   GemmKnobs gemm_knobs_;
   SyrkKnobs syrk_knobs_;
+  PolyKnobs poly_knobs_;
+  int32_t* poly_table_ = nullptr;
+  int64_t poly_table_key_ = -1;
   uint64_t entropy_ = 0, calls_ = 0, calls_sharded_ = 0;
   ThinQKnobs thinq_knobs_;  // thinq_plan.hpp
   const int* run_if_ = nullptr;
@@ -1116,6 +1158,7 @@ class HipDev {
   static void set_lds_limits_typed() {
     tall_stage::set_lds_limits<T>();
     rbf_stage::set_lds_limits<T>();
+    if (sizeof(T) == 8) polyfit_stage::set_lds_limits();
     lds_limit((const void*)k::syrk_kernel<T, true>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::syrk_kernel<T, false>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     thinq_stage::set_lds_limits<T>();

@@ -552,6 +552,58 @@ CORRLA_API corrla_status corrla_rbf_apply_dev_f64(corrla_ctx* ctx, const double*
                                                   int64_t lds, int64_t dim, int kernel, double eps, int poly_degree, const double* coeffs,
                                                   int64_t ldw, int64_t n_rhs, double* out, int64_t ld_out);
 
+/* ---- polynomial response surfaces: the normal equations of the fit and the evaluation --------------
+ * Replaces  linear_fit / jac_from_lin                            src/lib_math_utils/stats_corr.rs:146-169
+ *           build_full_vandermonde / build_vandermonde           src/lib_math_utils/stats_corr.rs:183-209
+ *           quad_fit / quad_eval / jac_from_quad                 src/lib_math_utils/stats_corr.rs:213-249
+ * The reference stores the m x p Vandermonde matrix V = [x, x_a x_b (a <= b, a outer), 1] (degree 2, p = k + k (k + 1) / 2 + 1;
+ * mat_col_interactions, stats_corr.rs:112-142) or [x, 1] (degree 1, p = k + 1) and applies pinv(V).  Here V is never stored.
+ *   corrla_polyfit_gram_*: G = W^T W of order p + r with W = [V(z), y], z = (x - mu) * fl(1 / sigma) when normalize is 1 (mu the
+ *     column means, sigma the population standard deviations, 1 for a constant column; the column pass of corrla_cov_*) and z = x
+ *     when it is 0.  One output holds V^T V (the leading p x p block), V^T y (its last r columns) and y^T y.  Every column of
+ *     W is the product of two entries of the augmented row [z, 1, y]; a workgroup stages those rows, forms its operands in
+ *     registers and feeds v_mfma_f64_16x16x4_f64.  All arithmetic is f64: an f32 x or y is read in place and widened, which
+ *     is exact.  G (row-major, row stride ldg >= p + r), means and scales (k each; written when normalize is 1; either may be
+ *     NULL) are double for both element types.  No atomics: the samples may be split over workgroups whose partial tiles a
+ *     finishing kernel adds in index order, writing G(i, j) and G(j, i) from one value -- G is bitwise symmetric and a fixed
+ *     input gives a bitwise fixed output.  CORRLA_POLYFIT_SLAB_ROWS (read when the context is created) sets the samples per
+ *     workgroup.
+ *   corrla_poly_eval_*: out (m x r, row stride ld_out) = V(x) coeffs, and when jac is not NULL the gradients
+ *     jac[(j m + i) ld_jac + a] = d out(i, j) / d x_a -- r slabs of m x k.  coeffs is double, p x r, row stride ldc, in the
+ *     column order of V above.  V(x) c = xt^T C xt with xt = [x, 1] and C the symmetric (k + 1) x (k + 1) matrix of c, and
+ *     the gradient is 2 (C xt)[:k]: analytic, where jac_from_quad differences forward with eps = 1e-10.
+ * Layouts: x (m x k) and y (m x r) row-major with unit stride along the columns, row strides ldx >= k, ldy >= r; any base
+ * alignment (an x whose base or row stride is off a 16-byte boundary is read with element loads: corrla_ctx_last_polyfit
+ * reports route 2, else 1; y is read by its own alignment).
+ * Limits: 1 <= k <= 128; degree 1 or 2; 0 <= r <= 64 (corrla_poly_eval_*: 1 <= r <= 64); m >= 1; f32 and f64.
+ * CORRLA_EINVAL (the message names the argument): NULL x, G, coeffs, out, or y with r > 0; m < 1; k, degree, r outside the
+ * limits; normalize not 0 or 1; ldx < k; ldy, ldc, ld_out < r; ldg < p + r; ld_jac < k; an output overlapping an input or
+ * another output.  Host-pointer entries copy the operands to the device as they lie and the results back; the *_dev entries
+ * take device pointers for every array, enqueue on the context's stream and return WITHOUT synchronising (but for a first-time
+ * growth of the workspace arena, and the upload of the column table when (k, r, degree) changes): corrla_ctx_synchronize
+ * orders the results. */
+CORRLA_API corrla_status corrla_polyfit_gram_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t k, int64_t ldx, const float* y,
+                                                 int64_t r, int64_t ldy, int degree, int normalize, double* G, int64_t ldg,
+                                                 double* means, double* scales);
+CORRLA_API corrla_status corrla_polyfit_gram_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t k, int64_t ldx, const double* y,
+                                                 int64_t r, int64_t ldy, int degree, int normalize, double* G, int64_t ldg,
+                                                 double* means, double* scales);
+CORRLA_API corrla_status corrla_polyfit_gram_dev_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t k, int64_t ldx, const float* y,
+                                                     int64_t r, int64_t ldy, int degree, int normalize, double* G, int64_t ldg,
+                                                     double* means, double* scales);
+CORRLA_API corrla_status corrla_polyfit_gram_dev_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t k, int64_t ldx, const double* y,
+                                                     int64_t r, int64_t ldy, int degree, int normalize, double* G, int64_t ldg,
+                                                     double* means, double* scales);
+CORRLA_API corrla_status corrla_poly_eval_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t k, int64_t ldx, const double* coeffs,
+                                              int64_t ldc, int64_t r, int degree, float* out, int64_t ld_out, float* jac, int64_t ld_jac);
+CORRLA_API corrla_status corrla_poly_eval_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t k, int64_t ldx, const double* coeffs,
+                                              int64_t ldc, int64_t r, int degree, double* out, int64_t ld_out, double* jac, int64_t ld_jac);
+CORRLA_API corrla_status corrla_poly_eval_dev_f32(corrla_ctx* ctx, const float* x, int64_t m, int64_t k, int64_t ldx, const double* coeffs,
+                                                  int64_t ldc, int64_t r, int degree, float* out, int64_t ld_out, float* jac, int64_t ld_jac);
+CORRLA_API corrla_status corrla_poly_eval_dev_f64(corrla_ctx* ctx, const double* x, int64_t m, int64_t k, int64_t ldx, const double* coeffs,
+                                                  int64_t ldc, int64_t r, int degree, double* out, int64_t ld_out, double* jac, int64_t ld_jac);
+CORRLA_API corrla_status corrla_ctx_last_polyfit(corrla_ctx* ctx, int* route_out);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller

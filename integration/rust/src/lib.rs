@@ -173,6 +173,29 @@ extern "C" {
     pub fn corrla_rbf_apply_dev_f32(ctx: *mut c_void, xq: *const f32, n_q: i64, ldq: i64, xs: *const f32, n_s: i64, lds: i64,
                                  dim: i64, kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *const f32, ldw: i64,
                                  n_rhs: i64, out: *mut f32, ld_out: i64) -> c_int;
+    // polynomial response surfaces (stats_corr.rs:146-249): G = [V(z), y]^T [V(z), y] without storing V; means, scales of z
+    pub fn corrla_polyfit_gram_f64(ctx: *mut c_void, x: *const f64, m: i64, k: i64, ldx: i64, y: *const f64, r: i64, ldy: i64,
+                                    degree: c_int, normalize: c_int, g: *mut f64, ldg: i64, means: *mut f64,
+                                    scales: *mut f64) -> c_int;
+    pub fn corrla_polyfit_gram_f32(ctx: *mut c_void, x: *const f32, m: i64, k: i64, ldx: i64, y: *const f32, r: i64, ldy: i64,
+                                    degree: c_int, normalize: c_int, g: *mut f64, ldg: i64, means: *mut f64,
+                                    scales: *mut f64) -> c_int;
+    pub fn corrla_polyfit_gram_dev_f64(ctx: *mut c_void, x: *const f64, m: i64, k: i64, ldx: i64, y: *const f64, r: i64, ldy: i64,
+                                    degree: c_int, normalize: c_int, g: *mut f64, ldg: i64, means: *mut f64,
+                                    scales: *mut f64) -> c_int;
+    pub fn corrla_polyfit_gram_dev_f32(ctx: *mut c_void, x: *const f32, m: i64, k: i64, ldx: i64, y: *const f32, r: i64, ldy: i64,
+                                    degree: c_int, normalize: c_int, g: *mut f64, ldg: i64, means: *mut f64,
+                                    scales: *mut f64) -> c_int;
+    // out (m x r, row-major) = V(x) coeffs; jac (nullable): r slabs of m x k analytic gradients
+    pub fn corrla_poly_eval_f64(ctx: *mut c_void, x: *const f64, m: i64, k: i64, ldx: i64, coeffs: *const f64, ldc: i64, r: i64,
+                                 degree: c_int, out: *mut f64, ld_out: i64, jac: *mut f64, ld_jac: i64) -> c_int;
+    pub fn corrla_poly_eval_f32(ctx: *mut c_void, x: *const f32, m: i64, k: i64, ldx: i64, coeffs: *const f64, ldc: i64, r: i64,
+                                 degree: c_int, out: *mut f32, ld_out: i64, jac: *mut f32, ld_jac: i64) -> c_int;
+    pub fn corrla_poly_eval_dev_f64(ctx: *mut c_void, x: *const f64, m: i64, k: i64, ldx: i64, coeffs: *const f64, ldc: i64, r: i64,
+                                 degree: c_int, out: *mut f64, ld_out: i64, jac: *mut f64, ld_jac: i64) -> c_int;
+    pub fn corrla_poly_eval_dev_f32(ctx: *mut c_void, x: *const f32, m: i64, k: i64, ldx: i64, coeffs: *const f64, ldc: i64, r: i64,
+                                 degree: c_int, out: *mut f32, ld_out: i64, jac: *mut f32, ld_jac: i64) -> c_int;
+    pub fn corrla_ctx_last_polyfit(ctx: *mut c_void, route_out: *mut c_int) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
