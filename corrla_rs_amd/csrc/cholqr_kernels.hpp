@@ -72,22 +72,26 @@ template <class T>
 __global__ __launch_bounds__(1024) void gram_inspect_kernel(T* g, int64_t ld, int l, float shift_rel, int shift_mode,
                                                             GramInspect<T>* out, const int* run_if) {
   if (run_if && *run_if == 0) return;
-  __shared__ float rd[16], rg[16];
+  __shared__ float rd[16];
+  __shared__ T rg[16];
   __shared__ int sbad;
   const int tid = threadIdx.x;
   if (tid == 0) sbad = 0;
-  float dv = 0.f, gm = 0.f;
+  // (the largest diagonal entry and the finiteness test in the element type: an f64 Gram of 2^800 or 2^-800 is inf / 0 as a
+  //  float, which made a finite sketch "non-finite" and a tiny one "zero")
+  float dv = 0.f;
+  T gm = (T)0;
   int bad = 0;
   for (int idx = tid; idx < l * l; idx += 1024) {
     const int j = idx / l, i = idx - j * l;
     const T x = g[(int64_t)j * ld + i];
-    if (!((float)fabs(x) < 3.0e38f)) bad = 1;
+    if (!(fabs(x) < (sizeof(T) == 4 ? (T)3.0e38f : (T)1.0e300))) bad = 1;
     dv = fmaxf(dv, (float)fabs(x - (i == j ? (T)1 : (T)0)));
-    if (i == j) gm = fmaxf(gm, (float)x);
+    if (i == j) gm = fmax(gm, x);
   }
   for (int off = 32; off > 0; off >>= 1) {
     dv = fmaxf(dv, __shfl_down(dv, off, 64));
-    gm = fmaxf(gm, __shfl_down(gm, off, 64));
+    gm = fmax(gm, __shfl_down(gm, off, 64));
   }
   __syncthreads();
   if ((tid & 63) == 0) {
@@ -97,13 +101,14 @@ __global__ __launch_bounds__(1024) void gram_inspect_kernel(T* g, int64_t ld, in
   if (bad) sbad = 1;
   __syncthreads();
   dv = 0.f;
-  gm = 0.f;
+  gm = (T)0;
   for (int i = 0; i < 16; ++i) {
     dv = fmaxf(dv, rd[i]);
-    gm = fmaxf(gm, rg[i]);
+    gm = fmax(gm, rg[i]);
   }
-  const bool shifted = !sbad && gm > 0.f && shift_rel > 0.f && (shift_mode == 1 || (shift_mode == 0 && dv > 0.25f));
-  const T sh = shifted ? (T)shift_rel * (T)gm : (T)0;
+  const bool shifted = !sbad && gm > (T)0 && shift_rel > 0.f && (shift_mode == 1 || (shift_mode == 0 && dv > 0.25f));
+  // (within float range the shift is taken from the float value, as it always was)
+  const T sh = shifted ? (T)shift_rel * ((gm < (T)3.0e38f && gm > (T)1.0e-37f) ? (T)(float)gm : gm) : (T)0;
   if (shifted)
     for (int i = tid; i < l; i += 1024) g[(int64_t)i * ld + i] += sh;
   if (tid == 0) {
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(1024) void gram_inspect_kernel(T* g, int64_t ld, in
     out->shifted = shifted ? 1 : 0;
     out->bad = sbad;
     out->d2 = dv;
-    out->gmax = gm;
+    out->gmax = (float)gm;
   }
 }
 template <class T>
@@ -172,6 +177,37 @@ __global__ __launch_bounds__(chol_inv_max_threads<T>()) void chol_inv_kernel(con
       const int i = min(i0 + aa, r - 1), k = min(k0 + b, r - 1);
       v[aa][b] = g[(int64_t)k * ldg + i];
     }
+  // Scale invariance.  The inspection below works in float and the elimination takes hardware reciprocals of its pivots: a
+  // Gram far from unit scale (an f64 sketch beyond 1e19 or below 1e-22, whose Gram is inf or 0 as a float; an f32 sketch
+  // whose small pivots are subnormal) is multiplied by the exact power of four that brings its largest diagonal entry
+  // into [1/2, 2), and R^-1 is scaled back on output.  Grams within 2^-40 .. 2^40 are left as they are.
+  int h = 0;
+  {
+    T gt = (T)0;
+    if (own && ti == tk) {
+#pragma unroll
+      for (int aa = 0; aa < 4; ++aa)
+        if (i0 + aa < r) gt = fmax(gt, v[aa][aa]);
+    }
+    for (int off = 32; off > 0; off >>= 1) gt = fmax(gt, __shfl_down(gt, off, 64));
+    // (one word per wave, at most 16 waves, in the 32-float scratch that thinq_plan.hpp: chol_inv_lds_bytes reserves)
+    static_assert(16 * sizeof(T) <= 32 * sizeof(float), "the wave maxima in the element type must fit the float scratch");
+    T* redt = (T*)red;
+    if ((tid & 63) == 0) redt[tid >> 6] = gt;
+    __syncthreads();
+    gt = (T)0;
+    for (int i = 0; i < nwave; ++i) gt = fmax(gt, redt[i]);
+    __syncthreads();
+    if (gt <= std::numeric_limits<T>::max() && (gt > (T)1099511627776.0 || (gt > (T)0 && gt < (T)9.094947017729282e-13))) {
+      int e;
+      (void)frexp((double)gt, &e);
+      h = e >> 1;
+#pragma unroll
+      for (int aa = 0; aa < 4; ++aa)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) v[aa][b] = (T)ldexp((double)v[aa][b], -2 * h);
+    }
+  }
 #pragma unroll
   for (int aa = 0; aa < 4; ++aa)
 #pragma unroll
@@ -236,7 +272,9 @@ __global__ __launch_bounds__(chol_inv_max_threads<T>()) void chol_inv_kernel(con
   // G = I + E with a tiny E (the polishing pass of CholeskyQR2): (I + E)^(-1/2) = I - E/2 + 3E^2/8 - ..., and
   // 3 ||E||^2 / 8 is below eps / 4, so the symmetric first-order factor replaces the elimination (uniform branch).
   const float series_tol = sizeof(T) == 4 ? 2.0e-4f : 1.0e-8f;
-  if (fl == 0 && d2 <= series_tol) {
+  // (h == 0 only: d2 of a prescaled Gram is that of the SCALED one -- 4^h (I + E) would pass for I + E and the factor written
+  //  here would lack its 2^-h; such a Gram goes through the elimination, whose output is scaled back)
+  if (fl == 0 && h == 0 && d2 <= series_tol) {
     if (own) {
 #pragma unroll
       for (int aa = 0; aa < 4; ++aa)
@@ -263,7 +301,8 @@ __global__ __launch_bounds__(chol_inv_max_threads<T>()) void chol_inv_kernel(con
     }
     return;
   }
-  const T pre_sh = rq.abs_shift ? *(const T*)rq.abs_shift : (T)0;  // blocked form: the shift is in the diagonal already
+  // blocked form: the shift is in the diagonal already (and was scaled with it)
+  const T pre_sh = rq.abs_shift ? (h ? (T)ldexp((double)*(const T*)rq.abs_shift, -2 * h) : *(const T*)rq.abs_shift) : (T)0;
   const bool shifted = rq.abs_shift ? pre_sh > (T)0
                                     : (robust && rq.shift_rel > 0.f && (rq.shift_mode == 1 || (rq.shift_mode == 0 && d2 > 0.25f)));
   const T sh = rq.abs_shift ? pre_sh : (shifted ? (T)rq.shift_rel * (T)g2 : (T)0);
@@ -361,8 +400,10 @@ __global__ __launch_bounds__(chol_inv_max_threads<T>()) void chol_inv_kernel(con
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         const int i = i0 + aa, k = k0 + b;
-        if (i <= k && k < r)
-          m[(int64_t)k * ldm + i] = (fl == 0) ? w[aa][b] * dis[k] : ((i == k && fl == 1) ? (T)1 : (T)0);
+        if (i <= k && k < r) {
+          const T val = (fl == 0) ? w[aa][b] * dis[k] : ((i == k && fl == 1) ? (T)1 : (T)0);
+          m[(int64_t)k * ldm + i] = (h && fl == 0) ? (T)ldexp((double)val, -h) : val;  // R^-1 of the unscaled Gram
+        }
       }
   }
   if (tid == 0) {

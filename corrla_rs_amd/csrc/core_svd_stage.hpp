@@ -114,10 +114,11 @@ inline void multi_wg(HipDev& dev, const CoreSvdCall<T>& a, const CoreSvdPlan& pl
 // One small launch scans the core first: optimistic runs find fail = 3 in the status record at the end of the call,
 // host-controlled ones read the word now.
 template <class T>
-inline void finite_check(HipDev& dev, const CoreSvdCall<T>& a) {
+inline void finite_check(HipDev& dev, const CoreSvdCall<T>& a, int* sexp_out = nullptr) {
+  // sexp_out (the block Jacobi): device word that receives the power-of-two prescale of a core far from unit scale
   int* bad = a.conv_status ? nullptr : dev.alloc_flags(1);
   hipLaunchKernelGGL((k::core_finite_check_kernel<T>), dim3(1), dim3(1024), 0, dev.stream, (const T*)a.c.p, a.c.ld, (int)a.l,
-                     (k::CholStatus*)a.conv_status, bad);
+                     (k::CholStatus*)a.conv_status, bad, sexp_out);
   CORRLA_HIP(hipGetLastError());
   if (bad) {
     int h = 0;
@@ -128,14 +129,14 @@ inline void finite_check(HipDev& dev, const CoreSvdCall<T>& a) {
 
 // ---- block Jacobi, one launch per round ----
 template <class T>
-inline void block(HipDev& dev, const CoreSvdCall<T>& a, const CoreSvdPlan& plan) {
+inline void block(HipDev& dev, const CoreSvdCall<T>& a, const CoreSvdPlan& plan, const int* sexp) {
   const CoreSvdPlan::Block& p = plan.blk;
   const int64_t ld = p.rows_pad;
   T* wj = (T*)dev.alloc_bytes(p.ws_bytes);
   T* vj = (T*)dev.alloc_bytes(p.ws_bytes);
   k::JacobiCtl* ctl = (k::JacobiCtl*)dev.alloc_bytes(sizeof(k::JacobiCtl));
   hipLaunchKernelGGL((k::jacobi_init_kernel<T>), dim3(64), dim3(256), 0, dev.stream, (const T*)a.c.p, a.c.ld, (int)a.l, wj, ld, vj,
-                     ld, p.cols_pad, p.rows_pad, ctl);
+                     ld, p.cols_pad, p.rows_pad, ctl, sexp);
   for (int sw = 0; sw < p.max_sweeps; ++sw) {
     for (int round = 0; round < p.nb - 1; ++round)
       hipLaunchKernelGGL((k::jacobi_block_round_kernel<T>), dim3(p.nb / 2), dim3(256), p.round_lds, dev.stream, wj, ld, vj, ld,
@@ -143,7 +144,7 @@ inline void block(HipDev& dev, const CoreSvdCall<T>& a, const CoreSvdPlan& plan)
     hipLaunchKernelGGL(k::jacobi_sweep_end_kernel, dim3(1), dim3(1), 0, dev.stream, ctl, (float)plan.tol_early);
   }
   hipLaunchKernelGGL((k::jacobi_finish_kernel<T>), dim3(1), dim3(1024), p.fin_lds, dev.stream, (const T*)wj, ld, (const T*)vj,
-                     ld, (int)a.l, a.m1.p, a.m1.ld, a.m2.p, a.m2.ld, a.s_dev, (int)a.k);
+                     ld, (int)a.l, a.m1.p, a.m1.ld, a.m2.p, a.m2.ld, a.s_dev, (int)a.k, sexp);
   CORRLA_HIP(hipGetLastError());
   if (env_int("CORRLA_DEBUG", 0)) {
     k::JacobiCtl h;
@@ -215,10 +216,12 @@ void HipDev::small_svd(const Skinny<T>& c, int64_t l, int64_t k, Skinny<T>& m1, 
     case CoreSvd::kHost:
       small_svd_host(*this, c, l, k, m1, m2, s_dev);
       return;
-    case CoreSvd::kBlock:
-      core_svd_stage::finite_check(*this, a);
-      core_svd_stage::block(*this, a, plan);
+    case CoreSvd::kBlock: {
+      int* sexp = (int*)alloc_bytes(sizeof(int));  // written by the check, read by the kernels behind it in stream order
+      core_svd_stage::finite_check(*this, a, sexp);
+      core_svd_stage::block(*this, a, plan, sexp);
       return;
+    }
     case CoreSvd::kRing:
       core_svd_stage::finite_check(*this, a);
       core_svd_stage::ring(*this, a, plan);

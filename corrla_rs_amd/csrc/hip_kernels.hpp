@@ -1590,12 +1590,15 @@ __global__ void jacobi_sweep_end_kernel(JacobiCtl* ctl, float tol_early) {
 
 template <class T>
 __global__ void jacobi_init_kernel(const T* c, int64_t ldc, int l, T* w, int64_t ldw, T* v, int64_t ldv, int cols_pad,
-                                   int rows_pad, JacobiCtl* ctl) {
+                                   int rows_pad, JacobiCtl* ctl, const int* sexp_p) {
+  // W <- 2^sexp * C: the prescale core_finite_check_kernel chose (0 for a core near unit scale), undone by the finish kernel
+  const int sexp = *sexp_p;
   const int64_t total = (int64_t)cols_pad * rows_pad;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int j = (int)(e / rows_pad), i = (int)(e - (int64_t)j * rows_pad);
     const bool in = i < l && j < l;
-    w[(int64_t)j * ldw + i] = in ? c[(int64_t)j * ldc + i] : (T)0;
+    const T x = in ? c[(int64_t)j * ldc + i] : (T)0;
+    w[(int64_t)j * ldw + i] = sexp ? (T)ldexp((double)x, sexp) : x;
     v[(int64_t)j * ldv + i] = (in && i == j) ? (T)1 : (T)0;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1609,10 +1612,11 @@ __global__ void jacobi_init_kernel(const T* c, int64_t ldc, int l, T* w, int64_t
 // sigma_j = ||w_j||, descending order, outputs (see the top of the core-SVD section)
 template <class T>
 __global__ __launch_bounds__(1024) void jacobi_finish_kernel(const T* w, int64_t ldw, const T* v, int64_t ldv, int l, T* m1,
-                                                             int64_t ld1, T* m2, int64_t ld2, T* s_out, int k) {
+                                                             int64_t ld1, T* m2, int64_t ld2, T* s_out, int k, const int* sexp_p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* sigma = (T*)smem;
   int* order = (int*)(sigma + l + 2);
+  const int sexp = *sexp_p;
   const int tid = threadIdx.x, group = tid >> 4, gl = tid & 15;
   for (int j = group; j < l; j += 64) {
     T a = 0;
@@ -1643,7 +1647,7 @@ __global__ __launch_bounds__(1024) void jacobi_finish_kernel(const T* w, int64_t
       m2[(int64_t)r * ld2 + i] = w[(int64_t)j * ldw + i] * inv;
       m1[(int64_t)r * ld1 + i] = v[(int64_t)j * ldv + i];
     }
-    if (gl == 0) s_out[r] = sj;
+    if (gl == 0) s_out[r] = sexp ? (T)ldexp((double)sj, -sexp) : sj;
   }
 }
 
@@ -1653,16 +1657,38 @@ __global__ __launch_bounds__(1024) void jacobi_finish_kernel(const T* w, int64_t
 // so that a non-finite core ends the call with CORRLA_ENUMERIC instead of a triplet of zeros.  (The multi-workgroup
 // Jacobi reports the same through jmc_init_kernel / jmc_finish_kernel.)
 template <class T>
-__global__ __launch_bounds__(1024) void core_finite_check_kernel(const T* __restrict__ c, int64_t ld, int l, CholStatus* st, int* bad_out) {
+__global__ __launch_bounds__(1024) void core_finite_check_kernel(const T* __restrict__ c, int64_t ld, int l, CholStatus* st, int* bad_out,
+                                                                  int* sexp_out) {
+  // (in the element type: an f64 core of 2^400 is finite, and inf as a float)
+  const T finite_below = sizeof(T) == 4 ? (T)3.0e38f : (T)1.0e300;
+  __shared__ T red[16];
   int bad = 0;
+  T mx = (T)0;
   for (int idx = threadIdx.x; idx < l * l; idx += 1024) {
     const int j = idx / l, i = idx - j * l;
-    if (!((float)fabs(c[(int64_t)j * ld + i]) < 3.0e38f)) bad = 1;
+    const T x = fabs(c[(int64_t)j * ld + i]);
+    if (!(x < finite_below)) bad = 1;
+    mx = fmax(mx, x);
   }
+  for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0 && bad) {
-    if (st) st->fail = 3;
-    if (bad_out) *bad_out = 1;
+  if (threadIdx.x == 0) {
+    if (bad) {
+      if (st) st->fail = 3;
+      if (bad_out) *bad_out = 1;
+    }
+    // sexp_out (the block Jacobi, which has no prescale of its own): the exponent that brings the largest entry of a core
+    // far from unit scale into [1, 2); 0 for a core within 2^-30 .. 2^30, whose kernels run on it as it is
+    if (sexp_out) {
+      for (int i = 0; i < 16; ++i) mx = fmax(mx, red[i]);
+      int e = 0;
+      if (!bad && mx > (T)0 && (mx > (T)1073741824.0 || mx < (T)9.313225746154785e-10)) {
+        (void)frexp((double)mx, &e);
+        e = 1 - e;
+      }
+      *sexp_out = e;
+    }
   }
 }
 // TEST HOOK (CORRLA_TEST_POISON_CORE, tests/test_gpu_parity.py): one entry of a device matrix <- NaN (kind 1) / +inf (2)

@@ -95,11 +95,14 @@ __device__ __forceinline__ double jmc_sum(double x) {
 template <class T>
 __global__ __launch_bounds__(1024) void jmc_init_kernel(const T* __restrict__ c, int64_t ldc, int l, T* w, T* v, int rp,
                                                         int ncols_pad, int force_v, JmcCtl* ctl) {
-  __shared__ float red[16];
+  __shared__ T red[16];
   __shared__ int sbad;
   const int tid = threadIdx.x;
   if (tid == 0) sbad = 0;
-  float mx = 0.f;
+  // (the largest entry and the finiteness test in the element type: an f64 core of 2^400 is inf as a float, one of 2^-400
+  //  is 0 and got no prescale)
+  const T finite_below = sizeof(T) == 4 ? (T)3.0e38f : (T)1.0e300;
+  T mx = (T)0;
   int bad = 0;
   // (loads in batches of four, clamped and unconditional: one load per loop iteration is one dependent L2 round trip per
   //  iteration -- this one-workgroup kernel was 20 us of round trips at l = 138)
@@ -114,21 +117,21 @@ __global__ __launch_bounds__(1024) void jmc_init_kernel(const T* __restrict__ c,
 #pragma unroll
     for (int u = 0; u < 4; ++u)
       if (idx0 + u * 1024 < l * l) {
-        const float x = (float)fabs(xb[u]);
-        if (!(x < 3.0e38f)) bad = 1;
-        mx = fmaxf(mx, x);
+        const T x = fabs(xb[u]);
+        if (!(x < finite_below)) bad = 1;
+        mx = fmax(mx, x);
       }
   }
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
   if ((tid & 63) == 0) red[tid >> 6] = mx;
   __syncthreads();
   if (bad) sbad = 1;
-  mx = 0.f;
-  for (int i = 0; i < 16; ++i) mx = fmaxf(mx, red[i]);
+  mx = (T)0;
+  for (int i = 0; i < 16; ++i) mx = fmax(mx, red[i]);
   __syncthreads();
   int sexp = 0;
-  if (mx > 0.f && !sbad) {
-    (void)frexpf(mx, &sexp);
+  if (mx > (T)0 && !sbad) {
+    (void)frexp((double)mx, &sexp);
     sexp = 1 - sexp;  // mx * 2^sexp in [1, 2)
   }
   const int total = rp * ncols_pad;
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(1024) void jmc_init_kernel(const T* __restrict__ c,
   // values well enough to choose the mode; the finish kernel verifies the choice against the computed sigma
   float dmin = 3.0e38f, dmax = 0.f;
   for (int i = tid; i < l; i += 1024) {
-    const float d = (float)fabs(c[(int64_t)i * ldc + i]);
+    const float d = (float)ldexp((double)fabs(c[(int64_t)i * ldc + i]), sexp);  // of the prescaled core: within float range
     dmin = fminf(dmin, d);
     dmax = fmaxf(dmax, d);
   }

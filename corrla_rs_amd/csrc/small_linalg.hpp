@@ -69,12 +69,23 @@ inline void triu_inverse(int n, double* r, int ld) {
 // when the input holds non-finite values.
 inline int jacobi_svd(int n, const double* c, int ld, double* u, double* s, double* v, double tol) {
   std::vector<double> w((size_t)n * n);
+  double mx = 0.0;
   for (int j = 0; j < n; ++j)
     for (int i = 0; i < n; ++i) {
       const double x = c[(size_t)j * ld + i];
       if (!std::isfinite(x)) return -1;
       w[(size_t)j * n + i] = x;
+      mx = std::max(mx, std::fabs(x));
     }
+  // Power-of-two prescale, as in the device kernels (jmc_init_kernel: sexp): the convergence test multiplies two SQUARED
+  // column norms, which leaves f64 for entries beyond 2^+-256 -- the product overflowed, every pair passed the test and
+  // the column norms of the input came back as its singular values.  Exact: every other result keeps its bits.
+  int sexp = 0;
+  if (mx > 0.0) {
+    (void)std::frexp(mx, &sexp);
+    sexp = 1 - sexp;  // mx * 2^sexp in [1, 2)
+    for (double& x : w) x = std::ldexp(x, sexp);
+  }
   std::vector<double> vv((size_t)n * n, 0.0);
   for (int i = 0; i < n; ++i) vv[(size_t)i * n + i] = 1.0;
   std::vector<double> nrm2(n);
@@ -133,7 +144,7 @@ inline int jacobi_svd(int n, const double* c, int ld, double* u, double* s, doub
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sv[a] > sv[b]; });
   for (int jj = 0; jj < n; ++jj) {
     const int j = order[jj];
-    s[jj] = sv[j];
+    s[jj] = std::ldexp(sv[j], -sexp);
     const double inv = sv[j] > 0.0 ? 1.0 / sv[j] : 0.0;
     for (int i = 0; i < n; ++i) {
       u[(size_t)jj * n + i] = w[(size_t)j * n + i] * inv;

@@ -41,6 +41,7 @@ CORRLA_HD inline int chol_inv_threads(int r) {
   const int nt = (r + 3) / 4;
   return ((nt * (nt + 1) / 2 + 63) / 64) * 64;
 }
+// (the 32 floats are the kernel's reduction scratch; it also holds 16 wave maxima in the element type -- 128 bytes in f64)
 CORRLA_HD inline size_t chol_inv_lds_bytes(int r, size_t esz) {
   return (size_t)6 * (((size_t)r + 3) / 4 * 4) * esz + 32 * sizeof(float) + 64;
 }
