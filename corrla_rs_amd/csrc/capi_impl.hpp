@@ -388,26 +388,15 @@ inline void pca_body(Dev& dev, const PcaCall<T>& c, Validate&& validate, Stage&&
   const int64_t m_global = c.sharded ? dev.allreduce_sum_host(c.m) : c.m;  // every rank makes this call (rank-invariant)
   need_two_samples(m_global);
   const bool fat = !c.sharded && c.m < c.n;  // the tall view is x^T: its ROWS are the data columns
-  // column means of x = (1/m) x^T 1: one pass of the transposed product against a ones vector
   RsvdDriver<Dev, T> drv(dev, c.profile);
-  const int64_t samples_dim_tall = fat ? ta.nt : ta.mt;  // n_samples as a dimension of the tall view
-  Skinny<T> ones = dev.template alloc_skinny<T>(samples_dim_tall, 1);
-  dev.fill_const(ones.p, samples_dim_tall, (T)1);
-  Skinny<T> mu = dev.template alloc_skinny<T>(fat ? ta.mt : ta.nt, 1);
-  T* inv_m = dev.template alloc_scalar<T>(1);
-  const T inv_m_host = (T)(1.0 / (double)m_global);
-  dev.store_values(&inv_m_host, (int64_t)1, inv_m, /*dst_is_host=*/false);
-  if (!fat)
-    drv.at_times(ta, ones, mu, inv_m, c.sharded);  // mu (n) = x^T 1 / m (all-reduced partial sums when sharded)
-  else
-    drv.a_times(ta, ones, mu, inv_m);            // tall view = x^T (n x m): mu (n) = x^T 1 / m
+  Skinny<T> mu = drv.column_means(ta, fat, m_global, c.sharded);
   // data columns run along the memory columns iff (tall & row-major) or (fat & column-major): tall view element (i, j)
   // is memory (i, j) when row-major, else memory (j, i); the data column index of x is j for tall input, i for fat
   const bool data_cols_along_mem_cols = (ta.row_major != fat);
   Skinny<T> sd, inv_sd;  // column standard deviations (1 for a constant column) and their reciprocals
   if (ro.pca_standardize) {
     if constexpr (dev_has_colvar<Dev>::value) {
-      double* ss = dev.alloc_f64((int)c.n);
+      double* ss = dev.alloc_f64(c.n);
       if (ta.sparse)
         dev.col_ss_csr(fat ? ta.csr : ta.csr_t, (const T*)mu.p, c.m, ss);  // the CSR whose rows are the data columns
       else if (ta.bf16)

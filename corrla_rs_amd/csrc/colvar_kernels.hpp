@@ -10,25 +10,27 @@
 #include <cstdint>
 #include <limits>
 
+#include "colstat_plan.hpp"  // kCvThreads, cv_vec
+
 namespace corrla {
 namespace k {
 
-// how an operand element is loaded and widened: kVec elements make one 16-byte load
+// how an operand element is loaded and widened: kVec elements make one 16-byte load (colstat_plan.hpp: cv_vec)
 template <class TI>
 struct CvIn;
 template <>
 struct CvIn<float> {
-  static constexpr int kVec = 4;
+  static constexpr int kVec = cv_vec(sizeof(float));
   static __device__ inline double widen(float v) { return (double)v; }
 };
 template <>
 struct CvIn<double> {
-  static constexpr int kVec = 2;
+  static constexpr int kVec = cv_vec(sizeof(double));
   static __device__ inline double widen(double v) { return v; }
 };
 template <>
 struct CvIn<uint16_t> {  // bfloat16: the upper 16 bits of a binary32
-  static constexpr int kVec = 8;
+  static constexpr int kVec = cv_vec(sizeof(uint16_t));
   static __device__ inline double widen(uint16_t v) { return (double)__uint_as_float((uint32_t)v << 16); }
 };
 
@@ -44,8 +46,6 @@ __device__ inline void cv_load(const TI* __restrict__ p, bool vec, int nvalid, T
     for (int u = 0; u < VEC; ++u) e[u] = u < nvalid ? p[u] : (TI)0;
   }
 }
-
-constexpr int kCvThreads = 256;
 
 // ---- data columns run along the memory columns: reduce DOWN the memory rows ------------------------------------------
 // x: rows x cols row-major (ld, cols_readable).  A workgroup covers `groups` (a power of two, <= 256) column groups of

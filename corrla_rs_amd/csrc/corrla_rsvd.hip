@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "capi_impl.hpp"
+#include "colstat_stage.hpp"
 #include "core_svd_stage.hpp"
 #include "cov_stage.hpp"
 #include "grad_stage.hpp"

@@ -304,6 +304,22 @@ struct RsvdDriver {
     // (only the l columns that exist: the padding columns up to cols_alloc are zero on every rank and stay zero)
     if (sharded) dev.allreduce(z.p, (size_t)z.ld * (size_t)z.cols);
   }
+  // The column means of x, mu (n_dim) = x^T 1 / m: one pass of the transposed product against a ones vector.  `a` is the
+  // tall view of x (fat: the tall view is x^T, its ROWS are the data columns), m_global the sample count over every rank;
+  // sharded: all-reduced partial sums.  Enqueues only: 1 / m reaches the device through a kernel (fill_const).
+  Skinny<T> column_means(const TallA<T>& a, bool fat, int64_t m_global, bool sharded) {
+    const int64_t samples_dim_tall = fat ? a.nt : a.mt;  // n_samples as a dimension of the tall view
+    Skinny<T> ones = dev.template alloc_skinny<T>(samples_dim_tall, 1);
+    dev.fill_const(ones.p, samples_dim_tall, (T)1);
+    Skinny<T> mu = dev.template alloc_skinny<T>(fat ? a.mt : a.nt, 1);
+    T* inv_m = dev.template alloc_scalar<T>(1);
+    dev.fill_const(inv_m, (int64_t)1, (T)(1.0 / (double)m_global));
+    if (!fat)
+      at_times(a, ones, mu, inv_m, sharded);  // mu (n) = x^T 1 / m
+    else
+      a_times(a, ones, mu, inv_m);            // tall view = x^T (n x m): mu (n) = x^T 1 / m
+    return mu;
+  }
 
   // ---- thin-Q orthonormalisation (replaces y.qr().compute_thin_q(), random_svd.rs:38,57) ----
   // Iterated Cholesky-QR on the device-computed Gram matrix: G = Y^T Y (tall GEMM + optional all-reduce),

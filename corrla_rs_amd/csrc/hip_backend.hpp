@@ -3,7 +3,8 @@
 // driver.hpp / capi_impl.hpp are written against.  Every operation is enqueued on the context's
 // stream; the only host synchronisations are the small l x l downloads the host factorizations need.
 // The compute stages are planned in their *_plan.hpp and launched from their *_stage.hpp, which define the members declared
-// here (tall products: tall_stage.hpp, core SVD: core_svd_stage.hpp, thin-Q: thinq_stage.hpp); this file keeps the device
+// here (tall products: tall_stage.hpp, core SVD: core_svd_stage.hpp, thin-Q: thinq_stage.hpp, column passes:
+// colstat_stage.hpp); this file keeps the device
 // services -- memory, transfers, collectives, events -- the state of a context and the small elementwise launches.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,7 +34,6 @@
 #include "knn2_kernels.hpp"
 #include "grad_wide_kernels.hpp"
 #include "spmm_kernels.hpp"
-#include "colvar_kernels.hpp"
 #include "syrk_kernels.hpp"
 #include "pca_apply_kernels.hpp"
 #include "rbf_kernels.hpp"
@@ -346,8 +346,8 @@ class HipDev {
     if (s.cols_alloc > cols) memset_zero(s.p + cols * s.ld, (size_t)(s.cols_alloc - cols) * s.ld * sizeof(T));
     return s;
   }
-  double* alloc_f64(int n) {
-    return (double*)alloc_zeroed(sizeof(double) * n);
+  double* alloc_f64(int64_t n) {
+    return (double*)alloc_zeroed(sizeof(double) * (size_t)n);
   }
   template <class T>
   T* alloc_scalar(int n) {
@@ -756,16 +756,7 @@ class HipDev {
 
   // ---- implicit centring ---------------------------------------------------------
   template <class T>
-  void weighted_colsum(const Skinny<T>& x, int64_t rows, const T* w, T* v) {
-    const int ncols = (int)x.cols_alloc;
-    const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(64, (rows + 4095) / 4096));
-    double* partial = (double*)alloc_bytes(sizeof(double) * (size_t)nblk * (size_t)ncols);
-    hipLaunchKernelGGL((k::wcolsum_partial_kernel<T>), dim3((unsigned)nblk, (unsigned)ncols), dim3(256), 0, stream,
-                       (const T*)x.p, x.ld, rows, w, partial, ncols);
-    hipLaunchKernelGGL((k::wcolsum_final_kernel<T>), dim3((unsigned)((ncols + 63) / 64)), dim3(64), 0, stream,
-                       (const double*)partial, nblk, ncols, v);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void weighted_colsum(const Skinny<T>& x, int64_t rows, const T* w, T* v);  // colstat_stage.hpp
   template <class T>
   void rank1_sub(Skinny<T>& out, int64_t rows, const T* u, const T* v, const T* scale) {
     dim3 grid((unsigned)((rows + 255) / 256), (unsigned)out.cols_alloc);
@@ -797,143 +788,23 @@ class HipDev {
     CORRLA_HIP(hipGetLastError());
   }
 
-  // ---- PCA on standardised columns (colvar_kernels.hpp) ----------------------------------------------------------
+  // ---- PCA on standardised columns: colstat_plan.hpp plans, colstat_stage.hpp launches colvar_kernels.hpp and defines
+  // the members declared here ----
   static constexpr bool kHasColVar = true;  // driver.hpp: dev_has_colvar
   // ss[j] (f64) = sum_i (x_ij - mu_j)^2 per data column j of the staged operand `a` (f32, f64 or bf16 bit patterns, read
   // in place).  along_cols: the data columns run along the memory columns (reduce down the rows), else they are the
   // memory rows (reduce along them).  Per-slab partial sums, then a final sum in index order.
   template <class TI, class T>
-  void col_ss(const Big<TI>& a, bool along_cols, const T* mu, double* ss) {
-    constexpr int VEC = k::CvIn<TI>::kVec;
-    const int aligned = ((uintptr_t)a.p % 16 == 0 && a.ld % VEC == 0) ? 1 : 0;
-    const int64_t n = along_cols ? a.cols : a.rows;
-    const int64_t target = (int64_t)num_cus * 8;  // workgroups that fill the device
-    int64_t nslab;
-    double* partial;
-    if (along_cols) {
-      const int64_t ngroups = (a.cols + VEC - 1) / VEC;
-      int groups = 1;
-      while (groups < k::kCvThreads && groups < ngroups) groups *= 2;
-      const int ny = k::kCvThreads / groups;
-      const int64_t col_blocks = (ngroups + groups - 1) / groups;
-      // every row lane gets at least eight rows
-      const int64_t want = std::max<int64_t>(1, std::min<int64_t>((target + col_blocks - 1) / col_blocks, (a.rows + 8 * ny - 1) / (8 * ny)));
-      const int64_t rows_per_slab = (a.rows + want - 1) / want;
-      nslab = (a.rows + rows_per_slab - 1) / rows_per_slab;
-      dim3 grid((unsigned)col_blocks, (unsigned)nslab);
-      check_grid(grid);
-      partial = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
-      hipLaunchKernelGGL((k::colss_down_kernel<TI, T>), grid, dim3(k::kCvThreads), 0, stream, a.p, a.rows, a.cols, a.ld, a.cols_readable,
-                         aligned, mu, groups, rows_per_slab, partial);
-    } else {
-      const int64_t quantum = 64 * VEC;  // what one wave reads per step
-      const int64_t max_segs = (a.cols + 4 * quantum - 1) / (4 * quantum);
-      const int64_t want = std::max<int64_t>(1, std::min<int64_t>((4 * target + a.rows - 1) / a.rows, max_segs));
-      const int64_t seg_len = round_up((a.cols + want - 1) / want, quantum);
-      nslab = (a.cols + seg_len - 1) / seg_len;
-      const int64_t units = a.rows * nslab;
-      const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 2 * target));
-      partial = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
-      hipLaunchKernelGGL((k::colss_along_kernel<TI, T>), dim3((unsigned)blocks), dim3(k::kCvThreads), 0, stream, a.p, a.rows, a.cols,
-                         a.ld, a.cols_readable, aligned, mu, (int)nslab, seg_len, partial);
-    }
-    hipLaunchKernelGGL(k::colss_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)partial, nslab, n, ss);
-    CORRLA_HIP(hipGetLastError());
-  }
-  // the same over a CSR whose ROWS are the data columns (a transpose built by csr_transpose: entries ordered by sample),
-  // the implicit zeros of the n_samples long columns included
+  void col_ss(const Big<TI>& a, bool along_cols, const T* mu, double* ss);
+  // the same over a CSR whose ROWS are the data columns (a transpose built by csr_transpose)
   template <class T>
-  void col_ss_csr(const CsrView<T>& s, const T* mu, int64_t n_samples, double* ss) {
-    const int64_t target = (int64_t)num_cus * 8;
-    const int64_t segs = std::max<int64_t>(1, std::min<int64_t>((4 * target + s.rows - 1) / s.rows, 64));
-    const int64_t units = s.rows * segs;
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 2 * target));
-    double* psum = (double*)alloc_bytes(sizeof(double) * (size_t)units);
-    double* pcnt = (double*)alloc_bytes(sizeof(double) * (size_t)units);
-    hipLaunchKernelGGL((k::csr_colss_kernel<T>), dim3((unsigned)blocks), dim3(k::kCvThreads), 0, stream, s.val, s.ci, s.rp, s.rows, mu,
-                       (int)segs, psum, pcnt);
-    hipLaunchKernelGGL((k::csr_colss_final_kernel<T>), dim3((unsigned)((s.rows + 255) / 256)), dim3(256), 0, stream, (const double*)psum,
-                       (const double*)pcnt, segs, s.rows, mu, (double)n_samples, ss);
-    CORRLA_HIP(hipGetLastError());
-  }
+  void col_ss_csr(const CsrView<T>& s, const T* mu, int64_t n_samples, double* ss);
   // sd[j] = sqrt(ss[j] / (m - 1)) -- 1 for a constant column -- and its reciprocal, on the device
   template <class T>
-  void sd_from_ss(const double* ss, const T* mu, int64_t n, int64_t m_samples, T* sd, T* inv_sd) {
-    hipLaunchKernelGGL((k::sd_from_ss_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ss, mu, n, (double)m_samples, sd,
-                       inv_sd);
-    CORRLA_HIP(hipGetLastError());
-  }
-  // ---- covariance / correlation matrices (syrk_plan.hpp, syrk_kernels.hpp) -----------------------------------------------
+  void sd_from_ss(const double* ss, const T* mu, int64_t n, int64_t m_samples, T* sd, T* inv_sd);
+  // ---- covariance / correlation matrices: syrk_plan.hpp plans, cov_stage.hpp launches syrk_kernels.hpp ---------------------
   static constexpr bool kHasSyrk = true;  // driver.hpp: dev_has_syrk
   const SyrkKnobs& syrk_knobs() const { return syrk_knobs_; }
-  // The column moments of x (m x n row-major, ld) in one pass with f64 accumulation (colmom_down_kernel, colmom_final_kernel):
-  // the f64 means and standard deviations (divisor denom; 1 for a constant column), both rounded to T, and the verdict.
-  // Workspace of the arena; enqueues only.
-  template <class T>
-  struct ColMoments {
-    double *mu64, *sd64;
-    T *mu_t, *sd_t;
-    int* is_const;
-  };
-  template <class T>
-  ColMoments<T> col_moments(const T* x, int64_t m, int64_t n, int64_t ld, int aligned, double denom) {
-    constexpr int VEC = k::CvIn<T>::kVec;
-    const int64_t ngroups = (n + VEC - 1) / VEC;
-    int groups = 1;
-    while (groups < k::kCvThreads && groups < ngroups) groups *= 2;
-    const int ny = k::kCvThreads / groups;
-    const int64_t col_blocks = (ngroups + groups - 1) / groups;
-    const int64_t target = (int64_t)num_cus * 8;
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((target + col_blocks - 1) / col_blocks, (m + 8 * ny - 1) / (8 * ny)));
-    const int64_t rows_per_slab = (m + want - 1) / want;
-    const int64_t nslab = (m + rows_per_slab - 1) / rows_per_slab;
-    dim3 grid((unsigned)col_blocks, (unsigned)nslab);
-    check_grid(grid);
-    double* psum = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
-    double* psq = (double*)alloc_bytes(sizeof(double) * (size_t)nslab * (size_t)n);
-    ColMoments<T> cm;
-    cm.mu64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
-    cm.sd64 = (double*)alloc_bytes(sizeof(double) * (size_t)n);
-    cm.mu_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
-    cm.sd_t = (T*)alloc_bytes(sizeof(T) * (size_t)n);
-    cm.is_const = (int*)alloc_bytes(sizeof(int) * (size_t)n);
-    hipLaunchKernelGGL((k::colmom_down_kernel<T>), grid, dim3(k::kCvThreads), 0, stream, x, m, n, ld, aligned, groups, rows_per_slab,
-                       psum, psq);
-    hipLaunchKernelGGL((k::colmom_final_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)psum,
-                       (const double*)psq, nslab, n, x, (double)m, denom, cm.mu64, cm.mu_t, cm.sd64, cm.sd_t, cm.is_const);
-    CORRLA_HIP(hipGetLastError());
-    return cm;
-  }
-  // C (n x n, ldc) = covariance (or, corr, Pearson correlation) of the columns of x: m x n row-major with leading dimension
-  // p.ld on the device, read in place.  center: the column moments first (one pass, f64 accumulation), means_out / scales_out
-  // (device, optional) receive the means and -- corr only -- the standard deviations.  Enqueues only: no synchronisation.
-  template <class T>
-  void syrk(const SyrkPlan& p, const T* x, int64_t m, int64_t n, bool center, bool corr, int ddof, T* means_out, T* scales_out,
-            T* c, int64_t ldc) {
-    const int aligned = p.route == SyrkRoute::kInPlaceChecked ? 0 : 1;
-    const double denom = (double)(m - ddof);
-    double *mu64 = nullptr, *sd64 = nullptr;
-    T *mu_t = nullptr, *sd_t = nullptr;
-    int* is_const = nullptr;
-    if (center) {
-      const ColMoments<T> cm = col_moments<T>(x, m, n, p.ld, aligned, denom);
-      mu64 = cm.mu64, sd64 = cm.sd64, mu_t = cm.mu_t, sd_t = cm.sd_t, is_const = cm.is_const;
-      if (means_out) CORRLA_HIP(hipMemcpyAsync(means_out, mu_t, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-      if (corr && scales_out) CORRLA_HIP(hipMemcpyAsync(scales_out, sd_t, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-    }
-    T* ws = (T*)alloc_bytes(p.ws_bytes);
-    k::SyrkArgs<T> a{x, m, n, p.ld, aligned, mu_t, p.slab_rows, p.npairs, ws};
-    dim3 grid(p.grid_x, p.grid_y);
-    check_grid(grid);
-    if (center)
-      hipLaunchKernelGGL((k::syrk_kernel<T, true>), grid, dim3(p.block), p.lds_bytes, stream, a);
-    else
-      hipLaunchKernelGGL((k::syrk_kernel<T, false>), grid, dim3(p.block), p.lds_bytes, stream, a);
-    CORRLA_HIP(hipGetLastError());
-    k::SyrkFinishArgs<T> f{ws, p.nsplit, p.npairs, n, (double)m, denom, mu64, mu_t, corr ? sd64 : nullptr, is_const, c, ldc};
-    hipLaunchKernelGGL((k::syrk_finish_kernel<T>), dim3(p.finish_grid_x, p.finish_grid_y), dim3(p.finish_block), 0, stream, f);
-    CORRLA_HIP(hipGetLastError());
-  }
   // ---- fitted PCA model on the device: pca_apply_plan.hpp plans, pca_apply_stage.hpp launches pca_apply_kernels.hpp ---------
   static constexpr bool kHasPcaApply = true;  // driver.hpp: dev_has_pca_apply
   // ---- radial-basis-function kernel matrices: rbf_plan.hpp plans, rbf_stage.hpp launches rbf_kernels.hpp ---------------------

@@ -79,13 +79,8 @@ void transform_dev(HipDev& dev, const PcaTransformCall<T>& c, const DenseX<T>& d
   dev.pack_strided(c.comps, k, n, (int64_t)1, c.ldc, vt.p, vt.ld);
   const T* mu = c.means;
   if (c.own_means()) {
-    // the target's own column means, by the routine pca_body uses: x^T 1 / m through the transposed product
-    Skinny<T> ones = dev.template alloc_skinny<T>(m, 1);
-    dev.fill_const(ones.p, m, (T)1);
-    Skinny<T> mus = dev.template alloc_skinny<T>(n, 1);
-    T* inv_m = dev.template alloc_scalar<T>(1);
-    dev.fill_const(inv_m, (int64_t)1, (T)(1.0 / (double)m));
-    drv.at_times(ta, ones, mus, inv_m, false);
+    // the target's own column means, by the routine pca_body uses (the operand is never transposed here)
+    const Skinny<T> mus = drv.column_means(ta, /*fat=*/false, m, /*sharded=*/false);
     mu = mus.p;
     if (c.means_out) dev.copy_values_out(mus.p, n, c.means_out, /*dst_is_host=*/false);
   }

@@ -10,6 +10,7 @@
 // padding columns of the outputs are never written.
 #pragma once
 #include "capi_impl.hpp"
+#include "colstat_stage.hpp"
 #include "hip_backend.hpp"
 
 namespace corrla {
@@ -66,7 +67,7 @@ void run_gram(HipDev& dev, bool host_ptrs, const PolyGramCall<T>& c, Ran* ran) {
   const double *mu = nullptr, *sg = nullptr;
   if (norm) {
     // the column pass of cov; the population standard deviation, 1 for a constant column
-    const auto cm = dev.col_moments<T>(xd, c.m, c.kf, c.ldx, aligned, (double)c.m);
+    const auto cm = colstat_stage::col_moments<T>(dev, xd, c.m, c.kf, c.ldx, aligned, (double)c.m);
     mu = cm.mu64, sg = cm.sd64;
   }
   double* ws = (double*)dev.alloc_bytes(p.ws_bytes);

@@ -1,4 +1,4 @@
-// The plan of the symmetric rank-k product behind corrla_cov_* (syrk_kernels.hpp, HipDev::syrk): the column tile width and
+// The plan of the symmetric rank-k product behind corrla_cov_* (syrk_kernels.hpp, launched by cov_stage::syrk): the column tile width and
 // the list of tile pairs (bi <= bj), the row split into slabs, the grid, the dynamic LDS, the workspace of the per-slab
 // partial tiles with its bound, the finishing launch, and the route -- X in place, X in place through the checked staging
 // path, a repacked copy, or a rejection with its reason.
