@@ -6,7 +6,10 @@ are interpolated by) -- and everything m- or n-sized is forwarded to corrla_rs_a
 scope.  mat_cov_centered, pearson_corr and rsquared_sens (stats_corr.rs) are ADDITIVE: the pyo3
 module does not expose them; here they run on the symmetric MFMA kernel behind ``Context.cov``.  linear_fit, quad_fit,
 quad_eval, jac_from_lin and jac_from_quad (stats_corr.rs:146-249) are additive in the same way, on the fused
-normal-equation and evaluation kernels behind ``Context.polyfit_gram`` / ``poly_eval``."""
+normal-equation and evaluation kernels behind ``Context.polyfit_gram`` / ``poly_eval``.  KdeRv and build_kde
+(univariate_rv.rs:384-497: the Gaussian kernel density estimate, its likelihood and the cross-validated bandwidth) are
+additive too, on the fused pairwise-sum kernels behind ``Context.kde_eval`` / ``kde_nll``; the other univariate random
+variables of that module (NormalRv, BetaRv, ExponentialRv, mlefit) stay outside this build's scope."""
 import numpy as _np
 
 from corrla_rs_amd.api import PcaRsvd, power_iter, random_svd, rpca, rsvd  # noqa: F401
@@ -15,10 +18,11 @@ from corrla_rs_amd.callers import PodI as _PodI
 from corrla_rs_amd.callers import RbfInterp as _RbfInterp
 from corrla_rs_amd.callers import mat_cov_centered, pearson_corr, rsquared_sens  # noqa: F401
 from corrla_rs_amd.callers import jac_from_lin, jac_from_quad, linear_fit, quad_eval, quad_fit  # noqa: F401
+from corrla_rs_amd.callers import KdeRv, build_kde  # noqa: F401
 
 __all__ = ["rsvd", "rpca", "random_svd", "power_iter", "PcaRsvd", "PyDMDc", "PyPodI", "PyRbfInterp", "active_ss",
            "mat_cov_centered", "pearson_corr", "rsquared_sens", "linear_fit", "quad_fit", "quad_eval", "jac_from_lin",
-           "jac_from_quad"]
+           "jac_from_quad", "KdeRv", "build_kde"]
 
 
 def active_ss(a_mat, y, order, n_nbr, n_comps):

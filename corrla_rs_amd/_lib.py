@@ -35,6 +35,10 @@ PCA_APPLY_ROUTES = {PCA_APPLY_ROUTE_INPLACE: "inplace", PCA_APPLY_ROUTE_INPLACE_
 PCA_APPLY_CENTRINGS = {1: "fused", 2: "copy"}
 # corrla_polyfit_gram_* / corrla_poly_eval_*: what corrla_ctx_last_polyfit reports
 POLYFIT_ROUTES = {1: "inplace", 2: "inplace_checked"}
+# corrla_kde_eval_* / corrla_kde_nll_*: what corrla_ctx_last_kde reports, and the `what` of the eval entries
+KDE_ROUTES = {1: "single", 2: "split"}
+KDE_WHAT = {"pdf": 0, "cdf": 1, "logpdf": 2}
+KDE_MAX_BANDWIDTHS = 64
 UNIQUE_ID_BYTES = 128
 
 
@@ -66,6 +70,7 @@ def _sigs():
         "corrla_ctx_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int]),
         "corrla_ctx_last_pca_apply": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "corrla_ctx_last_polyfit": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "corrla_ctx_last_kde": (C.c_int, [vp, C.POINTER(C.c_int)]),
     }
     for suf, sc in (("f32", flt), ("f64", dbl)):
         rsvd = [vp, vp, i64, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
@@ -107,6 +112,10 @@ def _sigs():
         s["corrla_polyfit_gram_" + suf] = s["corrla_polyfit_gram_dev_" + suf] = (C.c_int, gram)
         peval = [vp, vp, i64, i64, i64, vp, i64, i64, C.c_int, vp, i64, vp, i64]
         s["corrla_poly_eval_" + suf] = s["corrla_poly_eval_dev_" + suf] = (C.c_int, peval)
+        # kernel density estimates: x, n, incx, s, n_s, incs, then h, what, out, inco / h (host), n_h, nll, dnll
+        kde = [vp, vp, i64, i64, vp, i64, i64]
+        s["corrla_kde_eval_" + suf] = s["corrla_kde_eval_dev_" + suf] = (C.c_int, kde + [dbl, C.c_int, vp, i64])
+        s["corrla_kde_nll_" + suf] = s["corrla_kde_nll_dev_" + suf] = (C.c_int, kde + [vp, i64, vp, vp])
         s["corrla_fill_normal_dev_" + suf] =(C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])

@@ -908,6 +908,112 @@ class Context:
         first call.  y, the narrow operand, is read by its own alignment and does not change the route."""
         return getattr(self, "_polyfit_route", None)
 
+    # ---- Gaussian kernel density estimates (univariate_rv.rs:165-170, 423-444) ----------------------
+    def _kde_vector(self, v, name, what):
+        """-> (array as the entries read it, on_device, n, element stride, its shape): a vector, or an n x 1 column as the
+        reference's column matrices, read in place at its stride; float32 stays float32, anything else becomes float64."""
+        _reject_bf16(v, what)
+        if _is_sparse(v):
+            raise ValueError(f"{what} takes dense vectors")
+        if _is_torch(v) and v.is_cuda:
+            import torch
+            self._on_my_device(v)
+            a, on_dev = (v.detach() if v.dtype in (torch.float32, torch.float64) else v.detach().to(torch.float64)), True
+        else:
+            a = np.asarray(v.detach().numpy() if _is_torch(v) else v)
+            if a.dtype != np.float32:
+                a = a.astype(np.float64, copy=False)
+            on_dev = False
+        if a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] != 1):
+            raise ValueError(f"{name} must be a vector or an n x 1 column, got shape {tuple(a.shape)}")
+        n = int(a.shape[0])
+        if n == 0:
+            raise ValueError(f"{name} must be non-empty")
+        if on_dev:
+            inc = int(a.stride(0))
+        else:
+            inc = a.strides[0] // a.itemsize if a.strides[0] % a.itemsize == 0 else 0
+        if n > 1 and inc < 1:     # reversed or broadcast views: the entries take strides >= 1
+            a = a.contiguous() if on_dev else np.ascontiguousarray(a)
+            inc = 1
+        return a, on_dev, n, (inc if n > 1 else 1), tuple(a.shape)
+
+    def _kde_pair(self, x, supports, what):
+        xa, x_dev, n_q, incx, shape = self._kde_vector(x, "x", what)
+        sa, s_dev, n_s, incs, _ = self._kde_vector(supports, "supports", what)
+        if x_dev != s_dev:
+            raise ValueError(f"{what}: x and supports must both be numpy arrays or both be tensors on cuda:{self.device}")
+        if str(xa.dtype).split(".")[-1] != str(sa.dtype).split(".")[-1]:
+            raise ValueError(f"{what}: x is {xa.dtype}, supports {sa.dtype}: convert one of them")
+        return xa, n_q, incx, sa, n_s, incs, x_dev, shape
+
+    def _kde_done(self, on_device):
+        if on_device:  # the device entry only enqueues: torch's streams see the results after this
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        route = C.c_int(0)
+        L.check(self._lib.corrla_ctx_last_kde(self._h, C.byref(route)))
+        self._kde_route = L.KDE_ROUTES.get(route.value)
+
+    def kde_eval(self, x, supports, bandwidth, what="pdf"):
+        """The Gaussian kernel density estimate over `supports` (uniform weights) with the given bandwidth at the points x
+        (corrla_kde_eval_*; ``KdeRv::pdf`` / ``cdf``, univariate_rv.rs:423-444): what="pdf" the density, "cdf" the distribution
+        function (through erfc: relative accuracy in the lower tail), "logpdf" the log-density.  The sums are taken in the
+        stabilised form exp(-t*) sum exp(-(t - t*)) with t* the term of the nearest support, so "logpdf" is finite wherever
+        the reference's ``pdf(x).ln()`` is -inf, and "pdf" is right down to the underflow of the final product.  The
+        (n_q, n_s) matrix is never stored.  x and supports are vectors or n x 1 columns of one dtype (float32 stays float32,
+        anything else becomes float64), both numpy or both CUDA tensors, read in place at any stride.  Returns an array of the
+        shape, dtype and kind of x.  ValueError before the library is touched: dtypes that differ, bfloat16, an empty array,
+        a tensor on another device, a bandwidth that is not finite and > 0.  ``last_kde_route()`` names the route."""
+        if what not in L.KDE_WHAT:
+            raise ValueError(f'what must be "pdf", "cdf" or "logpdf", got {what!r}')
+        xa, n_q, incx, sa, n_s, incs, on_dev, shape = self._kde_pair(x, supports, "kde_eval")
+        h = float(bandwidth)
+        if not (np.isfinite(h) and h > 0.0):
+            raise ValueError(f"bandwidth must be finite and > 0, got {bandwidth!r}")
+        if on_dev:
+            import torch
+            out = torch.empty(shape, dtype=xa.dtype, device=xa.device)
+            _sync_stream(xa)
+        else:
+            out = np.empty(shape, dtype=xa.dtype)
+        L.check(self._entry("corrla_kde_eval_", on_dev, xa.dtype)(self._h, _ptr(xa), n_q, incx, _ptr(sa), n_s, incs, h, L.KDE_WHAT[what],
+                                                                 _ptr(out), 1))
+        self._kde_done(on_dev)
+        return out
+
+    def kde_nll(self, x_test, supports, bandwidths):
+        """-> (nll, dnll): for every bandwidth h_b the negative log-likelihood -sum_i logpdf_i(h_b) of the test points under the
+        estimate over `supports`, and its derivative in h at h_b (corrla_kde_nll_*; ``UniRv::nll``, univariate_rv.rs:165-170).
+        Up to 64 bandwidths per call share one sweep: the squared distance of a pair is formed once per group of bandwidths.
+        Both are float64 of length n_h for either input dtype -- numpy arrays for numpy input, tensors on the device for CUDA
+        tensors -- finite for every h > 0 (stabilised sums, see ``kde_eval``), bitwise reproducible, and a bandwidth's values
+        do not depend on the others of the call.  The derivative is analytic.  Inputs as for ``kde_eval``; `bandwidths` is a
+        scalar or a sequence on the host."""
+        xa, n_t, incx, sa, n_s, incs, on_dev, _ = self._kde_pair(x_test, supports, "kde_nll")
+        hb = np.ascontiguousarray(np.atleast_1d(np.asarray(bandwidths.detach().cpu().numpy() if _is_torch(bandwidths) else bandwidths,
+                                                           dtype=np.float64)))
+        if hb.ndim != 1 or not 1 <= hb.shape[0] <= L.KDE_MAX_BANDWIDTHS:
+            raise ValueError(f"bandwidths must be 1 to {L.KDE_MAX_BANDWIDTHS} values, got shape {tuple(hb.shape)}")
+        if not (np.all(np.isfinite(hb)) and np.all(hb > 0.0)):
+            raise ValueError("every bandwidth must be finite and > 0")
+        n_h = int(hb.shape[0])
+        if on_dev:
+            import torch
+            nll, dnll = (torch.empty(n_h, dtype=torch.float64, device=xa.device) for _ in range(2))
+            _sync_stream(xa)
+        else:
+            nll, dnll = np.empty(n_h, dtype=np.float64), np.empty(n_h, dtype=np.float64)
+        L.check(self._entry("corrla_kde_nll_", on_dev, xa.dtype)(self._h, _ptr(xa), n_t, incx, _ptr(sa), n_s, incs, hb.ctypes.data, n_h,
+                                                                _ptr(nll), _ptr(dnll)))
+        self._kde_done(on_dev)
+        return nll, dnll
+
+    def last_kde_route(self):
+        """The route of this context's last ``kde_eval`` / ``kde_nll`` call: "single" (every workgroup swept all supports) or
+        "split" (few points: the supports were split over workgroups and the partial sums added in index order); None before
+        the first call."""
+        return getattr(self, "_kde_route", None)
+
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
         """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that

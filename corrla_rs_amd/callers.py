@@ -19,6 +19,9 @@ reference also does after its random_svd calls (k = n_modes, a few tens), writte
                                               <- src/lib_math_utils/stats_corr.rs:146-249 (the normal equations and the
                                                  evaluation from the fused kernels, ``Context.polyfit_gram`` /
                                                  ``poly_eval``; the p-sized solve on the host)
+  KdeRv(bandwidth, samples) / build_kde(...)  <- KdeRv, build_kde        src/lib_math_utils/univariate_rv.rs:165-170,
+                                                 384-497 (the pairwise sums from ``Context.kde_eval`` / ``kde_nll``; the
+                                                 bandwidth search on the host over (nll, dnll) evaluations)
 Every product with an n_x- or N-sized dimension goes through the library's HIP GEMMs (``Context.matmul``); only
 snapshot-count- and n_modes-sized matrices are touched by numpy."""
 import numpy as np
@@ -27,7 +30,7 @@ from .api import _is_torch, default_context, rsvd
 
 __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyGradientEstimator", "ActiveSsRsvd",
            "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply",
-           "linear_fit", "quad_fit", "quad_eval", "jac_from_lin", "jac_from_quad", "polyfit_solve"]
+           "linear_fit", "quad_fit", "quad_eval", "jac_from_lin", "jac_from_quad", "polyfit_solve", "KdeRv", "build_kde"]
 
 
 def _on_gpu(x):
@@ -584,3 +587,265 @@ class PodI:
         w = self._interp.predict(np.asarray(t_queries, np.float64)).T           # (n_modes, n_q)
         out = self._ctx.matmul(self._modes, torch.as_tensor(np.ascontiguousarray(w), dtype=torch.float64, device=self._modes.device))
         return out if self.on_device else out.cpu().numpy()
+
+
+# ---- Gaussian kernel density estimates (univariate_rv.rs:165-170, 384-497) ------------------------------------------------------
+_KDE_HOST_PAIRS = 1 << 21        # (point, support) pairs the numpy path holds at once: 16 MiB of float64 per temporary
+_KDE_GRID = 64                   # bandwidths per likelihood evaluation: what one ``Context.kde_nll`` call takes
+_KDE_MAX_CALLS = 12              # likelihood evaluations of one ``est_bandwidth``
+_SQRT_2PI = float(np.sqrt(2.0 * np.pi))
+
+
+def _kde_host_blocks(n_q, n_s):
+    """row and support block lengths with rows x supports <= _KDE_HOST_PAIRS"""
+    sc = min(n_s, _KDE_HOST_PAIRS)
+    return max(1, _KDE_HOST_PAIRS // sc), sc
+
+
+def _kde_host_dstar(x, s, sc):
+    """min_j (x_i - s_j)^2 for a block of points, the supports taken sc at a time"""
+    m = np.full(x.shape[0], np.inf)
+    for j0 in range(0, s.shape[0], sc):
+        d = x[:, None] - s[None, j0:j0 + sc]
+        m = np.minimum(m, (d * d).min(axis=1))
+    return m
+
+
+def _kde_host_eval(x, s, h, what):
+    """The stabilised formulas of corrla_kde_eval_* restated in numpy (float64), block by block."""
+    import math
+    n_q, n_s = x.shape[0], s.shape[0]
+    rows, sc = _kde_host_blocks(n_q, n_s)
+    out = np.empty(n_q)
+    erfc = np.frompyfunc(math.erfc, 1, 1)  # numpy has no erfc
+    c = 1.0 / (2.0 * h * h)
+    for i0 in range(0, n_q, rows):
+        xb = x[i0:i0 + rows]
+        if what == "cdf":
+            acc = np.zeros(xb.shape[0])
+            for j0 in range(0, n_s, sc):
+                z = -(xb[:, None] - s[None, j0:j0 + sc]) * (1.0 / (h * np.sqrt(2.0)))
+                acc += erfc(z).astype(np.float64).sum(axis=1)
+            out[i0:i0 + rows] = 0.5 * acc / n_s
+            continue
+        dstar = _kde_host_dstar(xb, s, sc)
+        acc = np.zeros(xb.shape[0])
+        for j0 in range(0, n_s, sc):
+            d = xb[:, None] - s[None, j0:j0 + sc]
+            acc += np.exp((dstar[:, None] - d * d) * c).sum(axis=1)
+        tstar = dstar * c
+        if what == "pdf":
+            out[i0:i0 + rows] = np.exp(-tstar) * acc / (n_s * h * _SQRT_2PI)
+        else:
+            out[i0:i0 + rows] = -tstar + np.log(acc) - np.log(n_s * h * _SQRT_2PI)
+    return out
+
+
+def _kde_host_nll(x, s, hb):
+    """-> (nll, dnll) over the bandwidths hb: corrla_kde_nll_* restated in numpy (float64), block by block"""
+    n_t, n_s = x.shape[0], s.shape[0]
+    rows, sc = _kde_host_blocks(n_t, n_s)
+    nll, dnll = np.zeros(hb.shape[0]), np.zeros(hb.shape[0])
+    for i0 in range(0, n_t, rows):
+        xb = x[i0:i0 + rows]
+        dstar = _kde_host_dstar(xb, s, sc)
+        sk, se = np.zeros((hb.shape[0], xb.shape[0])), np.zeros((hb.shape[0], xb.shape[0]))
+        for j0 in range(0, n_s, sc):
+            d = xb[:, None] - s[None, j0:j0 + sc]
+            a = dstar[:, None] - d * d
+            for b, h in enumerate(hb):
+                e = a * (1.0 / (2.0 * h * h))
+                kk = np.exp(e)
+                sk[b] += kk.sum(axis=1)
+                se[b] += (e * kk).sum(axis=1)
+        for b, h in enumerate(hb):
+            tstar = dstar / (2.0 * h * h)
+            nll[b] -= (-tstar + np.log(sk[b]) - np.log(n_s * h * _SQRT_2PI)).sum()
+            dnll[b] -= ((2.0 * (tstar - se[b] / sk[b]) - 1.0) / h).sum()
+    return nll, dnll
+
+
+class KdeRv:
+    """Gaussian kernel density estimate with uniform weights (``KdeRv``, univariate_rv.rs:384-460): ``pdf``, ``cdf``,
+    ``logpdf``, ``nll``, ``sample``, and ``est_bandwidth`` by cross-validated likelihood.
+
+    device=True, or whenever a CUDA tensor is involved: the pairwise sums come from ``Context.kde_eval`` / ``kde_nll`` (fused
+    kernels, the (n, n_s) matrix is never stored; a CUDA tensor in -> a tensor out).  Otherwise numpy input runs the same
+    formulas in numpy on the host, at most 2^21 pairs at a time.  Both use the stabilised sums
+    exp(-t*) sum_j exp(-(t_j - t*)) with t* the term of the nearest support: ``logpdf`` and ``nll`` are finite wherever the
+    reference's ``pdf(x).ln()`` is -inf (every term underflowed), which is what lets the bandwidth search start at small h.
+
+    ``est_bandwidth`` differs from the reference on purpose.  There ``mlefit`` runs a local optimiser (L-BFGS on forward
+    differences, a random particle swarm as fallback) from the initial bandwidth, with a quadratic penalty outside the bounds.
+    Here the search is deterministic and global over the bounds, uses only (nll, dnll) evaluations of at most 64 bandwidths
+    each with the analytic derivative, and clamps to the bounds: (1) a log-spaced grid over the bounds brackets the grid
+    minimum; (2) grids inside the bracket, each keeping the cell where dnll/dh changes sign from - to + (the cells next to
+    the grid minimum where it does not), until the bracket is narrower than rtol in ln h; (3) the zero of dnll/dh inside the
+    final bracket by linear interpolation in ln h.  At most 12 evaluations; the result always lies inside the bounds.
+    `method` is accepted for signature compatibility and ignored."""
+
+    def __init__(self, bandwidth, samples, *, device=False, ctx=None):
+        self.bandwidth = float(bandwidth)
+        if not (np.isfinite(self.bandwidth) and self.bandwidth > 0.0):
+            raise ValueError(f"bandwidth must be finite and > 0, got {bandwidth!r}")
+        if _on_gpu(samples):
+            import torch
+            s = samples.detach().reshape(-1)
+            self.supports = s if s.dtype in (torch.float32, torch.float64) else s.double()
+        else:
+            s = np.asarray(samples.detach().cpu().numpy() if _is_torch(samples) else samples)
+            self.supports = np.ascontiguousarray(s.reshape(-1), dtype=np.float32 if s.dtype == np.float32 else np.float64)
+        if self.supports.shape[0] == 0:
+            raise ValueError("samples must be non-empty")
+        self.device, self._ctx = bool(device), ctx
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    def _on_device(self, x):
+        return self.device or _on_gpu(x) or _on_gpu(self.supports)
+
+    def _device_pair(self, x):
+        """x and the supports as ``Context.kde_*`` takes them: the kind of x decides, the dtype of the supports"""
+        if _on_gpu(x) or _on_gpu(self.supports):
+            import torch
+            dev = x.device if _on_gpu(x) else self.supports.device
+            dt = torch.float32 if str(self.supports.dtype).endswith("float32") else torch.float64
+            xt = x.detach() if _is_torch(x) else torch.as_tensor(np.asarray(x))
+            st = self.supports if _is_torch(self.supports) else torch.as_tensor(self.supports)
+            return xt.to(device=dev, dtype=dt), st.to(device=dev, dtype=dt), not _on_gpu(x)
+        return np.asarray(x.detach().numpy() if _is_torch(x) else x, dtype=self.supports.dtype), self.supports, False
+
+    def _host_pair(self, x):
+        return np.asarray(x, dtype=np.float64), np.asarray(self.supports, dtype=np.float64)
+
+    def _eval(self, x, what):
+        if self._on_device(x):
+            xa, sa, to_host = self._device_pair(x)
+            out = self._context().kde_eval(xa, sa, self.bandwidth, what)
+            return out.cpu().numpy() if to_host else out
+        xa, sa = self._host_pair(x)
+        if xa.size == 0:
+            raise ValueError("x must be non-empty")
+        return _kde_host_eval(xa.reshape(-1), sa, self.bandwidth, what).reshape(xa.shape)
+
+    def pdf(self, x):
+        """the density at the points x, in the shape of x"""
+        return self._eval(x, "pdf")
+
+    def cdf(self, x):
+        """the distribution function at the points x (through erfc)"""
+        return self._eval(x, "cdf")
+
+    def logpdf(self, x):
+        """the log-density at the points x: finite for every finite x"""
+        return self._eval(x, "logpdf")
+
+    def nll_dnll(self, samples, bandwidths):
+        """-> (nll, dnll), float64 numpy arrays over `bandwidths` (any number: evaluated 64 at a time)"""
+        hb = np.atleast_1d(np.asarray(bandwidths, dtype=np.float64))
+        if hb.ndim != 1 or hb.shape[0] == 0 or not (np.all(np.isfinite(hb)) and np.all(hb > 0.0)):
+            raise ValueError("bandwidths must be finite and > 0")
+        nll, dnll = np.empty(hb.shape[0]), np.empty(hb.shape[0])
+        if self._on_device(samples):
+            xa, sa, _ = self._device_pair(samples)
+        else:
+            xa, sa = self._host_pair(samples)
+            xa = xa.reshape(-1)
+            if xa.size == 0:
+                raise ValueError("samples must be non-empty")
+        for b0 in range(0, hb.shape[0], _KDE_GRID):
+            part = hb[b0:b0 + _KDE_GRID]
+            if self._on_device(samples):
+                a, b = self._context().kde_nll(xa, sa, part)
+                a, b = (a.cpu().numpy(), b.cpu().numpy()) if _is_torch(a) else (a, b)
+            else:
+                a, b = _kde_host_nll(xa, sa, part)
+            nll[b0:b0 + _KDE_GRID], dnll[b0:b0 + _KDE_GRID] = a, b
+        return nll, dnll
+
+    def nll(self, samples, bandwidth=None):
+        """``UniRv::nll`` (univariate_rv.rs:165-170): -sum_i ln pdf(samples_i), at this estimate's bandwidth or at the given
+        one; a sequence of bandwidths gives an array.  Finite for every h > 0."""
+        h = self.bandwidth if bandwidth is None else bandwidth
+        out = self.nll_dnll(samples, h)[0]
+        return float(out[0]) if np.ndim(h) == 0 else out
+
+    def sample(self, n, *, seed=None):
+        """n draws: a support picked uniformly plus h N(0, 1) (``KdeRv::sample``, univariate_rv.rs:445-459), on the host from
+        ``numpy.random.default_rng(seed)``"""
+        rng = np.random.default_rng(seed)
+        s = self.supports.cpu().numpy() if _is_torch(self.supports) else self.supports
+        return s[rng.integers(0, s.shape[0], int(n))].astype(np.float64) + self.bandwidth * rng.standard_normal(int(n))
+
+    def est_bandwidth(self, test_samples, method=None, *, bounds=(1e-9, 1000.0), rtol=1e-6):
+        """The bandwidth that minimises the negative log-likelihood of `test_samples` -- which should not be the supports --
+        inside `bounds` (``KdeRv::est_bandwidth``, univariate_rv.rs:406-420); sets ``self.bandwidth`` and returns it.  See the
+        class docstring for the search and its differences from the reference.  ``self.n_nll_calls`` counts the likelihood
+        evaluations (at most 12, of at most 64 bandwidths each)."""
+        lo, hi = float(bounds[0]), float(bounds[1])
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo < hi):
+            raise ValueError(f"bounds must be finite with 0 < lower < upper, got {bounds!r}")
+        rtol = float(rtol)
+        if not rtol > 0.0:
+            raise ValueError("rtol must be > 0")
+        a, b = np.log(lo), np.log(hi)
+        self.n_nll_calls = 0
+        a_is_lo = b_is_hi = True  # the bracket's ends are still the bounds themselves
+        while True:
+            grid = np.exp(np.linspace(a, b, _KDE_GRID))
+            grid[0], grid[-1] = np.exp(a), np.exp(b)
+            nll, dnll = self.nll_dnll(test_samples, grid)
+            self.n_nll_calls += 1
+            i = int(np.argmin(nll))
+            # the cells where the derivative goes from - to +: the one nearest the grid minimum
+            cells = np.nonzero((dnll[:-1] < 0.0) & (dnll[1:] >= 0.0))[0]
+            if cells.size:
+                j = int(cells[np.argmin(np.abs(cells + 0.5 - i))])
+                i0, i1 = j, j + 1
+            else:
+                i0, i1 = max(i - 1, 0), min(i + 1, _KDE_GRID - 1)
+            a, b = np.log(grid[i0]), np.log(grid[i1])
+            a_is_lo, b_is_hi = a_is_lo and i0 == 0, b_is_hi and i1 == _KDE_GRID - 1
+            ga, gb, na, nb = dnll[i0], dnll[i1], nll[i0], nll[i1]
+            if b - a <= rtol or self.n_nll_calls >= _KDE_MAX_CALLS:
+                break
+        if ga < 0.0 <= gb:      # the zero of dnll/dh inside the bracket, linear in ln h
+            t = a + (b - a) * (-ga / (gb - ga))
+        else:                   # no sign change: the minimum is at an end of the bracket
+            t = a if na <= nb else b
+        if (t == a and a_is_lo) or (t == b and b_is_hi):
+            self.bandwidth = lo if t == a else hi
+        else:
+            self.bandwidth = float(min(max(np.exp(min(max(t, a), b)), lo), hi))
+        return self.bandwidth
+
+
+def build_kde(init_bandwidth, samples, n_iter, method=None, *, seed=None, device=False, ctx=None):
+    """``build_kde`` (univariate_rv.rs:464-497): n_iter random splits of `samples` -- each sample goes to the supports with
+    probability 0.7, else to the test set -- one ``est_bandwidth`` per split, and the estimate over ALL samples with the
+    element sorted[n_iter // 2] of the per-split bandwidths.  The splits come from ``numpy.random.default_rng(seed)``: the
+    same seed gives the same estimate.  The per-split bandwidths are kept, in split order, as ``bandwidth_estimates``."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("n_iter must be >= 1")
+    flat = samples.detach().reshape(-1) if _is_torch(samples) else np.asarray(samples).reshape(-1)
+    n = int(flat.shape[0])
+    rng = np.random.default_rng(seed)
+    ests = []
+    for _ in range(n_iter):
+        mask = rng.random(n) < 0.7
+        if mask.all() or not mask.any():
+            raise ValueError("a split left the supports or the test set empty: build_kde needs more samples")
+        if _is_torch(flat):
+            import torch
+            m = torch.from_numpy(mask).to(flat.device)
+            sup, test = flat[m], flat[~m]
+        else:
+            sup, test = flat[mask], flat[~mask]
+        ests.append(KdeRv(init_bandwidth, sup, device=device, ctx=ctx).est_bandwidth(test, method))
+    out = KdeRv(sorted(ests)[len(ests) // 2], flat, device=device, ctx=ctx)
+    out.bandwidth_estimates = np.asarray(ests)
+    return out

@@ -12,6 +12,7 @@
 #include "driver.hpp"
 #include "rbf_plan.hpp"  // rbf_poly_terms, kRbfMaxDim
 #include "polyfit_plan.hpp"  // poly_terms, kPolyMaxK, kPolyMaxRhs
+#include "kde_plan.hpp"  // kKdeMaxH
 
 namespace corrla {
 
@@ -1008,6 +1009,82 @@ inline void poly_eval_entry(Dev&, const PolyEvalCall<T>& c, Run&& run) {
     run();
   else
     throw Error(ST_EINVAL, "this backend has no polynomial response-surface kernels: corrla_poly_eval_* is not supported");
+}
+
+// ---- kernel density estimates (corrla_kde_eval_* / corrla_kde_nll_*, univariate_rv.rs:165-170, 423-444) ----------------------
+// Argument checks of every entry, then `run` -- on a backend that carries the kernels (dev_has_kde); any other backend ends
+// the call with EINVAL, never with another way of computing the result.
+template <class T>
+struct KdeEvalCall {
+  const T* x;  // n_q points, element stride incx
+  int64_t n_q, incx;
+  const T* s;  // n_s supports, element stride incs
+  int64_t n_s, incs;
+  double h;
+  int what;    // 0 pdf, 1 cdf, 2 logpdf
+  T* out;      // n_q values, element stride inco
+  int64_t inco;
+};
+
+template <class Dev, class T, class Run>
+inline void kde_eval_entry(Dev&, const KdeEvalCall<T>& c, Run&& run) {
+  const char* who = "kde_eval";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.x) bad("x is NULL");
+  if (!c.s) bad("s is NULL");
+  if (!c.out) bad("out is NULL");
+  if (c.n_q < 1) bad("n_q must be >= 1");
+  if (c.n_s < 1) bad("n_s must be >= 1");
+  if (c.incx < 1) bad("incx must be >= 1");
+  if (c.incs < 1) bad("incs must be >= 1");
+  if (c.inco < 1) bad("inco must be >= 1");
+  if (!std::isfinite(c.h) || !(c.h > 0.0)) bad("h must be finite and > 0");
+  if (c.what < 0 || c.what > 2) bad("what must be 0 (pdf), 1 (cdf) or 2 (logpdf)");
+  const PcaApplyRange in[2] = {{c.x, (size_t)((c.n_q - 1) * c.incx + 1) * sizeof(T), "x"},
+                               {c.s, (size_t)((c.n_s - 1) * c.incs + 1) * sizeof(T), "s"}};
+  const PcaApplyRange o[1] = {{c.out, (size_t)((c.n_q - 1) * c.inco + 1) * sizeof(T), "out"}};
+  pca_apply_no_overlap(in, 2, o, 1, who);
+  if constexpr (dev_has_kde<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no kernel-density kernels: corrla_kde_eval_* is not supported");
+}
+
+template <class T>
+struct KdeNllCall {
+  const T* x;       // n_t test points, element stride incx
+  int64_t n_t, incx;
+  const T* s;
+  int64_t n_s, incs;
+  const double* h;  // n_h bandwidths, always on the host
+  int64_t n_h;
+  double* nll;      // n_h
+  double* dnll;     // n_h, nullable
+};
+
+template <class Dev, class T, class Run>
+inline void kde_nll_entry(Dev&, const KdeNllCall<T>& c, Run&& run) {
+  const char* who = "kde_nll";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.x) bad("x is NULL");
+  if (!c.s) bad("s is NULL");
+  if (!c.h) bad("h is NULL");
+  if (!c.nll) bad("nll is NULL");
+  if (c.n_t < 1) bad("n_t must be >= 1");
+  if (c.n_s < 1) bad("n_s must be >= 1");
+  if (c.incx < 1) bad("incx must be >= 1");
+  if (c.incs < 1) bad("incs must be >= 1");
+  if (c.n_h < 1 || c.n_h > k::kKdeMaxH) bad("n_h must be in [1, 64]");
+  for (int64_t b = 0; b < c.n_h; ++b)
+    if (!std::isfinite(c.h[b]) || !(c.h[b] > 0.0)) bad("every h must be finite and > 0");
+  const PcaApplyRange in[2] = {{c.x, (size_t)((c.n_t - 1) * c.incx + 1) * sizeof(T), "x"},
+                               {c.s, (size_t)((c.n_s - 1) * c.incs + 1) * sizeof(T), "s"}};
+  const PcaApplyRange o[2] = {{c.nll, (size_t)c.n_h * sizeof(double), "nll"}, {c.dnll, c.dnll ? (size_t)c.n_h * sizeof(double) : 0, "dnll"}};
+  pca_apply_no_overlap(in, 2, o, 2, who);
+  if constexpr (dev_has_kde<Dev>::value)
+    run();
+  else
+    throw Error(ST_EINVAL, "this backend has no kernel-density kernels: corrla_kde_nll_* is not supported");
 }
 
 }  // namespace corrla

@@ -10,6 +10,7 @@
 #include "cov_stage.hpp"
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
+#include "kde_stage.hpp"
 #include "pca_apply_stage.hpp"
 #include "polyfit_stage.hpp"
 #include "rbf_stage.hpp"
@@ -25,6 +26,7 @@ struct corrla_ctx {
   bool profile;
   pca_apply_stage::Ran pca_apply;  // how the last corrla_pca_transform_* / corrla_pca_inverse_* call ran
   polyfit_stage::Ran polyfit;      // how the last corrla_polyfit_gram_* / corrla_poly_eval_* call ran
+  kde_stage::Ran kde;              // how the last corrla_kde_eval_* / corrla_kde_nll_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -401,6 +403,37 @@ CORRLA_API corrla_status corrla_ctx_last_polyfit(corrla_ctx* ctx, int* route_out
     corrla_ctx* c = need(ctx);
     std::lock_guard<std::mutex> lk(c->mu);
     if (route_out) *route_out = c->polyfit.route;
+  });
+}
+
+// ---- kernel density estimates (KdeRv::pdf / cdf, UniRv::nll, univariate_rv.rs:165-170, 423-444) ------------------------------
+#define CORRLA_KDE_POINTS(T, N) const T *x, int64_t N, int64_t incx, const T *s, int64_t n_s, int64_t incs
+#define CORRLA_DEFINE_KDE(SUF, DEV, T, HOST)                                                                            \
+  CORRLA_API corrla_status corrla_kde_eval_##DEV##SUF(corrla_ctx* ctx, CORRLA_KDE_POINTS(T, n_q), double h, int what, T* out, \
+                                                      int64_t inco) {                                                   \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cx.kde = kde_stage::Ran();                                                                                        \
+      const KdeEvalCall<T> c{x, n_q, incx, s, n_s, incs, h, what, out, inco};                                           \
+      kde_eval_entry<HipDev, T>(cx.dev, c, [&] { kde_stage::run_eval<T>(cx.dev, HOST, c, &cx.kde); });                  \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  CORRLA_API corrla_status corrla_kde_nll_##DEV##SUF(corrla_ctx* ctx, CORRLA_KDE_POINTS(T, n_t), const double* h, int64_t n_h, \
+                                                     double* nll, double* dnll) {                                       \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      cx.kde = kde_stage::Ran();                                                                                        \
+      const KdeNllCall<T> c{x, n_t, incx, s, n_s, incs, h, n_h, nll, dnll};                                             \
+      kde_nll_entry<HipDev, T>(cx.dev, c, [&] { kde_stage::run_nll<T>(cx.dev, HOST, c, &cx.kde); });                    \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_KDE(f32, , float, true)
+CORRLA_DEFINE_KDE(f64, , double, true)
+CORRLA_DEFINE_KDE(f32, dev_, float, false)
+CORRLA_DEFINE_KDE(f64, dev_, double, false)
+CORRLA_API corrla_status corrla_ctx_last_kde(corrla_ctx* ctx, int* route_out) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (route_out) *route_out = c->kde.route;
   });
 }
 

@@ -128,6 +128,11 @@ template <class D, class = void>
 struct dev_has_polyfit : std::false_type {};
 template <class D>
 struct dev_has_polyfit<D, std::void_t<decltype(D::kHasPolyfit)>> : std::true_type {};
+// ... and those that carry the kernel-density kernels of corrla_kde_eval_* / corrla_kde_nll_* (kde_kernels.hpp) with kHasKde.
+template <class D, class = void>
+struct dev_has_kde : std::false_type {};
+template <class D>
+struct dev_has_kde<D, std::void_t<decltype(D::kHasKde)>> : std::true_type {};
 
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).

@@ -38,6 +38,7 @@
 #include "pca_apply_kernels.hpp"
 #include "rbf_kernels.hpp"
 #include "polyfit_kernels.hpp"
+#include "kde_kernels.hpp"
 
 namespace corrla {
 
@@ -811,6 +812,8 @@ class HipDev {
   static constexpr bool kHasRbf = true;  // driver.hpp: dev_has_rbf
   // ---- polynomial response surfaces: polyfit_plan.hpp plans, polyfit_stage.hpp launches polyfit_kernels.hpp ------------------
   static constexpr bool kHasPolyfit = true;  // driver.hpp: dev_has_polyfit
+  // ---- kernel density estimates: kde_plan.hpp plans, kde_stage.hpp launches kde_kernels.hpp -----------------------------------
+  static constexpr bool kHasKde = true;  // driver.hpp: dev_has_kde
   const PolyKnobs& poly_knobs() const { return poly_knobs_; }
   // The plan's pair table on the device.  It depends on (k, r, degree) alone, so it is uploaded when those change and kept
   // between calls: a repeated fit enqueues without a synchronising copy.

@@ -604,6 +604,57 @@ CORRLA_API corrla_status corrla_poly_eval_dev_f64(corrla_ctx* ctx, const double*
                                                   int64_t ldc, int64_t r, int degree, double* out, int64_t ld_out, double* jac, int64_t ld_jac);
 CORRLA_API corrla_status corrla_ctx_last_polyfit(corrla_ctx* ctx, int* route_out);
 
+/* ---- Gaussian kernel density estimates: density, distribution, likelihood of a bandwidth --------------
+ * Replaces  UniRv::nll                                           src/lib_math_utils/univariate_rv.rs:165-170
+ *           KdeRv::pdf / KdeRv::cdf                              src/lib_math_utils/univariate_rv.rs:423-444
+ * With supports s_j (j < n_s, uniform weights), points x_i, bandwidth h, d_ij = x_i - s_j and t_ij = d_ij^2 / (2 h^2):
+ *   corrla_kde_eval_*: what 0  pdf_i    = (n_s h sqrt(2 pi))^-1 sum_j exp(-t_ij)
+ *                      what 1  cdf_i    = n_s^-1 sum_j erfc(-d_ij / (h sqrt 2)) / 2
+ *                      what 2  logpdf_i = ln pdf_i
+ *   corrla_kde_nll_* : nll[b]  = -sum_i logpdf_i(h_b)            for each of the n_h bandwidths h_b
+ *                      dnll[b] = d nll / d h at h_b = -sum_i (R_i - 1) / h_b,  R_i = sum_j 2 t_ij K_ij / sum_j K_ij
+ * The n x n_s matrix of kernel values is never stored: a thread keeps a few points in registers and sweeps the supports;
+ * d^2 is formed once per pair and serves a group of bandwidths.
+ * Stabilised form: every sum is taken as exp(-t*_i) sum_j exp(-(t_ij - t*_i)) with t*_i = d*_i / (2 h^2) and
+ * d*_i = min_j d_ij^2, the squared distance to the nearest support, which does not depend on h and is computed once per
+ * call.  The nearest support contributes exactly 1, so logpdf, nll and dnll are finite for every finite input and every
+ * h > 0 (while (x - s)^2 is finite in the element type), and pdf is correct down to the underflow of the final product.
+ * This is the one deliberate difference from the reference: pdf(x).ln() is -inf there as soon as every term underflows, a
+ * few tens of bandwidths outside the supports.  dnll is analytic where the reference's optimiser differences forward.
+ * The cdf uses erfc, which keeps relative accuracy in the lower tail.
+ * Layouts: x, s and out are vectors with element strides incx, incs, inco >= 1, read and written in place whatever the
+ * alignment of their bases; the elements between the strided ones are never written.  h of corrla_kde_nll_* is ALWAYS a host
+ * pointer (the bandwidths travel in the kernel arguments); nll and dnll (n_h doubles each; dnll may be NULL) are host
+ * pointers for the host entries and device pointers for the *_dev entries, double for both element types: the sums over the
+ * supports are taken in the element type, the reduction over the points in f64.
+ * Limits: n_q, n_t, n_s >= 1; 1 <= n_h <= 64; f32 and f64.
+ * No atomics: the supports may be split over workgroups, whose partial sums a finishing kernel adds in index order; the
+ * likelihood is reduced over the points by a tree of fixed shape.  A fixed input gives a bitwise fixed output, and a
+ * bandwidth's nll and dnll do not depend on the other bandwidths of the call.  corrla_ctx_last_kde reports 1 when the last
+ * call swept the supports in one range and 2 when it split them.
+ * CORRLA_EINVAL (the message names the argument): NULL x, s, out, h or nll; n_q, n_t, n_s < 1; incx, incs, inco < 1; h not
+ * finite or <= 0; what outside [0, 2]; n_h outside [1, 64]; an output overlapping an input or the other output.  Host-pointer
+ * entries copy the strided spans to the device as they lie and the results back; the *_dev entries enqueue on the context's
+ * stream and return WITHOUT synchronising (but for a first-time growth of the workspace arena): corrla_ctx_synchronize
+ * orders the results. */
+CORRLA_API corrla_status corrla_kde_eval_f32(corrla_ctx* ctx, const float* x, int64_t n_q, int64_t incx, const float* s, int64_t n_s,
+                                             int64_t incs, double h, int what, float* out, int64_t inco);
+CORRLA_API corrla_status corrla_kde_eval_f64(corrla_ctx* ctx, const double* x, int64_t n_q, int64_t incx, const double* s, int64_t n_s,
+                                             int64_t incs, double h, int what, double* out, int64_t inco);
+CORRLA_API corrla_status corrla_kde_eval_dev_f32(corrla_ctx* ctx, const float* x, int64_t n_q, int64_t incx, const float* s, int64_t n_s,
+                                                 int64_t incs, double h, int what, float* out, int64_t inco);
+CORRLA_API corrla_status corrla_kde_eval_dev_f64(corrla_ctx* ctx, const double* x, int64_t n_q, int64_t incx, const double* s, int64_t n_s,
+                                                 int64_t incs, double h, int what, double* out, int64_t inco);
+CORRLA_API corrla_status corrla_kde_nll_f32(corrla_ctx* ctx, const float* x, int64_t n_t, int64_t incx, const float* s, int64_t n_s,
+                                            int64_t incs, const double* h, int64_t n_h, double* nll, double* dnll);
+CORRLA_API corrla_status corrla_kde_nll_f64(corrla_ctx* ctx, const double* x, int64_t n_t, int64_t incx, const double* s, int64_t n_s,
+                                            int64_t incs, const double* h, int64_t n_h, double* nll, double* dnll);
+CORRLA_API corrla_status corrla_kde_nll_dev_f32(corrla_ctx* ctx, const float* x, int64_t n_t, int64_t incx, const float* s, int64_t n_s,
+                                                int64_t incs, const double* h, int64_t n_h, double* nll, double* dnll);
+CORRLA_API corrla_status corrla_kde_nll_dev_f64(corrla_ctx* ctx, const double* x, int64_t n_t, int64_t incx, const double* s, int64_t n_s,
+                                                int64_t incs, const double* h, int64_t n_h, double* nll, double* dnll);
+CORRLA_API corrla_status corrla_ctx_last_kde(corrla_ctx* ctx, int* route_out);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller

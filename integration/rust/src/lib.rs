@@ -196,6 +196,25 @@ extern "C" {
     pub fn corrla_poly_eval_dev_f32(ctx: *mut c_void, x: *const f32, m: i64, k: i64, ldx: i64, coeffs: *const f64, ldc: i64, r: i64,
                                  degree: c_int, out: *mut f32, ld_out: i64, jac: *mut f32, ld_jac: i64) -> c_int;
     pub fn corrla_ctx_last_polyfit(ctx: *mut c_void, route_out: *mut c_int) -> c_int;
+    // Gaussian kernel density estimates (univariate_rv.rs:165-170, 423-444): what 0 pdf, 1 cdf, 2 logpdf at the points x
+    pub fn corrla_kde_eval_f64(ctx: *mut c_void, x: *const f64, n_q: i64, incx: i64, s: *const f64, n_s: i64, incs: i64, h: f64,
+                                what: c_int, out: *mut f64, inco: i64) -> c_int;
+    pub fn corrla_kde_eval_f32(ctx: *mut c_void, x: *const f32, n_q: i64, incx: i64, s: *const f32, n_s: i64, incs: i64, h: f64,
+                                what: c_int, out: *mut f32, inco: i64) -> c_int;
+    pub fn corrla_kde_eval_dev_f64(ctx: *mut c_void, x: *const f64, n_q: i64, incx: i64, s: *const f64, n_s: i64, incs: i64, h: f64,
+                                what: c_int, out: *mut f64, inco: i64) -> c_int;
+    pub fn corrla_kde_eval_dev_f32(ctx: *mut c_void, x: *const f32, n_q: i64, incx: i64, s: *const f32, n_s: i64, incs: i64, h: f64,
+                                what: c_int, out: *mut f32, inco: i64) -> c_int;
+    // nll[b] = -sum_i logpdf_i(h[b]) and dnll[b] = d nll / d h (nullable) for n_h <= 64 bandwidths; h is always a host pointer
+    pub fn corrla_kde_nll_f64(ctx: *mut c_void, x: *const f64, n_t: i64, incx: i64, s: *const f64, n_s: i64, incs: i64,
+                               h: *const f64, n_h: i64, nll: *mut f64, dnll: *mut f64) -> c_int;
+    pub fn corrla_kde_nll_f32(ctx: *mut c_void, x: *const f32, n_t: i64, incx: i64, s: *const f32, n_s: i64, incs: i64,
+                               h: *const f64, n_h: i64, nll: *mut f64, dnll: *mut f64) -> c_int;
+    pub fn corrla_kde_nll_dev_f64(ctx: *mut c_void, x: *const f64, n_t: i64, incx: i64, s: *const f64, n_s: i64, incs: i64,
+                               h: *const f64, n_h: i64, nll: *mut f64, dnll: *mut f64) -> c_int;
+    pub fn corrla_kde_nll_dev_f32(ctx: *mut c_void, x: *const f32, n_t: i64, incx: i64, s: *const f32, n_s: i64, incs: i64,
+                               h: *const f64, n_h: i64, nll: *mut f64, dnll: *mut f64) -> c_int;
+    pub fn corrla_ctx_last_kde(ctx: *mut c_void, route_out: *mut c_int) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
