@@ -561,15 +561,22 @@ class Context:
             vecs.append(a.contiguous() if on_device else np.ascontiguousarray(a))
         return vecs[0], vecs[1], comps, k
 
-    def _pca_apply_done(self, on_device):
-        """After a transform / inverse call: the device entries only enqueue, so torch's streams see the results after
-        this; then how the call ran (corrla_ctx_last_pca_apply)."""
+    def _call_done(self, on_device, last, **names):
+        """After a call of the fitted-model, polyfit or kde entries: the device entries only enqueue, so torch's streams see
+        the results after this; then how the call ran: `last` (a corrla_ctx_last_* function) fills one int per keyword, and
+        each is kept as the attribute the keyword names, through the keyword's table of names.  The keywords stand in the
+        order of the C function's out-parameters: they are passed on by position."""
         if on_device:
             L.check(self._lib.corrla_ctx_synchronize(self._h))
-        centring, route = C.c_int(0), C.c_int(0)
-        L.check(self._lib.corrla_ctx_last_pca_apply(self._h, C.byref(centring), C.byref(route)))
-        self._pca_apply_centring = L.PCA_APPLY_CENTRINGS.get(centring.value)
-        self._pca_apply_route = L.PCA_APPLY_ROUTES.get(route.value)
+        vals = [C.c_int(0) for _ in names]
+        L.check(getattr(self._lib, last)(self._h, *[C.byref(v) for v in vals]))
+        for (attr, table), v in zip(names.items(), vals):
+            setattr(self, attr, table.get(v.value))
+
+    def _pca_apply_done(self, on_device):
+        """_call_done for the transform / inverse entries (also what a caller of the raw entries ends with)"""
+        self._call_done(on_device, "corrla_ctx_last_pca_apply", _pca_apply_centring=L.PCA_APPLY_CENTRINGS,
+                        _pca_apply_route=L.PCA_APPLY_ROUTES)
 
     def pca_transform(self, x, means, components, scales=None, *, own_means=False, residuals=False, center=None):
         """A fitted PCA model applied to x (m x n) on the device (corrla_pca_transform_*): the scores
@@ -794,13 +801,6 @@ class Context:
             raise ValueError(f"{what}: x has {a.shape[1]} features, the kernels take 1 to 128")
         return self._rbf_rowmajor(a, on_dev), on_dev
 
-    def _polyfit_done(self, on_device):
-        if on_device:  # the device entry only enqueues: torch's streams see the results after this
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
-        route = C.c_int(0)
-        L.check(self._lib.corrla_ctx_last_polyfit(self._h, C.byref(route)))
-        self._polyfit_route = L.POLYFIT_ROUTES.get(route.value)
-
     def polyfit_gram(self, x, y=None, degree=2, *, normalize=True):
         """The normal equations of a polynomial least-squares fit without the Vandermonde matrix -> (G, means, scales).
 
@@ -853,7 +853,7 @@ class Context:
                                                                     None if yy is None else _ptr(yy), r, ldy, degree, int(normalize),
                                                                     _ptr(g), order, None if means is None else _ptr(means),
                                                                     None if scales is None else _ptr(scales)))
-        self._polyfit_done(on_dev)
+        self._call_done(on_dev, "corrla_ctx_last_polyfit", _polyfit_route=L.POLYFIT_ROUTES)
         return g, means, scales
 
     def poly_eval(self, x, coeffs, degree=2, *, jac=False):
@@ -897,7 +897,7 @@ class Context:
         L.check(self._entry("corrla_poly_eval_", on_dev, a.dtype)(self._h, _ptr(a), m, kf, self._row_stride(a), _ptr(c),
                                                                  self._row_stride(c), r, degree, _ptr(out), r,
                                                                  None if grad is None else _ptr(grad), kf))
-        self._polyfit_done(on_dev)
+        self._call_done(on_dev, "corrla_ctx_last_polyfit", _polyfit_route=L.POLYFIT_ROUTES)
         if not jac:
             return out
         return out, (grad[0] if r == 1 else grad)
@@ -947,13 +947,6 @@ class Context:
             raise ValueError(f"{what}: x is {xa.dtype}, supports {sa.dtype}: convert one of them")
         return xa, n_q, incx, sa, n_s, incs, x_dev, shape
 
-    def _kde_done(self, on_device):
-        if on_device:  # the device entry only enqueues: torch's streams see the results after this
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
-        route = C.c_int(0)
-        L.check(self._lib.corrla_ctx_last_kde(self._h, C.byref(route)))
-        self._kde_route = L.KDE_ROUTES.get(route.value)
-
     def kde_eval(self, x, supports, bandwidth, what="pdf"):
         """The Gaussian kernel density estimate over `supports` (uniform weights) with the given bandwidth at the points x
         (corrla_kde_eval_*; ``KdeRv::pdf`` / ``cdf``, univariate_rv.rs:423-444): what="pdf" the density, "cdf" the distribution
@@ -978,7 +971,7 @@ class Context:
             out = np.empty(shape, dtype=xa.dtype)
         L.check(self._entry("corrla_kde_eval_", on_dev, xa.dtype)(self._h, _ptr(xa), n_q, incx, _ptr(sa), n_s, incs, h, L.KDE_WHAT[what],
                                                                  _ptr(out), 1))
-        self._kde_done(on_dev)
+        self._call_done(on_dev, "corrla_ctx_last_kde", _kde_route=L.KDE_ROUTES)
         return out
 
     def kde_nll(self, x_test, supports, bandwidths):
@@ -1005,7 +998,7 @@ class Context:
             nll, dnll = np.empty(n_h, dtype=np.float64), np.empty(n_h, dtype=np.float64)
         L.check(self._entry("corrla_kde_nll_", on_dev, xa.dtype)(self._h, _ptr(xa), n_t, incx, _ptr(sa), n_s, incs, hb.ctypes.data, n_h,
                                                                 _ptr(nll), _ptr(dnll)))
-        self._kde_done(on_dev)
+        self._call_done(on_dev, "corrla_ctx_last_kde", _kde_route=L.KDE_ROUTES)
         return nll, dnll
 
     def last_kde_route(self):

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/corrla_rsvd.h"
+#include "call_spans.hpp"
 #include "driver.hpp"
 #include "rbf_plan.hpp"  // rbf_poly_terms, kRbfMaxDim
 #include "polyfit_plan.hpp"  // poly_terms, kPolyMaxK, kPolyMaxRhs
@@ -737,55 +738,47 @@ inline void matmul_bf16_entry(Dev& dev, int trans, const uint16_t* a, int64_t m,
 // ---- covariance / correlation matrices (corrla_cov_*) -------------------------------------------------------------------
 // Argument checks of every corrla_cov_* entry, then `run` -- on a backend that carries the symmetric rank-k kernel
 // (dev_has_syrk); any other backend ends the call with EINVAL, never with another way of computing the matrix.
-inline bool cov_ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-  if (!a || !b) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
+
+// The arguments of the prototype, in its order.  means_out / scales_out are written when the flags ask for them (the stage
+// decides); the overlap check takes them as given.
+template <class T>
+struct CovCall {
+  const T* x;
+  int64_t m, n, rs, cs;
+  uint64_t flags;
+  int ddof;
+  T* means_out;
+  T* scales_out;
+  T* c;
+  int64_t ldc;
+  int* route_out;
+  Span x_span() const { return Span(x, m, n, rs, cs, "x"); }
+  Span c_span() const { return Span(c, n, n, ldc, "c"); }
+  Span means_span() const { return Span(means_out, 1, n, n, "means_out"); }
+  Span scales_span() const { return Span(scales_out, 1, n, n, "scales_out"); }
+};
+
 template <class Dev, class T, class Run>
-inline void cov_entry(Dev&, const T* x, int64_t m, int64_t n, int64_t rs, int64_t cs, uint64_t flags, int ddof, T* means_out,
-                      T* scales_out, T* c, int64_t ldc, int* route_out, Run&& run) {
-  if (route_out) *route_out = 0;
-  if (flags & ~(uint64_t)(CORRLA_COV_CORRELATION | CORRLA_COV_NO_CENTER)) throw Error(ST_EINVAL, "cov: unknown flag");
-  if ((flags & CORRLA_COV_CORRELATION) && (flags & CORRLA_COV_NO_CENTER))
+inline void cov_entry(Dev&, const CovCall<T>& c, Run&& run) {
+  if (c.route_out) *c.route_out = 0;
+  if (c.flags & ~(uint64_t)(CORRLA_COV_CORRELATION | CORRLA_COV_NO_CENTER)) throw Error(ST_EINVAL, "cov: unknown flag");
+  if ((c.flags & CORRLA_COV_CORRELATION) && (c.flags & CORRLA_COV_NO_CENTER))
     throw Error(ST_EINVAL, "CORRLA_COV_CORRELATION and CORRLA_COV_NO_CENTER are mutually exclusive");
-  if (ddof != 0 && ddof != 1) throw Error(ST_EINVAL, "cov: ddof must be 0 or 1");
-  if (!x || !c) throw Error(ST_EINVAL, "cov: x or c is NULL");
-  if (n < 1 || m < 1) throw Error(ST_EINVAL, "cov: empty matrix");
-  if (m - ddof < 1) throw Error(ST_EINVAL, "cov: n_samples - ddof < 1");
-  if (ldc < n) throw Error(ST_EINVAL, "cov: ldc < n");
-  if (rs < 0 || cs < 0) throw Error(ST_EINVAL, "cov: negative strides are not supported");
-  const size_t xb = (size_t)((m - 1) * rs + (n - 1) * cs + 1) * sizeof(T), cb = (size_t)((n - 1) * ldc + n) * sizeof(T),
-               vb = (size_t)n * sizeof(T);
-  if (cov_ranges_overlap(x, xb, c, cb) || cov_ranges_overlap(x, xb, means_out, vb) || cov_ranges_overlap(x, xb, scales_out, vb) ||
-      cov_ranges_overlap(c, cb, means_out, vb) || cov_ranges_overlap(c, cb, scales_out, vb) ||
-      cov_ranges_overlap(means_out, vb, scales_out, vb))
-    throw Error(ST_EINVAL, "cov: buffers overlap");
-  if constexpr (dev_has_syrk<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no symmetric rank-k kernel: corrla_cov_* is not supported");
+  if (c.ddof != 0 && c.ddof != 1) throw Error(ST_EINVAL, "cov: ddof must be 0 or 1");
+  if (!c.x || !c.c) throw Error(ST_EINVAL, "cov: x or c is NULL");
+  if (c.n < 1 || c.m < 1) throw Error(ST_EINVAL, "cov: empty matrix");
+  if (c.m - c.ddof < 1) throw Error(ST_EINVAL, "cov: n_samples - ddof < 1");
+  if (c.ldc < c.n) throw Error(ST_EINVAL, "cov: ldc < n");
+  if (c.rs < 0 || c.cs < 0) throw Error(ST_EINVAL, "cov: negative strides are not supported");
+  const Span in[1] = {c.x_span()};
+  const Span out[3] = {c.c_span(), c.means_span(), c.scales_span()};
+  no_overlap("cov", in, 1, out, 3);
+  on_backend_with<dev_has_syrk<Dev>>(run, "symmetric rank-k kernel", "corrla_cov_*");
 }
 
 // ---- the fitted PCA model on the device (corrla_pca_transform_* / corrla_pca_inverse_*, pca_rsvd.rs:43-52) ---------------
 // Argument checks of every entry, then `run` -- on a backend that carries the back-projection kernel (dev_has_pca_apply);
 // any other backend ends the call with EINVAL, never with another way of computing the result.
-struct PcaApplyRange {
-  const void* p;
-  size_t bytes;
-  const char* name;
-};
-// every output against every input and every other output
-inline void pca_apply_no_overlap(const PcaApplyRange* in, int n_in, const PcaApplyRange* out, int n_out, const char* who) {
-  for (int o = 0; o < n_out; ++o) {
-    for (int i = 0; i < n_in; ++i)
-      if (cov_ranges_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes))
-        throw Error(ST_EINVAL, std::string(who) + ": " + out[o].name + " overlaps " + in[i].name);
-    for (int q = o + 1; q < n_out; ++q)
-      if (cov_ranges_overlap(out[o].p, out[o].bytes, out[q].p, out[q].bytes))
-        throw Error(ST_EINVAL, std::string(who) + ": " + out[o].name + " overlaps " + out[q].name);
-  }
-}
 
 // What a transform call is, apart from its operand: the arguments of the prototype after the operand, in its order.
 template <class T>
@@ -805,12 +798,18 @@ struct PcaTransformCall {
   int centring() const {
     return (flags & CORRLA_PCA_CENTER_FUSED) ? 1 : ((flags & CORRLA_PCA_CENTER_COPY) ? 2 : (sizeof(T) == 8 ? 1 : 2));
   }
+  // own_means: `means` is ignored and means_out is written; otherwise the other way round
+  Span means_span() const { return own_means() ? Span() : Span(means, 1, n, n, "means"); }
+  Span scales_span() const { return Span(scales, 1, n, n, "scales"); }
+  Span comps_span() const { return Span(comps, n, k, ldc, "components"); }
+  Span scores_span() const { return Span(scores, k, m, ld_scores, "scores"); }
+  Span resid_span() const { return Span(resid_out, 1, m, m, "resid_out"); }
+  Span means_out_span() const { return own_means() ? Span(means_out, 1, n, n, "means_out") : Span(); }
 };
 
-// `operand`: the ranges of the target (x, or the three CSR arrays), checked for overlap with the outputs
+// `operand`: the spans of the target (x, or the three CSR arrays), checked for overlap with the outputs
 template <class Dev, class T, class Run>
-inline void pca_transform_entry(Dev&, const PcaTransformCall<T>& c, bool sparse, const PcaApplyRange* operand, int n_operand,
-                                Run&& run) {
+inline void pca_transform_entry(Dev&, const PcaTransformCall<T>& c, bool sparse, const Span* operand, int n_operand, Run&& run) {
   const char* who = sparse ? "pca_transform_csr" : "pca_transform";
   auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
   if (c.flags & ~(uint64_t)(CORRLA_PCA_CENTER_FUSED | CORRLA_PCA_CENTER_COPY | CORRLA_PCA_APPLY_OWN_MEANS)) bad("unknown flag");
@@ -824,45 +823,47 @@ inline void pca_transform_entry(Dev&, const PcaTransformCall<T>& c, bool sparse,
   if (c.ldc < c.k) bad("ldc < k");
   if (c.ld_scores < c.m) bad("ld_scores < m");
   if (sparse && c.resid_out) bad("resid_out must be NULL: the residual over a sparse row's implicit zeros is a dense computation");
-  const size_t vb = (size_t)c.n * sizeof(T);
-  PcaApplyRange in[6] = {{c.own_means() ? nullptr : c.means, vb, "means"},
-                         {c.scales, vb, "scales"},
-                         {c.comps, (size_t)((c.n - 1) * c.ldc + c.k) * sizeof(T), "components"}};
+  Span in[6] = {c.means_span(), c.scales_span(), c.comps_span()};
   int n_in = 3;
   for (int i = 0; i < n_operand && n_in < 6; ++i) in[n_in++] = operand[i];
-  const PcaApplyRange out[3] = {{c.scores, (size_t)((c.k - 1) * c.ld_scores + c.m) * sizeof(T), "scores"},
-                                {c.resid_out, (size_t)c.m * sizeof(T), "resid_out"},
-                                {c.own_means() ? c.means_out : nullptr, vb, "means_out"}};
-  pca_apply_no_overlap(in, n_in, out, 3, who);
-  if constexpr (dev_has_pca_apply<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no PCA back-projection kernel: corrla_pca_transform_* is not supported");
+  const Span out[3] = {c.scores_span(), c.resid_span(), c.means_out_span()};
+  no_overlap(who, in, n_in, out, 3);
+  on_backend_with<dev_has_pca_apply<Dev>>(run, "PCA back-projection kernel", "corrla_pca_transform_*");
 }
 
+// the arguments of the prototype, in its order
+template <class T>
+struct PcaInverseCall {
+  const T* scores;
+  int64_t m, k, ld_scores;
+  const T* means;
+  const T* scales;
+  const T* comps;
+  int64_t ldc, n;
+  T* out;
+  int64_t row_stride_out;
+  Span scores_span() const { return Span(scores, k, m, ld_scores, "scores"); }
+  Span means_span() const { return Span(means, 1, n, n, "means"); }
+  Span scales_span() const { return Span(scales, 1, n, n, "scales"); }
+  Span comps_span() const { return Span(comps, n, k, ldc, "components"); }
+  Span out_span() const { return Span(out, m, n, row_stride_out, "out"); }
+};
+
 template <class Dev, class T, class Run>
-inline void pca_inverse_entry(Dev&, const T* scores, int64_t m, int64_t k, int64_t ld_scores, const T* means, const T* scales,
-                              const T* comps, int64_t ldc, int64_t n, T* out, int64_t row_stride_out, Run&& run) {
+inline void pca_inverse_entry(Dev&, const PcaInverseCall<T>& c, Run&& run) {
   auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string("pca_inverse: ") + what); };
-  if (m < 1 || n < 1) bad("m and n must be >= 1");
-  if (k < 1 || k > n) bad("k must be in [1, n]");
-  if (!scores) bad("scores is NULL");
-  if (!comps) bad("components is NULL");
-  if (!out) bad("out is NULL");
-  if (ldc < k) bad("ldc < k");
-  if (ld_scores < m) bad("ld_scores < m");
-  if (row_stride_out < n && m > 1) bad("row_stride_out < n");
-  const size_t vb = (size_t)n * sizeof(T);
-  const PcaApplyRange in[4] = {{scores, (size_t)((k - 1) * ld_scores + m) * sizeof(T), "scores"},
-                               {means, vb, "means"},
-                               {scales, vb, "scales"},
-                               {comps, (size_t)((n - 1) * ldc + k) * sizeof(T), "components"}};
-  const PcaApplyRange o[1] = {{out, (size_t)((m - 1) * row_stride_out + n) * sizeof(T), "out"}};
-  pca_apply_no_overlap(in, 4, o, 1, "pca_inverse");
-  if constexpr (dev_has_pca_apply<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no PCA back-projection kernel: corrla_pca_inverse_* is not supported");
+  if (c.m < 1 || c.n < 1) bad("m and n must be >= 1");
+  if (c.k < 1 || c.k > c.n) bad("k must be in [1, n]");
+  if (!c.scores) bad("scores is NULL");
+  if (!c.comps) bad("components is NULL");
+  if (!c.out) bad("out is NULL");
+  if (c.ldc < c.k) bad("ldc < k");
+  if (c.ld_scores < c.m) bad("ld_scores < m");
+  if (c.row_stride_out < c.n && c.m > 1) bad("row_stride_out < n");
+  const Span in[4] = {c.scores_span(), c.means_span(), c.scales_span(), c.comps_span()};
+  const Span out[1] = {c.out_span()};
+  no_overlap("pca_inverse", in, 4, out, 1);
+  on_backend_with<dev_has_pca_apply<Dev>>(run, "PCA back-projection kernel", "corrla_pca_inverse_*");
 }
 
 // ---- radial-basis-function kernel matrices (corrla_rbf_matrix_* / corrla_rbf_apply_*, interp_utils.rs:96-129, 146-153) ------
@@ -882,6 +883,11 @@ struct RbfCall {
   T* out;           // MATRIX: n_q x n_s; APPLY: n_q x n_rhs; row stride ld_out
   int64_t ld_out;
   int64_t n_poly() const { return rbf_poly_terms(dim, poly_degree); }
+  // apply: the call is corrla_rbf_apply_* (coefficients in, n_rhs columns out), else corrla_rbf_matrix_* (n_s columns out)
+  Span xq_span() const { return Span(xq, n_q, dim, ldq, "xq"); }
+  Span xs_span() const { return Span(xs, n_s, dim, ldxs, "xs"); }
+  Span coeffs_span(bool apply) const { return apply ? Span(coeffs, n_s + n_poly(), n_rhs, ldw, "coeffs") : Span(); }
+  Span out_span(bool apply) const { return Span(out, n_q, apply ? n_rhs : n_s, ld_out, "out"); }
 };
 
 template <class Dev, class T, class Run>
@@ -898,7 +904,6 @@ inline void rbf_entry(Dev&, const RbfCall<T>& c, bool apply, Run&& run) {
   if (!std::isfinite(c.eps)) bad("eps must be finite");
   if (c.ldq < c.dim) bad("ldq < dim");
   if (c.ldxs < c.dim) bad("lds < dim");
-  const int64_t out_cols = apply ? c.n_rhs : c.n_s;
   if (apply) {
     if (!c.coeffs) bad("coeffs is NULL");
     if (c.n_rhs < 1) bad("n_rhs must be >= 1");
@@ -907,15 +912,10 @@ inline void rbf_entry(Dev&, const RbfCall<T>& c, bool apply, Run&& run) {
   } else if (c.ld_out < c.n_s) {
     bad("ld_out < n_s");
   }
-  const PcaApplyRange in[3] = {{c.xq, (size_t)((c.n_q - 1) * c.ldq + c.dim) * sizeof(T), "xq"},
-                               {c.xs, (size_t)((c.n_s - 1) * c.ldxs + c.dim) * sizeof(T), "xs"},
-                               {apply ? c.coeffs : nullptr, apply ? (size_t)((c.n_s + c.n_poly() - 1) * c.ldw + c.n_rhs) * sizeof(T) : 0, "coeffs"}};
-  const PcaApplyRange o[1] = {{c.out, (size_t)((c.n_q - 1) * c.ld_out + out_cols) * sizeof(T), "out"}};
-  pca_apply_no_overlap(in, 3, o, 1, who);
-  if constexpr (dev_has_rbf<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no radial-basis-function kernels: corrla_rbf_* is not supported");
+  const Span in[3] = {c.xq_span(), c.xs_span(), c.coeffs_span(apply)};
+  const Span out[1] = {c.out_span(apply)};
+  no_overlap(who, in, 3, out, 1);
+  on_backend_with<dev_has_rbf<Dev>>(run, "radial-basis-function kernels", "corrla_rbf_*");
 }
 template <class Dev, class T, class Run>
 inline void rbf_apply_entry(Dev& dev, const RbfCall<T>& c, Run&& run) {
@@ -941,6 +941,11 @@ struct PolyGramCall {
   double* means;    // kf each, written when normalize is set; nullable
   double* scales;
   int64_t order() const { return poly_terms(kf, degree) + r; }
+  Span x_span() const { return Span(x, m, kf, ldx, "x"); }
+  Span y_span() const { return r > 0 ? Span(y, m, r, ldy, "y") : Span(); }
+  Span g_span() const { return Span(g, order(), order(), ldg, "G"); }
+  Span means_span() const { return normalize != 0 ? Span(means, 1, kf, kf, "means") : Span(); }
+  Span scales_span() const { return normalize != 0 ? Span(scales, 1, kf, kf, "scales") : Span(); }
 };
 
 template <class Dev, class T, class Run>
@@ -958,17 +963,10 @@ inline void polyfit_gram_entry(Dev&, const PolyGramCall<T>& c, Run&& run) {
   if (c.r > 0 && !c.y) bad("y is NULL");
   if (c.r > 0 && c.ldy < c.r) bad("ldy < r");
   if (c.ldg < c.order()) bad("ldg < p + r");
-  const bool norm = c.normalize != 0;
-  const PcaApplyRange in[2] = {{c.x, (size_t)((c.m - 1) * c.ldx + c.kf) * sizeof(T), "x"},
-                               {c.r > 0 ? c.y : nullptr, c.r > 0 ? (size_t)((c.m - 1) * c.ldy + c.r) * sizeof(T) : 0, "y"}};
-  const PcaApplyRange o[3] = {{c.g, (size_t)((c.order() - 1) * c.ldg + c.order()) * sizeof(double), "G"},
-                              {norm ? c.means : nullptr, (size_t)c.kf * sizeof(double), "means"},
-                              {norm ? c.scales : nullptr, (size_t)c.kf * sizeof(double), "scales"}};
-  pca_apply_no_overlap(in, 2, o, 3, who);
-  if constexpr (dev_has_polyfit<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no polynomial response-surface kernels: corrla_polyfit_gram_* is not supported");
+  const Span in[2] = {c.x_span(), c.y_span()};
+  const Span out[3] = {c.g_span(), c.means_span(), c.scales_span()};
+  no_overlap(who, in, 2, out, 3);
+  on_backend_with<dev_has_polyfit<Dev>>(run, "polynomial response-surface kernels", "corrla_polyfit_gram_*");
 }
 
 template <class T>
@@ -983,6 +981,10 @@ struct PolyEvalCall {
   T* jac;                // nullable: r slabs of m x kf, row stride ld_jac
   int64_t ld_jac;
   int64_t p() const { return poly_terms(kf, degree); }
+  Span x_span() const { return Span(x, m, kf, ldx, "x"); }
+  Span coeffs_span() const { return Span(coeffs, p(), r, ldc, "coeffs"); }
+  Span out_span() const { return Span(out, m, r, ld_out, "out"); }
+  Span jac_span() const { return Span(jac, r * m, kf, ld_jac, "jac"); }  // empty without jac
 };
 
 template <class Dev, class T, class Run>
@@ -1000,15 +1002,10 @@ inline void poly_eval_entry(Dev&, const PolyEvalCall<T>& c, Run&& run) {
   if (c.ldc < c.r) bad("ldc < r");
   if (c.ld_out < c.r) bad("ld_out < r");
   if (c.jac && c.ld_jac < c.kf) bad("ld_jac < k");
-  const PcaApplyRange in[2] = {{c.x, (size_t)((c.m - 1) * c.ldx + c.kf) * sizeof(T), "x"},
-                               {c.coeffs, (size_t)((c.p() - 1) * c.ldc + c.r) * sizeof(double), "coeffs"}};
-  const PcaApplyRange o[2] = {{c.out, (size_t)((c.m - 1) * c.ld_out + c.r) * sizeof(T), "out"},
-                              {c.jac, c.jac ? (size_t)((c.r * c.m - 1) * c.ld_jac + c.kf) * sizeof(T) : 0, "jac"}};
-  pca_apply_no_overlap(in, 2, o, 2, who);
-  if constexpr (dev_has_polyfit<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no polynomial response-surface kernels: corrla_poly_eval_* is not supported");
+  const Span in[2] = {c.x_span(), c.coeffs_span()};
+  const Span out[2] = {c.out_span(), c.jac_span()};
+  no_overlap(who, in, 2, out, 2);
+  on_backend_with<dev_has_polyfit<Dev>>(run, "polynomial response-surface kernels", "corrla_poly_eval_*");
 }
 
 // ---- kernel density estimates (corrla_kde_eval_* / corrla_kde_nll_*, univariate_rv.rs:165-170, 423-444) ----------------------
@@ -1024,6 +1021,9 @@ struct KdeEvalCall {
   int what;    // 0 pdf, 1 cdf, 2 logpdf
   T* out;      // n_q values, element stride inco
   int64_t inco;
+  Span x_span() const { return Span(x, n_q, 1, incx, "x"); }
+  Span s_span() const { return Span(s, n_s, 1, incs, "s"); }
+  Span out_span() const { return Span(out, n_q, 1, inco, "out"); }
 };
 
 template <class Dev, class T, class Run>
@@ -1040,14 +1040,10 @@ inline void kde_eval_entry(Dev&, const KdeEvalCall<T>& c, Run&& run) {
   if (c.inco < 1) bad("inco must be >= 1");
   if (!std::isfinite(c.h) || !(c.h > 0.0)) bad("h must be finite and > 0");
   if (c.what < 0 || c.what > 2) bad("what must be 0 (pdf), 1 (cdf) or 2 (logpdf)");
-  const PcaApplyRange in[2] = {{c.x, (size_t)((c.n_q - 1) * c.incx + 1) * sizeof(T), "x"},
-                               {c.s, (size_t)((c.n_s - 1) * c.incs + 1) * sizeof(T), "s"}};
-  const PcaApplyRange o[1] = {{c.out, (size_t)((c.n_q - 1) * c.inco + 1) * sizeof(T), "out"}};
-  pca_apply_no_overlap(in, 2, o, 1, who);
-  if constexpr (dev_has_kde<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no kernel-density kernels: corrla_kde_eval_* is not supported");
+  const Span in[2] = {c.x_span(), c.s_span()};
+  const Span out[1] = {c.out_span()};
+  no_overlap(who, in, 2, out, 1);
+  on_backend_with<dev_has_kde<Dev>>(run, "kernel-density kernels", "corrla_kde_eval_*");
 }
 
 template <class T>
@@ -1060,6 +1056,10 @@ struct KdeNllCall {
   int64_t n_h;
   double* nll;      // n_h
   double* dnll;     // n_h, nullable
+  Span x_span() const { return Span(x, n_t, 1, incx, "x"); }
+  Span s_span() const { return Span(s, n_s, 1, incs, "s"); }
+  Span nll_span() const { return Span(nll, 1, n_h, n_h, "nll"); }
+  Span dnll_span() const { return Span(dnll, 1, n_h, n_h, "dnll"); }  // empty without dnll
 };
 
 template <class Dev, class T, class Run>
@@ -1077,14 +1077,38 @@ inline void kde_nll_entry(Dev&, const KdeNllCall<T>& c, Run&& run) {
   if (c.n_h < 1 || c.n_h > k::kKdeMaxH) bad("n_h must be in [1, 64]");
   for (int64_t b = 0; b < c.n_h; ++b)
     if (!std::isfinite(c.h[b]) || !(c.h[b] > 0.0)) bad("every h must be finite and > 0");
-  const PcaApplyRange in[2] = {{c.x, (size_t)((c.n_t - 1) * c.incx + 1) * sizeof(T), "x"},
-                               {c.s, (size_t)((c.n_s - 1) * c.incs + 1) * sizeof(T), "s"}};
-  const PcaApplyRange o[2] = {{c.nll, (size_t)c.n_h * sizeof(double), "nll"}, {c.dnll, c.dnll ? (size_t)c.n_h * sizeof(double) : 0, "dnll"}};
-  pca_apply_no_overlap(in, 2, o, 2, who);
-  if constexpr (dev_has_kde<Dev>::value)
-    run();
-  else
-    throw Error(ST_EINVAL, "this backend has no kernel-density kernels: corrla_kde_nll_* is not supported");
+  const Span in[2] = {c.x_span(), c.s_span()};
+  const Span out[2] = {c.nll_span(), c.dnll_span()};
+  no_overlap(who, in, 2, out, 2);
+  on_backend_with<dev_has_kde<Dev>>(run, "kernel-density kernels", "corrla_kde_nll_*");
+}
+
+// ---- active-subspace gradient stage (corrla_grad_mat_*) -------------------------------------------------------
+// the arguments of the prototype, in its order
+struct GradMatCall {
+  const double* x;  // n_pts x k support points, row-major
+  int64_t n_pts, k;
+  const double* y;  // n_pts values
+  const double* xq; // n_q x k queries, row-major
+  int64_t n_q;
+  int est_order;
+  int64_t n_nbrs;
+  double out_scale;
+  double* g;        // n_q x k gradients, rows ldg apart
+  int64_t ldg;
+  int* n_regularised;  // host, nullable
+  Span x_span() const { return Span(x, n_pts, k, k, "x"); }
+  Span y_span() const { return Span(y, 1, n_pts, n_pts, "y"); }
+  Span xq_span() const { return Span(xq, n_q, k, k, "xq"); }
+  Span g_span() const { return Span(g, n_q, k, ldg, "g"); }
+};
+
+template <class Dev, class Run>
+inline void grad_entry(Dev&, const GradMatCall& c, Run&& run) {
+  if (!c.x || !c.y || !c.xq || !c.g) throw Error(ST_EINVAL, "NULL argument");
+  if (c.n_pts < 1 || c.n_q < 1 || c.k < 1) throw Error(ST_EINVAL, "empty point set");
+  if (c.ldg < c.k) throw Error(ST_EINVAL, "ldg < k");
+  run();
 }
 
 }  // namespace corrla

@@ -2,7 +2,6 @@
 // is the product: it contains no CPU compute path; without a gfx950 device every compute entry
 // point returns CORRLA_ENODEV / CORRLA_EHIP.
 #include <mutex>
-#include <vector>
 
 #include "capi_impl.hpp"
 #include "colstat_stage.hpp"
@@ -283,9 +282,8 @@ CORRLA_API corrla_status corrla_matmul_dev_bf16(corrla_ctx* ctx, int trans, CORR
   CORRLA_API corrla_status NAME(corrla_ctx* ctx, CORRLA_DENSE(T, x), uint64_t flags, int ddof, T* means_out, T* scales_out, \
                                 T* c, int64_t ldc, int* route_out) {                                                    \
     return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
-      cov_entry<HipDev, T>(cx.dev, x, m, n, rs, cs, flags, ddof, means_out, scales_out, c, ldc, route_out, [&] {        \
-        cov_stage::run<T>(cx.dev, HOST, x, m, n, rs, cs, flags, ddof, means_out, scales_out, c, ldc, route_out);        \
-      });                                                                                                               \
+      const CovCall<T> call{x, m, n, rs, cs, flags, ddof, means_out, scales_out, c, ldc, route_out};                    \
+      cov_entry<HipDev, T>(cx.dev, call, [&] { cov_stage::run<T>(cx.dev, HOST, call); });                               \
     });                                                                                                                 \
   }
 CORRLA_DEFINE_COV(corrla_cov_f32, float, true)
@@ -305,7 +303,7 @@ CORRLA_DEFINE_COV(corrla_cov_dev_f64, double, false)
       if (!x) throw Error(ST_EINVAL, "pca_transform: x is NULL");                                                       \
       if (m < 1 || n < 1) throw Error(ST_EINVAL, "pca_transform: m and n must be >= 1");                                \
       if (rs < 0 || cs < 0) throw Error(ST_EINVAL, "pca_transform: negative strides are not supported");                \
-      const PcaApplyRange xr{x, (size_t)((m - 1) * rs + (n - 1) * cs + 1) * sizeof(T), "x"};                            \
+      const Span xr(x, m, n, rs, cs, "x");                                                                              \
       pca_transform_entry<HipDev, T>(cx.dev, c, false, &xr, 1,                                                          \
                                      [&] { pca_apply_stage::run_dense<T>(cx.dev, HOST, x, rs, cs, c, &cx.pca_apply); }); \
     });                                                                                                                 \
@@ -316,9 +314,8 @@ CORRLA_DEFINE_COV(corrla_cov_dev_f64, double, false)
       cx.pca_apply = pca_apply_stage::Ran();                                                                            \
       const PcaTransformCall<T> c = CORRLA_PCA_MODEL_CALL(T);                                                           \
       validate_csr_args(values, col_idx, row_ptr, m, n, nnz);                                                           \
-      const PcaApplyRange op[3] = {{values, (size_t)nnz * sizeof(T), "values"},                                         \
-                                   {col_idx, (size_t)nnz * sizeof(int32_t), "col_idx"},                                 \
-                                   {row_ptr, (size_t)(m + 1) * sizeof(int64_t), "row_ptr"}};                            \
+      const Span op[3] = {Span(values, 1, nnz, nnz, "values"), Span(col_idx, 1, nnz, nnz, "col_idx"),                   \
+                          Span(row_ptr, 1, m + 1, m + 1, "row_ptr")};                                                   \
       pca_transform_entry<HipDev, T>(cx.dev, c, true, op, 3, [&] {                                                      \
         pca_apply_stage::run_csr<T>(cx.dev, HOST, values, col_idx, row_ptr, nnz, c, &cx.pca_apply);                     \
       });                                                                                                               \
@@ -329,10 +326,8 @@ CORRLA_DEFINE_COV(corrla_cov_dev_f64, double, false)
                                 const T* scales, const T* components, int64_t ldc, int64_t n, T* out, int64_t row_stride_out) { \
     return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
       cx.pca_apply = pca_apply_stage::Ran();                                                                            \
-      pca_inverse_entry<HipDev, T>(cx.dev, scores, m, k, ld_scores, means, scales, components, ldc, n, out, row_stride_out, [&] { \
-        pca_apply_stage::run_inverse<T>(cx.dev, HOST, scores, m, k, ld_scores, means, scales, components, ldc, n, out,   \
-                                        row_stride_out, &cx.pca_apply);                                                 \
-      });                                                                                                               \
+      const PcaInverseCall<T> c{scores, m, k, ld_scores, means, scales, components, ldc, n, out, row_stride_out};       \
+      pca_inverse_entry<HipDev, T>(cx.dev, c, [&] { pca_apply_stage::run_inverse<T>(cx.dev, HOST, c, &cx.pca_apply); }); \
     });                                                                                                                 \
   }
 #define CORRLA_DEFINE_PCA_APPLY(SUF, T)                                  \
@@ -438,58 +433,17 @@ CORRLA_API corrla_status corrla_ctx_last_kde(corrla_ctx* ctx, int* route_out) {
 }
 
 // ---- active-subspace gradient stage ------------------------------------------------------
-static corrla_status grad_mat_c(corrla_ctx* ctx, bool host_ptrs, const double* x, int64_t n_pts, int64_t kf, const double* y,
-                                const double* xq, int64_t n_q, int est_order, int64_t n_nbrs, double out_scale, double* g,
-                                int64_t ldg, int* n_regularised) {
-  return ctx_call(ctx, [&](corrla_ctx& c) {
-    HipDev& dev = c.dev;
-    if (!x || !y || !xq || !g) throw Error(ST_EINVAL, "NULL argument");
-    if (n_pts < 1 || n_q < 1 || kf < 1) throw Error(ST_EINVAL, "empty point set");
-    if (ldg < kf) throw Error(ST_EINVAL, "ldg < k");
-    // which scan and which fit, every grid and workspace (grad_plan.hpp)
-    const GradPlan plan = grad_plan(n_pts, kf, n_q, est_order, n_nbrs, env_int("CORRLA_KNN", 0), env_int("CORRLA_FIT", 0),
-                                    dev.num_cus, kGradWideBudgetBytes, env_int("CORRLA_KNN2_WGS_PER_CU", 1));
-    if (plan.error) throw Error(ST_EINVAL, plan.error);
-    dev.begin_call();
-    auto dbl = [&](int64_t n) { return (double*)dev.alloc_bytes(sizeof(double) * (size_t)n); };
-    auto staged = [&](const double* h, int64_t n) {  // a host array on the device
-      if (!host_ptrs) return h;
-      double* d = dbl(n);
-      CORRLA_HIP(hipMemcpyAsync(d, h, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, dev.stream));
-      return (const double*)d;
-    };
-    const GradCall call{staged(x, n_pts * kf), staged(y, n_pts), staged(xq, n_q * kf), host_ptrs ? dbl(n_q * kf) : g,
-                        host_ptrs ? kf : ldg, n_pts, kf, n_q, n_nbrs, est_order, out_scale,
-                        (int*)dev.alloc_bytes(sizeof(int) * (size_t)(n_q * n_nbrs)), (int*)dev.alloc_bytes(sizeof(int) * (size_t)n_q),
-                        env_int("CORRLA_KNN2_PROF", 0) != 0};
-    grad_stage::run(dev, call, plan);
-    // how many queries needed the ridge / failed: a short reduction on the host (n_q ints)
-    std::vector<int> hs((size_t)n_q);
-    CORRLA_HIP(hipMemcpyAsync(hs.data(), call.status, sizeof(int) * (size_t)n_q, hipMemcpyDeviceToHost, dev.stream));
-    if (host_ptrs)
-      CORRLA_HIP(hipMemcpy2DAsync(g, sizeof(double) * (size_t)ldg, call.g, sizeof(double) * (size_t)kf, sizeof(double) * (size_t)kf,
-                                  (size_t)n_q, hipMemcpyDeviceToHost, dev.stream));
-    dev.event_mark(2);
-    dev.end_call();
-    c.last = Timings();
-    c.last.knn_ms = dev.event_elapsed_ms(0, 1);
-    c.last.fit_ms = dev.event_elapsed_ms(1, 2);
-    c.last.total_ms = c.last.knn_ms + c.last.fit_ms;
-    int bad = 0;
-    for (int v : hs) bad += v != 0;
-    if (n_regularised) *n_regularised = bad;
-  });
-}
-CORRLA_API corrla_status corrla_grad_mat_f64(corrla_ctx* ctx, const double* x, int64_t n_pts, int64_t k, const double* y,
-                                             const double* xq, int64_t n_q, int est_order, int64_t n_nbrs, double out_scale,
-                                             double* g, int64_t ldg, int* n_regularised) {
-  return grad_mat_c(ctx, true, x, n_pts, k, y, xq, n_q, est_order, n_nbrs, out_scale, g, ldg, n_regularised);
-}
-CORRLA_API corrla_status corrla_grad_mat_dev_f64(corrla_ctx* ctx, const double* x, int64_t n_pts, int64_t k, const double* y,
-                                                 const double* xq, int64_t n_q, int est_order, int64_t n_nbrs,
-                                                 double out_scale, double* g, int64_t ldg, int* n_regularised) {
-  return grad_mat_c(ctx, false, x, n_pts, k, y, xq, n_q, est_order, n_nbrs, out_scale, g, ldg, n_regularised);
-}
+#define CORRLA_DEFINE_GRAD(NAME, HOST)                                                                                  \
+  CORRLA_API corrla_status NAME(corrla_ctx* ctx, const double* x, int64_t n_pts, int64_t k, const double* y, const double* xq, \
+                                int64_t n_q, int est_order, int64_t n_nbrs, double out_scale, double* g, int64_t ldg,   \
+                                int* n_regularised) {                                                                   \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const GradMatCall c{x, n_pts, k, y, xq, n_q, est_order, n_nbrs, out_scale, g, ldg, n_regularised};                \
+      grad_entry(cx.dev, c, [&] { grad_stage::run_entry(cx.dev, HOST, c, &cx.last); });                                 \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_GRAD(corrla_grad_mat_f64, true)
+CORRLA_DEFINE_GRAD(corrla_grad_mat_dev_f64, false)
 
 CORRLA_API corrla_status corrla_comm_unique_id(void* out128) {
   return guarded([&] {

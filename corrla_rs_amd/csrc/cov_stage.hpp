@@ -1,5 +1,6 @@
 // The covariance / correlation stage of the C ABI (corrla_cov_*): staging of x by the route syrk_plan gives, the launcher of
-// that plan (syrk) behind the column moments of colstat_stage.hpp, and for host pointers the copies around it.  The arguments were checked by cov_entry (capi_impl.hpp).
+// that plan (syrk) behind the column moments of colstat_stage.hpp, and for host pointers the copies around it (HostIo,
+// host_io.hpp).  The arguments were checked by cov_entry (capi_impl.hpp).
 // The device path enqueues and returns: begin_call has no end_call there (end_call is the synchronise), the workspace of
 // the arena is reused by later calls in stream order, and a throw after begin_call is drained by the entry's locked_call
 // like every other entry's.  The one synchronisation that can still happen is hipMalloc inside alloc_bytes, the first time a
@@ -9,6 +10,7 @@
 #include "capi_impl.hpp"
 #include "colstat_stage.hpp"
 #include "hip_backend.hpp"
+#include "host_io.hpp"
 
 namespace corrla {
 namespace cov_stage {
@@ -42,52 +44,34 @@ void syrk(HipDev& dev, const SyrkPlan& p, const T* x, int64_t m, int64_t n, bool
 }
 
 template <class T>
-void run(HipDev& dev, bool host_ptrs, const T* x, int64_t m, int64_t n, int64_t rs, int64_t cs, uint64_t flags, int ddof,
-         T* means_out, T* scales_out, T* c, int64_t ldc, int* route_out) {
-  const bool corr = (flags & CORRLA_COV_CORRELATION) != 0, center = (flags & CORRLA_COV_NO_CENTER) == 0;
+void run(HipDev& dev, bool host_ptrs, const CovCall<T>& c) {
+  const int64_t m = c.m, n = c.n;
+  const bool corr = (c.flags & CORRLA_COV_CORRELATION) != 0, center = (c.flags & CORRLA_COV_NO_CENTER) == 0;
   SyrkShape s;
   s.m = m;
   s.n = n;
-  s.row_stride = rs;
-  s.col_stride = cs;
+  s.row_stride = c.rs;
+  s.col_stride = c.cs;
   s.esz = (int)sizeof(T);
-  s.base_aligned = (uintptr_t)x % 16 == 0;
+  s.base_aligned = (uintptr_t)c.x % 16 == 0;
   s.num_cus = dev.num_cus;
   const SyrkPlan p = syrk_plan(s, dev.syrk_knobs());
   if (p.route == SyrkRoute::kReject) throw Error(ST_EINVAL, p.error);
   dev.begin_call();
-  const T* xd = x;
-  if (host_ptrs) {
-    // x to the device as it lies: the same strides and the same offset from a 16-byte boundary, so the route is the one a
-    // device pointer of this layout takes
-    const size_t span = (size_t)((m - 1) * rs + (n - 1) * cs + 1);
-    char* buf = (char*)dev.alloc_bytes(span * sizeof(T) + 16);
-    T* xs = (T*)(buf + (uintptr_t)x % 16);
-    dev.h2d_bytes(xs, x, span * sizeof(T));
-    xd = xs;
-  }
+  HostIo<HipDev> io(dev, host_ptrs);
+  const T* xd = io.in_as_lies<T>(c.x_span());  // so the route is the one a device pointer of this layout takes
   if (p.route == SyrkRoute::kRepacked) {
     T* packed = (T*)dev.alloc_bytes(p.repack_bytes);
-    dev.pack_strided(xd, m, n, rs, cs, packed, p.ld);
+    dev.pack_strided(xd, m, n, c.rs, c.cs, packed, p.ld);
     xd = packed;
   }
-  T* cd = c;
-  int64_t ldcd = ldc;
-  T *md = means_out, *sd = scales_out;
-  if (host_ptrs) {
-    cd = (T*)dev.alloc_bytes((size_t)n * (size_t)n * sizeof(T));
-    ldcd = n;
-    if (means_out && center) md = (T*)dev.alloc_bytes((size_t)n * sizeof(T));
-    if (scales_out && corr) sd = (T*)dev.alloc_bytes((size_t)n * sizeof(T));
-  }
-  syrk<T>(dev, p, xd, m, n, center, corr, ddof, center ? md : nullptr, corr ? sd : nullptr, cd, ldcd);
-  if (route_out) *route_out = (int)p.route;
-  if (!host_ptrs) return;  // enqueued on the context's stream; the workspace is reused by later calls in stream order
-  CORRLA_HIP(hipMemcpy2DAsync(c, (size_t)ldc * sizeof(T), cd, (size_t)n * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
-                              hipMemcpyDeviceToHost, dev.stream));
-  if (means_out && center) CORRLA_HIP(hipMemcpyAsync(means_out, md, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
-  if (scales_out && corr) CORRLA_HIP(hipMemcpyAsync(scales_out, sd, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
-  dev.end_call();
+  int64_t ldcd;
+  T* cd = io.out_packed<T>(c.c_span(), &ldcd);
+  T* md = center ? io.out_packed<T>(c.means_span()) : nullptr;
+  T* sd = corr ? io.out_packed<T>(c.scales_span()) : nullptr;
+  syrk<T>(dev, p, xd, m, n, center, corr, c.ddof, md, sd, cd, ldcd);
+  if (c.route_out) *c.route_out = (int)p.route;
+  io.finish();
 }
 
 }  // namespace cov_stage

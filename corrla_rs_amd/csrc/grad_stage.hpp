@@ -2,8 +2,12 @@
 // has decided every grid, workgroup size, LDS and workspace size; a launcher allocates what the plan sized, fills the
 // kernel's arguments and launches.  Events 0 - 1 enclose the scan (corrla_timings.knn_ms), 1 - 2 the fit (fit_ms).
 #pragma once
+#include <vector>
+
+#include "capi_impl.hpp"
 #include "grad_plan.hpp"
 #include "hip_backend.hpp"
+#include "host_io.hpp"
 
 namespace corrla {
 
@@ -154,6 +158,38 @@ inline void run(HipDev& dev, const GradCall& c, const GradPlan& p) {
     case GradFit::kLds:
     case GradFit::kGlobal: fit_general(dev, c, p); break;
   }
+}
+
+// One corrla_grad_mat_* call, its arguments checked by grad_entry (capi_impl.hpp): the plan, the copies around the stage
+// (HostIo: every host array at arena alignment, g packed), run, and what the call reports -- its device times in *last and
+// the number of queries that needed the ridge or failed, a short reduction on the host (n_q ints).  That count is a host
+// value, so a device-pointer call synchronises too.
+inline void run_entry(HipDev& dev, bool host_ptrs, const GradMatCall& c, Timings* last) {
+  // which scan and which fit, every grid and workspace (grad_plan.hpp)
+  const GradPlan plan = grad_plan(c.n_pts, c.k, c.n_q, c.est_order, c.n_nbrs, env_int("CORRLA_KNN", 0), env_int("CORRLA_FIT", 0),
+                                  dev.num_cus, kGradWideBudgetBytes, env_int("CORRLA_KNN2_WGS_PER_CU", 1));
+  if (plan.error) throw Error(ST_EINVAL, plan.error);
+  dev.begin_call();
+  HostIo<HipDev> io(dev, host_ptrs);
+  const double *x = io.in_aligned<double>(c.x_span()), *y = io.in_aligned<double>(c.y_span()), *xq = io.in_aligned<double>(c.xq_span());
+  int64_t ldg;
+  double* g = io.out_packed<double>(c.g_span(), &ldg);
+  const GradCall call{x, y, xq, g, ldg, c.n_pts, c.k, c.n_q, c.n_nbrs, c.est_order, c.out_scale,
+                      ws<int>(dev, sizeof(int) * (size_t)(c.n_q * c.n_nbrs)), ws<int>(dev, sizeof(int) * (size_t)c.n_q),
+                      env_int("CORRLA_KNN2_PROF", 0) != 0};
+  run(dev, call, plan);
+  std::vector<int> hs((size_t)c.n_q);
+  CORRLA_HIP(hipMemcpyAsync(hs.data(), call.status, sizeof(int) * (size_t)c.n_q, hipMemcpyDeviceToHost, dev.stream));
+  io.enqueue_back();  // g, behind the status; event 2 behind both, then the one synchronise of either kind of call
+  dev.event_mark(2);
+  dev.end_call();
+  *last = Timings();
+  last->knn_ms = dev.event_elapsed_ms(0, 1);
+  last->fit_ms = dev.event_elapsed_ms(1, 2);
+  last->total_ms = last->knn_ms + last->fit_ms;
+  int bad = 0;
+  for (int v : hs) bad += v != 0;
+  if (c.n_regularised) *c.n_regularised = bad;
 }
 
 }  // namespace grad_stage

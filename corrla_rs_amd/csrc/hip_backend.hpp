@@ -364,6 +364,16 @@ class HipDev {
   void h2d_2d(T* dst, int64_t dpitch_e, const T* src, int64_t spitch_e, int64_t width_e, int64_t rows) {
     h2d_2d((void*)dst, dpitch_e, (const void*)src, spitch_e, width_e, rows, sizeof(T));
   }
+  // HostIo (host_io.hpp): `rows` rows of `width` bytes, pitches in bytes; both enqueue only (HostIo::finish ends the call)
+  void h2d_2d_enqueue(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    CORRLA_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyHostToDevice, stream));
+  }
+  void d2h_2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    if (rows == 1)  // HostIo decides what is one row; a matrix whose rows touch measured slower as one large copy
+      CORRLA_HIP(hipMemcpyAsync(dst, src, width * rows, hipMemcpyDeviceToHost, stream));
+    else
+      CORRLA_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToHost, stream));
+  }
 
   // ---- tall products: gemm_plan.hpp decides, tall_stage.hpp launches what it says and defines these members -----------
   template <class T>

@@ -4,14 +4,15 @@
 // The device path enqueues and returns, as rbf_stage does: begin_call has no end_call there, every constant -- the
 // bandwidths among them, which always arrive through a host pointer -- travels in the kernel arguments, never through a
 // synchronising copy, and a throw after begin_call is drained by the entry's locked_call.  What can still synchronise:
-// hipMalloc inside alloc_bytes the first time a call needs more workspace than the arena holds.  The host path copies the
-// strided spans of x and s to the device as they lie (the same strides, the same offset from a 16-byte boundary) and the
-// n_q elements of the result back; the elements between them are never written.
+// hipMalloc inside alloc_bytes the first time a call needs more workspace than the arena holds.  The host path (HostIo,
+// host_io.hpp) copies the strided spans of x and s to the device as they lie (the same strides, the same offset from a
+// 16-byte boundary) and the n_q elements of the result back; the elements between them are never written.
 #pragma once
 #include <cmath>
 
 #include "capi_impl.hpp"
 #include "hip_backend.hpp"
+#include "host_io.hpp"
 
 namespace corrla {
 namespace kde_stage {
@@ -27,21 +28,6 @@ inline KdePlan plan_of(int64_t n_q, int64_t n_s, int64_t n_h, int esz, KdeMode m
   const KdePlan p = kde_plan(s);
   if (!p.ok) throw Error(ST_EINVAL, p.error);
   return p;
-}
-
-// room for `count` elements at the offset `like` has from a 16-byte boundary
-template <class T>
-T* alloc_like(HipDev& dev, const void* like, size_t count) {
-  char* buf = (char*)dev.alloc_bytes(count * sizeof(T) + 16);
-  return (T*)(buf + (uintptr_t)like % 16);
-}
-// a strided host span on the device as it lies
-template <class T>
-const T* span_to_device(HipDev& dev, const T* host, int64_t n, int64_t inc) {
-  const size_t count = (size_t)((n - 1) * inc + 1);
-  T* d = alloc_like<T>(dev, host, count);
-  dev.h2d_bytes(d, host, count * sizeof(T));
-  return d;
 }
 
 struct Workspace {
@@ -80,9 +66,10 @@ void run_eval(HipDev& dev, bool host_ptrs, const KdeEvalCall<T>& c, Ran* ran) {
   const KdeMode mode = c.what == 0 ? KdeMode::kPdf : (c.what == 1 ? KdeMode::kCdf : KdeMode::kLogpdf);
   const KdePlan p = plan_of(c.n_q, c.n_s, 1, (int)sizeof(T), mode);
   dev.begin_call();
-  const T* x = host_ptrs ? span_to_device(dev, c.x, c.n_q, c.incx) : c.x;
-  const T* s = host_ptrs ? span_to_device(dev, c.s, c.n_s, c.incs) : c.s;
-  T* out = host_ptrs ? alloc_like<T>(dev, c.out, (size_t)((c.n_q - 1) * c.inco + 1)) : c.out;
+  HostIo<HipDev> io(dev, host_ptrs);
+  const T* x = io.in_as_lies<T>(c.x_span());
+  const T* s = io.in_as_lies<T>(c.s_span());
+  T* out = io.out_as_lies<T>(c.out_span());
   const Workspace w = workspace(dev, p);
   launch_nearest<T>(dev, p, w, x, c.n_q, c.incx, s, c.n_s, c.incs);
   k::KdeSumArgs<T> a{x, c.incx, s, c.incs, c.n_q, c.n_s, p.nqt, p.split_len, p.nsplit, 1, 1, (const T*)w.ws_min, (T*)w.ws_sum, {}};
@@ -96,23 +83,18 @@ void run_eval(HipDev& dev, bool host_ptrs, const KdeEvalCall<T>& c, Ran* ran) {
   hipLaunchKernelGGL((k::kde_finish_kernel<T>), dim3(p.finish_grid_x), dim3(p.finish_block), 0, dev.stream, f);
   CORRLA_HIP(hipGetLastError());
   ran->route = (int)p.route;
-  if (!host_ptrs) return;  // enqueued on the context's stream; the workspace is reused by later calls in stream order
-  if (c.inco == 1)
-    CORRLA_HIP(hipMemcpyAsync(c.out, out, (size_t)c.n_q * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
-  else
-    CORRLA_HIP(hipMemcpy2DAsync(c.out, (size_t)c.inco * sizeof(T), out, (size_t)c.inco * sizeof(T), sizeof(T), (size_t)c.n_q,
-                                hipMemcpyDeviceToHost, dev.stream));
-  dev.end_call();
+  io.finish();
 }
 
 template <class T>
 void run_nll(HipDev& dev, bool host_ptrs, const KdeNllCall<T>& c, Ran* ran) {
   const KdePlan p = plan_of(c.n_t, c.n_s, c.n_h, (int)sizeof(T), KdeMode::kNll);
   dev.begin_call();
-  const T* x = host_ptrs ? span_to_device(dev, c.x, c.n_t, c.incx) : c.x;
-  const T* s = host_ptrs ? span_to_device(dev, c.s, c.n_s, c.incs) : c.s;
-  double* nll = host_ptrs ? (double*)dev.alloc_bytes((size_t)c.n_h * sizeof(double)) : c.nll;
-  double* dnll = !c.dnll ? nullptr : (host_ptrs ? (double*)dev.alloc_bytes((size_t)c.n_h * sizeof(double)) : c.dnll);
+  HostIo<HipDev> io(dev, host_ptrs);
+  const T* x = io.in_as_lies<T>(c.x_span());
+  const T* s = io.in_as_lies<T>(c.s_span());
+  double* nll = io.out_packed<double>(c.nll_span());
+  double* dnll = io.out_packed<double>(c.dnll_span());
   const Workspace w = workspace(dev, p);
   launch_nearest<T>(dev, p, w, x, c.n_t, c.incx, s, c.n_s, c.incs);
   for (int64_t l = 0; l < p.nlaunch; ++l) {  // the launches share the workspace of the sums, in stream order
@@ -135,10 +117,7 @@ void run_nll(HipDev& dev, bool host_ptrs, const KdeNllCall<T>& c, Ran* ran) {
   hipLaunchKernelGGL(k::kde_nll_reduce_kernel, dim3((unsigned)c.n_h), dim3(256), 0, dev.stream, r);
   CORRLA_HIP(hipGetLastError());
   ran->route = (int)p.route;
-  if (!host_ptrs) return;
-  CORRLA_HIP(hipMemcpyAsync(c.nll, nll, (size_t)c.n_h * sizeof(double), hipMemcpyDeviceToHost, dev.stream));
-  if (dnll) CORRLA_HIP(hipMemcpyAsync(c.dnll, dnll, (size_t)c.n_h * sizeof(double), hipMemcpyDeviceToHost, dev.stream));
-  dev.end_call();
+  io.finish();
 }
 
 }  // namespace kde_stage

@@ -5,11 +5,14 @@
 // The device path enqueues and returns, as cov_stage does: begin_call has no end_call there, every constant goes to the
 // device through a kernel (fill_const), never through a synchronising copy, and a throw after begin_call is drained by the
 // entry's locked_call.  What can still synchronise: hipMalloc inside alloc_bytes the first time a call needs more workspace
-// than the arena holds, and the validation of a CSR operand (csr_plan), as in every CSR entry.  The host path copies the
-// whole strided SPAN of x to the device as it lies, so the device path's routes serve it unchanged.
+// than the arena holds, and the validation of a CSR operand (csr_plan), as in every CSR entry.  The host path is the same
+// code behind HostIo (host_io.hpp): the whole strided SPAN of x and the output of the inverse are staged as they lie, so
+// the device path's routes serve them unchanged; the model goes in at arena alignment, the scores are a packed input of the
+// inverse and a packed output of the transform.
 #pragma once
 #include "capi_impl.hpp"
 #include "hip_backend.hpp"
+#include "host_io.hpp"
 
 namespace corrla {
 namespace pca_apply_stage {
@@ -19,14 +22,6 @@ struct Ran {
   int centring = 0;  // 0 none, 1 fused, 2 copy
   int route = 0;     // PcaApplyRoute of the back-projection kernel, 0: none ran
 };
-
-template <class T>
-const T* to_device(HipDev& dev, const T* host, size_t count) {
-  if (!host) return nullptr;
-  T* d = (T*)dev.alloc_bytes(count * sizeof(T));
-  dev.h2d_bytes(d, host, count * sizeof(T));
-  return d;
-}
 
 // One launch of pca_back_kernel<T, MODE> (and, RESID, of the finishing kernel).  t: m x k column-major (ldt); v: k rows of n
 // contiguous features (ldv); big: out (STORE) or x (RESID) with the plan's row stride.
@@ -55,11 +50,22 @@ struct DenseX {
   int64_t rs = 0, cs = 0;
 };
 
-// Everything on device pointers.  `stage`: the target as the tall operand (never transposed).
+// The transform on the device.  `call`: the arrays as the caller gave them; x, rs, cs: the dense target as the caller gave it
+// (an empty span: a CSR target); `stage`: the target, on the device by then, as the tall operand (never transposed).
 template <class T, class Stage>
-void transform_dev(HipDev& dev, const PcaTransformCall<T>& c, const DenseX<T>& dx, Stage&& stage, Ran* ran) {
-  const int64_t m = c.m, n = c.n, k = c.k;
-  const bool sparse = dx.x == nullptr;
+void transform(HipDev& dev, HostIo<HipDev>& io, const PcaTransformCall<T>& call, const Span& x, int64_t rs, int64_t cs, Stage&& stage,
+               Ran* ran) {
+  const int64_t m = call.m, n = call.n, k = call.k;
+  const bool sparse = x.p == nullptr;
+  PcaTransformCall<T> c = call;  // every array on the device
+  c.means = io.in_aligned<T>(call.means_span());
+  c.scales = io.in_aligned<T>(call.scales_span());
+  c.comps = io.in_aligned<T>(call.comps_span());
+  c.scores = io.out_packed<T>(call.scores_span(), &c.ld_scores);
+  c.resid_out = io.out_packed<T>(call.resid_span());
+  c.means_out = io.out_packed<T>(call.means_out_span());
+  // x as it lies, so the device path's routes serve a host pointer unchanged
+  const DenseX<T> dx{io.in_as_lies<T>(x), rs, cs};
   PcaApplyPlan rp;
   if (c.resid_out) {
     PcaApplyShape s;
@@ -71,7 +77,7 @@ void transform_dev(HipDev& dev, const PcaTransformCall<T>& c, const DenseX<T>& d
     rp = pca_apply_plan(s);
     if (rp.route == PcaApplyRoute::kReject) throw Error(ST_EINVAL, rp.error);
   }
-  TallA<T> ta = stage();
+  TallA<T> ta = stage(dx);
   RsvdDriver<HipDev, T> drv(dev, false);
   // V^T as the n x k skinny operand of the forward product; read row-wise it is V with unit stride along the features, which
   // is how the back-projection kernel stages it
@@ -110,62 +116,31 @@ void transform_dev(HipDev& dev, const PcaTransformCall<T>& c, const DenseX<T>& d
     tc.mem.ld = ldp;
     tc.mem.cols_readable = ldp;
   }
-  Skinny<T> y = caller_skinny(c.scores, m, k, c.ld_scores);  // the scores land in the caller's buffer
+  Skinny<T> y = caller_skinny(c.scores, m, k, c.ld_scores);  // the scores land in the caller's buffer (or its image)
   drv.a_times(tc, vt, y, nullptr);
   ran->centring = centring;
   ran->route = 0;
-  if (!c.resid_out) return;
-  const T* xr = dx.x;
-  if (rp.route == PcaApplyRoute::kRepacked) {
-    T* packed = (T*)dev.alloc_bytes(rp.repack_bytes);
-    dev.pack_strided(dx.x, m, n, dx.rs, dx.cs, packed, rp.ld);
-    xr = packed;
+  if (c.resid_out) {
+    const T* xr = dx.x;
+    if (rp.route == PcaApplyRoute::kRepacked) {
+      T* packed = (T*)dev.alloc_bytes(rp.repack_bytes);
+      dev.pack_strided(dx.x, m, n, dx.rs, dx.cs, packed, rp.ld);
+      xr = packed;
+    }
+    back<T>(dev, rp, PcaApplyMode::kResid, c.scores, c.ld_scores, vt.p, vt.ld, mu, c.scales, m, n, k, const_cast<T*>(xr), c.resid_out);
+    ran->route = (int)rp.route;
   }
-  back<T>(dev, rp, PcaApplyMode::kResid, c.scores, c.ld_scores, vt.p, vt.ld, mu, c.scales, m, n, k, const_cast<T*>(xr), c.resid_out);
-  ran->route = (int)rp.route;
-}
-
-// Host pointers: the model and the target to the device, the device path, the results back.
-template <class T, class StageHost>
-void transform_host(HipDev& dev, const PcaTransformCall<T>& c, const DenseX<T>& hx, StageHost&& stage_host, Ran* ran) {
-  const int64_t m = c.m, n = c.n, k = c.k;
-  PcaTransformCall<T> d = c;
-  d.means = c.own_means() ? nullptr : to_device(dev, c.means, (size_t)n);
-  d.scales = to_device(dev, c.scales, (size_t)n);
-  d.comps = to_device(dev, c.comps, (size_t)((n - 1) * c.ldc + k));
-  d.scores = (T*)dev.alloc_bytes((size_t)m * (size_t)k * sizeof(T));
-  d.ld_scores = m;
-  d.resid_out = c.resid_out ? (T*)dev.alloc_bytes((size_t)m * sizeof(T)) : nullptr;
-  d.means_out = (c.own_means() && c.means_out) ? (T*)dev.alloc_bytes((size_t)n * sizeof(T)) : nullptr;
-  DenseX<T> dx;
-  if (hx.x) {
-    // x to the device as it lies: the same strides and the same offset from a 16-byte boundary
-    const size_t span = (size_t)((m - 1) * hx.rs + (n - 1) * hx.cs + 1);
-    char* buf = (char*)dev.alloc_bytes(span * sizeof(T) + 16);
-    T* xs = (T*)(buf + (uintptr_t)hx.x % 16);
-    dev.h2d_bytes(xs, hx.x, span * sizeof(T));
-    dx.x = xs, dx.rs = hx.rs, dx.cs = hx.cs;
-  }
-  transform_dev<T>(dev, d, dx, [&] { return stage_host(dx); }, ran);
-  CORRLA_HIP(hipMemcpy2DAsync(c.scores, (size_t)c.ld_scores * sizeof(T), d.scores, (size_t)m * sizeof(T), (size_t)m * sizeof(T), (size_t)k,
-                              hipMemcpyDeviceToHost, dev.stream));
-  if (d.resid_out) CORRLA_HIP(hipMemcpyAsync(c.resid_out, d.resid_out, (size_t)m * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
-  if (d.means_out) CORRLA_HIP(hipMemcpyAsync(c.means_out, d.means_out, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
-  dev.end_call();
+  io.finish();
 }
 
 template <class T>
 void run_dense(HipDev& dev, bool host_ptrs, const T* x, int64_t rs, int64_t cs, const PcaTransformCall<T>& c, Ran* ran) {
   validate_matrix(x, c.m, c.n, rs, cs);
   dev.begin_call();
-  const DenseX<T> dx{x, rs, cs};
-  auto stage = [&](const DenseX<T>& on_dev) {
-    return stage_input<HipDev, T>(dev, false, on_dev.x, c.m, c.n, on_dev.rs, on_dev.cs, /*force_tall=*/true);
-  };
-  if (host_ptrs)
-    transform_host<T>(dev, c, dx, stage, ran);
-  else
-    transform_dev<T>(dev, c, dx, [&] { return stage(dx); }, ran);
+  HostIo<HipDev> io(dev, host_ptrs);
+  transform<T>(dev, io, c, Span(x, c.m, c.n, rs, cs, "x"), rs, cs, [&](const DenseX<T>& dx) {
+    return stage_input<HipDev, T>(dev, false, dx.x, c.m, c.n, rs, cs, /*force_tall=*/true);
+  }, ran);
 }
 
 template <class T>
@@ -173,55 +148,40 @@ void run_csr(HipDev& dev, bool host_ptrs, const T* values, const int32_t* ci, co
              const PcaTransformCall<T>& c, Ran* ran) {
   validate_csr_args(values, ci, rp, c.m, c.n, nnz);
   dev.begin_call();
-  auto stage = [&](const DenseX<T>&) {
+  HostIo<HipDev> io(dev, host_ptrs);
+  transform<T>(dev, io, c, Span(), 0, 0, [&](const DenseX<T>&) {
     return stage_csr<HipDev, T>(dev, host_ptrs, values, ci, rp, c.m, c.n, nnz, /*keep_orientation=*/true);
-  };
-  if (host_ptrs)
-    transform_host<T>(dev, c, DenseX<T>{}, stage, ran);
-  else
-    transform_dev<T>(dev, c, DenseX<T>{}, [&] { return stage(DenseX<T>{}); }, ran);
+  }, ran);
 }
 
 template <class T>
-void run_inverse(HipDev& dev, bool host_ptrs, const T* scores, int64_t m, int64_t k, int64_t ld_scores, const T* means,
-                 const T* scales, const T* comps, int64_t ldc, int64_t n, T* out, int64_t row_stride_out, Ran* ran) {
+void run_inverse(HipDev& dev, bool host_ptrs, const PcaInverseCall<T>& c, Ran* ran) {
+  const int64_t m = c.m, n = c.n, k = c.k;
   PcaApplyShape s;
   s.m = m, s.n = n, s.k = k;
-  s.row_stride = row_stride_out;
+  s.row_stride = c.row_stride_out;
   s.col_stride = 1;
   s.esz = (int)sizeof(T);
-  s.base_aligned = (uintptr_t)out % 16 == 0;
+  s.base_aligned = (uintptr_t)c.out % 16 == 0;
   s.mode = PcaApplyMode::kStore;
   const PcaApplyPlan p = pca_apply_plan(s);
   if (p.route == PcaApplyRoute::kReject) throw Error(ST_EINVAL, p.error);
   dev.begin_call();
-  const T *td = scores, *md = means, *sd = scales, *cd = comps;
-  int64_t ldt = ld_scores;
-  T* od = out;
-  if (host_ptrs) {
-    T* ts = (T*)dev.alloc_bytes((size_t)m * (size_t)k * sizeof(T));
-    CORRLA_HIP(hipMemcpy2DAsync(ts, (size_t)m * sizeof(T), scores, (size_t)ld_scores * sizeof(T), (size_t)m * sizeof(T), (size_t)k,
-                                hipMemcpyHostToDevice, dev.stream));
-    td = ts, ldt = m;
-    md = to_device(dev, means, (size_t)n);
-    sd = to_device(dev, scales, (size_t)n);
-    cd = to_device(dev, comps, (size_t)((n - 1) * ldc + k));
-    // out on the device as it lies on the host: the same row stride and the same offset from a 16-byte boundary, so the
-    // route is the one a device pointer of this layout takes
-    char* buf = (char*)dev.alloc_bytes((size_t)((m - 1) * p.ld + n) * sizeof(T) + 16);
-    od = (T*)(buf + (uintptr_t)out % 16);
-  }
+  HostIo<HipDev> io(dev, host_ptrs);
+  int64_t ldt;
+  const T* td = io.in_packed<T>(c.scores_span(), &ldt);
+  const T* md = io.in_aligned<T>(c.means_span());
+  const T* sd = io.in_aligned<T>(c.scales_span());
+  const T* cd = io.in_aligned<T>(c.comps_span());
+  T* od = io.out_as_lies<T>(c.out_span());  // so the route is the one a device pointer of this layout takes
   // V with unit stride along the features (k rows, padded row stride): one small transposing copy
   const int64_t ldv = round_up(n, kLdPad);
   T* v = (T*)dev.alloc_bytes((size_t)k * (size_t)ldv * sizeof(T));
-  dev.pack_strided(cd, k, n, (int64_t)1, ldc, v, ldv);
+  dev.pack_strided(cd, k, n, (int64_t)1, c.ldc, v, ldv);
   back<T>(dev, p, PcaApplyMode::kStore, td, ldt, (const T*)v, ldv, md, sd, m, n, k, od, (T*)nullptr);
   ran->centring = 0;
   ran->route = (int)p.route;
-  if (!host_ptrs) return;  // enqueued on the context's stream; the workspace is reused by later calls in stream order
-  CORRLA_HIP(hipMemcpy2DAsync(out, (size_t)p.ld * sizeof(T), od, (size_t)p.ld * sizeof(T), (size_t)n * sizeof(T), (size_t)m,
-                              hipMemcpyDeviceToHost, dev.stream));
-  dev.end_call();
+  io.finish();
 }
 
 }  // namespace pca_apply_stage

@@ -5,13 +5,14 @@
 // The device path enqueues and returns, as rbf_stage does: begin_call has no end_call there, and a throw after begin_call is
 // drained by the entry's locked_call.  What can still synchronise: hipMalloc inside alloc_bytes the first time a call needs
 // more workspace than the arena holds, and the upload of the pair table the first time a context sees a (k, r, degree).
-// The host path copies the strided spans of x, y and the coefficients to the device as they lie (the same row strides, the
-// same offset from a 16-byte boundary, so the route is the one a device pointer of this layout takes) and the results back;
-// padding columns of the outputs are never written.
+// The host path (HostIo, host_io.hpp) copies the strided spans of x, y and the coefficients to the device as they lie (the
+// same row strides, the same offset from a 16-byte boundary, so the route is the one a device pointer of this layout takes)
+// and the results back; padding columns of the outputs are never written.
 #pragma once
 #include "capi_impl.hpp"
 #include "colstat_stage.hpp"
 #include "hip_backend.hpp"
+#include "host_io.hpp"
 
 namespace corrla {
 namespace polyfit_stage {
@@ -33,15 +34,6 @@ inline void set_lds_limits() {
   lds_limit((const void*)k::poly_eval_kernel<double>, kEval);
 }
 
-// a strided host span on the device as it lies: the same offset from a 16-byte boundary
-template <class T>
-const T* span_to_device(HipDev& dev, const T* host, size_t count) {
-  char* buf = (char*)dev.alloc_bytes(count * sizeof(T) + 16);
-  T* d = (T*)(buf + (uintptr_t)host % 16);
-  dev.h2d_bytes(d, host, count * sizeof(T));
-  return d;
-}
-
 template <class T>
 void run_gram(HipDev& dev, bool host_ptrs, const PolyGramCall<T>& c, Ran* ran) {
   PolyGramShape s;
@@ -53,16 +45,12 @@ void run_gram(HipDev& dev, bool host_ptrs, const PolyGramCall<T>& c, Ran* ran) {
   if (p.route == PolyRoute::kReject) throw Error(ST_EINVAL, p.error);
   dev.begin_call();
   const int32_t* table = dev.poly_table(c.kf, c.r, c.degree);
-  const T *xd = c.x, *yd = c.y;
-  double *gd = c.g, *md = c.means, *sd = c.scales;
-  int64_t ldg = c.ldg;
+  HostIo<HipDev> io(dev, host_ptrs);
+  const T* xd = io.in_as_lies<T>(c.x_span());
+  const T* yd = io.in_as_lies<T>(c.y_span());  // null when r == 0
+  int64_t ldg;
+  double* gd = io.out_packed<double>(c.g_span(), &ldg);
   const bool norm = c.normalize != 0;
-  if (host_ptrs) {
-    xd = span_to_device(dev, c.x, (size_t)((c.m - 1) * c.ldx + c.kf));
-    if (c.r > 0) yd = span_to_device(dev, c.y, (size_t)((c.m - 1) * c.ldy + c.r));
-    gd = (double*)dev.alloc_bytes((size_t)p.order * (size_t)p.order * sizeof(double));
-    ldg = p.order;
-  }
   const int aligned = p.route == PolyRoute::kInPlace ? 1 : 0;
   const double *mu = nullptr, *sg = nullptr;
   if (norm) {
@@ -82,17 +70,12 @@ void run_gram(HipDev& dev, bool host_ptrs, const PolyGramCall<T>& c, Ran* ran) {
   hipLaunchKernelGGL(k::polyfit_finish_kernel, dim3(p.finish_grid_x, p.finish_grid_y), dim3(p.finish_block), 0, dev.stream, f);
   CORRLA_HIP(hipGetLastError());
   if (ran) ran->route = (int)p.route;
+  // the moments of the column pass to the caller's vectors (empty spans without normalize): host pointers take them from
+  // where they are, device pointers by a copy on the stream
   const size_t vb = (size_t)c.kf * sizeof(double);
-  if (!host_ptrs) {  // enqueued on the context's stream; the workspace is reused by later calls in stream order
-    if (norm && md) CORRLA_HIP(hipMemcpyAsync(md, mu, vb, hipMemcpyDeviceToDevice, dev.stream));
-    if (norm && sd) CORRLA_HIP(hipMemcpyAsync(sd, sg, vb, hipMemcpyDeviceToDevice, dev.stream));
-    return;
-  }
-  const size_t rowb = (size_t)p.order * sizeof(double);
-  CORRLA_HIP(hipMemcpy2DAsync(c.g, (size_t)c.ldg * sizeof(double), gd, rowb, rowb, (size_t)p.order, hipMemcpyDeviceToHost, dev.stream));
-  if (norm && md) CORRLA_HIP(hipMemcpyAsync(md, mu, vb, hipMemcpyDeviceToHost, dev.stream));
-  if (norm && sd) CORRLA_HIP(hipMemcpyAsync(sd, sg, vb, hipMemcpyDeviceToHost, dev.stream));
-  dev.end_call();
+  if (double* md = io.out_from<double>(c.means_span(), mu)) CORRLA_HIP(hipMemcpyAsync(md, mu, vb, hipMemcpyDeviceToDevice, dev.stream));
+  if (double* sd = io.out_from<double>(c.scales_span(), sg)) CORRLA_HIP(hipMemcpyAsync(sd, sg, vb, hipMemcpyDeviceToDevice, dev.stream));
+  io.finish();
 }
 
 template <class T>
@@ -100,20 +83,12 @@ void run_eval(HipDev& dev, bool host_ptrs, const PolyEvalCall<T>& c, Ran* ran) {
   const PolyEvalPlan p = poly_eval_plan(c.m, c.kf, c.r, c.degree, c.ldx, (int)sizeof(T), (uintptr_t)c.x % 16 == 0);
   if (!p.ok) throw Error(ST_EINVAL, p.error);
   dev.begin_call();
-  const T* xd = c.x;
-  const double* cd = c.coeffs;
-  T *od = c.out, *jd = c.jac;
-  int64_t ld_out = c.ld_out, ld_jac = c.ld_jac;
-  if (host_ptrs) {
-    xd = span_to_device(dev, c.x, (size_t)((c.m - 1) * c.ldx + c.kf));
-    cd = span_to_device(dev, c.coeffs, (size_t)((p.p - 1) * c.ldc + c.r));
-    od = (T*)dev.alloc_bytes((size_t)c.m * (size_t)c.r * sizeof(T));
-    ld_out = c.r;
-    if (c.jac) {
-      jd = (T*)dev.alloc_bytes((size_t)c.r * (size_t)c.m * (size_t)c.kf * sizeof(T));
-      ld_jac = c.kf;
-    }
-  }
+  HostIo<HipDev> io(dev, host_ptrs);
+  const T* xd = io.in_as_lies<T>(c.x_span());
+  const double* cd = io.in_as_lies<double>(c.coeffs_span());
+  int64_t ld_out, ld_jac = c.ld_jac;
+  T* od = io.out_packed<T>(c.out_span(), &ld_out);
+  T* jd = io.out_packed<T>(c.jac_span(), &ld_jac);
   double* cimg = (double*)dev.alloc_bytes(p.c_bytes);
   hipLaunchKernelGGL(k::poly_c_assemble_kernel, dim3(p.assemble_grid_x), dim3(256), 0, dev.stream, cd, c.ldc, p.p, (int)c.kf, c.degree,
                      (int)c.r, p.k4, p.ncb * p.cb, cimg);
@@ -123,13 +98,7 @@ void run_eval(HipDev& dev, bool host_ptrs, const PolyEvalCall<T>& c, Ran* ran) {
   hipLaunchKernelGGL((k::poly_eval_kernel<T>), dim3(p.grid_x), dim3(p.block), p.lds_bytes, dev.stream, a);
   CORRLA_HIP(hipGetLastError());
   if (ran) ran->route = (int)p.route;
-  if (!host_ptrs) return;  // enqueued on the context's stream; the workspace is reused by later calls in stream order
-  CORRLA_HIP(hipMemcpy2DAsync(c.out, (size_t)c.ld_out * sizeof(T), od, (size_t)c.r * sizeof(T), (size_t)c.r * sizeof(T), (size_t)c.m,
-                              hipMemcpyDeviceToHost, dev.stream));
-  if (c.jac)
-    CORRLA_HIP(hipMemcpy2DAsync(c.jac, (size_t)c.ld_jac * sizeof(T), jd, (size_t)c.kf * sizeof(T), (size_t)c.kf * sizeof(T),
-                                (size_t)(c.r * c.m), hipMemcpyDeviceToHost, dev.stream));
-  dev.end_call();
+  io.finish();
 }
 
 }  // namespace polyfit_stage

@@ -4,12 +4,13 @@
 // The device path enqueues and returns, as pca_apply_stage does: begin_call has no end_call there, every constant travels
 // in the kernel arguments, never through a synchronising copy, and a throw after begin_call is drained by the entry's
 // locked_call.  What can still synchronise: hipMalloc inside alloc_bytes the first time a call needs more workspace than the
-// arena holds.  The host path copies the strided spans of xq, xs and the coefficients to the device as they lie (the same
-// row strides, the same offset from a 16-byte boundary) and the n_q x n_rhs (or n_q x n_s) block of the result back; the
-// padding columns of out are never written.
+// arena holds.  The host path (HostIo, host_io.hpp) copies the strided spans of xq, xs and the coefficients to the device as
+// they lie (the same row strides, the same offset from a 16-byte boundary) and the n_q x n_rhs (or n_q x n_s) block of the
+// result back; the padding columns of out are never written.
 #pragma once
 #include "capi_impl.hpp"
 #include "hip_backend.hpp"
+#include "host_io.hpp"
 
 namespace corrla {
 namespace rbf_stage {
@@ -34,56 +35,29 @@ inline RbfPlan plan_of(int64_t n_q, int64_t n_s, int64_t dim, int64_t n_rhs, int
   return p;
 }
 
-// a strided host span on the device as it lies: the same offset from a 16-byte boundary
+// the call with every array on the device, all of them as they lie
 template <class T>
-const T* span_to_device(HipDev& dev, const T* host, size_t count) {
-  char* buf = (char*)dev.alloc_bytes(count * sizeof(T) + 16);
-  T* d = (T*)(buf + (uintptr_t)host % 16);
-  dev.h2d_bytes(d, host, count * sizeof(T));
-  return d;
-}
-
-// the call with every array on the device: c.out is where the result is built (the caller's out, or its image of the host
-// path, which finish_host copies to host_out)
-template <class T>
-struct OnDevice {
-  RbfCall<T> c;
-  T* host_out = nullptr;
-};
-template <class T>
-OnDevice<T> stage(HipDev& dev, bool host_ptrs, const RbfCall<T>& c, bool apply) {
-  OnDevice<T> d{c, nullptr};
-  if (!host_ptrs) return d;
-  d.c.xq = span_to_device(dev, c.xq, (size_t)((c.n_q - 1) * c.ldq + c.dim));
-  d.c.xs = span_to_device(dev, c.xs, (size_t)((c.n_s - 1) * c.ldxs + c.dim));
-  if (apply) d.c.coeffs = span_to_device(dev, c.coeffs, (size_t)((c.n_s + c.n_poly() - 1) * c.ldw + c.n_rhs));
-  const int64_t cols = apply ? c.n_rhs : c.n_s;
-  char* buf = (char*)dev.alloc_bytes((size_t)((c.n_q - 1) * c.ld_out + cols) * sizeof(T) + 16);
-  d.c.out = (T*)(buf + (uintptr_t)c.out % 16);
-  d.host_out = c.out;
-  return d;
-}
-template <class T>
-void finish_host(HipDev& dev, const OnDevice<T>& d, int64_t cols) {
-  if (!d.host_out) return;  // enqueued on the context's stream; the workspace is reused by later calls in stream order
-  const size_t pitch = (size_t)d.c.ld_out * sizeof(T);
-  CORRLA_HIP(hipMemcpy2DAsync(d.host_out, pitch, d.c.out, pitch, (size_t)cols * sizeof(T), (size_t)d.c.n_q, hipMemcpyDeviceToHost,
-                              dev.stream));
-  dev.end_call();
+RbfCall<T> on_device(HostIo<HipDev>& io, const RbfCall<T>& call, bool apply) {
+  RbfCall<T> c = call;
+  c.xq = io.in_as_lies<T>(call.xq_span());
+  c.xs = io.in_as_lies<T>(call.xs_span());
+  c.coeffs = io.in_as_lies<T>(call.coeffs_span(apply));
+  c.out = io.out_as_lies<T>(call.out_span(apply));
+  return c;
 }
 
 template <class T>
 void run_matrix(HipDev& dev, bool host_ptrs, const RbfCall<T>& call) {
   const RbfPlan p = plan_of(call.n_q, call.n_s, call.dim, 1, 0, (int)sizeof(T), RbfMode::kMatrix);
   dev.begin_call();
-  const OnDevice<T> d = stage<T>(dev, host_ptrs, call, false);
-  const RbfCall<T>& c = d.c;
+  HostIo<HipDev> io(dev, host_ptrs);
+  const RbfCall<T> c = on_device<T>(io, call, false);
   k::RbfMatrixArgs<T> a{c.xq, c.ldq, c.xs, c.ldxs, c.n_q, c.n_s, (int)c.dim, (T)c.eps, p.nrg, c.out, c.ld_out};
   with_nt<4>(c.kernel, [&](auto kn) {  // the kernel id is a template argument: one switch per launch, outside every loop
     hipLaunchKernelGGL((k::rbf_matrix_kernel<T, decltype(kn)::value>), dim3(p.grid_x), dim3(p.block), p.lds_bytes, dev.stream, a);
   });
   CORRLA_HIP(hipGetLastError());
-  finish_host<T>(dev, d, c.n_s);
+  io.finish();
 }
 
 template <class T>
@@ -91,8 +65,8 @@ void run_apply(HipDev& dev, bool host_ptrs, const RbfCall<T>& call) {
   const int64_t n_poly = call.n_poly();
   const RbfPlan p = plan_of(call.n_q, call.n_s, call.dim, call.n_rhs, n_poly, (int)sizeof(T), RbfMode::kApply);
   dev.begin_call();
-  const OnDevice<T> d = stage<T>(dev, host_ptrs, call, true);
-  const RbfCall<T>& c = d.c;
+  HostIo<HipDev> io(dev, host_ptrs);
+  const RbfCall<T> c = on_device<T>(io, call, true);
   T* ws = (T*)dev.alloc_bytes(p.ws_bytes);
   k::RbfApplyArgs<T> a{c.xq, c.ldq, c.xs, c.ldxs, c.coeffs, c.ldw, c.n_q, c.n_s, c.n_rhs, (int)c.dim, (T)c.eps, p.nbm, p.nrg, p.split_len, ws};
   with_nt<4>(c.kernel, [&](auto kn) {  // the kernel id is a template argument: one switch per launch, outside every loop
@@ -103,7 +77,7 @@ void run_apply(HipDev& dev, bool host_ptrs, const RbfCall<T>& call) {
   k::RbfFinishArgs<T> f{ws, p.nsplit, c.n_q, c.n_rhs, c.xq, c.ldq, (int)c.dim, tail, tail ? c.coeffs + c.n_s * c.ldw : nullptr, c.ldw, c.out, c.ld_out};
   hipLaunchKernelGGL((k::rbf_finish_kernel<T>), dim3(p.finish_grid_x), dim3(p.finish_block), 0, dev.stream, f);
   CORRLA_HIP(hipGetLastError());
-  finish_host<T>(dev, d, c.n_rhs);
+  io.finish();
 }
 
 }  // namespace rbf_stage

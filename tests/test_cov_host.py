@@ -142,8 +142,8 @@ extern "C" __attribute__((visibility("default"))) int probe_cov(const double* x,
   EmuDev dev;
   bool ran = false;
   int st = (int)corrla::guarded([&] {
-    corrla::cov_entry<EmuDev, double>(dev, x, m, n, rs, cs, flags, ddof, (double*)nullptr, (double*)nullptr, c, ldc, route,
-                                      [&] { ran = true; });
+    const corrla::CovCall<double> call{x, m, n, rs, cs, flags, ddof, nullptr, nullptr, c, ldc, route};
+    corrla::cov_entry<EmuDev, double>(dev, call, [&] { ran = true; });
   });
   return ran ? -1 : st;
 }
@@ -193,7 +193,7 @@ def test_argument_checks_of_the_entry(emu_probe):
         assert rc == L.EINVAL and word in msg and route == 0, (kw, msg)
     # overlapping buffers: c inside x
     rc, _, msg = _probe(emu_probe, x, c=x[:6, :6])
-    assert rc == L.EINVAL and b"overlap" in msg
+    assert rc == L.EINVAL and b"cov: c overlaps x" in msg
     # m = 1 with ddof = 0 passes the checks (and then meets the backend's refusal)
     rc, _, msg = _probe(emu_probe, x, m=1, ddof=0)
     assert rc == L.EINVAL and b"no symmetric rank-k kernel" in msg

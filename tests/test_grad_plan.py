@@ -2,7 +2,7 @@
 with the host compiler in a temporary directory.
 
 Every call the stage accepted before the wide kernels existed must keep its kernels: EXPECTED_* below is that routing and
-those LDS sizes, written from corrla_rsvd.hip's grad_mat_c as it was (the validation, then the scan and fit choices and
+those LDS sizes, written from the former body of corrla_grad_mat_* in corrla_rsvd.hip (today grad_entry and grad_stage::run_entry) as it was (the validation, then the scan and fit choices and
 the LDS helpers of grad_kernels.hpp / knn2_kernels.hpp), independent of grad_plan.  old_launches further down restates in
 the same way the grids, workgroup sizes and workspaces that function computed beside the plan before the plan carried them."""
 import itertools
@@ -65,7 +65,7 @@ def fit_lds(k, n, order, m_in_lds):
 
 
 def old_routing(n_pts, k, n_q, order, n, knn_mode, fit_mode):
-    """grad_mat_c before the wide kernels: None when it rejected the call, else (scan, fit) descriptions"""
+    """the entry of corrla_grad_mat_* (today grad_entry / grad_stage::run_entry) before the wide kernels: None when it rejected the call, else (scan, fit) descriptions"""
     need = k + 1 if order == 1 else k * (k + 3) // 2
     if k > 64 or not (n_pts > need and n > need) or n > n_pts or n > 512 or fit_lds(k, n, order, False) > KMAX:
         return None
@@ -271,7 +271,7 @@ def test_memory_rejection_starts_at_the_budget(plan):
 
 # ---- every launch: grids, workgroup sizes, the bf16 scan's geometry, workspaces ----------------------------------------
 def old_launches(c, scan, fit, wgs_per_cu=1):
-    """What grad_mat_c computed beside the plan when it launched (scan, fit) for the call c, written from that function as
+    """What the entry of corrla_grad_mat_* (today grad_stage::run_entry) computed beside the plan when it launched (scan, fit) for the call c, written from that function as
     it was: (scan grid, scan workspace, fit grid, fit workspace) and the GEOMETRY fields."""
     n_pts, k, n_q, order, n = c[:5]
     P = k + 1 if order == 1 else k + k * (k + 1) // 2 + 1

@@ -222,7 +222,8 @@ def test_every_bad_argument_raises_before_the_library_is_touched(stub):
 EMU_PROBE = r"""
 #include "emu_backend.cpp"
 using corrla::PcaTransformCall;
-using corrla::PcaApplyRange;
+using corrla::PcaInverseCall;
+using corrla::Span;
 #define API extern "C" __attribute__((visibility("default")))
 API int probe_transform(const double* x, long long m, long long n, long long rs, long long cs, const double* means, const double* scales,
                         const double* comps, long long ldc, long long k, unsigned long long flags, double* scores, long long ld_scores,
@@ -231,7 +232,7 @@ API int probe_transform(const double* x, long long m, long long n, long long rs,
   bool ran = false;
   int st = (int)corrla::guarded([&] {
     const PcaTransformCall<double> c{m, n, means, scales, comps, ldc, k, flags, scores, ld_scores, resid, means_out};
-    const PcaApplyRange xr{x, (size_t)((m - 1) * rs + (n - 1) * cs + 1) * sizeof(double), "x"};
+    const Span xr(x, m, n, rs, cs, "x");
     corrla::pca_transform_entry<EmuDev, double>(dev, c, sparse != 0, &xr, 1, [&] { ran = true; });
   });
   return ran ? -1 : st;
@@ -241,7 +242,8 @@ API int probe_inverse(const double* scores, long long m, long long k, long long 
   EmuDev dev;
   bool ran = false;
   int st = (int)corrla::guarded([&] {
-    corrla::pca_inverse_entry<EmuDev, double>(dev, scores, m, k, ld_scores, means, scales, comps, ldc, n, out, rso, [&] { ran = true; });
+    const PcaInverseCall<double> c{scores, m, k, ld_scores, means, scales, comps, ldc, n, out, rso};
+    corrla::pca_inverse_entry<EmuDev, double>(dev, c, [&] { ran = true; });
   });
   return ran ? -1 : st;
 }
