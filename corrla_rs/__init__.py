@@ -2,8 +2,10 @@
 hrl.rsvd(A, 4, 8, 10)`, examples/benchmark_rsvd.py:13,101; `from corrla_rs import PyDMDc`, examples/benchmark_dmd.py:12).
 The RSVD hot path and its callers are provided -- rpca (PCA), PyDMDc, PyPodI (with the PyRbfInterp its mode weights
 are interpolated by) -- and everything m- or n-sized is forwarded to corrla_rs_amd (HIP, gfx950).  active_ss
-(gradient stage on the GPU) is provided too; the samplers (cs_*_sample) of the pyo3 module are outside this build's
-scope.  mat_cov_centered, pearson_corr and rsquared_sens (stats_corr.rs) are ADDITIVE: the pyo3
+(gradient stage on the GPU) is provided too, and so are the samplers cs_dirichlet_sample and cs_mcmc_dirichlet_sample
+(lib_math_utils_py.rs:89-168): the Dirichlet draws, the box test and the count run on the device behind
+``Context.dirichlet_sample``, the differential-evolution chains on the host.  With them every function and class of the
+pyo3 module is provided.  mat_cov_centered, pearson_corr and rsquared_sens (stats_corr.rs) are ADDITIVE: the pyo3
 module does not expose them; here they run on the symmetric MFMA kernel behind ``Context.cov``.  linear_fit, quad_fit,
 quad_eval, jac_from_lin and jac_from_quad (stats_corr.rs:146-249) are additive in the same way, on the fused
 normal-equation and evaluation kernels behind ``Context.polyfit_gram`` / ``poly_eval``.  KdeRv and build_kde
@@ -19,10 +21,12 @@ from corrla_rs_amd.callers import RbfInterp as _RbfInterp
 from corrla_rs_amd.callers import mat_cov_centered, pearson_corr, rsquared_sens  # noqa: F401
 from corrla_rs_amd.callers import jac_from_lin, jac_from_quad, linear_fit, quad_eval, quad_fit  # noqa: F401
 from corrla_rs_amd.callers import KdeRv, build_kde  # noqa: F401
+from corrla_rs_amd.callers import constr_dirichlet_sample as _constr_dirichlet_sample
+from corrla_rs_amd.callers import cs_mcmc_dirichlet_sample as _cs_mcmc_dirichlet_sample
 
 __all__ = ["rsvd", "rpca", "random_svd", "power_iter", "PcaRsvd", "PyDMDc", "PyPodI", "PyRbfInterp", "active_ss",
            "mat_cov_centered", "pearson_corr", "rsquared_sens", "linear_fit", "quad_fit", "quad_eval", "jac_from_lin",
-           "jac_from_quad", "KdeRv", "build_kde"]
+           "jac_from_quad", "KdeRv", "build_kde", "cs_dirichlet_sample", "cs_mcmc_dirichlet_sample"]
 
 
 def active_ss(a_mat, y, order, n_nbr, n_comps):
@@ -33,6 +37,33 @@ def active_ss(a_mat, y, order, n_nbr, n_comps):
     x = _np.asarray(a_mat, dtype=_np.float64)
     fit = ActiveSsRsvd(PolyGradientEstimator(x, _np.asarray(y, dtype=_np.float64), int(order), int(n_nbr)), int(n_comps)).fit(x)
     return fit.components(), fit.singular_vals(), fit.var_diag_evd_sensi()
+
+
+def _alphas_1d(np_alphas):
+    a = _np.asarray(np_alphas, dtype=_np.float64)
+    if a.ndim != 1:
+        raise TypeError(f"np_alphas must be a 1-D array, got shape {tuple(a.shape)}")
+    return a
+
+
+def cs_dirichlet_sample(np_bounds, n_samples, max_zshots, chunk_size, c_scale, np_alphas):
+    """pyo3 ``cs_dirichlet_sample(np_bounds, n_samples, max_zshots, chunk_size, c_scale, np_alphas)``
+    (src/lib_math_utils_py.rs:89-105): n_samples points with sum x = c_scale inside the (d, 2) box, by rejection from
+    Dirichlet(np_alphas) (d values, or one for the symmetric case) on the GPU.  Rows that were not found in max_zshots shots of
+    chunk_size stay zero, as in the reference, with a RuntimeWarning.  Every call takes a fresh seed, as the reference's
+    thread_rng does; ``corrla_rs_amd.callers.constr_dirichlet_sample`` takes one."""
+    return _constr_dirichlet_sample(_np.asarray(np_bounds, dtype=_np.float64), int(n_samples), int(max_zshots), int(chunk_size),
+                                    float(c_scale), _alphas_1d(np_alphas))
+
+
+def cs_mcmc_dirichlet_sample(np_bounds, n_samples, n_seed_samples, max_zshots, chunk_size, c_scale, np_alphas, gamma, var_epsilon):
+    """pyo3 ``cs_mcmc_dirichlet_sample(np_bounds, n_samples, n_seed_samples, max_zshots, chunk_size, c_scale, np_alphas, gamma,
+    var_epsilon)`` (src/lib_math_utils_py.rs:107-168) -> (samples, accept_ratio): n_seed_samples seeds by rejection on the
+    GPU, then n_samples steps of differential-evolution chains towards the uniform distribution on the boxed simplex;
+    samples is (n_samples * n_seed_samples, d).  The differences from the reference are those of
+    ``corrla_rs_amd.callers.DeMcSampler``."""
+    return _cs_mcmc_dirichlet_sample(_np.asarray(np_bounds, dtype=_np.float64), int(n_samples), int(n_seed_samples), int(max_zshots),
+                                     int(chunk_size), float(c_scale), _alphas_1d(np_alphas), float(gamma), float(var_epsilon))
 
 
 class PyRbfInterp:

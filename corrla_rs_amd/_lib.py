@@ -39,6 +39,10 @@ POLYFIT_ROUTES = {1: "inplace", 2: "inplace_checked"}
 KDE_ROUTES = {1: "single", 2: "split"}
 KDE_WHAT = {"pdf": 0, "cdf": 1, "logpdf": 2}
 KDE_MAX_BANDWIDTHS = 64
+# corrla_dirichlet_draws_* / corrla_dirichlet_sample_*: the low byte of what corrla_ctx_last_dirichlet reports, and the limits
+DIRICHLET_ROUTES = {1: "registers/exponential", 2: "registers/general", 3: "regenerate/exponential", 4: "regenerate/general"}
+DIRICHLET_MAX_D = 128
+DIRICHLET_MAX_DRAWS = 1 << 62
 UNIQUE_ID_BYTES = 128
 
 
@@ -71,7 +75,13 @@ def _sigs():
         "corrla_ctx_last_pca_apply": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "corrla_ctx_last_polyfit": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "corrla_ctx_last_kde": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "corrla_ctx_last_dirichlet": (C.c_int, [vp, C.POINTER(C.c_int)]),
     }
+    # constrained Dirichlet sampling, f64 only: alphas, d, c_scale, seed, first, n, out, ldo / bounds, alphas, d, c_scale, seed,
+    # n_samples, max_zshots, chunk_size, out, ldo, n_found, n_drawn
+    s["corrla_dirichlet_draws_f64"] = s["corrla_dirichlet_draws_dev_f64"] = (C.c_int, [vp, vp, i64, dbl, u64, i64, i64, vp, i64])
+    s["corrla_dirichlet_sample_f64"] = s["corrla_dirichlet_sample_dev_f64"] = (
+        C.c_int, [vp, vp, vp, i64, dbl, u64, i64, i64, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)])
     for suf, sc in (("f32", flt), ("f64", dbl)):
         rsvd = [vp, vp, i64, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
         s["corrla_rsvd_" + suf] = (C.c_int, rsvd)

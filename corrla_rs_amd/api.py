@@ -1007,6 +1007,117 @@ class Context:
         the first call."""
         return getattr(self, "_kde_route", None)
 
+    # ---- constrained Dirichlet sampling (space_samplers.rs:14-126) ------------------------------------
+    @staticmethod
+    def _dirichlet_stream(alphas, d, c_scale, seed):
+        """-> (alphas as d float64, c_scale, seed), checked as the entries check them.  alphas: None (all ones), one value
+        (symmetric) or d values -- the rules of ``constr_dirichlet_sample``, space_samplers.rs:73-95."""
+        if alphas is None:
+            al = np.ones(d if d is not None else 0, dtype=np.float64)
+        else:
+            al = np.atleast_1d(np.asarray(alphas.detach().cpu().numpy() if _is_torch(alphas) else alphas, dtype=np.float64))
+            if al.ndim != 1:
+                raise ValueError(f"alphas must be a scalar or a vector, got shape {tuple(al.shape)}")
+            if d is not None and al.shape[0] == 1:
+                al = np.full(d, al[0])
+        if d is not None and al.shape[0] != d:
+            raise ValueError(f"alphas must hold {d} values or 1 (the symmetric case), got {al.shape[0]}")
+        if not 2 <= al.shape[0] <= L.DIRICHLET_MAX_D:
+            raise ValueError(f"d must be in [2, {L.DIRICHLET_MAX_D}], got {al.shape[0]}")
+        if not (np.all(np.isfinite(al)) and np.all(al > 0.0)):
+            raise ValueError("every alphas[j] must be finite and > 0")
+        c = float(c_scale)
+        if not (np.isfinite(c) and c > 0.0):
+            raise ValueError(f"c_scale must be finite and > 0, got {c_scale!r}")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+        return np.ascontiguousarray(al), c, seed
+
+    def _dirichlet_out(self, n, d, device):
+        if device:
+            import torch
+            return torch.empty((n, d), dtype=torch.float64, device=f"cuda:{self.device}")
+        return np.empty((n, d), dtype=np.float64)
+
+    def _dirichlet_done(self, device):
+        if device:  # the draws entry only enqueues: torch's streams see the rows after this
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        route = C.c_int(0)
+        L.check(self._lib.corrla_ctx_last_dirichlet(self._h, C.byref(route)))
+        self._dirichlet_route = L.DIRICHLET_ROUTES.get(route.value & 0xFF)
+        self._dirichlet_readbacks = route.value >> 8
+
+    def dirichlet_draws(self, n, alphas, *, c_scale=1.0, seed=0, first=0, device=False):
+        """Rows [first, first + n) of the Dirichlet stream of (seed, alphas, c_scale) (corrla_dirichlet_draws_*): row t is
+        x_j = c_scale g_j / sum_i g_i with g_j ~ Gamma(alphas[j], 1), a pure function of (seed, alphas, c_scale, t) -- the
+        stream is defined in include/corrla_rsvd.h -- so any slice of the stream is the same bits whichever call makes it.
+        Returns (n, d) float64, numpy by default, a CUDA tensor with device=True.  alphas: d values, d in [2, 128].
+        ValueError before the library is touched: alphas or c_scale not finite and > 0, d outside [2, 128], n < 1, first < 0,
+        first + n > 2^62."""
+        al, c, seed = self._dirichlet_stream(alphas, None, c_scale, seed)
+        n, first = int(n), int(first)
+        if n < 1:
+            raise ValueError(f"n must be >= 1, got {n}")
+        if first < 0 or first + n > L.DIRICHLET_MAX_DRAWS:
+            raise ValueError(f"first must be >= 0 and first + n <= 2^62, got first = {first}, n = {n}")
+        d = int(al.shape[0])
+        out = self._dirichlet_out(n, d, device)
+        fn = self._lib.corrla_dirichlet_draws_dev_f64 if device else self._lib.corrla_dirichlet_draws_f64
+        L.check(fn(self._h, al.ctypes.data, d, c, seed, first, n, _ptr(out), d))
+        self._dirichlet_done(device)
+        return out
+
+    def dirichlet_sample(self, bounds, n_samples, alphas=None, *, c_scale=1.0, seed=0, max_zshots=500, chunk_size=1_000_000,
+                         device=False):
+        """-> (samples, n_found, n_drawn): the first n_samples draws of the Dirichlet stream of (seed, alphas, c_scale) that lie
+        in the box bounds[j, 0] <= x_j <= bounds[j, 1] (closed, as space_samplers.rs:42), among the draws
+        [0, max_zshots * chunk_size), in increasing draw index (corrla_dirichlet_sample_*; ``constr_dirichlet_sample``).
+        samples is (n_samples, d) float64 -- numpy by default, a CUDA tensor with device=True -- with rows [n_found, n_samples)
+        zero, which is what the reference leaves where it found nothing; n_drawn = chunk_size times the shots that were needed.
+        The samples do not depend on chunk_size (n_drawn does), are bitwise reproducible for a seed, and lie inside the box
+        exactly: the test is made on the stored doubles.  No candidate row is stored on the device: a draw is tested where it
+        is generated and the accepted ones are generated again.  bounds: (d, 2); alphas: None (all ones), one value
+        (symmetric) or d values.  ValueError before the library is touched: the conditions of ``dirichlet_draws``, n_samples,
+        max_zshots or chunk_size < 1, max_zshots * chunk_size >= 2^62, a bound that is not finite, a lower bound above its
+        upper bound, a box that holds no point with sum c_scale.  ``last_dirichlet_route()`` names the route,
+        ``last_dirichlet_readbacks()`` how often the call waited for the device's count."""
+        b = np.ascontiguousarray(np.asarray(bounds.detach().cpu().numpy() if _is_torch(bounds) else bounds, dtype=np.float64))
+        if b.ndim != 2 or b.shape[1] != 2:
+            raise ValueError(f"bounds must be (d, 2), got shape {tuple(b.shape)}")
+        d = int(b.shape[0])
+        al, c, seed = self._dirichlet_stream(alphas, d, c_scale, seed)
+        n_samples, max_zshots, chunk_size = int(n_samples), int(max_zshots), int(chunk_size)
+        for name, v in (("n_samples", n_samples), ("max_zshots", max_zshots), ("chunk_size", chunk_size)):
+            if v < 1:
+                raise ValueError(f"{name} must be >= 1, got {v}")
+        if max_zshots * chunk_size >= L.DIRICHLET_MAX_DRAWS:
+            raise ValueError("max_zshots * chunk_size must be < 2^62")
+        if not np.all(np.isfinite(b)):
+            raise ValueError("every bounds[j] must be finite")
+        if np.any(b[:, 0] > b[:, 1]):
+            raise ValueError("bounds[j][0] must be <= bounds[j][1]")
+        slack = 8.0 * np.finfo(np.float64).eps * d * c
+        if sum(b[:, 0].tolist()) > c + slack or sum(b[:, 1].tolist()) < c - slack:
+            raise ValueError("bounds leave no point with sum c_scale (infeasible box)")
+        out = self._dirichlet_out(n_samples, d, device)
+        n_found, n_drawn = C.c_int64(0), C.c_int64(0)
+        fn = self._lib.corrla_dirichlet_sample_dev_f64 if device else self._lib.corrla_dirichlet_sample_f64
+        L.check(fn(self._h, b.ctypes.data, al.ctypes.data, d, c, seed, n_samples, max_zshots, chunk_size, _ptr(out), d,
+                   C.byref(n_found), C.byref(n_drawn)))
+        self._dirichlet_done(device)
+        return out, int(n_found.value), int(n_drawn.value)
+
+    def last_dirichlet_route(self):
+        """The route of this context's last ``dirichlet_draws`` / ``dirichlet_sample`` call: "registers/..." (d <= 16: the
+        gammas of a row stay in registers) or "regenerate/..." (wider rows: one sweep forms the sum, a second draws each gamma
+        again from its counter), then ".../exponential" (every alpha is 1) or ".../general"; None before the first call."""
+        return getattr(self, "_dirichlet_route", None)
+
+    def last_dirichlet_readbacks(self):
+        """How many times the last ``dirichlet_sample`` call read the device's running count back (0 for ``dirichlet_draws``)."""
+        return getattr(self, "_dirichlet_readbacks", None)
+
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
         """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that

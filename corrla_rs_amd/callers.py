@@ -22,6 +22,10 @@ reference also does after its random_svd calls (k = n_modes, a few tens), writte
   KdeRv(bandwidth, samples) / build_kde(...)  <- KdeRv, build_kde        src/lib_math_utils/univariate_rv.rs:165-170,
                                                  384-497 (the pairwise sums from ``Context.kde_eval`` / ``kde_nll``; the
                                                  bandwidth search on the host over (nll, dnll) evaluations)
+  constr_dirichlet_sample / DeMcSampler / cs_mcmc_dirichlet_sample
+                                              <- src/lib_math_utils/space_samplers.rs:14-418, lib_math_utils_py.rs:89-168 (the
+                                                 draws, the box test and the count on the device, ``Context.dirichlet_sample``;
+                                                 the chains, which advance one step after the other, on the host)
 Every product with an n_x- or N-sized dimension goes through the library's HIP GEMMs (``Context.matmul``); only
 snapshot-count- and n_modes-sized matrices are touched by numpy."""
 import numpy as np
@@ -30,7 +34,8 @@ from .api import _is_torch, default_context, rsvd
 
 __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyGradientEstimator", "ActiveSsRsvd",
            "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply",
-           "linear_fit", "quad_fit", "quad_eval", "jac_from_lin", "jac_from_quad", "polyfit_solve", "KdeRv", "build_kde"]
+           "linear_fit", "quad_fit", "quad_eval", "jac_from_lin", "jac_from_quad", "polyfit_solve", "KdeRv", "build_kde",
+           "constr_dirichlet_sample", "DeMcSampler", "cs_mcmc_dirichlet_sample"]
 
 
 def _on_gpu(x):
@@ -849,3 +854,122 @@ def build_kde(init_bandwidth, samples, n_iter, method=None, *, seed=None, device
     out = KdeRv(sorted(ests)[len(ests) // 2], flat, device=device, ctx=ctx)
     out.bandwidth_estimates = np.asarray(ests)
     return out
+
+
+# ---- constrained Dirichlet sampling (space_samplers.rs, lib_math_utils_py.rs:89-168) -----------------------------------------
+def _fresh_seed():
+    """a 64-bit seed from the operating system's entropy: repeated calls differ, as with the reference's thread_rng"""
+    return int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+
+
+def constr_dirichlet_sample(bounds, n_samples, max_zshots, chunk_size, c_scale, alphas=None, *, seed=None, ctx=None):
+    """``constr_dirichlet_sample`` (space_samplers.rs:64-126): n_samples points with sum x = c_scale and
+    bounds[j, 0] <= x_j <= bounds[j, 1], by rejection from Dirichlet(alphas) -- None: all ones, one value: symmetric, else d
+    values.  The draws are made, tested and counted on the device (``Context.dirichlet_sample``); the (n_samples, d) array
+    that comes back holds the first n_samples accepted draws of at most max_zshots shots of chunk_size, and zeros in the rows
+    that were not found, as the reference leaves them -- but here a RuntimeWarning says how many were found.  The reference
+    splits the request over 10 workers of max_zshots shots each; here it is one stream, reproducible for a seed.  seed=None
+    takes a fresh seed."""
+    import warnings
+    c = ctx or default_context()
+    out, n_found, _n_drawn = c.dirichlet_sample(bounds, n_samples, alphas, c_scale=c_scale, seed=_fresh_seed() if seed is None else seed,
+                                                max_zshots=max_zshots, chunk_size=chunk_size)
+    if n_found < int(n_samples):
+        warnings.warn(f"constr_dirichlet_sample found {n_found} of {int(n_samples)} samples in {int(max_zshots)} shots of "
+                      f"{int(chunk_size)}: rows [{n_found}, {int(n_samples)}) are zero", RuntimeWarning, stacklevel=2)
+    return out
+
+
+class DeMcSampler:
+    """``DeMcSampler`` (space_samplers.rs:252-418) for the target of ``cs_mcmc_dirichlet_sample``: differential-evolution
+    Markov chains on the simplex sum x = c_scale inside a box, with the log-density ln Dirichlet(x / c_scale; alphas) plus the
+    flat prior of the open box (``LnLikeDirichlet`` + ``LnPriorUniform``).  The chains advance in lock step
+    (``sample_mcmc_par``): every proposal of a step is built from the heads at the start of the step.  For chain c
+    (``step_chain``): two distinct other chains a, b; the proposal head_c + gamma (head_a - head_b) + e with e uniform in
+    [0, var_epsilon)^d; the fix-up x <- c_scale x / sum x (lib_math_utils_py.rs:136-141); accepted with probability
+    min(1, exp(lnp(proposal) - lnp(head_c))) (``accept_prob_ratio``, ``metropolis_accept``).  There is no hot path in this:
+    it is numpy, vectorised over the chains, on ``numpy.random.Generator(Philox(seed))``.
+    Deliberate differences from the reference: the dimension is that of the seeds (``McmcChain::new(3, ...)`` is hard-coded
+    there); the likelihood is evaluated on x / c_scale (there it asserts sum x = 1 and panics for any other c_scale); the
+    log-density is formed in logs, sum (alpha_j - 1) ln x_j - ln B(alpha), not as ln of a product that underflows, and a
+    proposal with a component <= 0 has log-density -inf and is rejected.  At least 3 chains, as the reference asserts."""
+
+    def __init__(self, bounds, seeds, alphas, gamma, var_epsilon, *, c_scale=1.0, seed=None):
+        import math
+        self.heads = np.array(seeds, dtype=np.float64)
+        if self.heads.ndim != 2:
+            raise ValueError(f"seeds must be (n_chains, d), got shape {tuple(self.heads.shape)}")
+        self.n_chains, self.ndim = self.heads.shape
+        if self.n_chains < 3:
+            raise ValueError(f"at least 3 chains are needed, got {self.n_chains}")
+        self.bounds = np.asarray(bounds, dtype=np.float64)
+        if self.bounds.shape != (self.ndim, 2):
+            raise ValueError(f"bounds must be ({self.ndim}, 2), got shape {tuple(self.bounds.shape)}")
+        self.alphas = np.broadcast_to(np.asarray(alphas, dtype=np.float64), (self.ndim,)).copy()
+        self.gamma, self.var_epsilon, self.c_scale = float(gamma), float(var_epsilon), float(c_scale)
+        self._ln_beta = sum(math.lgamma(a) for a in self.alphas) - math.lgamma(float(self.alphas.sum()))
+        self._rng = np.random.Generator(np.random.Philox(_fresh_seed() if seed is None else seed))
+        self._history = [self.heads.copy()]
+        self.n_accept = self.n_reject = 0
+
+    def ln_prob(self, x):
+        """(n, d) -> (n,): the Dirichlet log-density of x / c_scale plus 0 inside the open box, -inf outside"""
+        inside = np.all((self.bounds[:, 0] < x) & (x < self.bounds[:, 1]), axis=1) & np.all(x > 0.0, axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            like = np.sum((self.alphas - 1.0) * np.log(x / self.c_scale), axis=1) - self._ln_beta
+        return np.where(inside, like, -np.inf)
+
+    def _step(self):
+        n, cur = self.n_chains, self.heads
+        me = np.arange(n)
+        r1, r2 = self._rng.integers(0, n - 1, size=n), self._rng.integers(0, n - 2, size=n)
+        r2 = r2 + (r2 >= r1)                    # two distinct places among the n - 1 other chains ...
+        a, b = r1 + (r1 >= me), r2 + (r2 >= me)  # ... as chain numbers
+        prop = cur + self.gamma * (cur[a] - cur[b]) + self._rng.uniform(0.0, self.var_epsilon, size=cur.shape)
+        prop = self.c_scale * prop / prop.sum(axis=1, keepdims=True)
+        lp, lc = self.ln_prob(prop), self.ln_prob(cur)
+        with np.errstate(invalid="ignore", over="ignore"):
+            ratio = np.where(np.isneginf(lp), 0.0, np.minimum(np.exp(lp - lc), 1.0))
+        accept = self._rng.random(n) < ratio
+        self.heads = np.where(accept[:, None], prop, cur)
+        self.n_accept += int(accept.sum())
+        self.n_reject += int(n - accept.sum())
+        self._history.append(self.heads.copy())
+
+    def sample_mcmc(self, n_samples):
+        for _ in range(int(n_samples)):
+            self._step()
+
+    def accept_ratio(self):
+        return self.n_accept / float(self.n_accept + self.n_reject)
+
+    def get_samples(self, n_tail):
+        """the last n_tail heads of every chain, interleaved chain-fastest: (n_tail * n_chains, d)"""
+        n_tail = int(n_tail)
+        if not 1 <= n_tail <= len(self._history):
+            raise ValueError(f"n_tail must be in [1, {len(self._history)}], got {n_tail}")
+        return np.concatenate(self._history[-n_tail:], axis=0)
+
+
+def cs_mcmc_dirichlet_sample(bounds, n_samples, n_seed_samples, max_zshots, chunk_size, c_scale, alphas, gamma, var_epsilon, *,
+                             seed=None, ctx=None):
+    """``cs_mcmc_dirichlet_sample`` (lib_math_utils_py.rs:107-168) -> (samples, accept_ratio): n_seed_samples seeds from
+    ``constr_dirichlet_sample`` (on the device, with `alphas`), one chain of a ``DeMcSampler`` per seed with the target
+    Dirichlet(1, ..., 1) -- uniform on the simplex, inside the box -- advanced n_samples steps; samples are the last n_samples
+    heads of every chain, chain-fastest: (n_samples * n_seed_samples, d).  See ``DeMcSampler`` for the differences from the
+    reference.  A seed that was not found would start a chain outside the box: RuntimeError instead of the reference's rows
+    of zeros.  seed=None takes a fresh seed; one seed fixes both stages."""
+    import warnings
+    if int(n_seed_samples) < 3:
+        raise ValueError(f"at least 3 chains (n_seed_samples) are needed, got {int(n_seed_samples)}")
+    seed = _fresh_seed() if seed is None else int(seed)
+    c = ctx or default_context()
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        seeds, n_found, _ = c.dirichlet_sample(bounds, n_seed_samples, alphas, c_scale=c_scale, seed=seed, max_zshots=max_zshots,
+                                               chunk_size=chunk_size)
+    if n_found < int(n_seed_samples):
+        raise RuntimeError(f"only {n_found} of {int(n_seed_samples)} seed samples were found in {int(max_zshots)} shots of {int(chunk_size)}")
+    sampler = DeMcSampler(bounds, seeds, np.ones(seeds.shape[1]), gamma, var_epsilon, c_scale=c_scale, seed=seed)
+    sampler.sample_mcmc(n_samples)
+    return sampler.get_samples(n_samples), sampler.accept_ratio()

@@ -14,6 +14,7 @@
 #include "rbf_plan.hpp"  // rbf_poly_terms, kRbfMaxDim
 #include "polyfit_plan.hpp"  // poly_terms, kPolyMaxK, kPolyMaxRhs
 #include "kde_plan.hpp"  // kKdeMaxH
+#include "dirichlet_plan.hpp"  // dir_plan: the limits of the Dirichlet entries
 
 namespace corrla {
 
@@ -1081,6 +1082,74 @@ inline void kde_nll_entry(Dev&, const KdeNllCall<T>& c, Run&& run) {
   const Span out[2] = {c.nll_span(), c.dnll_span()};
   no_overlap(who, in, 2, out, 2);
   on_backend_with<dev_has_kde<Dev>>(run, "kernel-density kernels", "corrla_kde_nll_*");
+}
+
+// ---- constrained Dirichlet sampling (corrla_dirichlet_draws_* / corrla_dirichlet_sample_*, space_samplers.rs:14-126) ---------
+// Argument checks of every entry -- the limits are the plan's (dir_plan names the argument it rejects) -- then `run` with
+// that plan, on a backend that carries the kernels (dev_has_dirichlet).  alphas and bounds are host arrays in both kinds of call.
+struct DirichletDrawsCall {
+  const double* alphas;  // d, host
+  int64_t d;
+  double c_scale;
+  uint64_t seed;
+  int64_t first, n;
+  double* out;  // n x d, row stride ldo
+  int64_t ldo;
+  Span out_span() const { return Span(out, n, d, ldo, "out"); }
+};
+
+template <class Dev, class Run>
+inline void dirichlet_draws_entry(Dev&, const DirichletDrawsCall& c, Run&& run) {
+  const char* who = "dirichlet_draws";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.alphas) bad("alphas is NULL");
+  if (!c.out) bad("out is NULL");
+  DirShape s;
+  s.d = c.d, s.alphas = c.alphas, s.c_scale = c.c_scale, s.first = c.first, s.n = c.n;
+  const DirPlan p = dir_plan(s);
+  if (!p.ok) throw Error(ST_EINVAL, p.error);
+  if (c.ldo < c.d) bad("ldo must be >= d");
+  const Span in[2] = {Span(c.alphas, 1, c.d, c.d, "alphas"), Span()};
+  const Span out[1] = {c.out_span()};
+  no_overlap(who, in, 1, out, 1);
+  on_backend_with<dev_has_dirichlet<Dev>>([&] { run(p); }, "Dirichlet sampling kernels", "corrla_dirichlet_draws_*");
+}
+
+struct DirichletSampleCall {
+  const double* bounds;  // d x 2 row-major (lb_j, ub_j), host
+  const double* alphas;  // d, host
+  int64_t d;
+  double c_scale;
+  uint64_t seed;
+  int64_t n_samples, max_zshots, chunk_size;
+  double* out;  // n_samples x d, row stride ldo
+  int64_t ldo;
+  int64_t* n_found;  // host
+  int64_t* n_drawn;  // host
+  Span out_span() const { return Span(out, n_samples, d, ldo, "out"); }
+};
+
+template <class Dev, class Run>
+inline void dirichlet_sample_entry(Dev&, bool host_ptrs, const DirichletSampleCall& c, Run&& run) {
+  const char* who = "dirichlet_sample";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.bounds) bad("bounds is NULL");
+  if (!c.alphas) bad("alphas is NULL");
+  if (!c.out) bad("out is NULL");
+  if (!c.n_found) bad("n_found is NULL");
+  if (!c.n_drawn) bad("n_drawn is NULL");
+  if (c.n_samples < 1) bad("n_samples must be >= 1");
+  DirShape s;
+  s.d = c.d, s.alphas = c.alphas, s.c_scale = c.c_scale, s.bounds = c.bounds;
+  s.n_samples = c.n_samples, s.max_zshots = c.max_zshots, s.chunk_size = c.chunk_size;
+  const DirPlan p = dir_plan(s);
+  if (!p.ok) throw Error(ST_EINVAL, p.error);
+  if (c.ldo < c.d) bad("ldo must be >= d");
+  const Span in[4] = {Span(c.bounds, 1, 2 * c.d, 2 * c.d, "bounds"), Span(c.alphas, 1, c.d, c.d, "alphas"),
+                      Span(c.n_found, 1, 1, 1, "n_found"), Span(c.n_drawn, 1, 1, 1, "n_drawn")};
+  const Span out[1] = {c.out_span()};
+  if (host_ptrs) no_overlap(who, in, 4, out, 1);  // a device `out` shares no address space with the host arrays
+  on_backend_with<dev_has_dirichlet<Dev>>([&] { run(p); }, "Dirichlet sampling kernels", "corrla_dirichlet_sample_*");
 }
 
 // ---- active-subspace gradient stage (corrla_grad_mat_*) -------------------------------------------------------

@@ -7,6 +7,7 @@
 #include "colstat_stage.hpp"
 #include "core_svd_stage.hpp"
 #include "cov_stage.hpp"
+#include "dirichlet_stage.hpp"
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "kde_stage.hpp"
@@ -26,6 +27,7 @@ struct corrla_ctx {
   pca_apply_stage::Ran pca_apply;  // how the last corrla_pca_transform_* / corrla_pca_inverse_* call ran
   polyfit_stage::Ran polyfit;      // how the last corrla_polyfit_gram_* / corrla_poly_eval_* call ran
   kde_stage::Ran kde;              // how the last corrla_kde_eval_* / corrla_kde_nll_* call ran
+  dirichlet_stage::Ran dirichlet;  // how the last corrla_dirichlet_draws_* / corrla_dirichlet_sample_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -429,6 +431,42 @@ CORRLA_API corrla_status corrla_ctx_last_kde(corrla_ctx* ctx, int* route_out) {
     corrla_ctx* c = need(ctx);
     std::lock_guard<std::mutex> lk(c->mu);
     if (route_out) *route_out = c->kde.route;
+  });
+}
+
+// ---- constrained Dirichlet sampling (constr_dirichlet_sample, space_samplers.rs:14-126) -------------------------------------
+#define CORRLA_DEFINE_DIRICHLET(DEV, HOST)                                                                              \
+  CORRLA_API corrla_status corrla_dirichlet_draws_##DEV##f64(corrla_ctx* ctx, const double* alphas, int64_t d, double c_scale, \
+                                                             uint64_t seed, int64_t first, int64_t n, double* out, int64_t ldo) { \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const DirichletDrawsCall c{alphas, d, c_scale, seed, first, n, out, ldo};                                         \
+      dirichlet_draws_entry<HipDev>(cx.dev, c, [&](const DirPlan& p) {                                                  \
+        cx.dirichlet = dirichlet_stage::Ran();                                                                          \
+        dirichlet_stage::run_draws(cx.dev, HOST, c, p, &cx.dirichlet);                                                  \
+      });                                                                                                               \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  CORRLA_API corrla_status corrla_dirichlet_sample_##DEV##f64(corrla_ctx* ctx, const double* bounds, const double* alphas, int64_t d, \
+                                                              double c_scale, uint64_t seed, int64_t n_samples, int64_t max_zshots, \
+                                                              int64_t chunk_size, double* out, int64_t ldo, int64_t* n_found, \
+                                                              int64_t* n_drawn) {                                        \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const DirichletSampleCall c{bounds, alphas, d, c_scale, seed, n_samples, max_zshots, chunk_size, out, ldo, n_found, n_drawn}; \
+      dirichlet_sample_entry<HipDev>(cx.dev, HOST, c, [&](const DirPlan& p) {                                           \
+        cx.dirichlet = dirichlet_stage::Ran();                                                                          \
+        dirichlet_stage::run_sample(cx.dev, HOST, c, p, &cx.dirichlet);                                                 \
+      });                                                                                                               \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_DIRICHLET(, true)
+CORRLA_DEFINE_DIRICHLET(dev_, false)
+// route_out: the route (1 registers / exponential-only, 2 registers / general, 3 regenerate / exponential-only, 4 regenerate /
+// general) in the low byte, the read-backs of the state the call made above it.  A rejected call leaves it as it was.
+CORRLA_API corrla_status corrla_ctx_last_dirichlet(corrla_ctx* ctx, int* route_out) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (route_out) *route_out = c->dirichlet.route | (c->dirichlet.readbacks << 8);
   });
 }
 

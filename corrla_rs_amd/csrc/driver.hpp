@@ -133,6 +133,12 @@ template <class D, class = void>
 struct dev_has_kde : std::false_type {};
 template <class D>
 struct dev_has_kde<D, std::void_t<decltype(D::kHasKde)>> : std::true_type {};
+// ... and those that carry the Dirichlet sampling kernels of corrla_dirichlet_draws_* / corrla_dirichlet_sample_*
+// (dirichlet_kernels.hpp) with kHasDirichlet.
+template <class D, class = void>
+struct dev_has_dirichlet : std::false_type {};
+template <class D>
+struct dev_has_dirichlet<D, std::void_t<decltype(D::kHasDirichlet)>> : std::true_type {};
 
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).

@@ -39,6 +39,7 @@
 #include "rbf_kernels.hpp"
 #include "polyfit_kernels.hpp"
 #include "kde_kernels.hpp"
+#include "dirichlet_kernels.hpp"
 
 namespace corrla {
 
@@ -824,6 +825,8 @@ class HipDev {
   static constexpr bool kHasPolyfit = true;  // driver.hpp: dev_has_polyfit
   // ---- kernel density estimates: kde_plan.hpp plans, kde_stage.hpp launches kde_kernels.hpp -----------------------------------
   static constexpr bool kHasKde = true;  // driver.hpp: dev_has_kde
+  // ---- constrained Dirichlet sampling: dirichlet_plan.hpp plans, dirichlet_stage.hpp launches dirichlet_kernels.hpp ---------
+  static constexpr bool kHasDirichlet = true;  // driver.hpp: dev_has_dirichlet
   const PolyKnobs& poly_knobs() const { return poly_knobs_; }
   // The plan's pair table on the device.  It depends on (k, r, degree) alone, so it is uploaded when those change and kept
   // between calls: a repeated fit enqueues without a synchronising copy.

@@ -889,15 +889,24 @@ __device__ __forceinline__ float normal_from_index<float>(uint64_t idx, uint64_t
   const float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
   return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
-template <>
-__device__ __forceinline__ double normal_from_index<double>(uint64_t idx, uint64_t seed) {
-  uint32_t c[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), 0u, 0u};
+// The two f64 uniforms of one Philox block: the top 53 bits of words (0, 1) and of words (2, 3), plus one half, times 2^-53.
+// Never 0; below 1 but for the one pattern of 53 ones, where the sum rounds up to 2^53.  Counter (c0, c1, c2, c3), key = the two halves of seed.  Shared by the Gaussian generator
+// (counter (idx, 0, 0)) and the Dirichlet stream (dirichlet_kernels.hpp).
+__device__ __forceinline__ void philox_uniform_pair(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t seed, double& u1, double& u2) {
+  uint32_t c[4] = {c0, c1, c2, c3};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   const uint64_t a = (((uint64_t)c[0] << 32) | c[1]) >> 11;
   const uint64_t b = (((uint64_t)c[2] << 32) | c[3]) >> 11;
-  const double u1 = ((double)a + 0.5) * (1.0 / 9007199254740992.0);
-  const double u2 = ((double)b + 0.5) * (1.0 / 9007199254740992.0);
-  return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+  u1 = ((double)a + 0.5) * (1.0 / 9007199254740992.0);
+  u2 = ((double)b + 0.5) * (1.0 / 9007199254740992.0);
+}
+// Box-Muller, the cosine branch
+__device__ __forceinline__ double box_muller_f64(double u1, double u2) { return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2); }
+template <>
+__device__ __forceinline__ double normal_from_index<double>(uint64_t idx, uint64_t seed) {
+  double u1, u2;
+  philox_uniform_pair((uint32_t)idx, (uint32_t)(idx >> 32), 0u, 0u, seed, u1, u2);
+  return box_muller_f64(u1, u2);
 }
 // element (i, j) -> p[i * rs + j * cs] = N(0,1) keyed by (seed, (row0 + i) * global_cols + j);
 // consecutive threads walk the unit-stride direction

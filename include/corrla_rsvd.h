@@ -655,6 +655,59 @@ CORRLA_API corrla_status corrla_kde_nll_dev_f64(corrla_ctx* ctx, const double* x
                                                 int64_t incs, const double* h, int64_t n_h, double* nll, double* dnll);
 CORRLA_API corrla_status corrla_ctx_last_kde(corrla_ctx* ctx, int* route_out);
 
+/* ---- constrained Dirichlet sampling: draws on the simplex, rejection against a box ---------------------
+ * Replaces  dirichlet_shot_sample / constr_dirichlet_sample       src/lib_math_utils/space_samplers.rs:14-126
+ * THE STREAM.  Draw t (0 <= t < 2^62) of (seed, alphas[0..d), c_scale) is the row x[0..d), all in IEEE double:
+ *   U(t, j, a, p) = (u1, u2): the two uniforms of ONE Philox4x32-10 block with key (seed mod 2^32, seed >> 32) and counter
+ *     (t mod 2^32, t >> 32, j + 65536 p, a) -- component j, attempt a, purpose p (0 the normal of an attempt, 1 the
+ *     uniform of its acceptance test, 2 the component's own uniform, with a = 0); from the output words w0..w3,
+ *     u1 = (((w0 << 32 | w1) >> 11) + 0.5) 2^-53 and u2 likewise from w2, w3, as corrla_fill_normal_dev_f64 maps them.
+ *   g_j ~ Gamma(alphas[j], 1), the method chosen by alphas[j] alone:
+ *     = 1:  g = -log(u1) with (u1, .) = U(t, j, 0, 2).
+ *     > 1:  Marsaglia-Tsang at shape s = alphas[j]: D = s - 1/3, C = 1 / sqrt(9 D).  Attempt a = 0, 1, ...:
+ *           (u1, u2) = U(t, j, a, 0), z = sqrt(-2 log(u1)) * cospi(2 u2), w = 1 + C z, rejected if w <= 0;
+ *           v = (w w) w, (q, .) = U(t, j, a, 1), z2 = z z; accepted if q < 1 - 0.0331 (z2 z2), else if
+ *           log(q) < 0.5 z2 + D ((1 - v) + log(v)).  g = D v of the first accepted attempt (g = D after 64 rejected
+ *           attempts, which has probability below 1e-83).
+ *     < 1:  the same at shape s = alphas[j] + 1, then g = (D v) * pow(u1, 1 / alphas[j]) with (u1, .) = U(t, j, 0, 2).
+ *   S = ((g_0 + g_1) + g_2) + ... in index order, x_j = (c_scale g_j) / S.  Every operation is rounded once, in the order
+ *   written; no FMA is formed.  A draw depends on nothing but (seed, alphas, c_scale, t).
+ * corrla_dirichlet_draws_*: rows i < n of out are the draws first + i.
+ * corrla_dirichlet_sample_*: the draws of shot s are [s chunk_size, (s + 1) chunk_size); a draw is accepted when
+ *   bounds[2 j] <= x_j <= bounds[2 j + 1] for every j, compared on the very doubles that are stored, so a returned row
+ *   lies inside its box exactly.  out receives the first n_samples accepted draws among the draws
+ *   [0, max_zshots chunk_size) in increasing draw index, whatever chunk_size is; *n_found = how many there were
+ *   (<= n_samples); rows [n_found, n_samples) are written as zeros, which is what the reference leaves there;
+ *   *n_drawn = chunk_size times the shots that were needed (max_zshots when n_found < n_samples).
+ *   Nothing data-sized is stored: a workgroup generates 1024 draws, tests them and writes one bit per draw and a count;
+ *   a one-block scan ranks the counts; the accepted draws below rank n_samples are generated again into their rows.  No
+ *   atomics: the result is bitwise reproducible for a seed.  The call reads a 24-byte state back once per batch of
+ *   launches; batches at least double from 1024 workgroups, so at most 1 + ceil(log2(workgroups / 1024)) read-backs.
+ * Layouts: alphas (d doubles) and bounds (d x 2 row-major) are ALWAYS host pointers, as are n_found and n_drawn.  out is
+ * n x d (n_samples x d) with row stride ldo >= d, a host pointer for the plain entries and a device pointer for *_dev;
+ * the elements between d and ldo are never written.  Both kinds of corrla_dirichlet_sample_* synchronise;
+ * corrla_dirichlet_draws_dev_f64 enqueues after one synchronising copy of the component table.
+ * Limits: 2 <= d <= 128; alphas[j] and c_scale finite and > 0; first >= 0, n >= 1, first + n <= 2^62; n_samples,
+ * max_zshots, chunk_size >= 1; max_zshots chunk_size < 2^62.
+ * CORRLA_EINVAL (the message names the argument): any of these limits; NULL alphas, bounds, out, n_found or n_drawn;
+ * ldo < d; bounds[2 j] > bounds[2 j + 1]; a bound that is not finite; an infeasible box (sum of the lower bounds above
+ * c_scale or of the upper bounds below it, with 8 d ulp of slack); out overlapping a host input.
+ * corrla_ctx_last_dirichlet: the low byte of *route_out is the route of the last accepted call -- 1 registers /
+ * exponential-only (d <= 16, every alpha 1), 2 registers / general, 3 regenerate / exponential-only (d > 16: one sweep
+ * forms S, a second draws each g_j again from its counter), 4 regenerate / general -- and the bits above it the
+ * read-backs it made. */
+CORRLA_API corrla_status corrla_dirichlet_draws_f64(corrla_ctx* ctx, const double* alphas, int64_t d, double c_scale, uint64_t seed,
+                                                    int64_t first, int64_t n, double* out, int64_t ldo);
+CORRLA_API corrla_status corrla_dirichlet_draws_dev_f64(corrla_ctx* ctx, const double* alphas, int64_t d, double c_scale, uint64_t seed,
+                                                        int64_t first, int64_t n, double* out, int64_t ldo);
+CORRLA_API corrla_status corrla_dirichlet_sample_f64(corrla_ctx* ctx, const double* bounds, const double* alphas, int64_t d, double c_scale,
+                                                     uint64_t seed, int64_t n_samples, int64_t max_zshots, int64_t chunk_size, double* out,
+                                                     int64_t ldo, int64_t* n_found, int64_t* n_drawn);
+CORRLA_API corrla_status corrla_dirichlet_sample_dev_f64(corrla_ctx* ctx, const double* bounds, const double* alphas, int64_t d, double c_scale,
+                                                         uint64_t seed, int64_t n_samples, int64_t max_zshots, int64_t chunk_size, double* out,
+                                                         int64_t ldo, int64_t* n_found, int64_t* n_drawn);
+CORRLA_API corrla_status corrla_ctx_last_dirichlet(corrla_ctx* ctx, int* route_out);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller
