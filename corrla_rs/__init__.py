@@ -8,7 +8,9 @@ are interpolated by) -- and everything m- or n-sized is forwarded to corrla_rs_a
 pyo3 module is provided.  mat_cov_centered, pearson_corr and rsquared_sens (stats_corr.rs) are ADDITIVE: the pyo3
 module does not expose them; here they run on the symmetric MFMA kernel behind ``Context.cov``.  linear_fit, quad_fit,
 quad_eval, jac_from_lin and jac_from_quad (stats_corr.rs:146-249) are additive in the same way, on the fused
-normal-equation and evaluation kernels behind ``Context.polyfit_gram`` / ``poly_eval``.  KdeRv and build_kde
+normal-equation and evaluation kernels behind ``Context.polyfit_gram`` / ``poly_eval``.  sample_mv_normal and
+sandwich_prop (stats_corr.rs:46-68) are additive too, on the fused kernels behind ``Context.mvn_sample`` /
+``sandwich_diag`` (samples have covariance cov, not the reference's cov^2).  KdeRv and build_kde
 (univariate_rv.rs:384-497: the Gaussian kernel density estimate, its likelihood and the cross-validated bandwidth) are
 additive too, on the fused pairwise-sum kernels behind ``Context.kde_eval`` / ``kde_nll``; the other univariate random
 variables of that module (NormalRv, BetaRv, ExponentialRv, mlefit) stay outside this build's scope."""
@@ -21,12 +23,14 @@ from corrla_rs_amd.callers import RbfInterp as _RbfInterp
 from corrla_rs_amd.callers import mat_cov_centered, pearson_corr, rsquared_sens  # noqa: F401
 from corrla_rs_amd.callers import jac_from_lin, jac_from_quad, linear_fit, quad_eval, quad_fit  # noqa: F401
 from corrla_rs_amd.callers import KdeRv, build_kde  # noqa: F401
+from corrla_rs_amd.callers import mvn_factor, sample_mv_normal, sandwich_prop  # noqa: F401
 from corrla_rs_amd.callers import constr_dirichlet_sample as _constr_dirichlet_sample
 from corrla_rs_amd.callers import cs_mcmc_dirichlet_sample as _cs_mcmc_dirichlet_sample
 
 __all__ = ["rsvd", "rpca", "random_svd", "power_iter", "PcaRsvd", "PyDMDc", "PyPodI", "PyRbfInterp", "active_ss",
            "mat_cov_centered", "pearson_corr", "rsquared_sens", "linear_fit", "quad_fit", "quad_eval", "jac_from_lin",
-           "jac_from_quad", "KdeRv", "build_kde", "cs_dirichlet_sample", "cs_mcmc_dirichlet_sample"]
+           "jac_from_quad", "KdeRv", "build_kde", "cs_dirichlet_sample", "cs_mcmc_dirichlet_sample", "mvn_factor",
+           "sample_mv_normal", "sandwich_prop"]
 
 
 def active_ss(a_mat, y, order, n_nbr, n_comps):

@@ -43,6 +43,10 @@ KDE_MAX_BANDWIDTHS = 64
 DIRICHLET_ROUTES = {1: "registers/exponential", 2: "registers/general", 3: "regenerate/exponential", 4: "regenerate/general"}
 DIRICHLET_MAX_D = 128
 DIRICHLET_MAX_DRAWS = 1 << 62
+# corrla_mvn_sample_* / corrla_sandwich_diag_*: what corrla_ctx_last_mvn reports, and the limits
+MVN_ROUTES = {1: "fused", 2: "staged", 3: "empty"}
+MVN_MAX_D = 65536
+SANDWICH_MAX_D = 512
 UNIQUE_ID_BYTES = 128
 
 
@@ -76,6 +80,7 @@ def _sigs():
         "corrla_ctx_last_polyfit": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "corrla_ctx_last_kde": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "corrla_ctx_last_dirichlet": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "corrla_ctx_last_mvn": (C.c_int, [vp, C.POINTER(C.c_int)]),
     }
     # constrained Dirichlet sampling, f64 only: alphas, d, c_scale, seed, first, n, out, ldo / bounds, alphas, d, c_scale, seed,
     # n_samples, max_zshots, chunk_size, out, ldo, n_found, n_drawn
@@ -126,6 +131,9 @@ def _sigs():
         kde = [vp, vp, i64, i64, vp, i64, i64]
         s["corrla_kde_eval_" + suf] = s["corrla_kde_eval_dev_" + suf] = (C.c_int, kde + [dbl, C.c_int, vp, i64])
         s["corrla_kde_nll_" + suf] = s["corrla_kde_nll_dev_" + suf] = (C.c_int, kde + [vp, i64, vp, vp])
+        # multivariate normal rows: n, d, r, factor, ldf, mean, seed, first, lower, out, ldo / sandwich: jac, m, d, ldj, cov, ldc, v
+        s["corrla_mvn_sample_" + suf] = s["corrla_mvn_sample_dev_" + suf] = (C.c_int, [vp, i64, i64, i64, vp, i64, vp, u64, i64, C.c_int, vp, i64])
+        s["corrla_sandwich_diag_" + suf] = s["corrla_sandwich_diag_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp])
         s["corrla_fill_normal_dev_" + suf] =(C.c_int, [vp, vp, i64, i64, i64, i64, u64, i64, i64])
         s["corrla_time_sketch_dev_" + suf] = (C.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, C.c_int,
                                                          C.POINTER(dbl)])

@@ -1118,6 +1118,140 @@ class Context:
         """How many times the last ``dirichlet_sample`` call read the device's running count back (0 for ``dirichlet_draws``)."""
         return getattr(self, "_dirichlet_readbacks", None)
 
+    # ---- multivariate normal rows and sandwich variances (stats_corr.rs:46-68) -----------------------------
+    def _mvn_small(self, v, name, on_device, dtype_of=None):
+        """A dense float32 / float64 argument (factor, mean, cov, jac) as a numpy array (host call) or a tensor on this
+        context's device (device call); bfloat16, sparse and other dtypes raise ValueError.  dtype_of: the array whose type
+        it has to share."""
+        _reject_bf16(v, name)
+        if _is_sparse(v):
+            raise ValueError(f"{name} must be dense")
+        if _is_torch(v) and v.is_cuda:
+            self._on_my_device(v)
+            a = v.detach()
+            if str(a.dtype) not in ("torch.float32", "torch.float64"):
+                raise ValueError(f"{name} must be float32 or float64, got {a.dtype}")
+            if not on_device:
+                a = a.cpu().numpy()
+        else:
+            a = np.asarray(v.detach().numpy() if _is_torch(v) else v)
+            if a.dtype not in (np.float32, np.float64):
+                raise ValueError(f"{name} must be float32 or float64, got {a.dtype}")
+            if on_device:
+                import torch
+                a = torch.tensor(a, device=f"cuda:{self.device}")
+        if dtype_of is not None and _suffix(a.dtype) != _suffix(dtype_of.dtype):
+            raise ValueError(f"{name} must have the dtype of the other arguments ({dtype_of.dtype}), got {a.dtype}")
+        return a
+
+    def mvn_sample(self, n, factor, mean=None, *, seed=0, first=0, lower=False, device=False, out=None):
+        """Rows of N(mean, factor factor^T): X (n, d) with x_i = mean + factor z_i on the device (corrla_mvn_sample_*).
+
+        `factor` is (d, r), 1 <= r <= d, float32 or float64 -- the dtype of X; `mean` (d,) of the same dtype, None: zeros.
+        z_i[j] is the N(0,1) value of counter (first + i) r + j of the library's Philox4x32-10 / Box-Muller stream under
+        `seed`: the values ``fill_normal(t, seed, row0=first, global_cols=r)`` writes into an (n, r) tensor (the stream is
+        defined in include/corrla_rsvd.h).  So X is a pure function of (seed, first, factor, mean): bitwise reproducible,
+        and rows [a, b) of a call are bitwise the call with first + a and n = b - a.
+        lower=True: factor is square lower-triangular (a Cholesky factor); its strict upper triangle is taken as zero and
+        the products above the diagonal are skipped -- bitwise the result of lower=False on the same triangular matrix.
+        numpy by default; a CUDA `factor`, device=True or a CUDA `out` give a CUDA tensor.  out: an (n, d) array of that
+        kind with unit stride along d, filled in place (any row stride >= d).  n = 0 returns an empty array without a
+        launch.  ``last_mvn_route()``: "fused" (z lives in LDS only; r <= 288 in float32, 144 in float64) or "staged".
+        ValueError before the library is touched: r < 1, r > d, n < 0, first < 0, (first + n) r >= 2^63, lower with a
+        non-square factor, bfloat16 or sparse arguments, mismatched dtypes, an `out` of another shape or layout."""
+        lower = _check_bool("lower", lower, ValueError)
+        device = _check_bool("device", device, ValueError)
+        on_dev = device or (_is_torch(factor) and factor.is_cuda) or (out is not None and _is_torch(out) and out.is_cuda)
+        f = self._mvn_small(factor, "factor", on_dev)
+        if f.ndim != 2:
+            raise ValueError(f"factor must be (d, r), got shape {tuple(f.shape)}")
+        d, r = (int(v) for v in f.shape)
+        n, first, seed = int(n), int(first), int(seed)
+        if r < 1 or d < 1:
+            raise ValueError(f"factor must have r >= 1 columns, got shape {(d, r)}")
+        if r > d:
+            raise ValueError(f"factor has more columns than rows (r = {r} > d = {d})")
+        if lower and r != d:
+            raise ValueError(f"lower=True takes a square factor, got shape {(d, r)}")
+        if n < 0:
+            raise ValueError(f"n must be >= 0, got {n}")
+        if first < 0 or (first + n) * r >= 1 << 63:
+            raise ValueError(f"first must be >= 0 and (first + n) * r < 2^63, got first = {first}, n = {n}, r = {r}")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+        f = self._rbf_rowmajor(f, on_dev)
+        mu = None
+        if mean is not None:
+            mu = self._mvn_small(mean, "mean", on_dev, f).reshape(-1)
+            if mu.shape[0] != d:
+                raise ValueError(f"mean must have d = {d} entries, got {mu.shape[0]}")
+            mu = mu.contiguous() if on_dev else np.ascontiguousarray(mu)
+        if out is None:
+            if on_dev:
+                import torch
+                out = torch.empty((n, d), dtype=f.dtype, device=f.device)
+            else:
+                out = np.empty((n, d), dtype=f.dtype)
+        else:
+            _reject_bf16(out, "out")
+            if (_is_torch(out) and out.is_cuda) != on_dev or not (_is_torch(out) or isinstance(out, np.ndarray)):
+                raise ValueError("out must be a numpy array for a host call and a CUDA tensor for a device call")
+            if tuple(out.shape) != (n, d) or _suffix(out.dtype) != _suffix(f.dtype) or str(out.dtype) != str(f.dtype):
+                raise ValueError(f"out must be ({n}, {d}) of {f.dtype}, got {tuple(out.shape)} of {out.dtype}")
+            rs, cs = _strides(out)
+            if (cs != 1 and d > 1) or (rs < d and n > 1):
+                raise ValueError("out must have unit stride along d and a row stride >= d")
+            if on_dev:
+                self._on_my_device(out)
+        if n == 0:
+            self._mvn_route = "empty"
+            return out
+        if on_dev:
+            _sync_stream(f)
+        ldo = int(_strides(out)[0]) if n > 1 else d
+        L.check(self._entry("corrla_mvn_sample_", on_dev, f.dtype)(self._h, n, d, r, _ptr(f), self._row_stride(f),
+                                                                  None if mu is None else _ptr(mu), seed, first, int(lower),
+                                                                  _ptr(out), ldo))
+        self._call_done(on_dev, "corrla_ctx_last_mvn", _mvn_route=L.MVN_ROUTES)
+        return out
+
+    def last_mvn_route(self):
+        """The route of this context's last ``mvn_sample`` call: "fused" (the normals of a row tile are generated once into
+        LDS and multiplied there), "staged" (r > 288 in float32 / 144 in float64: ``fill_normal`` into a bounded workspace, then the
+        back-projection kernel, a row chunk at a time) or "empty" (n = 0: nothing launched); None before the first call."""
+        return getattr(self, "_mvn_route", None)
+
+    def sandwich_diag(self, jac, cov):
+        """The first-order output variances v_i = jac[i] @ cov @ jac[i] -> (m,), on the device (corrla_sandwich_diag_*; the
+        diagonal of ``sandwich_prop``, stats_corr.rs:64-68) without the (m, d) temporary jac @ cov: a row tile of jac is
+        staged once, multiplied with cov on the MFMAs and contracted with itself in registers.  jac: (m, d), float32 or
+        float64, numpy or a CUDA tensor, any row stride (one gradient block of ``poly_eval(..., jac=True)`` as it is); cov:
+        (d, d) of the same dtype, d <= 512, used as given -- it is not symmetrised.  Bitwise reproducible.  numpy in -> numpy
+        out, a CUDA jac -> a tensor on its device.  ValueError: d > 512, shapes that do not fit, bfloat16 or sparse arguments,
+        mismatched dtypes."""
+        on_dev = _is_torch(jac) and jac.is_cuda
+        j = self._mvn_small(jac, "jac", on_dev)
+        if j.ndim != 2 or j.shape[0] == 0 or j.shape[1] == 0:
+            raise ValueError(f"jac must be a non-empty (m, d) matrix, got shape {tuple(j.shape)}")
+        m, d = (int(v) for v in j.shape)
+        if d > L.SANDWICH_MAX_D:
+            raise ValueError(f"sandwich_diag: jac has d = {d} features, the kernel takes at most {L.SANDWICH_MAX_D}")
+        c = self._mvn_small(cov, "cov", on_dev, j)
+        if c.ndim != 2 or tuple(c.shape) != (d, d):
+            raise ValueError(f"cov must be ({d}, {d}), got shape {tuple(c.shape)}")
+        j, c = self._rbf_rowmajor(j, on_dev), self._rbf_rowmajor(c, on_dev)
+        if on_dev:
+            import torch
+            v = torch.empty((m,), dtype=j.dtype, device=j.device)
+            _sync_stream(j)
+        else:
+            v = np.empty((m,), dtype=j.dtype)
+        L.check(self._entry("corrla_sandwich_diag_", on_dev, j.dtype)(self._h, _ptr(j), m, d, self._row_stride(j), _ptr(c),
+                                                                     self._row_stride(c), _ptr(v)))
+        if on_dev:  # the device entry only enqueues: torch's streams see the result after this
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        return v
+
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------
     def _run_product(self, name, operand, m, n, xt, trans, beta, in_dtype=None):
         """res = beta * op(A) @ xt through corrla_matmul_dev_* / corrla_spmm_csr_dev_* (`operand`: the arguments that
@@ -1282,6 +1416,40 @@ def rpca(a_mat, n_rank, n_iters=None, n_oversamples=None, *, seed=None, omega=No
     return s, comps
 
 
+def normal_stream_host(seed, first, n, r, dtype=np.float64):
+    """The library's N(0,1) stream restated in numpy -> (n, r): element (i, j) is the value of counter t = (first + i) r + j
+    under `seed` -- one Philox4x32-10 block with key (seed mod 2^32, seed >> 32) and counter (t mod 2^32, t >> 32, 0, 0),
+    the uniforms and the cosine branch of Box-Muller as include/corrla_rsvd.h defines them.  The integer part is exact; log,
+    sqrt and cos are numpy's, so a value agrees with the device's to a few ulp, not bitwise.  What a host-fitted
+    ``PcaRsvd.sample`` draws from."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.float32, np.float64):
+        raise ValueError(f"dtype must be float32 or float64, got {dtype}")
+    n, r, seed, first = int(n), int(r), int(seed), int(first)
+    if n < 0 or r < 1 or first < 0 or (first + n) * r >= 1 << 63:
+        raise ValueError("need n >= 0, r >= 1, first >= 0 and (first + n) * r < 2^63")
+    m32, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    t = (np.uint64(first) + np.arange(n, dtype=np.uint64))[:, None] * np.uint64(r) + np.arange(r, dtype=np.uint64)[None, :]
+    c0, c1, c2, c3 = t & m32, t >> sh, np.zeros_like(t), np.zeros_like(t)
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2  # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & m32, (p0 >> sh) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    if dtype == np.float64:
+        u1 = ((((c0 << sh) | c1) >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+        u2 = ((((c2 << sh) | c3) >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+    else:
+        u1 = ((c0 >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+        u2 = ((c1 >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+    # cos(2 pi u2) with the argument folded exactly into [0, 1/2] half turns, so that the zeros keep relative accuracy
+    x = dtype.type(2.0) * u2
+    y = np.where(x > 1.0, dtype.type(2.0) - x, x)
+    pi = dtype.type(np.pi)
+    c = np.where(y < 0.25, np.cos(pi * y), np.where(y > 0.75, -np.cos(pi * (dtype.type(1.0) - y)), np.sin(pi * (dtype.type(0.5) - y))))
+    return (np.sqrt(dtype.type(-2.0) * np.log(u1)) * c).astype(dtype)
+
+
 class PcaRsvd:
     """Mirror of ``PcaRsvd`` (src/lib_math_utils/pca_rsvd.rs:13-112): fit on construction, keeps the means, the
     singular values (k, 1) and ``components_`` (k, n_dim).  The fit (means, centring, RSVD) runs on the GPU.  A host input
@@ -1341,6 +1509,34 @@ class PcaRsvd:
         """fit(x_mat, rank, **kw), then the scores of x_mat."""
         self.fit(x_mat, rank, **kw)
         return self.transform(x_mat)
+
+    def sample(self, n, *, seed=None, first=0):
+        """n draws from the fitted model, (n, n_dim): means + scales_ * ((z * pca_s / sqrt(n_samples - 1)) @ components_) with
+        z (n, k) the rows [first, first + n) of the library's N(0,1) stream under `seed` (width k; include/corrla_rsvd.h) --
+        the Gaussian whose covariance is the model's rank-k estimate.  A device-fitted model draws z with
+        ``Context.fill_normal`` and back-projects with ``Context.pca_inverse_transform``: k is small and n_dim may be large,
+        which is that kernel's shape.  A host-fitted model does the same in numpy (``normal_stream_host``), like apply_inv_tr.
+        seed=None takes a fresh one from ``numpy.random.SeedSequence``."""
+        n, first = int(n), int(first)
+        if n < 0 or first < 0:
+            raise ValueError(f"n and first must be >= 0, got n = {n}, first = {first}")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+        k = int(self.components_.shape[0])
+        if _is_torch(self.components_):
+            import torch
+            comps = self.components_
+            z = torch.empty((n, k), dtype=comps.dtype, device=comps.device)
+            if n == 0:
+                return torch.empty((0, int(comps.shape[1])), dtype=comps.dtype, device=comps.device)
+            self._context().fill_normal(z, seed, row0=first, global_cols=k)
+            L.check(self._context()._lib.corrla_ctx_synchronize(self._context()._h))  # fill_normal only enqueues
+            sig = (self.pca_s.reshape(1, -1) / float(np.sqrt(self.n_samples - 1.0))).to(comps.dtype)
+            return self.inverse_transform(z * sig)
+        dt = self.components_.dtype
+        z = normal_stream_host(seed, first, n, k, dt)
+        sig = (np.asarray(self.pca_s, dtype=dt).reshape(1, -1) / dt.type(np.sqrt(self.n_samples - 1.0))).astype(dt)
+        return self.apply_inv_tr(z * sig)
 
     def apply_tr(self, targ_mat):  # pca_rsvd.rs:43-46: centres the TARGET by its own column means
         if self._on_device(targ_mat):

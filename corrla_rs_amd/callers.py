@@ -26,6 +26,10 @@ reference also does after its random_svd calls (k = n_modes, a few tens), writte
                                               <- src/lib_math_utils/space_samplers.rs:14-418, lib_math_utils_py.rs:89-168 (the
                                                  draws, the box test and the count on the device, ``Context.dirichlet_sample``;
                                                  the chains, which advance one step after the other, on the host)
+  mvn_factor(cov) / sample_mv_normal(cov, n) / sandwich_prop(cov, jac)
+                                              <- src/lib_math_utils/stats_corr.rs:46-68 (the d-sized factorisation on the host;
+                                                 the rows from the fused kernel, ``Context.mvn_sample``; the per-sample
+                                                 variances from ``Context.sandwich_diag``)
 Every product with an n_x- or N-sized dimension goes through the library's HIP GEMMs (``Context.matmul``); only
 snapshot-count- and n_modes-sized matrices are touched by numpy."""
 import numpy as np
@@ -35,7 +39,8 @@ from .api import _is_torch, default_context, rsvd
 __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyGradientEstimator", "ActiveSsRsvd",
            "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply",
            "linear_fit", "quad_fit", "quad_eval", "jac_from_lin", "jac_from_quad", "polyfit_solve", "KdeRv", "build_kde",
-           "constr_dirichlet_sample", "DeMcSampler", "cs_mcmc_dirichlet_sample"]
+           "constr_dirichlet_sample", "DeMcSampler", "cs_mcmc_dirichlet_sample", "mvn_factor", "sample_mv_normal",
+           "sandwich_prop"]
 
 
 def _on_gpu(x):
@@ -973,3 +978,75 @@ def cs_mcmc_dirichlet_sample(bounds, n_samples, n_seed_samples, max_zshots, chun
     sampler = DeMcSampler(bounds, seeds, np.ones(seeds.shape[1]), gamma, var_epsilon, c_scale=c_scale, seed=seed)
     sampler.sample_mcmc(n_samples)
     return sampler.get_samples(n_samples), sampler.accept_ratio()
+
+
+# ---- multivariate normal samples and sandwich variances (stats_corr.rs:46-68) ----------------------------------------------
+def mvn_factor(cov):
+    """A factor F of a covariance matrix, F F^T = cov -> (F, lower), on the host in float64 (d-sized work).
+      1. cov must be square and symmetric to 8 * 2^-52 * max|cov|, else ValueError;
+      2. the Cholesky factor of the diagonally equilibrated matrix D^-1/2 cov D^-1/2 is tried: (D^1/2 L, True);
+      3. otherwise the symmetric eigendecomposition: an eigenvalue below -d 2^-52 lambda_max is a ValueError (the matrix is
+         indefinite); directions with lambda <= d 2^-52 lambda_max are dropped -- the rule of ``polyfit_solve`` -- and the rest
+         gives (V sqrt(Lambda), False) with r < d columns.
+    So a singular covariance (fewer samples than features, or the output of ``sandwich_prop``) can be sampled from."""
+    c = np.asarray(cov.detach().cpu().numpy() if _is_torch(cov) else cov, dtype=np.float64)
+    if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] == 0:
+        raise ValueError(f"cov must be a non-empty square matrix, got shape {tuple(c.shape)}")
+    if not np.all(np.isfinite(c)):
+        raise ValueError("cov must be finite")
+    d = int(c.shape[0])
+    big = float(np.max(np.abs(c)))
+    if float(np.max(np.abs(c - c.T))) > 8.0 * 2.0 ** -52 * big:
+        raise ValueError("cov is not symmetric")
+    c = 0.5 * (c + c.T)
+    sd = np.sqrt(np.diag(c).clip(min=0.0))
+    sd = np.where(sd > 0.0, sd, 1.0)
+    try:
+        return sd[:, None] * np.linalg.cholesky(c / np.outer(sd, sd)), True
+    except np.linalg.LinAlgError:
+        pass
+    w, v = np.linalg.eigh(c)
+    cut = d * 2.0 ** -52 * max(float(w[-1]), 0.0)
+    if float(w[0]) < -cut or float(w[-1]) <= 0.0 and big > 0.0:
+        raise ValueError(f"cov is not positive semi-definite: smallest eigenvalue {float(w[0]):.3e}")
+    keep = w > cut
+    if not np.any(keep):  # the zero matrix: one column of zeros, so that r >= 1
+        return np.zeros((d, 1)), False
+    return v[:, keep] * np.sqrt(w[keep])[None, :], False
+
+
+def sample_mv_normal(cov, n, *, mean=None, seed=None, device=False, ctx=None):
+    """``sample_mv_normal(cov, n)`` (stats_corr.rs:46-58): n rows of N(mean, cov), (n, d) float64.  The covariance is factored
+    on the host (``mvn_factor``), the rows come from ``Context.mvn_sample``.  numpy in -> numpy out; a CUDA cov or device=True
+    gives a tensor.  seed=None takes a fresh one from ``numpy.random.SeedSequence``.
+    The one deliberate difference from the reference: it multiplies z by cov itself, so its samples have covariance cov^2;
+    these have covariance cov.  ``Context.mvn_sample(n, cov)`` (factor = cov) reproduces the reference's law."""
+    f, lower = mvn_factor(cov)
+    mu = None if mean is None else np.asarray(mean.detach().cpu().numpy() if _is_torch(mean) else mean, dtype=np.float64).reshape(-1)
+    return (ctx or default_context()).mvn_sample(n, f, mu, seed=_fresh_seed() if seed is None else seed, lower=lower,
+                                                 device=bool(device) or _on_gpu(cov))
+
+
+def sandwich_prop(cov, jac, *, diag=False, ctx=None):
+    """``sandwich_prop(cov, jac)`` (stats_corr.rs:64-68): jac @ cov @ jac.T, outputs x outputs -- plain numpy or torch, it is
+    tiny.  diag=True: jac holds one gradient per SAMPLE (m, d) and only the m first-order variances jac[i] @ cov @ jac[i]
+    are wanted: ``Context.sandwich_diag``, without the (m, m) product or an (m, d) temporary."""
+    if diag:
+        c = ctx or default_context()
+        if _is_torch(jac) and not _is_torch(cov):
+            import torch
+            cov = torch.as_tensor(np.asarray(cov), dtype=jac.dtype, device=jac.device)
+        elif not _is_torch(jac):
+            jac = np.asarray(jac)
+            jac = jac if jac.dtype == np.float32 else jac.astype(np.float64, copy=False)
+            cov = np.asarray(cov.detach().cpu().numpy() if _is_torch(cov) else cov, dtype=jac.dtype)
+        else:
+            cov = cov.to(device=jac.device, dtype=jac.dtype)
+        return c.sandwich_diag(jac, cov)
+    if _is_torch(jac) or _is_torch(cov):
+        import torch
+        j = jac if _is_torch(jac) else torch.as_tensor(np.asarray(jac), dtype=cov.dtype, device=cov.device)
+        cv = cov if _is_torch(cov) else torch.as_tensor(np.asarray(cov), dtype=j.dtype, device=j.device)
+        return j @ cv.to(device=j.device, dtype=j.dtype) @ j.T
+    j = np.asarray(jac, dtype=np.float64)
+    return j @ np.asarray(cov, dtype=np.float64) @ j.T

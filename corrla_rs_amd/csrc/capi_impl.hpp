@@ -15,6 +15,7 @@
 #include "polyfit_plan.hpp"  // poly_terms, kPolyMaxK, kPolyMaxRhs
 #include "kde_plan.hpp"  // kKdeMaxH
 #include "dirichlet_plan.hpp"  // dir_plan: the limits of the Dirichlet entries
+#include "mvn_plan.hpp"  // mvn_plan, sandwich_plan: the limits of the multivariate normal entries
 
 namespace corrla {
 
@@ -1150,6 +1151,76 @@ inline void dirichlet_sample_entry(Dev&, bool host_ptrs, const DirichletSampleCa
   const Span out[1] = {c.out_span()};
   if (host_ptrs) no_overlap(who, in, 4, out, 1);  // a device `out` shares no address space with the host arrays
   on_backend_with<dev_has_dirichlet<Dev>>([&] { run(p); }, "Dirichlet sampling kernels", "corrla_dirichlet_sample_*");
+}
+
+// ---- multivariate normal rows and sandwich variances (corrla_mvn_sample_* / corrla_sandwich_diag_*, stats_corr.rs:46-68) -----
+// Argument checks of every entry -- the limits are the plans' (mvn_plan / sandwich_plan name the argument they reject) -- then
+// `run` with that plan, on a backend that carries the kernels (dev_has_mvn).
+template <class T>
+struct MvnSampleCall {
+  int64_t n, d, r;
+  const T* factor;  // d x r, row stride ldf
+  int64_t ldf;
+  const T* mean;    // d, or NULL (0)
+  uint64_t seed;
+  int64_t first;
+  int lower;
+  T* out;           // n x d, row stride ldo
+  int64_t ldo;
+  Span factor_span() const { return Span(factor, d, r, ldf, "factor"); }
+  Span mean_span() const { return Span(mean, 1, d, d, "mean"); }
+  Span out_span() const { return Span(out, n, d, ldo, "out"); }
+};
+
+template <class Dev, class T, class Run>
+inline void mvn_sample_entry(Dev&, const MvnSampleCall<T>& c, Run&& run) {
+  const char* who = "mvn_sample";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  MvnShape s;
+  s.n = c.n, s.d = c.d, s.r = c.r, s.first = c.first, s.ldo = c.ldo, s.esz = (int)sizeof(T);
+  s.out_aligned = (uintptr_t)c.out % 16 == 0;
+  s.lower = c.lower != 0;
+  const MvnPlan p = mvn_plan(s);
+  if (p.route == MvnRoute::kReject) throw Error(ST_EINVAL, p.error);
+  if (!c.factor) bad("factor is NULL");
+  if (c.ldf < 0) bad("negative strides are not supported");
+  if (c.ldf < c.r && c.d > 1) bad("ldf must be >= r");
+  if (p.route != MvnRoute::kEmpty) {  // n = 0: no array of n rows is looked at
+    if (!c.out) bad("out is NULL");
+    const Span in[2] = {c.factor_span(), c.mean_span()};
+    const Span out[1] = {c.out_span()};
+    no_overlap(who, in, 2, out, 1);
+  }
+  on_backend_with<dev_has_mvn<Dev>>([&] { run(p); }, "multivariate normal kernels", "corrla_mvn_sample_*");
+}
+
+template <class T>
+struct SandwichDiagCall {
+  const T* jac;  // m x d, row stride ldj
+  int64_t m, d, ldj;
+  const T* cov;  // d x d, row stride ldc
+  int64_t ldc;
+  T* v;          // m
+  Span jac_span() const { return Span(jac, m, d, ldj, "jac"); }
+  Span cov_span() const { return Span(cov, d, d, ldc, "cov"); }
+  Span v_span() const { return Span(v, 1, m, m, "v"); }
+};
+
+template <class Dev, class T, class Run>
+inline void sandwich_diag_entry(Dev&, const SandwichDiagCall<T>& c, Run&& run) {
+  const char* who = "sandwich_diag";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  SandwichShape s;
+  s.m = c.m, s.d = c.d, s.ldj = c.ldj, s.ldc = c.ldc, s.esz = (int)sizeof(T);
+  const SandwichPlan p = sandwich_plan(s);
+  if (!p.ok) throw Error(ST_EINVAL, p.error);
+  if (!c.jac) bad("jac is NULL");
+  if (!c.cov) bad("cov is NULL");
+  if (!c.v) bad("v is NULL");
+  const Span in[2] = {c.jac_span(), c.cov_span()};
+  const Span out[1] = {c.v_span()};
+  no_overlap(who, in, 2, out, 1);
+  on_backend_with<dev_has_mvn<Dev>>([&] { run(p); }, "multivariate normal kernels", "corrla_sandwich_diag_*");
 }
 
 // ---- active-subspace gradient stage (corrla_grad_mat_*) -------------------------------------------------------

@@ -11,6 +11,7 @@
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "kde_stage.hpp"
+#include "mvn_stage.hpp"
 #include "pca_apply_stage.hpp"
 #include "polyfit_stage.hpp"
 #include "rbf_stage.hpp"
@@ -28,6 +29,7 @@ struct corrla_ctx {
   polyfit_stage::Ran polyfit;      // how the last corrla_polyfit_gram_* / corrla_poly_eval_* call ran
   kde_stage::Ran kde;              // how the last corrla_kde_eval_* / corrla_kde_nll_* call ran
   dirichlet_stage::Ran dirichlet;  // how the last corrla_dirichlet_draws_* / corrla_dirichlet_sample_* call ran
+  mvn_stage::Ran mvn;              // how the last corrla_mvn_sample_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -467,6 +469,38 @@ CORRLA_API corrla_status corrla_ctx_last_dirichlet(corrla_ctx* ctx, int* route_o
     corrla_ctx* c = need(ctx);
     std::lock_guard<std::mutex> lk(c->mu);
     if (route_out) *route_out = c->dirichlet.route | (c->dirichlet.readbacks << 8);
+  });
+}
+
+// ---- multivariate normal rows and sandwich variances (sample_mv_normal / sandwich_prop, stats_corr.rs:46-68) -----------------
+#define CORRLA_DEFINE_MVN(DEV, SUF, T, HOST)                                                                            \
+  CORRLA_API corrla_status corrla_mvn_sample_##DEV##SUF(corrla_ctx* ctx, int64_t n, int64_t d, int64_t r, const T* factor, int64_t ldf, \
+                                                        const T* mean, uint64_t seed, int64_t first, int lower, T* out, int64_t ldo) { \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const MvnSampleCall<T> c{n, d, r, factor, ldf, mean, seed, first, lower, out, ldo};                               \
+      mvn_sample_entry<HipDev, T>(cx.dev, c, [&](const MvnPlan& p) {                                                    \
+        cx.mvn = mvn_stage::Ran();                                                                                      \
+        mvn_stage::run_sample<T>(cx.dev, HOST, c, p, &cx.mvn);                                                          \
+      });                                                                                                               \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  CORRLA_API corrla_status corrla_sandwich_diag_##DEV##SUF(corrla_ctx* ctx, const T* jac, int64_t m, int64_t d, int64_t ldj, const T* cov, \
+                                                           int64_t ldc, T* v) {                                         \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const SandwichDiagCall<T> c{jac, m, d, ldj, cov, ldc, v};                                                         \
+      sandwich_diag_entry<HipDev, T>(cx.dev, c, [&](const SandwichPlan& p) { mvn_stage::run_sandwich<T>(cx.dev, HOST, c, p); }); \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_MVN(, f32, float, true)
+CORRLA_DEFINE_MVN(, f64, double, true)
+CORRLA_DEFINE_MVN(dev_, f32, float, false)
+CORRLA_DEFINE_MVN(dev_, f64, double, false)
+// route_out: 1 fused, 2 staged, 3 no rows (nothing launched), 0 before the first call.  A rejected call leaves it as it was.
+CORRLA_API corrla_status corrla_ctx_last_mvn(corrla_ctx* ctx, int* route_out) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (route_out) *route_out = c->mvn.route;
   });
 }
 

@@ -139,6 +139,12 @@ template <class D, class = void>
 struct dev_has_dirichlet : std::false_type {};
 template <class D>
 struct dev_has_dirichlet<D, std::void_t<decltype(D::kHasDirichlet)>> : std::true_type {};
+// ... and those that carry the multivariate normal and sandwich kernels of corrla_mvn_sample_* / corrla_sandwich_diag_*
+// (mvn_kernels.hpp) with kHasMvn.
+template <class D, class = void>
+struct dev_has_mvn : std::false_type {};
+template <class D>
+struct dev_has_mvn<D, std::void_t<decltype(D::kHasMvn)>> : std::true_type {};
 
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).

@@ -40,6 +40,7 @@
 #include "polyfit_kernels.hpp"
 #include "kde_kernels.hpp"
 #include "dirichlet_kernels.hpp"
+#include "mvn_kernels.hpp"
 
 namespace corrla {
 
@@ -128,6 +129,10 @@ inline void set_lds_limits();  // polyfit_stage.hpp: the polynomial response-sur
 namespace thinq_stage {
 template <class T>
 void set_lds_limits();  // thinq_stage.hpp: the Householder panels
+}
+namespace mvn_stage {
+template <class T>
+void set_lds_limits();  // mvn_stage.hpp: the multivariate normal and sandwich kernels
 }
 
 class HipDev {
@@ -827,6 +832,8 @@ class HipDev {
   static constexpr bool kHasKde = true;  // driver.hpp: dev_has_kde
   // ---- constrained Dirichlet sampling: dirichlet_plan.hpp plans, dirichlet_stage.hpp launches dirichlet_kernels.hpp ---------
   static constexpr bool kHasDirichlet = true;  // driver.hpp: dev_has_dirichlet
+  // ---- multivariate normal rows and sandwich variances: mvn_plan.hpp plans, mvn_stage.hpp launches mvn_kernels.hpp ----------
+  static constexpr bool kHasMvn = true;  // driver.hpp: dev_has_mvn
   const PolyKnobs& poly_knobs() const { return poly_knobs_; }
   // The plan's pair table on the device.  It depends on (k, r, degree) alone, so it is uploaded when those change and kept
   // between calls: a repeated fit enqueues without a synchronising copy.
@@ -1049,6 +1056,7 @@ class HipDev {
     lds_limit((const void*)k::syrk_kernel<T, true>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     lds_limit((const void*)k::syrk_kernel<T, false>, (size_t)k::syrk_lds_bytes((int)sizeof(T)));
     thinq_stage::set_lds_limits<T>();
+    mvn_stage::set_lds_limits<T>();
   }
   // ---- the tall products' launch (tall_stage.hpp) ----
   // what a launcher of the stage needs of this context beyond the plan

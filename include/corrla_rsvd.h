@@ -708,6 +708,56 @@ CORRLA_API corrla_status corrla_dirichlet_sample_dev_f64(corrla_ctx* ctx, const 
                                                          int64_t ldo, int64_t* n_found, int64_t* n_drawn);
 CORRLA_API corrla_status corrla_ctx_last_dirichlet(corrla_ctx* ctx, int* route_out);
 
+/* ---- multivariate normal rows and sandwich variances ----------------------------------------------------
+ * Replaces  sample_mv_normal / sandwich_prop (its diagonal)        src/lib_math_utils/stats_corr.rs:46-58, 64-68
+ * corrla_mvn_sample_*: row i < n of out is x_i = mean + factor z_i, factor d x r (1 <= r <= d), so the rows have
+ *   covariance factor factor^T.  (The reference multiplies z by the covariance itself, which gives covariance C^2; pass
+ *   factor = C for that law.)
+ * THE STREAM.  z_i[j] (0 <= j < r) of (seed, first, r) is the N(0,1) value of counter t = (first + i) r + j:
+ *   ONE Philox4x32-10 block with key (seed mod 2^32, seed >> 32) and counter (t mod 2^32, t >> 32, 0, 0), output words
+ *   w0..w3;  f64: u1 = (((w0 << 32 | w1) >> 11) + 0.5) 2^-53, u2 likewise from w2, w3;  f32: u1 = ((w0 >> 8) + 0.5) 2^-24,
+ *   u2 likewise from w1;  z = sqrt(-2 log(u1)) * cospi(2 u2) in the element type.  These are the values
+ *   corrla_fill_normal_dev_* writes into an n x r matrix with row0 = first and global_cols = r.  The result is a pure
+ *   function of (seed, first, factor, mean): rows [a, b) of a call are, bit for bit, the call with first + a and n = b - a,
+ *   and a call repeated gives the same bits.  No atomics, and nothing is read back inside the call.
+ * Routes (corrla_ctx_last_mvn: 1 fused, 2 staged, 3 n = 0, nothing launched):
+ *   fused, r <= 288 (f32) / 144 (f64): a workgroup generates the z of 64 rows once into LDS -- no z is generated twice,
+ *     none reaches global memory --, walks the columns of out on the exact f32 / f64 MFMAs with factor^T read in chunks,
+ *     and writes acc + mean once.  The limit is what lets two such workgroups share the 160 KiB of LDS of a compute unit.
+ *   staged, any larger r with d <= 65536: z of a row chunk is filled into a workspace of at most max(256 MiB, 64 r
+ *     elements) and multiplied by the back-projection kernel of corrla_pca_inverse_*.  The same stream; against the fused
+ *     route equal to rounding (both sum r products in their own order), not bitwise.
+ *   lower != 0: factor is square lower-triangular (a Cholesky factor); its strict upper triangle is taken as zero and never
+ *     read, and the fused route skips the MFMA steps that lie wholly above the diagonal.  The result is bitwise that of
+ *     lower = 0 on the same triangular matrix: the skipped terms are exact zeros.
+ * corrla_sandwich_diag_*: v[i] = sum_a sum_b jac[i][a] cov[a][b] jac[i][b], i < m; cov is used as given, never symmetrised.
+ *   The row tile of jac is staged in LDS once, jac cov runs on the MFMAs a column tile at a time and is multiplied by the
+ *   staged tile and summed along the row in a fixed order: no m x d temporary, no atomics, bitwise reproducible.
+ * Layouts: factor d x r with row stride ldf >= r; mean d contiguous values or NULL (zeros); out n x d with unit stride
+ *   along d and row stride ldo >= d, the elements between d and ldo are never written (16-byte stores where the base and
+ *   ldo allow, element stores otherwise); jac m x d with row stride ldj >= d, cov d x d with row stride ldc >= d, v m
+ *   contiguous values.  Host pointers for the plain entries, device pointers for *_dev, which enqueue and return.
+ * Limits: n >= 0 (n = 0 returns without a launch), first >= 0, (first + n) r < 2^63; sandwich: m >= 1, 1 <= d <= 512.
+ * CORRLA_EINVAL (the message names the argument): any of these limits; r < 1, r > d; lower with r != d; a negative stride
+ *   or one below the row length; NULL factor, out, jac, cov or v; an output overlapping an input. */
+CORRLA_API corrla_status corrla_mvn_sample_f32(corrla_ctx* ctx, int64_t n, int64_t d, int64_t r, const float* factor, int64_t ldf,
+                                               const float* mean, uint64_t seed, int64_t first, int lower, float* out, int64_t ldo);
+CORRLA_API corrla_status corrla_mvn_sample_f64(corrla_ctx* ctx, int64_t n, int64_t d, int64_t r, const double* factor, int64_t ldf,
+                                               const double* mean, uint64_t seed, int64_t first, int lower, double* out, int64_t ldo);
+CORRLA_API corrla_status corrla_mvn_sample_dev_f32(corrla_ctx* ctx, int64_t n, int64_t d, int64_t r, const float* factor, int64_t ldf,
+                                                   const float* mean, uint64_t seed, int64_t first, int lower, float* out, int64_t ldo);
+CORRLA_API corrla_status corrla_mvn_sample_dev_f64(corrla_ctx* ctx, int64_t n, int64_t d, int64_t r, const double* factor, int64_t ldf,
+                                                   const double* mean, uint64_t seed, int64_t first, int lower, double* out, int64_t ldo);
+CORRLA_API corrla_status corrla_sandwich_diag_f32(corrla_ctx* ctx, const float* jac, int64_t m, int64_t d, int64_t ldj, const float* cov,
+                                                  int64_t ldc, float* v);
+CORRLA_API corrla_status corrla_sandwich_diag_f64(corrla_ctx* ctx, const double* jac, int64_t m, int64_t d, int64_t ldj, const double* cov,
+                                                  int64_t ldc, double* v);
+CORRLA_API corrla_status corrla_sandwich_diag_dev_f32(corrla_ctx* ctx, const float* jac, int64_t m, int64_t d, int64_t ldj, const float* cov,
+                                                      int64_t ldc, float* v);
+CORRLA_API corrla_status corrla_sandwich_diag_dev_f64(corrla_ctx* ctx, const double* jac, int64_t m, int64_t d, int64_t ldj, const double* cov,
+                                                      int64_t ldc, double* v);
+CORRLA_API corrla_status corrla_ctx_last_mvn(corrla_ctx* ctx, int* route_out);
+
 /* ---- the Gaussian generator: random_mat_normal --------------------------------------
  * Replaces  random_mat_normal<T>(n_rows, n_cols)               src/lib_math_utils/mat_utils.rs:161-175
  * Fills a DEVICE matrix with i.i.d. N(0,1) from a counter-based Philox4x32-10 + Box-Muller

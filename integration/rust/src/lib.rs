@@ -215,6 +215,21 @@ extern "C" {
     pub fn corrla_kde_nll_dev_f32(ctx: *mut c_void, x: *const f32, n_t: i64, incx: i64, s: *const f32, n_s: i64, incs: i64,
                                h: *const f64, n_h: i64, nll: *mut f64, dnll: *mut f64) -> c_int;
     pub fn corrla_ctx_last_kde(ctx: *mut c_void, route_out: *mut c_int) -> c_int;
+    // multivariate normal rows x_i = mean + factor z_i (stats_corr.rs:46-58; factor d x r, covariance factor factor^T -- the
+    // reference's own law, covariance C^2, is factor = C) and the sandwich variances j_i^T C j_i (stats_corr.rs:64-68)
+    pub fn corrla_mvn_sample_f64(ctx: *mut c_void, n: i64, d: i64, r: i64, factor: *const f64, ldf: i64, mean: *const f64, seed: u64,
+                                 first: i64, lower: c_int, out: *mut f64, ldo: i64) -> c_int;
+    pub fn corrla_mvn_sample_f32(ctx: *mut c_void, n: i64, d: i64, r: i64, factor: *const f32, ldf: i64, mean: *const f32, seed: u64,
+                                 first: i64, lower: c_int, out: *mut f32, ldo: i64) -> c_int;
+    pub fn corrla_mvn_sample_dev_f64(ctx: *mut c_void, n: i64, d: i64, r: i64, factor: *const f64, ldf: i64, mean: *const f64, seed: u64,
+                                     first: i64, lower: c_int, out: *mut f64, ldo: i64) -> c_int;
+    pub fn corrla_mvn_sample_dev_f32(ctx: *mut c_void, n: i64, d: i64, r: i64, factor: *const f32, ldf: i64, mean: *const f32, seed: u64,
+                                     first: i64, lower: c_int, out: *mut f32, ldo: i64) -> c_int;
+    pub fn corrla_sandwich_diag_f64(ctx: *mut c_void, jac: *const f64, m: i64, d: i64, ldj: i64, cov: *const f64, ldc: i64, v: *mut f64) -> c_int;
+    pub fn corrla_sandwich_diag_f32(ctx: *mut c_void, jac: *const f32, m: i64, d: i64, ldj: i64, cov: *const f32, ldc: i64, v: *mut f32) -> c_int;
+    pub fn corrla_sandwich_diag_dev_f64(ctx: *mut c_void, jac: *const f64, m: i64, d: i64, ldj: i64, cov: *const f64, ldc: i64, v: *mut f64) -> c_int;
+    pub fn corrla_sandwich_diag_dev_f32(ctx: *mut c_void, jac: *const f32, m: i64, d: i64, ldj: i64, cov: *const f32, ldc: i64, v: *mut f32) -> c_int;
+    pub fn corrla_ctx_last_mvn(ctx: *mut c_void, route_out: *mut c_int) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
