@@ -7,4 +7,4 @@ from .api import (Context, PcaRsvd, algorithmic_flops, default_context, power_it
 __version__ = "0.1.0"
 from .callers import (ActiveSsRsvd, DeMcSampler, DMDc, FittedActiveSsRsvd, KdeRv, PodI, PolyGradientEstimator, RbfInterp,  # noqa: E402,F401
                       active_ss_fit_svd, build_kde, constr_dirichlet_sample, cs_mcmc_dirichlet_sample, jac_from_lin, jac_from_quad, linear_fit, mat_cov_centered, pearson_corr, pod_modes,
-                      mvn_factor, polyfit_solve, quad_eval, quad_fit, rbf_apply, rbf_matrix, rsquared_sens, sample_mv_normal, sandwich_prop)
+                      mvn_factor, polyfit_solve, quad_eval, quad_fit, rbf_apply, rbf_fit, rbf_matrix, rsquared_sens, sample_mv_normal, sandwich_prop)

@@ -47,6 +47,11 @@ DIRICHLET_MAX_DRAWS = 1 << 62
 MVN_ROUTES = {1: "fused", 2: "staged", 3: "empty"}
 MVN_MAX_D = 65536
 SANDWICH_MAX_D = 512
+# corrla_lu_solve_* / corrla_rbffit_*: what corrla_ctx_last_solve reports, and the limits
+SOLVE_ROUTES = {1: "small", 2: "blocked"}
+LU_SMALL_N = 128
+LU_NB = 64
+LU_MAX_N = 1 << 17
 UNIQUE_ID_BYTES = 128
 
 
@@ -87,6 +92,13 @@ def _sigs():
     s["corrla_dirichlet_draws_f64"] = s["corrla_dirichlet_draws_dev_f64"] = (C.c_int, [vp, vp, i64, dbl, u64, i64, i64, vp, i64])
     s["corrla_dirichlet_sample_f64"] = s["corrla_dirichlet_sample_dev_f64"] = (
         C.c_int, [vp, vp, vp, i64, dbl, u64, i64, i64, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)])
+    # dense LU solve, f64 only, row-major: a, n, lda, b, n_rhs, ldb, then x, ldx (host) / ipiv (device, in place)
+    s["corrla_lu_solve_f64"] = (C.c_int, [vp, vp, i64, i64, vp, i64, i64, vp, i64])
+    s["corrla_lu_solve_dev_f64"] = (C.c_int, [vp, vp, i64, i64, vp, i64, i64, vp])
+    # the RBF system and fit: xs, n_s, ldxs, dim, [y, n_rhs, ldy,] kernel, eps, poly_degree, m | coeffs, ld
+    s["corrla_rbffit_system_f64"] = s["corrla_rbffit_system_dev_f64"] = (C.c_int, [vp, vp, i64, i64, i64, C.c_int, dbl, C.c_int, vp, i64])
+    s["corrla_rbffit_f64"] = s["corrla_rbffit_dev_f64"] = (C.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, C.c_int, dbl, C.c_int, vp, i64])
+    s["corrla_ctx_last_solve"] = (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)])
     for suf, sc in (("f32", flt), ("f64", dbl)):
         rsvd = [vp, vp, i64, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
         s["corrla_rsvd_" + suf] = (C.c_int, rsvd)

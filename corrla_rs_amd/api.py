@@ -780,6 +780,146 @@ class Context:
             L.check(self._lib.corrla_ctx_synchronize(self._h))
         return out
 
+    # ---- dense LU solve and the RBF fit on it (corrla_lu_solve_* / corrla_rbffit_system_* / corrla_rbffit_*) ---------
+    def _f64_matrix(self, v, name, what, like=None):
+        """-> (v as a float64 matrix the solve entries read: row-major, unit column stride, rows that do not overlap;
+        on_device).  like: an array whose kind and device v is converted to; None: v's own."""
+        _reject_bf16(v, what)
+        if _is_sparse(v):
+            raise ValueError(f"{what} takes a dense {name}")
+        if like is None:
+            a, on_dev = _as_dense(v, name)
+            if on_dev:
+                import torch
+                self._on_my_device(a)
+                a = a.detach().to(torch.float64)
+            else:
+                a = a.astype(np.float64, copy=False)
+        else:
+            on_dev = _is_torch(like)
+            a = self._model_array(v, like, on_dev)
+            if a.ndim != 2:
+                raise ValueError(f"{name} must be 2-D")
+        return self._rbf_rowmajor(a, on_dev), on_dev
+
+    def _solve_done(self):
+        """how the last solve ran, whether it succeeded or ended with CORRLA_ENUMERIC"""
+        route, info, minp, maxu = C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        L.check(self._lib.corrla_ctx_last_solve(self._h, C.byref(route), C.byref(info), C.byref(minp), C.byref(maxu)))
+        self._solve_route = L.SOLVE_ROUTES.get(route.value)
+        self._solve_info = {"info": int(info.value), "min_pivot": float(minp.value), "max_u": float(maxu.value)}
+
+    def _solve_call(self, fn, *args):
+        """one solve or fit entry; the status record is kept before a failure is raised"""
+        rc = fn(self._h, *args)
+        if rc in (L.OK, L.ENUMERIC):
+            self._solve_done()
+        L.check(rc)
+
+    def solve(self, a, b, *, overwrite=False):
+        """x with a x = b on the device (corrla_lu_solve_*): LU with partial pivoting (P A = L U, ties to the lowest row,
+        |l_ij| <= 1 exactly, no atomics: a fixed input gives bitwise fixed output), then the substitutions.  a is (n, n), b is
+        (n,) or (n, n_rhs); x has the shape of b.  float64 only: anything else is converted.  numpy `a` -> numpy out (a and b
+        are left untouched), a CUDA tensor as `a` -> a tensor on its device; b is converted to the kind and device of a.
+        overwrite=True (tensors only, float64 row-major): a is overwritten with L and U and b with x, nothing is copied.
+        A pivot that is exactly zero or not finite raises RuntimeError (``CorrlaError``, code ENUMERIC) naming the 1-based
+        column.  ``last_solve_route`` ("small": n <= 128, one workgroup in LDS; "blocked") and ``last_solve_info`` (info, the
+        smallest |pivot|, the largest |u_ij|) describe the call.  ValueError: a not square, b with other than n rows, empty,
+        sparse or bfloat16 inputs, a tensor on another device, n above 131072."""
+        overwrite = _check_bool("overwrite", overwrite, ValueError)
+        am, on_dev = self._f64_matrix(a, "a", "solve")
+        n = int(am.shape[0])
+        if n == 0 or am.shape[1] != n:
+            raise ValueError(f"a must be square and non-empty, got {tuple(am.shape)}")
+        vec = (b.dim() if _is_torch(b) else np.ndim(b)) == 1
+        b2 = b.reshape(-1, 1) if vec else b
+        bm, _ = self._f64_matrix(b2, "b", "solve", like=am)
+        if bm.shape[0] != n or bm.shape[1] == 0:
+            raise ValueError(f"b must have n = {n} rows and at least one column, got {tuple(bm.shape)}")
+        n_rhs = int(bm.shape[1])
+        if on_dev:
+            if overwrite:
+                if not (_is_torch(a) and _is_torch(b) and am.data_ptr() == a.data_ptr() and bm.data_ptr() == b.data_ptr()):
+                    raise ValueError("overwrite=True takes float64 row-major CUDA tensors that need no conversion")
+            else:
+                am, bm = am.clone(), bm.clone()
+            _sync_stream(am)
+            self._solve_call(self._lib.corrla_lu_solve_dev_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
+                             None)
+            x = bm
+        else:
+            if overwrite:
+                raise ValueError("overwrite=True needs CUDA tensors: the host entry leaves a and b untouched")
+            x = np.empty((n, n_rhs), dtype=np.float64)
+            self._solve_call(self._lib.corrla_lu_solve_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
+                             _ptr(x), n_rhs)
+        return x.reshape(-1) if vec else x
+
+    @property
+    def last_solve_route(self):
+        """"small" or "blocked": the route of this context's last ``solve`` / ``rbf_fit``; None before the first."""
+        return getattr(self, "_solve_route", None)
+
+    @property
+    def last_solve_info(self):
+        """{"info": 0 or the 1-based column of the failed pivot, "min_pivot": smallest |pivot|, "max_u": largest |u_ij|} of
+        this context's last ``solve`` / ``rbf_fit``; None before the first."""
+        return getattr(self, "_solve_info", None)
+
+    def _rbf_fit_args(self, x, poly_degree, what):
+        xs, on_dev = self._f64_matrix(x, "x", what)
+        n_s, dim = (int(v) for v in xs.shape)
+        if n_s == 0 or dim == 0:
+            raise ValueError("x must be non-empty")
+        if poly_degree is not None and (isinstance(poly_degree, (bool, np.bool_)) or not isinstance(poly_degree, (int, np.integer))):
+            raise ValueError("poly_degree must be None or an integer")
+        degree = -1 if poly_degree is None or poly_degree < 0 else int(poly_degree)
+        n_poly = 0 if degree < 0 else (dim + 1 if degree < 2 else dim + dim * (dim + 1) // 2 + 1)
+        return xs, on_dev, n_s, dim, degree, n_s + n_poly
+
+    def rbf_system(self, x, kernel_type, kernel_param=0.0, *, poly_degree=None):
+        """The block system M = [[K, P], [P^T, 0]] of an RBF fit over the supports x (n_s, dim), (N, N) with
+        N = n_s + n_poly, float64, on the device (corrla_rbffit_system_*): K is bitwise ``rbf_matrix(x, x)``, P the polynomial
+        tail of ``rbf_apply`` ([x, 1] for poly_degree 0 or 1, [x, x_a x_b (a <= b), 1] from 2 on, none for None) with one
+        rounding per product, the corner exactly zero.  numpy in -> numpy out, a CUDA tensor in -> a tensor on its device."""
+        xs, on_dev, n_s, dim, degree, n = self._rbf_fit_args(x, poly_degree, "rbf_system")
+        if on_dev:
+            import torch
+            out = torch.empty((n, n), dtype=torch.float64, device=xs.device)
+            _sync_stream(xs)
+        else:
+            out = np.empty((n, n), dtype=np.float64)
+        L.check(self._entry("corrla_rbffit_system_", on_dev, np.float64)(self._h, _ptr(xs), n_s, self._row_stride(xs), dim,
+                                                                     self._rbf_kernel_id(kernel_type), float(kernel_param), degree,
+                                                                     _ptr(out), n))
+        if on_dev:  # the device entry only enqueues
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        return out
+
+    def rbf_fit(self, x, y, kernel_type, kernel_param=0.0, *, poly_degree=None):
+        """The coefficients of the RBF interpolant through (x, y) by an LU solve that never leaves the device
+        (corrla_rbffit_*): ``solve(rbf_system(x, ...), [y; 0])`` bitwise, with the system in workspace.  x is (n_s, dim), y
+        (n_s,) or (n_s, n_rhs); the result is (n_s + n_poly, n_rhs), the layout ``rbf_apply`` reads.  float64.  numpy x ->
+        numpy out, a CUDA tensor as x -> a tensor on its device (y is converted to the kind and device of x; no N-sized
+        array comes back to the host).  A singular system raises RuntimeError naming the column; ``last_solve_route`` and
+        ``last_solve_info`` describe the call.  This is NOT the reference's solve: ``RbfInterp`` takes the regularised
+        pseudo-inverse unless asked for solver="lu"."""
+        xs, on_dev, n_s, dim, degree, n = self._rbf_fit_args(x, poly_degree, "rbf_fit")
+        y2 = y.reshape(n_s, -1) if (y.dim() if _is_torch(y) else np.ndim(y)) == 1 else y
+        ym, _ = self._f64_matrix(y2, "y", "rbf_fit", like=xs)
+        if ym.shape[0] != n_s or ym.shape[1] == 0:
+            raise ValueError(f"y must have n_s = {n_s} rows and at least one column, got {tuple(ym.shape)}")
+        n_rhs = int(ym.shape[1])
+        if on_dev:
+            import torch
+            out = torch.empty((n, n_rhs), dtype=torch.float64, device=xs.device)
+            _sync_stream(xs)
+        else:
+            out = np.empty((n, n_rhs), dtype=np.float64)
+        self._solve_call(self._entry("corrla_rbffit_", on_dev, np.float64), _ptr(xs), n_s, self._row_stride(xs), dim, _ptr(ym), n_rhs,
+                         self._row_stride(ym), self._rbf_kernel_id(kernel_type), float(kernel_param), degree, _ptr(out), n_rhs)
+        return out
+
     # ---- polynomial response surfaces (stats_corr.rs:146-249) ---------------------------------------
     @staticmethod
     def _poly_degree(degree):

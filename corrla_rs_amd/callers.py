@@ -467,6 +467,11 @@ def rbf_apply(x_query, x_support, coeffs, kernel_type, kernel_param=0.0, *, poly
     return (ctx or default_context()).rbf_apply(x_query, x_support, coeffs, kernel_type, kernel_param, poly_degree=poly_degree)
 
 
+def rbf_fit(x, y, kernel_type, kernel_param=0.0, *, poly_degree=None, ctx=None):
+    """The coefficients of the RBF interpolant through (x, y) by an LU solve on the device: ``Context.rbf_fit``."""
+    return (ctx or default_context()).rbf_fit(x, y, kernel_type, kernel_param, poly_degree=poly_degree)
+
+
 class RbfInterp:
     """Radial-basis-function interpolant with a polynomial tail (interp_utils.rs:11-160; pyo3 ``PyRbfInterp(kernel_type,
     kernel_param, dim, poly_degree)``: 1 linear r, 2 multiquadric sqrt(1 + (eps r)^2), 3 cubic r^3, otherwise Gaussian
@@ -479,12 +484,25 @@ class RbfInterp:
     queries is never stored, so 10^5 queries against 10^4 supports need no 8 GB temporary.  The solve of the
     (n_s + n_poly)-sized block system stays on the host in float64: its SVD pseudo-inverse with every singular value
     inverted as 1 / (s + 1e-14) (``mat_pinv``) is what parity with the reference means.  numpy in -> numpy out, a tensor
-    in -> a tensor out; ``predict`` with a CUDA query on a host-fitted model uploads the small model per call."""
+    in -> a tensor out; ``predict`` with a CUDA query on a host-fitted model uploads the small model per call.
 
-    def __init__(self, kernel_type, kernel_param, dim, poly_degree, *, device=False, ctx=None):
+    solver="pinv" (the default) is that route, bit for bit.  solver="lu" is opt-in and always runs on the device: ``fit`` is
+    one ``Context.rbf_fit`` -- the block system is built in device workspace and solved there by LU with partial pivoting;
+    with the supports on the device only `y` crosses to it (if it was a host array) and no system-sized array returns.  Its
+    coefficients differ from the pseudo-inverse's within the conditioning of the system (both are backward stable), not bit
+    for bit.  A singular system (coincident supports, fewer supports than the polynomial tail needs) raises RuntimeError
+    naming the column where the pseudo-inverse would return a minimum-norm answer; what is detected is an exactly zero or
+    non-finite pivot -- a nearly singular system completes, and ``Context.last_solve_info["min_pivot"]`` is the witness.
+    Measured on one MI355X (dim 3, cubic kernel, linear tail, 8 right-hand sides): "lu" 33 ms / 168 ms / 543 ms at 2048 /
+    8192 / 16384 supports against 0.81 s / 25 s for "pinv" at the first two -- faster at every size from 2048 up."""
+
+    def __init__(self, kernel_type, kernel_param, dim, poly_degree, *, device=False, ctx=None, solver="pinv"):
         self.kernel_type, self.eps, self.dim, self.poly_degree = int(kernel_type), float(kernel_param), int(dim), int(poly_degree)
         self.x_known = self.coeffs = None
         self.device, self._ctx = bool(device), ctx
+        if solver not in ("pinv", "lu"):
+            raise ValueError("solver must be 'pinv' or 'lu'")
+        self.solver = solver
 
     def _phi(self, r):
         if self.kernel_type == 1:
@@ -505,6 +523,8 @@ class RbfInterp:
         return self._ctx
 
     def fit(self, x_in, y_in):
+        if self.solver == "lu":
+            return self._fit_lu(x_in, y_in)
         if self.device or _on_gpu(x_in) or _on_gpu(y_in):
             return self._fit_device(x_in, y_in)
         x = np.asarray(x_in, np.float64)
@@ -537,8 +557,18 @@ class RbfInterp:
         else:
             self.x_known, self.coeffs = x.copy(), coeffs
 
+    def _fit_lu(self, x_in, y_in):
+        """one Context.rbf_fit in float64; the model stays where the supports were given"""
+        on_gpu = _on_gpu(x_in)
+        x = x_in.detach().double() if on_gpu else np.asarray(x_in.detach().cpu().numpy() if _is_torch(x_in) else x_in, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError("x_in must have `dim` columns")
+        y = y_in.detach() if _is_torch(y_in) else np.asarray(y_in, np.float64)
+        coeffs = self._context().rbf_fit(x, y.reshape(x.shape[0], -1), self.kernel_type, self.eps, poly_degree=self.poly_degree)
+        self.x_known, self.coeffs = (x.clone() if on_gpu else x.copy()), coeffs
+
     def predict(self, x_query):
-        if self.device or _on_gpu(x_query) or _on_gpu(self.x_known):
+        if self.device or self.solver == "lu" or _on_gpu(x_query) or _on_gpu(self.x_known):
             return self._predict_device(x_query)
         xq = np.asarray(x_query, np.float64)
         if xq.shape[1] != self.dim:

@@ -16,6 +16,7 @@
 #include "kde_plan.hpp"  // kKdeMaxH
 #include "dirichlet_plan.hpp"  // dir_plan: the limits of the Dirichlet entries
 #include "mvn_plan.hpp"  // mvn_plan, sandwich_plan: the limits of the multivariate normal entries
+#include "lu_plan.hpp"  // lu_plan: the limits of the dense-solve entries
 
 namespace corrla {
 
@@ -1083,6 +1084,103 @@ inline void kde_nll_entry(Dev&, const KdeNllCall<T>& c, Run&& run) {
   const Span out[2] = {c.nll_span(), c.dnll_span()};
   no_overlap(who, in, 2, out, 2);
   on_backend_with<dev_has_kde<Dev>>(run, "kernel-density kernels", "corrla_kde_nll_*");
+}
+
+// ---- dense LU solve and the RBF fit on it (corrla_lu_solve_* / corrla_rbffit_system_* / corrla_rbffit_*) ------------------------
+// Argument checks of every entry -- the limits of n and n_rhs are the plan's (lu_plan names the argument it rejects) -- then
+// `run`, on a backend that carries the kernels (dev_has_lu).  f64 only.
+struct LuSolveCall {
+  // host entry: a and b are read, x is written.  Device entry: a_rw becomes LU, b_rw becomes X, ipiv (nullable) is written.
+  const double* a;
+  int64_t n, lda;
+  const double* b;
+  int64_t n_rhs, ldb;
+  double* x;
+  int64_t ldx;
+  double* a_rw;
+  double* b_rw;
+  int64_t* ipiv;
+  Span a_span() const { return Span(a, n, n, lda, "a"); }
+  Span b_span() const { return Span(b, n, n_rhs, ldb, "b"); }
+  Span x_span() const { return Span(x, n, n_rhs, ldx, "x"); }
+  Span ipiv_span() const { return Span(ipiv, 1, n, n, "ipiv"); }  // empty without ipiv
+};
+
+template <class Dev, class Run>
+inline void lu_solve_entry(Dev&, bool host_ptrs, const LuSolveCall& c, Run&& run) {
+  const char* who = "lu_solve";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.a) bad("a is NULL");
+  if (!c.b) bad("b is NULL");
+  if (host_ptrs && !c.x) bad("x is NULL");
+  if (c.n_rhs < 1) bad("n_rhs must be >= 1");
+  LuShape s;
+  s.n = c.n, s.n_rhs = c.n_rhs;
+  const LuPlan p = lu_plan(s);
+  if (!p.ok) throw Error(ST_EINVAL, p.error);
+  if (c.lda < c.n) bad("lda < n");
+  if (c.ldb < c.n_rhs) bad("ldb < n_rhs");
+  if (host_ptrs && c.ldx < c.n_rhs) bad("ldx < n_rhs");
+  if (host_ptrs) {
+    const Span in[2] = {c.a_span(), c.b_span()};
+    const Span out[1] = {c.x_span()};
+    no_overlap(who, in, 2, out, 1);
+  } else {  // all three are written
+    const Span out[3] = {c.a_span(), c.b_span(), c.ipiv_span()};
+    no_overlap(who, nullptr, 0, out, 3);
+  }
+  on_backend_with<dev_has_lu<Dev>>(run, "LU kernels", "corrla_lu_solve_*");
+}
+
+// corrla_rbffit_system_* (m, ldm; no y, no coeffs) and corrla_rbffit_* (y, coeffs; the system lives in workspace)
+struct RbfFitCall {
+  const double* xs;
+  int64_t n_s, ldxs, dim;
+  const double* y;  // n_s x n_rhs, row stride ldy
+  int64_t n_rhs, ldy;
+  int kernel;
+  double eps;
+  int poly_degree;  // < 0 no tail
+  double* coeffs;   // (n_s + n_poly) x n_rhs, row stride ldw: the layout corrla_rbf_apply_* reads
+  int64_t ldw;
+  double* m;        // (n_s + n_poly)^2, row stride ldm
+  int64_t ldm;
+  int64_t n_poly() const { return rbf_poly_terms(dim, poly_degree); }
+  int64_t order() const { return n_s + n_poly(); }
+  Span xs_span() const { return Span(xs, n_s, dim, ldxs, "xs"); }
+  Span y_span() const { return Span(y, n_s, n_rhs, ldy, "y"); }
+  Span coeffs_span() const { return Span(coeffs, order(), n_rhs, ldw, "coeffs"); }
+  Span system_span() const { return Span(m, order(), order(), ldm, "m"); }
+};
+
+template <class Dev, class Run>
+inline void rbf_fit_entry(Dev&, const RbfFitCall& c, bool fit, Run&& run) {
+  const char* who = fit ? "rbf_fit" : "rbf_system";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.xs) bad("xs is NULL");
+  if (c.n_s < 1) bad("n_s must be >= 1");
+  if (c.dim < 1 || c.dim > k::kRbfMaxDim) bad("dim must be in [1, 128]");
+  if (c.kernel < 1 || c.kernel > 4) bad("kernel must be in [1, 4]");
+  if (!std::isfinite(c.eps)) bad("eps must be finite");
+  if (c.ldxs < c.dim) bad("ldxs < dim");
+  if (c.n_s > k::kLuMaxN || c.order() > k::kLuMaxN) bad("n_s + n_poly must be <= 131072");
+  if (fit) {
+    if (!c.y) bad("y is NULL");
+    if (!c.coeffs) bad("coeffs is NULL");
+    if (c.n_rhs < 1 || c.n_rhs > k::kLuMaxRhs) bad("n_rhs must be in [1, 1048576]");
+    if (c.ldy < c.n_rhs) bad("ldy < n_rhs");
+    if (c.ldw < c.n_rhs) bad("ldw < n_rhs");
+    const Span in[2] = {c.xs_span(), c.y_span()};
+    const Span out[1] = {c.coeffs_span()};
+    no_overlap(who, in, 2, out, 1);
+  } else {
+    if (!c.m) bad("m is NULL");
+    if (c.ldm < c.order()) bad("ldm < n_s + n_poly");
+    const Span in[1] = {c.xs_span()};
+    const Span out[1] = {c.system_span()};
+    no_overlap(who, in, 1, out, 1);
+  }
+  on_backend_with<dev_has_lu<Dev>>(run, "LU kernels", fit ? "corrla_rbffit_*" : "corrla_rbffit_system_*");
 }
 
 // ---- constrained Dirichlet sampling (corrla_dirichlet_draws_* / corrla_dirichlet_sample_*, space_samplers.rs:14-126) ---------

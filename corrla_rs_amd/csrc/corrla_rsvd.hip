@@ -11,6 +11,7 @@
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "kde_stage.hpp"
+#include "lu_stage.hpp"
 #include "mvn_stage.hpp"
 #include "pca_apply_stage.hpp"
 #include "polyfit_stage.hpp"
@@ -30,6 +31,7 @@ struct corrla_ctx {
   kde_stage::Ran kde;              // how the last corrla_kde_eval_* / corrla_kde_nll_* call ran
   dirichlet_stage::Ran dirichlet;  // how the last corrla_dirichlet_draws_* / corrla_dirichlet_sample_* call ran
   mvn_stage::Ran mvn;              // how the last corrla_mvn_sample_* call ran
+  lu_stage::Ran lu;                // how the last corrla_lu_solve_* / corrla_rbffit_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -501,6 +503,61 @@ CORRLA_API corrla_status corrla_ctx_last_mvn(corrla_ctx* ctx, int* route_out) {
     corrla_ctx* c = need(ctx);
     std::lock_guard<std::mutex> lk(c->mu);
     if (route_out) *route_out = c->mvn.route;
+  });
+}
+
+// ---- dense LU solve (P A = L U, partial pivoting) and the RBF fit on it ---------------------------------------------------------
+CORRLA_API corrla_status corrla_lu_solve_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, const double* b, int64_t n_rhs,
+                                             int64_t ldb, double* x, int64_t ldx) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const LuSolveCall c{a, n, lda, b, n_rhs, ldb, x, ldx, nullptr, nullptr, nullptr};
+    lu_solve_entry<HipDev>(cx.dev, true, c, [&] {
+      cx.lu = lu_stage::Ran();
+      lu_stage::run_solve(cx.dev, true, c, &cx.lu);
+    });
+  });
+}
+CORRLA_API corrla_status corrla_lu_solve_dev_f64(corrla_ctx* ctx, double* a, int64_t n, int64_t lda, double* b, int64_t n_rhs, int64_t ldb,
+                                                 int64_t* ipiv) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const LuSolveCall c{a, n, lda, b, n_rhs, ldb, nullptr, 0, a, b, ipiv};
+    lu_solve_entry<HipDev>(cx.dev, false, c, [&] {
+      cx.lu = lu_stage::Ran();
+      lu_stage::run_solve(cx.dev, false, c, &cx.lu);
+    });
+  });
+}
+#define CORRLA_DEFINE_RBF_FIT(DEV, HOST)                                                                                \
+  CORRLA_API corrla_status corrla_rbffit_system_##DEV##f64(corrla_ctx* ctx, const double* xs, int64_t n_s, int64_t ldxs, int64_t dim, \
+                                                        int kernel, double eps, int poly_degree, double* m, int64_t ldm) { \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const RbfFitCall c{xs, n_s, ldxs, dim, nullptr, 0, 0, kernel, eps, poly_degree, nullptr, 0, m, ldm};              \
+      rbf_fit_entry<HipDev>(cx.dev, c, false, [&] { lu_stage::run_rbf_system(cx.dev, HOST, c); });                      \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  CORRLA_API corrla_status corrla_rbffit_##DEV##f64(corrla_ctx* ctx, const double* xs, int64_t n_s, int64_t ldxs, int64_t dim, \
+                                                     const double* y, int64_t n_rhs, int64_t ldy, int kernel, double eps, \
+                                                     int poly_degree, double* coeffs, int64_t ldw) {                    \
+    return ctx_call(ctx, [&](corrla_ctx& cx) {                                                                          \
+      const RbfFitCall c{xs, n_s, ldxs, dim, y, n_rhs, ldy, kernel, eps, poly_degree, coeffs, ldw, nullptr, 0};         \
+      rbf_fit_entry<HipDev>(cx.dev, c, true, [&] {                                                                      \
+        cx.lu = lu_stage::Ran();                                                                                        \
+        lu_stage::run_rbf_fit(cx.dev, HOST, c, &cx.lu);                                                                 \
+      });                                                                                                               \
+    });                                                                                                                 \
+  }
+CORRLA_DEFINE_RBF_FIT(, true)
+CORRLA_DEFINE_RBF_FIT(dev_, false)
+// route: 1 small, 2 blocked, 0 before the first call; info, min_pivot, max_u: the status record of that call.  A call rejected
+// for its arguments leaves them as they were; one that ended with CORRLA_ENUMERIC has set them.
+CORRLA_API corrla_status corrla_ctx_last_solve(corrla_ctx* ctx, int* route, int64_t* info, double* min_pivot, double* max_u) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (route) *route = c->lu.route;
+    if (info) *info = c->lu.info;
+    if (min_pivot) *min_pivot = c->lu.min_pivot;
+    if (max_u) *max_u = c->lu.max_u;
   });
 }
 

@@ -145,6 +145,12 @@ template <class D, class = void>
 struct dev_has_mvn : std::false_type {};
 template <class D>
 struct dev_has_mvn<D, std::void_t<decltype(D::kHasMvn)>> : std::true_type {};
+// ... and those that carry the LU kernels of corrla_lu_solve_* / corrla_rbffit_system_* / corrla_rbffit_* (lu_kernels.hpp)
+// with kHasLu.
+template <class D, class = void>
+struct dev_has_lu : std::false_type {};
+template <class D>
+struct dev_has_lu<D, std::void_t<decltype(D::kHasLu)>> : std::true_type {};
 
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).

@@ -134,6 +134,9 @@ namespace mvn_stage {
 template <class T>
 void set_lds_limits();  // mvn_stage.hpp: the multivariate normal and sandwich kernels
 }
+namespace lu_stage {
+inline void set_lds_limits();  // lu_stage.hpp: the LU kernels
+}
 
 class HipDev {
  public:
@@ -373,6 +376,10 @@ class HipDev {
   // HostIo (host_io.hpp): `rows` rows of `width` bytes, pitches in bytes; both enqueue only (HostIo::finish ends the call)
   void h2d_2d_enqueue(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
     CORRLA_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyHostToDevice, stream));
+  }
+  // lu_staging.hpp: B into the image of X
+  void d2d_2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    CORRLA_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToDevice, stream));
   }
   void d2h_2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
     if (rows == 1)  // HostIo decides what is one row; a matrix whose rows touch measured slower as one large copy
@@ -834,6 +841,8 @@ class HipDev {
   static constexpr bool kHasDirichlet = true;  // driver.hpp: dev_has_dirichlet
   // ---- multivariate normal rows and sandwich variances: mvn_plan.hpp plans, mvn_stage.hpp launches mvn_kernels.hpp ----------
   static constexpr bool kHasMvn = true;  // driver.hpp: dev_has_mvn
+  // ---- dense LU solve and the RBF fit on it: lu_plan.hpp plans, lu_stage.hpp launches lu_kernels.hpp --------------------------
+  static constexpr bool kHasLu = true;  // driver.hpp: dev_has_lu
   const PolyKnobs& poly_knobs() const { return poly_knobs_; }
   // The plan's pair table on the device.  It depends on (k, r, degree) alone, so it is uploaded when those change and kept
   // between calls: a repeated fit enqueues without a synchronising copy.
@@ -1029,6 +1038,7 @@ class HipDev {
     core_svd_stage::set_lds_limits<float>();
     core_svd_stage::set_lds_limits<double>();
     tall_stage::set_lds_limits();
+    lu_stage::set_lds_limits();
     // nearest neighbours and local fits of the gradient stage (grad_stage.hpp)
     lds_limit((const void*)k::knn_kernel, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);

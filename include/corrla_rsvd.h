@@ -655,6 +655,47 @@ CORRLA_API corrla_status corrla_kde_nll_dev_f64(corrla_ctx* ctx, const double* x
                                                 int64_t incs, const double* h, int64_t n_h, double* nll, double* dnll);
 CORRLA_API corrla_status corrla_ctx_last_kde(corrla_ctx* ctx, int* route_out);
 
+/* ---- dense linear solve: LU with partial pivoting; the RBF fit on it -----------------------------------
+ * Replaces  the solve of RbfInterp::fit (opt-in: the reference takes mat_pinv)   src/lib_math_utils/interp_utils.rs:96-143
+ * P A = L U with LAPACK getrf semantics: unit lower L and upper U stored over A, ipiv[j] (0-based, >= j) the row exchanged with
+ * row j at step j.  f64 only.
+ * STORAGE ORDER: every matrix here is ROW-major -- a is n x n with row stride lda >= n, b and x are n x n_rhs with row strides
+ * ldb, ldx >= n_rhs, ipiv is n int64.  (The RBF system is symmetric: row-major and column-major hold the same matrix.)
+ * Pivot rule: the entry of largest magnitude on or below the diagonal, ties to the lowest row index; the comparisons are
+ * exact and the multipliers are quotients, so |l_ij| <= 1 holds exactly.  No atomics: a fixed input gives bitwise fixed
+ * output.  Routes (corrla_ctx_last_solve): 1 small, n <= 128, one workgroup factors the matrix in LDS; 2 blocked, right-looking
+ * with panels of 64 columns, the trailing update on v_mfma_f64_16x16x4_f64.  Then the interchanges are applied to B and L and U
+ * are substituted block row by block row, for any n_rhs.
+ *   corrla_lu_solve_f64    : host pointers; a and b are left untouched, x = A^-1 b is written (its padding columns are not).
+ *   corrla_lu_solve_dev_f64: device pointers, in place: a becomes LU, b becomes X, ipiv (NULL: not wanted) the interchanges.
+ *   corrla_rbffit_system_*    : m = [[K, P], [P^T, 0]], N x N with N = n_s + n_poly, row stride ldm >= N: K = Phi(xs, xs) exactly
+ *                            as corrla_rbf_matrix_* forms it, P the polynomial tail of corrla_rbf_apply_* (poly_degree < 0: none,
+ *                            0 or 1: [x, 1], >= 2: [x, x_a x_b (a <= b), 1]; one rounding per product), the corner exactly zero.
+ *   corrla_rbffit_*       : coeffs (N x n_rhs, row stride ldw >= n_rhs) = M^-1 [y; 0] with M as above, built in workspace:
+ *                            the layout corrla_rbf_apply_* reads.  y is n_s x n_rhs with row stride ldy.  Bitwise what
+ *                            corrla_rbffit_system_* followed by corrla_lu_solve_* gives.
+ * An exactly zero or non-finite pivot ends the call with CORRLA_ENUMERIC; the message carries the 1-based column, and the
+ * outputs then hold a partial factorisation (device entries) or are not written (host entries).  The one read-back of a solve
+ * or fit carries info (0 or that column), the smallest |pivot| and the largest |u_ij|: corrla_ctx_last_solve returns them
+ * (any pointer may be NULL).  So the *_dev solve and fit entries synchronise once; corrla_rbffit_system_dev_f64 only enqueues.
+ * Limits: 1 <= n (N) <= 131072; 1 <= n_rhs <= 1048576; dim, kernel and eps as for corrla_rbf_matrix_*.
+ * CORRLA_EINVAL (the message names the argument): a NULL array, n or n_rhs outside the limits, lda < n, ldb / ldx / ldy / ldw
+ * < n_rhs, ldxs < dim, ldm < N, an output overlapping an input or another output. */
+CORRLA_API corrla_status corrla_lu_solve_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, const double* b, int64_t n_rhs,
+                                             int64_t ldb, double* x, int64_t ldx);
+CORRLA_API corrla_status corrla_lu_solve_dev_f64(corrla_ctx* ctx, double* a, int64_t n, int64_t lda, double* b, int64_t n_rhs, int64_t ldb,
+                                                 int64_t* ipiv);
+CORRLA_API corrla_status corrla_rbffit_system_f64(corrla_ctx* ctx, const double* xs, int64_t n_s, int64_t ldxs, int64_t dim, int kernel,
+                                               double eps, int poly_degree, double* m, int64_t ldm);
+CORRLA_API corrla_status corrla_rbffit_system_dev_f64(corrla_ctx* ctx, const double* xs, int64_t n_s, int64_t ldxs, int64_t dim, int kernel,
+                                                   double eps, int poly_degree, double* m, int64_t ldm);
+CORRLA_API corrla_status corrla_rbffit_f64(corrla_ctx* ctx, const double* xs, int64_t n_s, int64_t ldxs, int64_t dim, const double* y,
+                                            int64_t n_rhs, int64_t ldy, int kernel, double eps, int poly_degree, double* coeffs, int64_t ldw);
+CORRLA_API corrla_status corrla_rbffit_dev_f64(corrla_ctx* ctx, const double* xs, int64_t n_s, int64_t ldxs, int64_t dim, const double* y,
+                                                int64_t n_rhs, int64_t ldy, int kernel, double eps, int poly_degree, double* coeffs,
+                                                int64_t ldw);
+CORRLA_API corrla_status corrla_ctx_last_solve(corrla_ctx* ctx, int* route, int64_t* info, double* min_pivot, double* max_u);
+
 /* ---- constrained Dirichlet sampling: draws on the simplex, rejection against a box ---------------------
  * Replaces  dirichlet_shot_sample / constr_dirichlet_sample       src/lib_math_utils/space_samplers.rs:14-126
  * THE STREAM.  Draw t (0 <= t < 2^62) of (seed, alphas[0..d), c_scale) is the row x[0..d), all in IEEE double:

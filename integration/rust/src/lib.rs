@@ -230,6 +230,22 @@ extern "C" {
     pub fn corrla_sandwich_diag_dev_f64(ctx: *mut c_void, jac: *const f64, m: i64, d: i64, ldj: i64, cov: *const f64, ldc: i64, v: *mut f64) -> c_int;
     pub fn corrla_sandwich_diag_dev_f32(ctx: *mut c_void, jac: *const f32, m: i64, d: i64, ldj: i64, cov: *const f32, ldc: i64, v: *mut f32) -> c_int;
     pub fn corrla_ctx_last_mvn(ctx: *mut c_void, route_out: *mut c_int) -> c_int;
+    // dense LU solve, partial pivoting, every matrix ROW-major: x = a^-1 b (host pointers, a and b untouched) / in place on the
+    // device (a becomes LU, b becomes X, ipiv nullable)
+    pub fn corrla_lu_solve_f64(ctx: *mut c_void, a: *const f64, n: i64, lda: i64, b: *const f64, n_rhs: i64, ldb: i64, x: *mut f64,
+                               ldx: i64) -> c_int;
+    pub fn corrla_lu_solve_dev_f64(ctx: *mut c_void, a: *mut f64, n: i64, lda: i64, b: *mut f64, n_rhs: i64, ldb: i64,
+                                   ipiv: *mut i64) -> c_int;
+    // the RBF block system [[K, P], [P^T, 0]] (N x N, N = n_s + n_poly) and the fit coeffs = M^-1 [y; 0] in rbf_apply's layout
+    pub fn corrla_rbffit_system_f64(ctx: *mut c_void, xs: *const f64, n_s: i64, ldxs: i64, dim: i64, kernel: c_int, eps: f64,
+                                 poly_degree: c_int, m: *mut f64, ldm: i64) -> c_int;
+    pub fn corrla_rbffit_system_dev_f64(ctx: *mut c_void, xs: *const f64, n_s: i64, ldxs: i64, dim: i64, kernel: c_int, eps: f64,
+                                     poly_degree: c_int, m: *mut f64, ldm: i64) -> c_int;
+    pub fn corrla_rbffit_f64(ctx: *mut c_void, xs: *const f64, n_s: i64, ldxs: i64, dim: i64, y: *const f64, n_rhs: i64, ldy: i64,
+                              kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *mut f64, ldw: i64) -> c_int;
+    pub fn corrla_rbffit_dev_f64(ctx: *mut c_void, xs: *const f64, n_s: i64, ldxs: i64, dim: i64, y: *const f64, n_rhs: i64, ldy: i64,
+                                  kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *mut f64, ldw: i64) -> c_int;
+    pub fn corrla_ctx_last_solve(ctx: *mut c_void, route: *mut c_int, info: *mut i64, min_pivot: *mut f64, max_u: *mut f64) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
