@@ -15,7 +15,9 @@ sandwich_prop (stats_corr.rs:46-68) are additive too, on the fused kernels behin
 additive too, on the fused pairwise-sum kernels behind ``Context.kde_eval`` / ``kde_nll``; the other univariate random
 variables of that module (NormalRv, BetaRv, ExponentialRv, mlefit) stay outside this build's scope.  rbf_fit is additive
 as well: the coefficients of an RBF interpolant by an LU solve on the device (``Context.rbf_fit``), where PyRbfInterp
-keeps the reference's pseudo-inverse."""
+keeps the reference's pseudo-inverse.  cholesky is additive too: the Cholesky factor of a symmetric positive definite matrix on
+the device (``Context.cholesky``; ``Context.solve(a, b, assume="pos")`` solves with it), which mvn_factor(device=True),
+sample_mv_normal(factor="device") and corrla_rs_amd.RbfInterp(solver="chol") take on request; every default is unchanged."""
 import numpy as _np
 
 from corrla_rs_amd.api import PcaRsvd, power_iter, random_svd, rpca, rsvd  # noqa: F401
@@ -26,14 +28,14 @@ from corrla_rs_amd.callers import mat_cov_centered, pearson_corr, rsquared_sens 
 from corrla_rs_amd.callers import jac_from_lin, jac_from_quad, linear_fit, quad_eval, quad_fit  # noqa: F401
 from corrla_rs_amd.callers import KdeRv, build_kde  # noqa: F401
 from corrla_rs_amd.callers import mvn_factor, sample_mv_normal, sandwich_prop  # noqa: F401
-from corrla_rs_amd.callers import rbf_fit  # noqa: F401
+from corrla_rs_amd.callers import cholesky, rbf_fit  # noqa: F401
 from corrla_rs_amd.callers import constr_dirichlet_sample as _constr_dirichlet_sample
 from corrla_rs_amd.callers import cs_mcmc_dirichlet_sample as _cs_mcmc_dirichlet_sample
 
 __all__ = ["rsvd", "rpca", "random_svd", "power_iter", "PcaRsvd", "PyDMDc", "PyPodI", "PyRbfInterp", "active_ss",
            "mat_cov_centered", "pearson_corr", "rsquared_sens", "linear_fit", "quad_fit", "quad_eval", "jac_from_lin",
            "jac_from_quad", "KdeRv", "build_kde", "cs_dirichlet_sample", "cs_mcmc_dirichlet_sample", "mvn_factor",
-           "sample_mv_normal", "sandwich_prop", "rbf_fit"]
+           "sample_mv_normal", "sandwich_prop", "rbf_fit", "cholesky"]
 
 
 def active_ss(a_mat, y, order, n_nbr, n_comps):

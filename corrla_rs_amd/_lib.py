@@ -52,6 +52,11 @@ SOLVE_ROUTES = {1: "small", 2: "blocked"}
 LU_SMALL_N = 128
 LU_NB = 64
 LU_MAX_N = 1 << 17
+# corrla_chol_factor_* / corrla_chol_solve_*: what corrla_ctx_last_chol reports, and the limits
+CHOL_ROUTES = {1: "small", 2: "blocked"}
+CHOL_SMALL_N = 128
+CHOL_NB = 64
+CHOL_MAX_N = 1 << 17
 UNIQUE_ID_BYTES = 128
 
 
@@ -99,6 +104,13 @@ def _sigs():
     s["corrla_rbffit_system_f64"] = s["corrla_rbffit_system_dev_f64"] = (C.c_int, [vp, vp, i64, i64, i64, C.c_int, dbl, C.c_int, vp, i64])
     s["corrla_rbffit_f64"] = s["corrla_rbffit_dev_f64"] = (C.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, C.c_int, dbl, C.c_int, vp, i64])
     s["corrla_ctx_last_solve"] = (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)])
+    # dense Cholesky factor and SPD solve, f64 only, row-major, lower triangle: a, n, lda, then l, ldl (host factor) / nothing
+    # (device factor, in place); a, n, lda, b, n_rhs, ldb, then x, ldx (host solve) / nothing (device solve, in place)
+    s["corrla_chol_factor_f64"] = (C.c_int, [vp, vp, i64, i64, vp, i64])
+    s["corrla_chol_factor_dev_f64"] = (C.c_int, [vp, vp, i64, i64])
+    s["corrla_chol_solve_f64"] = (C.c_int, [vp, vp, i64, i64, vp, i64, i64, vp, i64])
+    s["corrla_chol_solve_dev_f64"] = (C.c_int, [vp, vp, i64, i64, vp, i64, i64])
+    s["corrla_ctx_last_chol"] = (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)])
     for suf, sc in (("f32", flt), ("f64", dbl)):
         rsvd = [vp, vp, i64, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
         s["corrla_rsvd_" + suf] = (C.c_int, rsvd)

@@ -816,7 +816,7 @@ class Context:
             self._solve_done()
         L.check(rc)
 
-    def solve(self, a, b, *, overwrite=False):
+    def solve(self, a, b, *, overwrite=False, assume="general"):
         """x with a x = b on the device (corrla_lu_solve_*): LU with partial pivoting (P A = L U, ties to the lowest row,
         |l_ij| <= 1 exactly, no atomics: a fixed input gives bitwise fixed output), then the substitutions.  a is (n, n), b is
         (n,) or (n, n_rhs); x has the shape of b.  float64 only: anything else is converted.  numpy `a` -> numpy out (a and b
@@ -825,7 +825,15 @@ class Context:
         A pivot that is exactly zero or not finite raises RuntimeError (``CorrlaError``, code ENUMERIC) naming the 1-based
         column.  ``last_solve_route`` ("small": n <= 128, one workgroup in LDS; "blocked") and ``last_solve_info`` (info, the
         smallest |pivot|, the largest |u_ij|) describe the call.  ValueError: a not square, b with other than n rows, empty,
-        sparse or bfloat16 inputs, a tensor on another device, n above 131072."""
+        sparse or bfloat16 inputs, a tensor on another device, n above 131072.
+        assume="general" (the default) is that route.  assume="pos": a is symmetric positive definite and the solve goes
+        through its Cholesky factor (corrla_chol_solve_*): only the LOWER triangle of a is read, overwrite=True leaves L in
+        it (the strict upper triangle as it was) and x in b, a pivot that is not positive or not finite raises the same
+        ``CorrlaError`` naming the column, and ``last_chol_route`` / ``last_chol_info`` describe the call instead.  Any other
+        value of assume is a ValueError."""
+        if assume not in ("general", "pos"):
+            raise ValueError("assume must be 'general' or 'pos'")
+        pos = assume == "pos"
         overwrite = _check_bool("overwrite", overwrite, ValueError)
         am, on_dev = self._f64_matrix(a, "a", "solve")
         n = int(am.shape[0])
@@ -844,16 +852,79 @@ class Context:
             else:
                 am, bm = am.clone(), bm.clone()
             _sync_stream(am)
-            self._solve_call(self._lib.corrla_lu_solve_dev_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
-                             None)
+            if pos:
+                self._chol_call(self._lib.corrla_chol_solve_dev_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm))
+            else:
+                self._solve_call(self._lib.corrla_lu_solve_dev_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
+                                 None)
             x = bm
         else:
             if overwrite:
                 raise ValueError("overwrite=True needs CUDA tensors: the host entry leaves a and b untouched")
             x = np.empty((n, n_rhs), dtype=np.float64)
-            self._solve_call(self._lib.corrla_lu_solve_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
-                             _ptr(x), n_rhs)
+            if pos:
+                self._chol_call(self._lib.corrla_chol_solve_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
+                                _ptr(x), n_rhs)
+            else:
+                self._solve_call(self._lib.corrla_lu_solve_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
+                                 _ptr(x), n_rhs)
         return x.reshape(-1) if vec else x
+
+    # ---- dense Cholesky factor and SPD solve (corrla_chol_factor_* / corrla_chol_solve_*) ----------------------------
+    def _chol_call(self, fn, *args):
+        """one Cholesky entry; the status record is kept before a failure is raised"""
+        rc = fn(self._h, *args)
+        if rc in (L.OK, L.ENUMERIC):
+            route, info = C.c_int(0), C.c_int64(0)
+            mind, maxd, logdet = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+            L.check(self._lib.corrla_ctx_last_chol(self._h, C.byref(route), C.byref(info), C.byref(mind), C.byref(maxd), C.byref(logdet)))
+            self._chol_route = L.CHOL_ROUTES.get(route.value)
+            self._chol_info = {"info": int(info.value), "min_diag": float(mind.value), "max_diag": float(maxd.value),
+                               "logdet": float(logdet.value)}
+        L.check(rc)
+
+    def cholesky(self, a, *, overwrite=False):
+        """The Cholesky factor L of a symmetric positive definite a, a = L L^T, on the device (corrla_chol_factor_*): (n, n),
+        lower triangular with a positive diagonal, its strict upper triangle zero.  Only the LOWER triangle of a is read: what
+        lies above the diagonal is never looked at (nobody checks the symmetry).  float64 only: anything else is converted.
+        numpy in -> numpy out (a is left untouched), a CUDA tensor in -> a tensor on its device.  overwrite=True (float64
+        row-major CUDA tensors only) factors in place and returns `a` itself: L over its lower triangle, the strict upper
+        triangle as it was.  No pivoting, no atomics: a fixed input gives bitwise fixed output.  A pivot that is not positive
+        or not finite raises RuntimeError (``CorrlaError``, code ENUMERIC) naming the 1-based column.  ``last_chol_route``
+        ("small": n <= 128, one workgroup in LDS; "blocked") and ``last_chol_info`` (info, the smallest and largest l_jj,
+        logdet = log det a) describe the call.  ValueError: a not square, empty, sparse or bfloat16, a tensor on another
+        device, n above 131072."""
+        overwrite = _check_bool("overwrite", overwrite, ValueError)
+        am, on_dev = self._f64_matrix(a, "a", "cholesky")
+        n = int(am.shape[0])
+        if n == 0 or am.shape[1] != n:
+            raise ValueError(f"a must be square and non-empty, got {tuple(am.shape)}")
+        if on_dev:
+            if overwrite:
+                if not (_is_torch(a) and am.data_ptr() == a.data_ptr()):
+                    raise ValueError("overwrite=True takes a float64 row-major CUDA tensor that needs no conversion")
+            else:
+                am = am.clone()
+            _sync_stream(am)
+            self._chol_call(self._lib.corrla_chol_factor_dev_f64, _ptr(am), n, self._row_stride(am))
+            return a if overwrite else am.tril_()
+        if overwrite:
+            raise ValueError("overwrite=True needs a CUDA tensor: the host entry leaves a untouched")
+        out = np.empty((n, n), dtype=np.float64)
+        self._chol_call(self._lib.corrla_chol_factor_f64, _ptr(am), n, self._row_stride(am), _ptr(out), n)
+        return out
+
+    @property
+    def last_chol_route(self):
+        """"small" or "blocked": the route of this context's last ``cholesky`` / ``solve(assume="pos")``; None before the first."""
+        return getattr(self, "_chol_route", None)
+
+    @property
+    def last_chol_info(self):
+        """{"info": 0 or the 1-based column of the failed pivot, "min_diag", "max_diag": smallest and largest l_jj of the
+        columns factored, "logdet": log det a (0.0 when info != 0)} of this context's last ``cholesky`` /
+        ``solve(assume="pos")``; None before the first."""
+        return getattr(self, "_chol_info", None)
 
     @property
     def last_solve_route(self):

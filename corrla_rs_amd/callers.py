@@ -40,7 +40,7 @@ __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyG
            "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply",
            "linear_fit", "quad_fit", "quad_eval", "jac_from_lin", "jac_from_quad", "polyfit_solve", "KdeRv", "build_kde",
            "constr_dirichlet_sample", "DeMcSampler", "cs_mcmc_dirichlet_sample", "mvn_factor", "sample_mv_normal",
-           "sandwich_prop"]
+           "sandwich_prop", "cholesky"]
 
 
 def _on_gpu(x):
@@ -472,6 +472,12 @@ def rbf_fit(x, y, kernel_type, kernel_param=0.0, *, poly_degree=None, ctx=None):
     return (ctx or default_context()).rbf_fit(x, y, kernel_type, kernel_param, poly_degree=poly_degree)
 
 
+def cholesky(a, *, overwrite=False, ctx=None):
+    """The Cholesky factor L of a symmetric positive definite matrix, a = L L^T, on the device: ``Context.cholesky`` (only the
+    lower triangle of `a` is read).  ``Context.solve(a, b, assume="pos")`` solves with it."""
+    return (ctx or default_context()).cholesky(a, overwrite=overwrite)
+
+
 class RbfInterp:
     """Radial-basis-function interpolant with a polynomial tail (interp_utils.rs:11-160; pyo3 ``PyRbfInterp(kernel_type,
     kernel_param, dim, poly_degree)``: 1 linear r, 2 multiquadric sqrt(1 + (eps r)^2), 3 cubic r^3, otherwise Gaussian
@@ -494,14 +500,26 @@ class RbfInterp:
     naming the column where the pseudo-inverse would return a minimum-norm answer; what is detected is an exactly zero or
     non-finite pivot -- a nearly singular system completes, and ``Context.last_solve_info["min_pivot"]`` is the witness.
     Measured on one MI355X (dim 3, cubic kernel, linear tail, 8 right-hand sides): "lu" 33 ms / 168 ms / 543 ms at 2048 /
-    8192 / 16384 supports against 0.81 s / 25 s for "pinv" at the first two -- faster at every size from 2048 up."""
+    8192 / 16384 supports against 0.81 s / 25 s for "pinv" at the first two -- faster at every size from 2048 up.
+
+    solver="chol" is opt-in too and is accepted only where the kernel matrix is positive definite and nothing else enters the
+    system: the Gaussian kernel with poly_degree=None (no polynomial tail); anything else is a ValueError at construction.
+    ``fit`` is ``Context.rbf_system`` followed by ``Context.solve(..., assume="pos", overwrite=True)`` on the device: a
+    Cholesky factorisation of the lower triangle, half the work of "lu" and no pivot search.  A kernel matrix that is
+    numerically not positive definite (supports too close together for the kernel parameter) raises the ``CorrlaError``
+    naming the column of the failed pivot: "lu" and "pinv" remain for that case."""
 
     def __init__(self, kernel_type, kernel_param, dim, poly_degree, *, device=False, ctx=None, solver="pinv"):
-        self.kernel_type, self.eps, self.dim, self.poly_degree = int(kernel_type), float(kernel_param), int(dim), int(poly_degree)
+        if solver not in ("pinv", "lu", "chol"):
+            raise ValueError("solver must be 'pinv', 'lu' or 'chol'")
+        if solver == "chol":
+            if int(kernel_type) in (1, 2, 3) or poly_degree is not None:
+                raise ValueError("solver='chol' takes a positive-definite system: the Gaussian kernel with poly_degree=None")
+        else:
+            poly_degree = int(poly_degree)
+        self.kernel_type, self.eps, self.dim, self.poly_degree = int(kernel_type), float(kernel_param), int(dim), poly_degree
         self.x_known = self.coeffs = None
         self.device, self._ctx = bool(device), ctx
-        if solver not in ("pinv", "lu"):
-            raise ValueError("solver must be 'pinv' or 'lu'")
         self.solver = solver
 
     def _phi(self, r):
@@ -525,6 +543,8 @@ class RbfInterp:
     def fit(self, x_in, y_in):
         if self.solver == "lu":
             return self._fit_lu(x_in, y_in)
+        if self.solver == "chol":
+            return self._fit_chol(x_in, y_in)
         if self.device or _on_gpu(x_in) or _on_gpu(y_in):
             return self._fit_device(x_in, y_in)
         x = np.asarray(x_in, np.float64)
@@ -567,8 +587,24 @@ class RbfInterp:
         coeffs = self._context().rbf_fit(x, y.reshape(x.shape[0], -1), self.kernel_type, self.eps, poly_degree=self.poly_degree)
         self.x_known, self.coeffs = (x.clone() if on_gpu else x.copy()), coeffs
 
+    def _fit_chol(self, x_in, y_in):
+        """Context.rbf_system, then the Cholesky solve in place, in float64 on the device; the model stays where the supports
+        were given"""
+        import torch
+        ctx = self._context()
+        on_gpu = _on_gpu(x_in)
+        x = x_in.detach().double() if on_gpu else np.asarray(x_in.detach().cpu().numpy() if _is_torch(x_in) else x_in, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError("x_in must have `dim` columns")
+        xd = x if on_gpu else torch.tensor(x, device=f"cuda:{ctx.device}")  # (copies: the arrays may be read-only)
+        y = y_in.detach() if _is_torch(y_in) else torch.tensor(np.asarray(y_in, np.float64))
+        yd = y.to(device=xd.device, dtype=torch.float64).reshape(x.shape[0], -1).contiguous().clone()
+        m = ctx.rbf_system(xd, self.kernel_type, self.eps, poly_degree=None)
+        coeffs = ctx.solve(m, yd, assume="pos", overwrite=True)
+        self.x_known, self.coeffs = (x.clone(), coeffs) if on_gpu else (x.copy(), coeffs.cpu().numpy())
+
     def predict(self, x_query):
-        if self.device or self.solver == "lu" or _on_gpu(x_query) or _on_gpu(self.x_known):
+        if self.device or self.solver in ("lu", "chol") or _on_gpu(x_query) or _on_gpu(self.x_known):
             return self._predict_device(x_query)
         xq = np.asarray(x_query, np.float64)
         if xq.shape[1] != self.dim:
@@ -1011,14 +1047,62 @@ def cs_mcmc_dirichlet_sample(bounds, n_samples, n_seed_samples, max_zshots, chun
 
 
 # ---- multivariate normal samples and sandwich variances (stats_corr.rs:46-68) ----------------------------------------------
-def mvn_factor(cov):
+def _mvn_eig_factor(c, d, big):
+    """step 3 of ``mvn_factor`` on the host: c is the symmetrised (d, d) numpy matrix, big its largest magnitude"""
+    w, v = np.linalg.eigh(c)
+    cut = d * 2.0 ** -52 * max(float(w[-1]), 0.0)
+    if float(w[0]) < -cut or float(w[-1]) <= 0.0 and big > 0.0:
+        raise ValueError(f"cov is not positive semi-definite: smallest eigenvalue {float(w[0]):.3e}")
+    keep = w > cut
+    if not np.any(keep):  # the zero matrix: one column of zeros, so that r >= 1
+        return np.zeros((d, 1)), False
+    return v[:, keep] * np.sqrt(w[keep])[None, :], False
+
+
+def _mvn_factor_device(cov, ctx):
+    """``mvn_factor`` with steps 1 and 2 on the device; -> (F tensor, lower)"""
+    import torch
+    from ._lib import ENUMERIC, CorrlaError
+    ctx = ctx or default_context()
+    if _on_gpu(cov):
+        c = cov.detach().to(torch.float64)
+    else:
+        c = torch.tensor(np.asarray(cov.detach().numpy() if _is_torch(cov) else cov, dtype=np.float64), device=f"cuda:{ctx.device}")
+    if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] == 0:
+        raise ValueError(f"cov must be a non-empty square matrix, got shape {tuple(c.shape)}")
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError("cov must be finite")
+    d = int(c.shape[0])
+    big = float(c.abs().max())
+    if float((c - c.T).abs().max()) > 8.0 * 2.0 ** -52 * big:
+        raise ValueError("cov is not symmetric")
+    c = 0.5 * (c + c.T)
+    sd = torch.sqrt(torch.diagonal(c).clamp(min=0.0))
+    sd = torch.where(sd > 0.0, sd, torch.ones_like(sd))
+    try:
+        lo = ctx.cholesky(c / torch.outer(sd, sd), overwrite=True).tril_()  # in place: the quotient is a temporary of this call
+        return sd[:, None] * lo, True
+    except CorrlaError as e:
+        if e.code != ENUMERIC:
+            raise
+    f, lower = _mvn_eig_factor(c.cpu().numpy(), d, big)  # the one route that reads the matrix back
+    return torch.as_tensor(f, device=c.device), lower
+
+
+def mvn_factor(cov, *, device=False, ctx=None):
     """A factor F of a covariance matrix, F F^T = cov -> (F, lower), on the host in float64 (d-sized work).
       1. cov must be square and symmetric to 8 * 2^-52 * max|cov|, else ValueError;
       2. the Cholesky factor of the diagonally equilibrated matrix D^-1/2 cov D^-1/2 is tried: (D^1/2 L, True);
       3. otherwise the symmetric eigendecomposition: an eigenvalue below -d 2^-52 lambda_max is a ValueError (the matrix is
          indefinite); directions with lambda <= d 2^-52 lambda_max are dropped -- the rule of ``polyfit_solve`` -- and the rest
          gives (V sqrt(Lambda), False) with r < d columns.
-    So a singular covariance (fewer samples than features, or the output of ``sandwich_prop``) can be sampled from."""
+    So a singular covariance (fewer samples than features, or the output of ``sandwich_prop``) can be sampled from.
+    device=True: steps 1 and 2 -- the symmetry check, the equilibration, the Cholesky factorisation (``Context.cholesky`` of
+    `ctx` or the default context) and the rescaling -- run on the device in float64 and F is a CUDA tensor; a CUDA `cov`
+    never visits the host.  Only when the factorisation reports a pivot that is not positive does the matrix come back for
+    step 3, whose F is uploaded again.  The device factor agrees with the host's within rounding, not bit for bit."""
+    if device:
+        return _mvn_factor_device(cov, ctx)
     c = np.asarray(cov.detach().cpu().numpy() if _is_torch(cov) else cov, dtype=np.float64)
     if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] == 0:
         raise ValueError(f"cov must be a non-empty square matrix, got shape {tuple(c.shape)}")
@@ -1045,12 +1129,22 @@ def mvn_factor(cov):
     return v[:, keep] * np.sqrt(w[keep])[None, :], False
 
 
-def sample_mv_normal(cov, n, *, mean=None, seed=None, device=False, ctx=None):
+def sample_mv_normal(cov, n, *, mean=None, seed=None, device=False, ctx=None, factor="host"):
     """``sample_mv_normal(cov, n)`` (stats_corr.rs:46-58): n rows of N(mean, cov), (n, d) float64.  The covariance is factored
     on the host (``mvn_factor``), the rows come from ``Context.mvn_sample``.  numpy in -> numpy out; a CUDA cov or device=True
     gives a tensor.  seed=None takes a fresh one from ``numpy.random.SeedSequence``.
     The one deliberate difference from the reference: it multiplies z by cov itself, so its samples have covariance cov^2;
-    these have covariance cov.  ``Context.mvn_sample(n, cov)`` (factor = cov) reproduces the reference's law."""
+    these have covariance cov.  ``Context.mvn_sample(n, cov)`` (factor = cov) reproduces the reference's law.
+    factor="device" factors the covariance on the device instead (``mvn_factor(cov, device=True)``): nothing d x d is computed
+    on the host; the rows are ``Context.mvn_sample(n, F, lower=True)`` of that F, in the kind the default returns."""
+    if factor not in ("host", "device"):
+        raise ValueError("factor must be 'host' or 'device'")
+    if factor == "device":
+        c = ctx or default_context()
+        f, lower = mvn_factor(cov, device=True, ctx=c)
+        mu = None if mean is None else np.asarray(mean.detach().cpu().numpy() if _is_torch(mean) else mean, dtype=np.float64).reshape(-1)
+        out = c.mvn_sample(n, f, mu, seed=_fresh_seed() if seed is None else seed, lower=lower, device=True)
+        return out if bool(device) or _on_gpu(cov) else out.cpu().numpy()
     f, lower = mvn_factor(cov)
     mu = None if mean is None else np.asarray(mean.detach().cpu().numpy() if _is_torch(mean) else mean, dtype=np.float64).reshape(-1)
     return (ctx or default_context()).mvn_sample(n, f, mu, seed=_fresh_seed() if seed is None else seed, lower=lower,

@@ -16,6 +16,7 @@
 #include "kde_plan.hpp"  // kKdeMaxH
 #include "dirichlet_plan.hpp"  // dir_plan: the limits of the Dirichlet entries
 #include "mvn_plan.hpp"  // mvn_plan, sandwich_plan: the limits of the multivariate normal entries
+#include "chol_plan.hpp"  // chol_plan: the limits of the Cholesky entries
 #include "lu_plan.hpp"  // lu_plan: the limits of the dense-solve entries
 
 namespace corrla {
@@ -1181,6 +1182,68 @@ inline void rbf_fit_entry(Dev&, const RbfFitCall& c, bool fit, Run&& run) {
     no_overlap(who, in, 1, out, 1);
   }
   on_backend_with<dev_has_lu<Dev>>(run, "LU kernels", fit ? "corrla_rbffit_*" : "corrla_rbffit_system_*");
+}
+
+// ---- dense Cholesky factor and SPD solve (corrla_chol_factor_* / corrla_chol_solve_*) -------------------------------------------
+// Argument checks of every entry -- the limits of n and n_rhs are the plan's (chol_plan names the argument it rejects) -- then
+// `run`, on a backend that carries the kernels (dev_has_chol).  f64 only.  A solve takes the call record of the LU solve
+// (LuSolveCall, without an ipiv): the same arrays with the same roles, so the same spans and the same staging.
+struct CholFactorCall {
+  // host entry: a is read, l is written.  Device entry: a_rw's lower triangle becomes L.
+  const double* a;
+  int64_t n, lda;
+  double* l;
+  int64_t ldl;
+  double* a_rw;
+  Span a_span() const { return Span(a, n, n, lda, "a"); }
+  Span l_span() const { return Span(l, n, n, ldl, "l"); }
+};
+
+inline void chol_limits(int64_t n, int64_t n_rhs) {
+  CholShape s;
+  s.n = n, s.n_rhs = n_rhs;
+  const CholPlan p = chol_plan(s);
+  if (!p.ok) throw Error(ST_EINVAL, p.error);
+}
+
+template <class Dev, class Run>
+inline void chol_factor_entry(Dev&, bool host_ptrs, const CholFactorCall& c, Run&& run) {
+  const char* who = "chol_factor";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.a) bad("a is NULL");
+  if (host_ptrs && !c.l) bad("l is NULL");
+  chol_limits(c.n, 0);
+  if (c.lda < c.n) bad("lda < n");
+  if (host_ptrs && c.ldl < c.n) bad("ldl < n");
+  if (host_ptrs) {
+    const Span in[1] = {c.a_span()};
+    const Span out[1] = {c.l_span()};
+    no_overlap(who, in, 1, out, 1);
+  }
+  on_backend_with<dev_has_chol<Dev>>(run, "Cholesky kernels", "corrla_chol_factor_*");
+}
+
+template <class Dev, class Run>
+inline void chol_solve_entry(Dev&, bool host_ptrs, const LuSolveCall& c, Run&& run) {
+  const char* who = "chol_solve";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.a) bad("a is NULL");
+  if (!c.b) bad("b is NULL");
+  if (host_ptrs && !c.x) bad("x is NULL");
+  if (c.n_rhs < 1) bad("n_rhs must be >= 1");
+  chol_limits(c.n, c.n_rhs);
+  if (c.lda < c.n) bad("lda < n");
+  if (c.ldb < c.n_rhs) bad("ldb < n_rhs");
+  if (host_ptrs && c.ldx < c.n_rhs) bad("ldx < n_rhs");
+  if (host_ptrs) {
+    const Span in[2] = {c.a_span(), c.b_span()};
+    const Span out[1] = {c.x_span()};
+    no_overlap(who, in, 2, out, 1);
+  } else {  // both are written
+    const Span out[2] = {c.a_span(), c.b_span()};
+    no_overlap(who, nullptr, 0, out, 2);
+  }
+  on_backend_with<dev_has_chol<Dev>>(run, "Cholesky kernels", "corrla_chol_solve_*");
 }
 
 // ---- constrained Dirichlet sampling (corrla_dirichlet_draws_* / corrla_dirichlet_sample_*, space_samplers.rs:14-126) ---------

@@ -11,6 +11,7 @@
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "kde_stage.hpp"
+#include "chol_stage.hpp"
 #include "lu_stage.hpp"
 #include "mvn_stage.hpp"
 #include "pca_apply_stage.hpp"
@@ -32,6 +33,7 @@ struct corrla_ctx {
   dirichlet_stage::Ran dirichlet;  // how the last corrla_dirichlet_draws_* / corrla_dirichlet_sample_* call ran
   mvn_stage::Ran mvn;              // how the last corrla_mvn_sample_* call ran
   lu_stage::Ran lu;                // how the last corrla_lu_solve_* / corrla_rbffit_* call ran
+  chol_stage::Ran chol;            // how the last corrla_chol_factor_* / corrla_chol_solve_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -558,6 +560,58 @@ CORRLA_API corrla_status corrla_ctx_last_solve(corrla_ctx* ctx, int* route, int6
     if (info) *info = c->lu.info;
     if (min_pivot) *min_pivot = c->lu.min_pivot;
     if (max_u) *max_u = c->lu.max_u;
+  });
+}
+
+// ---- dense Cholesky factor and SPD solve (A = L L^T over the lower triangle) ----------------------------------------------------
+CORRLA_API corrla_status corrla_chol_factor_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, double* l, int64_t ldl) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const CholFactorCall c{a, n, lda, l, ldl, nullptr};
+    chol_factor_entry<HipDev>(cx.dev, true, c, [&] {
+      cx.chol = chol_stage::Ran();
+      chol_stage::run_factor(cx.dev, true, c, &cx.chol);
+    });
+  });
+}
+CORRLA_API corrla_status corrla_chol_factor_dev_f64(corrla_ctx* ctx, double* a, int64_t n, int64_t lda) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const CholFactorCall c{a, n, lda, nullptr, 0, a};
+    chol_factor_entry<HipDev>(cx.dev, false, c, [&] {
+      cx.chol = chol_stage::Ran();
+      chol_stage::run_factor(cx.dev, false, c, &cx.chol);
+    });
+  });
+}
+CORRLA_API corrla_status corrla_chol_solve_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, const double* b, int64_t n_rhs,
+                                               int64_t ldb, double* x, int64_t ldx) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const LuSolveCall c{a, n, lda, b, n_rhs, ldb, x, ldx, nullptr, nullptr, nullptr};
+    chol_solve_entry<HipDev>(cx.dev, true, c, [&] {
+      cx.chol = chol_stage::Ran();
+      chol_stage::run_solve(cx.dev, true, c, &cx.chol);
+    });
+  });
+}
+CORRLA_API corrla_status corrla_chol_solve_dev_f64(corrla_ctx* ctx, double* a, int64_t n, int64_t lda, double* b, int64_t n_rhs, int64_t ldb) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const LuSolveCall c{a, n, lda, b, n_rhs, ldb, nullptr, 0, a, b, nullptr};
+    chol_solve_entry<HipDev>(cx.dev, false, c, [&] {
+      cx.chol = chol_stage::Ran();
+      chol_stage::run_solve(cx.dev, false, c, &cx.chol);
+    });
+  });
+}
+// route: 1 small, 2 blocked, 0 before the first call; info, min_diag, max_diag, logdet: the status record of that call.  A call
+// rejected for its arguments leaves them as they were; one that ended with CORRLA_ENUMERIC has set them.
+CORRLA_API corrla_status corrla_ctx_last_chol(corrla_ctx* ctx, int* route, int64_t* info, double* min_diag, double* max_diag, double* logdet) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (route) *route = c->chol.route;
+    if (info) *info = c->chol.info;
+    if (min_diag) *min_diag = c->chol.min_diag;
+    if (max_diag) *max_diag = c->chol.max_diag;
+    if (logdet) *logdet = c->chol.logdet;
   });
 }
 

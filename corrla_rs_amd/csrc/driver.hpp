@@ -151,6 +151,11 @@ template <class D, class = void>
 struct dev_has_lu : std::false_type {};
 template <class D>
 struct dev_has_lu<D, std::void_t<decltype(D::kHasLu)>> : std::true_type {};
+// ... and those that carry the Cholesky kernels of corrla_chol_factor_* / corrla_chol_solve_* (chol_kernels.hpp) with kHasChol.
+template <class D, class = void>
+struct dev_has_chol : std::false_type {};
+template <class D>
+struct dev_has_chol<D, std::void_t<decltype(D::kHasChol)>> : std::true_type {};
 
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).

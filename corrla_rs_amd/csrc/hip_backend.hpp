@@ -137,6 +137,9 @@ void set_lds_limits();  // mvn_stage.hpp: the multivariate normal and sandwich k
 namespace lu_stage {
 inline void set_lds_limits();  // lu_stage.hpp: the LU kernels
 }
+namespace chol_stage {
+inline void set_lds_limits();  // chol_stage.hpp: the Cholesky kernels
+}
 
 class HipDev {
  public:
@@ -843,6 +846,8 @@ class HipDev {
   static constexpr bool kHasMvn = true;  // driver.hpp: dev_has_mvn
   // ---- dense LU solve and the RBF fit on it: lu_plan.hpp plans, lu_stage.hpp launches lu_kernels.hpp --------------------------
   static constexpr bool kHasLu = true;  // driver.hpp: dev_has_lu
+  // ---- dense Cholesky factor and SPD solve: chol_plan.hpp plans, chol_stage.hpp launches chol_kernels.hpp ---------------------
+  static constexpr bool kHasChol = true;  // driver.hpp: dev_has_chol
   const PolyKnobs& poly_knobs() const { return poly_knobs_; }
   // The plan's pair table on the device.  It depends on (k, r, degree) alone, so it is uploaded when those change and kept
   // between calls: a repeated fit enqueues without a synchronising copy.
@@ -1039,6 +1044,7 @@ class HipDev {
     core_svd_stage::set_lds_limits<double>();
     tall_stage::set_lds_limits();
     lu_stage::set_lds_limits();
+    chol_stage::set_lds_limits();
     // nearest neighbours and local fits of the gradient stage (grad_stage.hpp)
     lds_limit((const void*)k::knn_kernel, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);

@@ -696,6 +696,37 @@ CORRLA_API corrla_status corrla_rbffit_dev_f64(corrla_ctx* ctx, const double* xs
                                                 int64_t ldw);
 CORRLA_API corrla_status corrla_ctx_last_solve(corrla_ctx* ctx, int* route, int64_t* info, double* min_pivot, double* max_u);
 
+/* ---- dense Cholesky factor and symmetric positive definite solve ------------------------------------------
+ * Replaces  the host Cholesky of the covariance factor (numpy) and, opt-in, the solve of a positive definite RBF system
+ * A = L L^T, L lower triangular with a positive diagonal.  f64 only.
+ * STORAGE ORDER: every matrix here is ROW-major -- a and l are n x n with row strides lda, ldl >= n, b and x are n x n_rhs with
+ * row strides ldb, ldx >= n_rhs.  Only the LOWER triangle of a (i >= j) is read; the in-place entries write only it: the strict
+ * upper triangle is neither read nor written and may hold anything.
+ * No pivoting and no atomics: a fixed input gives bitwise fixed output.  Square roots and quotients are correctly rounded.
+ * Routes (corrla_ctx_last_chol): 1 small, n <= 128, one workgroup factors the triangle in LDS; 2 blocked, right-looking with
+ * panels of 64 columns -- the diagonal block in LDS, L21 = A21 L11^-T, and the trailing update of the lower-triangle tiles on
+ * v_mfma_f64_16x16x4_f64: 3 launches per panel, 3 ceil(n / 64) - 1 in all.  A solve then substitutes L and L^T block row by
+ * block row, for any n_rhs.
+ *   corrla_chol_factor_f64    : host pointers; a is left untouched; the full n x n of l is written -- L on and below the
+ *                               diagonal, exact zeros above; its padding columns are not.
+ *   corrla_chol_factor_dev_f64: device pointer, in place: the lower triangle of a becomes L.
+ *   corrla_chol_solve_f64     : host pointers; a and b are left untouched, x = A^-1 b is written (its padding columns are not).
+ *   corrla_chol_solve_dev_f64 : device pointers, in place: a becomes L (lower triangle), b becomes X.
+ * A pivot a_jj - sum_k l_jk^2 that is <= 0 or not finite ends the call with CORRLA_ENUMERIC; the message carries the 1-based
+ * column of the first such pivot.  The device entries then leave a partial factor whose columns before that one are final; the
+ * host entries write nothing.  The one read-back of a call carries info (0 or that column), the smallest and the largest l_jj
+ * of the columns factored, and logdet = log det A = 2 sum_j log l_jj, summed on the device in a fixed order (0 when info != 0):
+ * corrla_ctx_last_chol returns them (any pointer may be NULL).  So the *_dev entries synchronise once.
+ * Limits: 1 <= n <= 131072; 1 <= n_rhs <= 1048576.
+ * CORRLA_EINVAL (the message names the argument): a NULL array, n or n_rhs outside the limits, lda / ldl < n, ldb / ldx < n_rhs,
+ * an output overlapping an input or another output. */
+CORRLA_API corrla_status corrla_chol_factor_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, double* l, int64_t ldl);
+CORRLA_API corrla_status corrla_chol_factor_dev_f64(corrla_ctx* ctx, double* a, int64_t n, int64_t lda);
+CORRLA_API corrla_status corrla_chol_solve_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, const double* b, int64_t n_rhs,
+                                               int64_t ldb, double* x, int64_t ldx);
+CORRLA_API corrla_status corrla_chol_solve_dev_f64(corrla_ctx* ctx, double* a, int64_t n, int64_t lda, double* b, int64_t n_rhs, int64_t ldb);
+CORRLA_API corrla_status corrla_ctx_last_chol(corrla_ctx* ctx, int* route, int64_t* info, double* min_diag, double* max_diag, double* logdet);
+
 /* ---- constrained Dirichlet sampling: draws on the simplex, rejection against a box ---------------------
  * Replaces  dirichlet_shot_sample / constr_dirichlet_sample       src/lib_math_utils/space_samplers.rs:14-126
  * THE STREAM.  Draw t (0 <= t < 2^62) of (seed, alphas[0..d), c_scale) is the row x[0..d), all in IEEE double:

@@ -246,6 +246,15 @@ extern "C" {
     pub fn corrla_rbffit_dev_f64(ctx: *mut c_void, xs: *const f64, n_s: i64, ldxs: i64, dim: i64, y: *const f64, n_rhs: i64, ldy: i64,
                                   kernel: c_int, eps: f64, poly_degree: c_int, coeffs: *mut f64, ldw: i64) -> c_int;
     pub fn corrla_ctx_last_solve(ctx: *mut c_void, route: *mut c_int, info: *mut i64, min_pivot: *mut f64, max_u: *mut f64) -> c_int;
+    // dense Cholesky A = L L^T over the LOWER triangle, every matrix ROW-major: the factor (host pointers: l gets L and zeros above;
+    // device: in place) and x = a^-1 b for a symmetric positive definite a (host pointers, a and b untouched / in place on the device)
+    pub fn corrla_chol_factor_f64(ctx: *mut c_void, a: *const f64, n: i64, lda: i64, l: *mut f64, ldl: i64) -> c_int;
+    pub fn corrla_chol_factor_dev_f64(ctx: *mut c_void, a: *mut f64, n: i64, lda: i64) -> c_int;
+    pub fn corrla_chol_solve_f64(ctx: *mut c_void, a: *const f64, n: i64, lda: i64, b: *const f64, n_rhs: i64, ldb: i64, x: *mut f64,
+                                 ldx: i64) -> c_int;
+    pub fn corrla_chol_solve_dev_f64(ctx: *mut c_void, a: *mut f64, n: i64, lda: i64, b: *mut f64, n_rhs: i64, ldb: i64) -> c_int;
+    pub fn corrla_ctx_last_chol(ctx: *mut c_void, route: *mut c_int, info: *mut i64, min_diag: *mut f64, max_diag: *mut f64,
+                                logdet: *mut f64) -> c_int;
 }
 
 /// One context per thread (device 0): replaces faer's process-global `Parallelism` (mat_utils.rs:31).
