@@ -202,6 +202,77 @@ def _empty_colmajor(like, rows, cols):
     return np.empty((rows, cols), dtype=like.dtype, order="F")
 
 
+def _empty(like, shape, dtype=None):
+    """Uninitialised row-major output of `shape`, of the array kind, device and -- unless `dtype`, a numpy dtype, names
+    another -- dtype of `like`.  `like` is an array or, for the entries that have none to model on, a device index (a tensor
+    on that device) or None (numpy)."""
+    if _is_torch(like) or isinstance(like, int):
+        import torch
+        return torch.empty(shape, dtype=like.dtype if dtype is None else getattr(torch, np.dtype(dtype).name),
+                           device=like.device if _is_torch(like) else f"cuda:{like}")
+    return np.empty(shape, dtype=like.dtype if dtype is None else dtype)
+
+
+def _opt_ptr(v):
+    """an optional array as the entries take it: NULL for None"""
+    return None if v is None else _ptr(v)
+
+
+def _reject(v, what, sparse):
+    """the two kinds of input the statistics entries have no kernels for; `sparse`: what the entry says about the second"""
+    _reject_bf16(v, what)
+    if _is_sparse(v):
+        raise ValueError(sparse)
+
+
+def _rowmajor(a):
+    """`a` as the entries read a matrix: unit stride along the columns, rows that do not overlap; a view with a padded row
+    stride stays the view it is."""
+    rs, cs = _strides(a)
+    if (cs != 1 and a.shape[1] > 1) or (rs < a.shape[1] and a.shape[0] > 1):
+        return a.contiguous() if _is_torch(a) else np.ascontiguousarray(a)
+    return a
+
+
+def _row_stride(a):
+    """the row stride of what _rowmajor returned (a single row has none: its length serves)"""
+    return int(_strides(a)[0]) if a.shape[0] > 1 else int(a.shape[1])
+
+
+def _poly_terms(k, degree):
+    """The columns of ``build_vandermonde`` (stats_corr.rs:201-209) over k features: [x, 1] below degree 2,
+    [x, x_a x_b (a <= b), 1] from there on.  Also the rows of the polynomial tail of an RBF interpolant."""
+    return k + 1 if degree < 2 else k + k * (k + 1) // 2 + 1
+
+
+def _rbf_tail(poly_degree, dim):
+    """-> (poly_degree as the RBF entries take it: -1 for no tail, the rows of the tail over dim coordinates)"""
+    if poly_degree is not None and (isinstance(poly_degree, (bool, np.bool_)) or not isinstance(poly_degree, (int, np.integer))):
+        raise ValueError("poly_degree must be None or an integer")
+    degree = -1 if poly_degree is None or poly_degree < 0 else int(poly_degree)
+    return degree, (0 if degree < 0 else _poly_terms(dim, degree))
+
+
+# What a corrla_ctx_last_* function reports -> the entries of Context._last that the last_* accessors read.  The out-values
+# arrive in the order of the C function's out-parameters.
+_RECORDS = {
+    "pca_apply": lambda centring, route: {"pca_apply_centring": L.PCA_APPLY_CENTRINGS.get(centring),
+                                          "pca_apply_route": L.PCA_APPLY_ROUTES.get(route)},
+    "polyfit": lambda route: {"polyfit_route": L.POLYFIT_ROUTES.get(route)},
+    "kde": lambda route: {"kde_route": L.KDE_ROUTES.get(route)},
+    "mvn": lambda route: {"mvn_route": L.MVN_ROUTES.get(route)},
+    "dirichlet": lambda word: {"dirichlet_route": L.DIRICHLET_ROUTES.get(word & 0xFF), "dirichlet_readbacks": word >> 8},
+    "solve": lambda route, info, min_pivot, max_u: {"solve_route": L.SOLVE_ROUTES.get(route),
+                                                    "solve_info": {"info": info, "min_pivot": min_pivot, "max_u": max_u}},
+    "chol": lambda route, info, min_diag, max_diag, logdet: {
+        "chol_route": L.CHOL_ROUTES.get(route),
+        "chol_info": {"info": info, "min_diag": min_diag, "max_diag": max_diag, "logdet": logdet}},
+}
+# The status records: they are valid after a numeric failure too (CORRLA_ENUMERIC), and the device entries that write them
+# (LU, Cholesky, RBF fit) synchronise themselves.
+_STATUS_RECORDS = ("solve", "chol")
+
+
 def _sync_stream(t):
     """Inputs produced on torch's current stream are complete before the library's own (non-blocking) stream reads them:
     called last before a library call, after every torch operation that prepares an argument."""
@@ -343,6 +414,75 @@ class Context:
 
     def _entry(self, stem, on_device, dtype):
         return getattr(self._lib, stem + ("dev_" if on_device else "") + _suffix(dtype))
+
+    @property
+    def _last(self):
+        """How this context's last calls ran, by the names the last_* accessors read: one store for every record, made on
+        first use (so that a Context made without __init__ has one too)."""
+        return self.__dict__.setdefault("_last_store", {})
+
+    def _read_last(self, record):
+        """corrla_ctx_last_<record> into _last: one out-value per POINTER(t) the signature lists after the context."""
+        name = "corrla_ctx_last_" + record
+        outs = [p._type_() for p in L.SIGNATURES[name][1][1:]]
+        L.check(getattr(self._lib, name)(self._h, *[C.byref(v) for v in outs]))
+        self._last.update(_RECORDS[record](*[v.value for v in outs]))
+
+    def _call(self, stem, dtype, args, on_device, inputs=None, last=None):
+        """What every statistics entry ends with: the call of `stem`[dev_]<dtype>(ctx, *args), and the three ordering rules
+        around it, which live here and nowhere else.
+        1. `inputs` (a tensor the call reads) were prepared on torch's current stream: that stream is waited for last before
+           the call, so after every torch operation that prepared an argument.
+        2. A status record (`last` in _STATUS_RECORDS) is read before a failure is raised: it describes a numeric failure too.
+        3. A device entry only enqueues, unless it writes a status record: the context is synchronised before torch sees the
+           outputs, and before `last`, the corrla_ctx_last_* record of the entry if it has one, is read."""
+        status = last in _STATUS_RECORDS
+        if on_device and inputs is not None:
+            _sync_stream(inputs)
+        rc = self._entry(stem, on_device, dtype)(self._h, *args)
+        if status and rc in (L.OK, L.ENUMERIC):
+            self._read_last(last)
+        L.check(rc)
+        if not status:
+            self._finish(on_device, last)
+
+    def _finish(self, on_device, last):
+        """rule 3 of _call, after a call that succeeded"""
+        if on_device:
+            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        if last is not None:
+            self._read_last(last)
+
+    def _pca_apply_done(self, on_device):
+        """what a caller of the raw transform / inverse entries ends with (tests/test_gpu_pca_apply.py)"""
+        self._finish(on_device, "pca_apply")
+
+    def _dense_arg(self, v, name, what, *, sparse=None, like=None, f64=False, nonempty=True, rowmajor=False):
+        """The one adapter of the dense matrix argument `name` of the entry `what` -> (array, on_device).  bfloat16 raises, a
+        sparse input raises `sparse` (None: the entry has dealt with it).  Then `v` as _as_dense gives it -- 2-D, float32
+        as it is and anything else as float64, numpy or a CUDA tensor, which has to be on this context's device -- or, with
+        `like`, converted to the kind, device and dtype of that array.  f64: float64 whatever came.  nonempty: neither side
+        may be 0.  rowmajor: see _rowmajor."""
+        _reject_bf16(v, what)
+        if sparse is not None and _is_sparse(v):
+            raise ValueError(sparse)
+        if like is None:
+            a, on_dev = _as_dense(v, name)
+            if on_dev:
+                self._on_my_device(a)
+        else:
+            on_dev = _is_torch(like)
+            a = self._model_array(v, like, on_dev)
+            if a.ndim != 2:
+                raise ValueError(f"{name} must be 2-D")
+        if f64 and on_dev:
+            import torch
+            a = a.detach().to(torch.float64)
+        elif f64:
+            a = a.astype(np.float64, copy=False)
+        if nonempty and (a.shape[0] == 0 or a.shape[1] == 0):
+            raise ValueError(f"{name} must be non-empty")
+        return (_rowmajor(a) if rowmajor else a), on_dev
 
     def _run_rsvd(self, stem, operand, m, n, nt, like, on_device, k, q, p, seed, omega, flags, in_dtype=None):
         """The one caller of the rsvd entries `stem`[dev_]{f32,f64,bf16}: `operand` describes the m x n matrix (its arrays
@@ -493,39 +633,23 @@ class Context:
             raise ValueError("correlation=True needs center=True: a correlation matrix is one of centred columns")
         if _is_sparse(x):
             raise ValueError("cov has no sparse entry: a covariance matrix is dense; pass a dense matrix (.toarray() / .to_dense())")
-        _reject_bf16(x, "cov")
-        a, on_dev = _as_dense(x, "x")
-        if on_dev:
-            self._on_my_device(a)
+        a, on_dev = self._dense_arg(x, "x", "cov")
         m, n = a.shape
-        if m == 0 or n == 0:
-            raise ValueError("x must be non-empty")
         flags = (L.COV_CORRELATION if correlation else 0) | (0 if center else L.COV_NO_CENTER)
-        if on_dev:
-            import torch
-            c = torch.empty((n, n), dtype=a.dtype, device=a.device)
-            means = torch.empty((1, n), dtype=a.dtype, device=a.device) if center else None
-            scales = torch.empty((1, n), dtype=a.dtype, device=a.device) if correlation else None
-        else:
-            c = np.empty((n, n), dtype=a.dtype)
-            means = np.empty((1, n), dtype=a.dtype) if center else None
-            scales = np.empty((1, n), dtype=a.dtype) if correlation else None
-        route = C.c_int(0)
-        if on_dev:
-            _sync_stream(a)
-        L.check(self._entry("corrla_cov_", on_dev, a.dtype)(self._h, _ptr(a), m, n, *_strides(a), flags, int(ddof),
-                                                            None if means is None else _ptr(means),
-                                                            None if scales is None else _ptr(scales), _ptr(c), n, C.byref(route)))
-        if on_dev:  # the device entry only enqueues: torch's streams see the results after this
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
-        self._cov_route = L.COV_ROUTES.get(route.value)
+        c = _empty(a, (n, n))
+        means = _empty(a, (1, n)) if center else None
+        scales = _empty(a, (1, n)) if correlation else None
+        route = C.c_int(0)   # this entry reports its route itself
+        self._call("corrla_cov_", a.dtype, (_ptr(a), m, n, *_strides(a), flags, int(ddof), _opt_ptr(means), _opt_ptr(scales), _ptr(c), n,
+                   C.byref(route)), on_dev, a)
+        self._last["cov_route"] = L.COV_ROUTES.get(route.value)
         return c, means, scales
 
     def last_cov_route(self):
         """The route of this context's last ``cov`` call: "inplace" (x read where it lies with 16-byte loads),
         "inplace_checked" (in place through bounds-checked element loads: base or row stride not 16-byte aligned) or
         "repacked" (feature-strided x, transposed once into workspace); None before the first call."""
-        return getattr(self, "_cov_route", None)
+        return self._last.get("cov_route")
 
     # ---- the fitted PCA model on the device (pca_rsvd.rs:43-52) ----------------------------------
     def _model_array(self, v, like, on_device):
@@ -561,23 +685,6 @@ class Context:
             vecs.append(a.contiguous() if on_device else np.ascontiguousarray(a))
         return vecs[0], vecs[1], comps, k
 
-    def _call_done(self, on_device, last, **names):
-        """After a call of the fitted-model, polyfit or kde entries: the device entries only enqueue, so torch's streams see
-        the results after this; then how the call ran: `last` (a corrla_ctx_last_* function) fills one int per keyword, and
-        each is kept as the attribute the keyword names, through the keyword's table of names.  The keywords stand in the
-        order of the C function's out-parameters: they are passed on by position."""
-        if on_device:
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
-        vals = [C.c_int(0) for _ in names]
-        L.check(getattr(self._lib, last)(self._h, *[C.byref(v) for v in vals]))
-        for (attr, table), v in zip(names.items(), vals):
-            setattr(self, attr, table.get(v.value))
-
-    def _pca_apply_done(self, on_device):
-        """_call_done for the transform / inverse entries (also what a caller of the raw entries ends with)"""
-        self._call_done(on_device, "corrla_ctx_last_pca_apply", _pca_apply_centring=L.PCA_APPLY_CENTRINGS,
-                        _pca_apply_route=L.PCA_APPLY_ROUTES)
-
     def pca_transform(self, x, means, components, scales=None, *, own_means=False, residuals=False, center=None):
         """A fitted PCA model applied to x (m x n) on the device (corrla_pca_transform_*): the scores
         t = ((x - means) / scales) @ components.T, shape (m, k), column-major like U.  `means` (n values), `components`
@@ -609,27 +716,15 @@ class Context:
             operand, m, n, like, on_dev = self._csr_operand(x)
             stem = "corrla_pca_transform_csr_"
         else:
-            a, on_dev = _as_dense(x, "x")
-            if on_dev:
-                self._on_my_device(a)
+            a, on_dev = self._dense_arg(x, "x", "pca_transform")
             m, n = a.shape
-            if m == 0 or n == 0:
-                raise ValueError("x must be non-empty")
             operand, like, stem = (a, m, n, *_strides(a)), a, "corrla_pca_transform_"
         mu, sd, comps, k = self._model(None if own_means else means, components, scales, n, like, on_dev)
         scores = _empty_colmajor(like, m, k)
-        if on_dev:
-            import torch
-            q = torch.empty((m,), dtype=like.dtype, device=like.device) if residuals else None
-            mu_out = torch.empty((1, n), dtype=like.dtype, device=like.device) if own_means else None
-            _sync_stream(like)
-        else:
-            q = np.empty((m,), dtype=like.dtype) if residuals else None
-            mu_out = np.empty((1, n), dtype=like.dtype) if own_means else None
-        opt = lambda v: None if v is None else _ptr(v)  # noqa: E731
-        L.check(self._entry(stem, on_dev, like.dtype)(self._h, *_c_args(operand), opt(mu), opt(sd), _ptr(comps), k, k, flags,
-                                                      _ptr(scores), m, opt(q), opt(mu_out)))
-        self._pca_apply_done(on_dev)
+        q = _empty(like, (m,)) if residuals else None
+        mu_out = _empty(like, (1, n)) if own_means else None
+        self._call(stem, like.dtype, (*_c_args(operand), _opt_ptr(mu), _opt_ptr(sd), _ptr(comps), k, k, flags, _ptr(scores), m, _opt_ptr(q),
+                   _opt_ptr(mu_out)), on_dev, like, "pca_apply")
         out = (scores,) + ((q,) if residuals else ()) + ((mu_out,) if own_means else ())
         return out[0] if len(out) == 1 else out
 
@@ -637,31 +732,17 @@ class Context:
         """The reconstruction (scores @ components) * scales + means, (m, n) row-major, in one kernel and one write of m x n
         (corrla_pca_inverse_*; ``apply_inv_tr``, pca_rsvd.rs:49-52).  means / scales None: 0 / 1.  numpy in -> numpy out, a
         CUDA tensor in -> a tensor on its device; float32 stays float32, anything else becomes float64."""
-        _reject_bf16(scores, "pca_inverse_transform")
-        if _is_sparse(scores):
-            raise ValueError("pca_inverse_transform takes dense scores")
-        t, on_dev = _as_dense(scores, "scores")
-        if on_dev:
-            self._on_my_device(t)
+        t, on_dev = self._dense_arg(scores, "scores", "pca_inverse_transform", sparse="pca_inverse_transform takes dense scores")
         m, k_in = t.shape
-        if m == 0 or k_in == 0:
-            raise ValueError("scores must be non-empty")
         mu, sd, comps, k = self._model(means, components, scales, None, t, on_dev)
         n = int(comps.shape[0] if on_dev else comps.shape[1])
         if k != k_in:
             raise ValueError(f"scores have {k_in} columns, components {k} rows")
         # (m, k) column-major with ld = m: no copy for what pca_transform returned
         tc = t.t().contiguous() if on_dev else np.asfortranarray(t)
-        if on_dev:
-            import torch
-            out = torch.empty((m, n), dtype=t.dtype, device=t.device)
-            _sync_stream(t)
-        else:
-            out = np.empty((m, n), dtype=t.dtype)
-        opt = lambda v: None if v is None else _ptr(v)  # noqa: E731
-        L.check(self._entry("corrla_pca_inverse_", on_dev, t.dtype)(self._h, _ptr(tc), m, k, m, opt(mu), opt(sd), _ptr(comps), k, n,
-                                                                    _ptr(out), n))
-        self._pca_apply_done(on_dev)
+        out = _empty(t, (m, n))
+        self._call("corrla_pca_inverse_", t.dtype, (_ptr(tc), m, k, m, _opt_ptr(mu), _opt_ptr(sd), _ptr(comps), k, n, _ptr(out), n), on_dev, t,
+                   "pca_apply")
         return out
 
     def last_pca_apply_route(self):
@@ -669,11 +750,11 @@ class Context:
         its m x n operand (x of the residuals, the output of the inverse): "inplace" (16-byte accesses), "inplace_checked"
         (element accesses: base or row stride not 16-byte aligned) or "repacked" (feature-strided x, transposed once into
         workspace); None when the call ran no such kernel, and before the first call."""
-        return getattr(self, "_pca_apply_route", None)
+        return self._last.get("pca_apply_route")
 
     def last_pca_apply_centring(self):
         """The centring of the last ``pca_transform`` call: "fused", "copy", or None (no centring, or no such call yet)."""
-        return getattr(self, "_pca_apply_centring", None)
+        return self._last.get("pca_apply_centring")
 
     # ---- radial-basis-function kernel matrices (interp_utils.rs:96-129, 146-153) -------------------
     @staticmethod
@@ -686,34 +767,14 @@ class Context:
         """-> (queries, supports, on_device): both row-major with unit stride along the coordinates, the supports in the
         kind, dtype and device of the queries."""
         for v in (x_query, x_support):
-            _reject_bf16(v, what)
-            if _is_sparse(v):
-                raise ValueError(f"{what} takes dense points")
-        xq, on_dev = _as_dense(x_query, "x_query")
-        if on_dev:
-            self._on_my_device(xq)
-        xs = self._model_array(x_support, xq, on_dev)
-        if xs.ndim != 2:
-            raise ValueError("x_support must be 2-D")
+            _reject(v, what, f"{what} takes dense points")
+        xq, on_dev = self._dense_arg(x_query, "x_query", what, nonempty=False)
+        xs, _ = self._dense_arg(x_support, "x_support", what, like=xq, nonempty=False)
         if xq.shape[0] == 0 or xs.shape[0] == 0 or xq.shape[1] == 0:
             raise ValueError("x_query and x_support must be non-empty")
         if xs.shape[1] != xq.shape[1]:
             raise ValueError(f"x_query has {xq.shape[1]} coordinates, x_support {xs.shape[1]}")
-        return self._rbf_rowmajor(xq, on_dev), self._rbf_rowmajor(xs, on_dev), on_dev
-
-    @staticmethod
-    def _rbf_rowmajor(a, on_device):
-        """`a` as the entries read it: unit stride along the columns, rows that do not overlap; a view with a padded row
-        stride stays the view it is."""
-        rs, cs = _strides(a)
-        if (cs != 1 and a.shape[1] > 1) or (rs < a.shape[1] and a.shape[0] > 1):
-            return a.contiguous() if on_device else np.ascontiguousarray(a)
-        return a
-
-    @staticmethod
-    def _row_stride(a):
-        """the row stride of what _rbf_rowmajor returned (a single row has none: its length serves)"""
-        return int(_strides(a)[0]) if a.shape[0] > 1 else int(a.shape[1])
+        return _rowmajor(xq), _rowmajor(xs), on_dev
 
     def rbf_matrix(self, x_query, x_support, kernel_type, kernel_param=0.0):
         """The kernel matrix Phi[i, j] = phi(||x_query_i - x_support_j||_2), (n_q, n_s) row-major, on the device
@@ -725,17 +786,9 @@ class Context:
         xq, xs, on_dev = self._rbf_points(x_query, x_support, "rbf_matrix")
         n_q, dim = (int(v) for v in xq.shape)
         n_s = int(xs.shape[0])
-        if on_dev:
-            import torch
-            out = torch.empty((n_q, n_s), dtype=xq.dtype, device=xq.device)
-            _sync_stream(xq)
-        else:
-            out = np.empty((n_q, n_s), dtype=xq.dtype)
-        L.check(self._entry("corrla_rbf_matrix_", on_dev, xq.dtype)(self._h, _ptr(xq), n_q, self._row_stride(xq), _ptr(xs), n_s,
-                                                                   self._row_stride(xs), dim, self._rbf_kernel_id(kernel_type),
-                                                                   float(kernel_param), _ptr(out), n_s))
-        if on_dev:  # the device entry only enqueues: torch's streams see the results after this
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        out = _empty(xq, (n_q, n_s))
+        self._call("corrla_rbf_matrix_", xq.dtype, (_ptr(xq), n_q, _row_stride(xq), _ptr(xs), n_s, _row_stride(xs), dim,
+                   self._rbf_kernel_id(kernel_type), float(kernel_param), _ptr(out), n_s), on_dev, xq)
         return out
 
     def rbf_apply(self, x_query, x_support, coeffs, kernel_type, kernel_param=0.0, *, poly_degree=None):
@@ -750,13 +803,8 @@ class Context:
         xq, xs, on_dev = self._rbf_points(x_query, x_support, "rbf_apply")
         n_q, dim = (int(v) for v in xq.shape)
         n_s = int(xs.shape[0])
-        if poly_degree is not None and (isinstance(poly_degree, (bool, np.bool_)) or not isinstance(poly_degree, (int, np.integer))):
-            raise ValueError("poly_degree must be None or an integer")
-        degree = -1 if poly_degree is None or poly_degree < 0 else int(poly_degree)
-        n_poly = 0 if degree < 0 else (dim + 1 if degree < 2 else dim + dim * (dim + 1) // 2 + 1)
-        _reject_bf16(coeffs, "rbf_apply")
-        if _is_sparse(coeffs):
-            raise ValueError("rbf_apply takes dense coefficients")
+        degree, n_poly = _rbf_tail(poly_degree, dim)
+        _reject(coeffs, "rbf_apply", "rbf_apply takes dense coefficients")
         w = self._model_array(coeffs, xq, on_dev)
         if w.ndim == 1:
             w = w.reshape(-1, 1)
@@ -764,57 +812,18 @@ class Context:
             raise ValueError("coeffs must be a non-empty matrix")
         if w.shape[0] != n_s + n_poly:
             raise ValueError(f"coeffs must have n_s + n_poly = {n_s} + {n_poly} rows, got {w.shape[0]}")
-        w = self._rbf_rowmajor(w, on_dev)
+        w = _rowmajor(w)
         n_rhs = int(w.shape[1])
-        if on_dev:
-            import torch
-            out = torch.empty((n_q, n_rhs), dtype=xq.dtype, device=xq.device)
-            _sync_stream(xq)
-        else:
-            out = np.empty((n_q, n_rhs), dtype=xq.dtype)
-        L.check(self._entry("corrla_rbf_apply_", on_dev, xq.dtype)(self._h, _ptr(xq), n_q, self._row_stride(xq), _ptr(xs), n_s,
-                                                                  self._row_stride(xs), dim, self._rbf_kernel_id(kernel_type),
-                                                                  float(kernel_param), degree, _ptr(w), self._row_stride(w), n_rhs,
-                                                                  _ptr(out), n_rhs))
-        if on_dev:
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        out = _empty(xq, (n_q, n_rhs))
+        self._call("corrla_rbf_apply_", xq.dtype, (_ptr(xq), n_q, _row_stride(xq), _ptr(xs), n_s, _row_stride(xs), dim,
+                   self._rbf_kernel_id(kernel_type), float(kernel_param), degree, _ptr(w), _row_stride(w), n_rhs, _ptr(out), n_rhs), on_dev, xq)
         return out
 
     # ---- dense LU solve and the RBF fit on it (corrla_lu_solve_* / corrla_rbffit_system_* / corrla_rbffit_*) ---------
-    def _f64_matrix(self, v, name, what, like=None):
+    def _f64_matrix(self, v, name, what, like=None, nonempty=False):
         """-> (v as a float64 matrix the solve entries read: row-major, unit column stride, rows that do not overlap;
         on_device).  like: an array whose kind and device v is converted to; None: v's own."""
-        _reject_bf16(v, what)
-        if _is_sparse(v):
-            raise ValueError(f"{what} takes a dense {name}")
-        if like is None:
-            a, on_dev = _as_dense(v, name)
-            if on_dev:
-                import torch
-                self._on_my_device(a)
-                a = a.detach().to(torch.float64)
-            else:
-                a = a.astype(np.float64, copy=False)
-        else:
-            on_dev = _is_torch(like)
-            a = self._model_array(v, like, on_dev)
-            if a.ndim != 2:
-                raise ValueError(f"{name} must be 2-D")
-        return self._rbf_rowmajor(a, on_dev), on_dev
-
-    def _solve_done(self):
-        """how the last solve ran, whether it succeeded or ended with CORRLA_ENUMERIC"""
-        route, info, minp, maxu = C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-        L.check(self._lib.corrla_ctx_last_solve(self._h, C.byref(route), C.byref(info), C.byref(minp), C.byref(maxu)))
-        self._solve_route = L.SOLVE_ROUTES.get(route.value)
-        self._solve_info = {"info": int(info.value), "min_pivot": float(minp.value), "max_u": float(maxu.value)}
-
-    def _solve_call(self, fn, *args):
-        """one solve or fit entry; the status record is kept before a failure is raised"""
-        rc = fn(self._h, *args)
-        if rc in (L.OK, L.ENUMERIC):
-            self._solve_done()
-        L.check(rc)
+        return self._dense_arg(v, name, what, sparse=f"{what} takes a dense {name}", like=like, f64=True, nonempty=nonempty, rowmajor=True)
 
     def solve(self, a, b, *, overwrite=False, assume="general"):
         """x with a x = b on the device (corrla_lu_solve_*): LU with partial pivoting (P A = L U, ties to the lowest row,
@@ -851,38 +860,17 @@ class Context:
                     raise ValueError("overwrite=True takes float64 row-major CUDA tensors that need no conversion")
             else:
                 am, bm = am.clone(), bm.clone()
-            _sync_stream(am)
-            if pos:
-                self._chol_call(self._lib.corrla_chol_solve_dev_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm))
-            else:
-                self._solve_call(self._lib.corrla_lu_solve_dev_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
-                                 None)
-            x = bm
+            x, out = bm, (() if pos else (None,))   # in place: x over b; the interchanges of the LU entry (ipiv) are not wanted
         else:
             if overwrite:
                 raise ValueError("overwrite=True needs CUDA tensors: the host entry leaves a and b untouched")
-            x = np.empty((n, n_rhs), dtype=np.float64)
-            if pos:
-                self._chol_call(self._lib.corrla_chol_solve_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
-                                _ptr(x), n_rhs)
-            else:
-                self._solve_call(self._lib.corrla_lu_solve_f64, _ptr(am), n, self._row_stride(am), _ptr(bm), n_rhs, self._row_stride(bm),
-                                 _ptr(x), n_rhs)
+            x = _empty(am, (n, n_rhs))
+            out = (_ptr(x), n_rhs)
+        self._call("corrla_chol_solve_" if pos else "corrla_lu_solve_", np.float64, (_ptr(am), n, _row_stride(am), _ptr(bm), n_rhs, _row_stride(bm),
+                   *out), on_dev, am, "chol" if pos else "solve")
         return x.reshape(-1) if vec else x
 
     # ---- dense Cholesky factor and SPD solve (corrla_chol_factor_* / corrla_chol_solve_*) ----------------------------
-    def _chol_call(self, fn, *args):
-        """one Cholesky entry; the status record is kept before a failure is raised"""
-        rc = fn(self._h, *args)
-        if rc in (L.OK, L.ENUMERIC):
-            route, info = C.c_int(0), C.c_int64(0)
-            mind, maxd, logdet = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-            L.check(self._lib.corrla_ctx_last_chol(self._h, C.byref(route), C.byref(info), C.byref(mind), C.byref(maxd), C.byref(logdet)))
-            self._chol_route = L.CHOL_ROUTES.get(route.value)
-            self._chol_info = {"info": int(info.value), "min_diag": float(mind.value), "max_diag": float(maxd.value),
-                               "logdet": float(logdet.value)}
-        L.check(rc)
-
     def cholesky(self, a, *, overwrite=False):
         """The Cholesky factor L of a symmetric positive definite a, a = L L^T, on the device (corrla_chol_factor_*): (n, n),
         lower triangular with a positive diagonal, its strict upper triangle zero.  Only the LOWER triangle of a is read: what
@@ -905,47 +893,41 @@ class Context:
                     raise ValueError("overwrite=True takes a float64 row-major CUDA tensor that needs no conversion")
             else:
                 am = am.clone()
-            _sync_stream(am)
-            self._chol_call(self._lib.corrla_chol_factor_dev_f64, _ptr(am), n, self._row_stride(am))
+            self._call("corrla_chol_factor_", np.float64, (_ptr(am), n, _row_stride(am)), True, am, "chol")
             return a if overwrite else am.tril_()
         if overwrite:
             raise ValueError("overwrite=True needs a CUDA tensor: the host entry leaves a untouched")
-        out = np.empty((n, n), dtype=np.float64)
-        self._chol_call(self._lib.corrla_chol_factor_f64, _ptr(am), n, self._row_stride(am), _ptr(out), n)
+        out = _empty(am, (n, n))
+        self._call("corrla_chol_factor_", np.float64, (_ptr(am), n, _row_stride(am), _ptr(out), n), False, last="chol")
         return out
 
     @property
     def last_chol_route(self):
         """"small" or "blocked": the route of this context's last ``cholesky`` / ``solve(assume="pos")``; None before the first."""
-        return getattr(self, "_chol_route", None)
+        return self._last.get("chol_route")
 
     @property
     def last_chol_info(self):
         """{"info": 0 or the 1-based column of the failed pivot, "min_diag", "max_diag": smallest and largest l_jj of the
         columns factored, "logdet": log det a (0.0 when info != 0)} of this context's last ``cholesky`` /
         ``solve(assume="pos")``; None before the first."""
-        return getattr(self, "_chol_info", None)
+        return self._last.get("chol_info")
 
     @property
     def last_solve_route(self):
         """"small" or "blocked": the route of this context's last ``solve`` / ``rbf_fit``; None before the first."""
-        return getattr(self, "_solve_route", None)
+        return self._last.get("solve_route")
 
     @property
     def last_solve_info(self):
         """{"info": 0 or the 1-based column of the failed pivot, "min_pivot": smallest |pivot|, "max_u": largest |u_ij|} of
         this context's last ``solve`` / ``rbf_fit``; None before the first."""
-        return getattr(self, "_solve_info", None)
+        return self._last.get("solve_info")
 
     def _rbf_fit_args(self, x, poly_degree, what):
-        xs, on_dev = self._f64_matrix(x, "x", what)
+        xs, on_dev = self._f64_matrix(x, "x", what, nonempty=True)
         n_s, dim = (int(v) for v in xs.shape)
-        if n_s == 0 or dim == 0:
-            raise ValueError("x must be non-empty")
-        if poly_degree is not None and (isinstance(poly_degree, (bool, np.bool_)) or not isinstance(poly_degree, (int, np.integer))):
-            raise ValueError("poly_degree must be None or an integer")
-        degree = -1 if poly_degree is None or poly_degree < 0 else int(poly_degree)
-        n_poly = 0 if degree < 0 else (dim + 1 if degree < 2 else dim + dim * (dim + 1) // 2 + 1)
+        degree, n_poly = _rbf_tail(poly_degree, dim)
         return xs, on_dev, n_s, dim, degree, n_s + n_poly
 
     def rbf_system(self, x, kernel_type, kernel_param=0.0, *, poly_degree=None):
@@ -954,17 +936,9 @@ class Context:
         tail of ``rbf_apply`` ([x, 1] for poly_degree 0 or 1, [x, x_a x_b (a <= b), 1] from 2 on, none for None) with one
         rounding per product, the corner exactly zero.  numpy in -> numpy out, a CUDA tensor in -> a tensor on its device."""
         xs, on_dev, n_s, dim, degree, n = self._rbf_fit_args(x, poly_degree, "rbf_system")
-        if on_dev:
-            import torch
-            out = torch.empty((n, n), dtype=torch.float64, device=xs.device)
-            _sync_stream(xs)
-        else:
-            out = np.empty((n, n), dtype=np.float64)
-        L.check(self._entry("corrla_rbffit_system_", on_dev, np.float64)(self._h, _ptr(xs), n_s, self._row_stride(xs), dim,
-                                                                     self._rbf_kernel_id(kernel_type), float(kernel_param), degree,
-                                                                     _ptr(out), n))
-        if on_dev:  # the device entry only enqueues
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        out = _empty(xs, (n, n))
+        self._call("corrla_rbffit_system_", np.float64, (_ptr(xs), n_s, _row_stride(xs), dim, self._rbf_kernel_id(kernel_type), float(kernel_param),
+                   degree, _ptr(out), n), on_dev, xs)
         return out
 
     def rbf_fit(self, x, y, kernel_type, kernel_param=0.0, *, poly_degree=None):
@@ -981,14 +955,9 @@ class Context:
         if ym.shape[0] != n_s or ym.shape[1] == 0:
             raise ValueError(f"y must have n_s = {n_s} rows and at least one column, got {tuple(ym.shape)}")
         n_rhs = int(ym.shape[1])
-        if on_dev:
-            import torch
-            out = torch.empty((n, n_rhs), dtype=torch.float64, device=xs.device)
-            _sync_stream(xs)
-        else:
-            out = np.empty((n, n_rhs), dtype=np.float64)
-        self._solve_call(self._entry("corrla_rbffit_", on_dev, np.float64), _ptr(xs), n_s, self._row_stride(xs), dim, _ptr(ym), n_rhs,
-                         self._row_stride(ym), self._rbf_kernel_id(kernel_type), float(kernel_param), degree, _ptr(out), n_rhs)
+        out = _empty(xs, (n, n_rhs))
+        self._call("corrla_rbffit_", np.float64, (_ptr(xs), n_s, _row_stride(xs), dim, _ptr(ym), n_rhs, _row_stride(ym),
+                   self._rbf_kernel_id(kernel_type), float(kernel_param), degree, _ptr(out), n_rhs), on_dev, xs, "solve")
         return out
 
     # ---- polynomial response surfaces (stats_corr.rs:146-249) ---------------------------------------
@@ -1000,17 +969,10 @@ class Context:
 
     def _poly_x(self, x, what):
         """-> (x row-major with unit stride along the features, on_device)"""
-        _reject_bf16(x, what)
-        if _is_sparse(x):
-            raise ValueError(f"{what} takes a dense x")
-        a, on_dev = _as_dense(x, "x")
-        if on_dev:
-            self._on_my_device(a)
-        if a.shape[0] == 0 or a.shape[1] == 0:
-            raise ValueError("x must be non-empty")
+        a, on_dev = self._dense_arg(x, "x", what, sparse=f"{what} takes a dense x")
         if a.shape[1] > 128:
             raise ValueError(f"{what}: x has {a.shape[1]} features, the kernels take 1 to 128")
-        return self._rbf_rowmajor(a, on_dev), on_dev
+        return _rowmajor(a), on_dev
 
     def polyfit_gram(self, x, y=None, degree=2, *, normalize=True):
         """The normal equations of a polynomial least-squares fit without the Vandermonde matrix -> (G, means, scales).
@@ -1033,9 +995,7 @@ class Context:
         if y is None:
             yy, r, ldy = None, 0, 0
         else:
-            _reject_bf16(y, "polyfit_gram")
-            if _is_sparse(y):
-                raise ValueError("polyfit_gram takes a dense y")
+            _reject(y, "polyfit_gram", "polyfit_gram takes a dense y")
             yy = self._model_array(y, a, on_dev)
             if yy.ndim == 1:
                 yy = yy.reshape(-1, 1)
@@ -1044,27 +1004,14 @@ class Context:
             r = int(yy.shape[1])
             if r > 64:
                 raise ValueError(f"polyfit_gram: y has {r} columns, the kernels take at most 64")
-            if r == 0:
-                yy = None
-            else:
-                yy = self._rbf_rowmajor(yy, on_dev)
-            ldy = self._row_stride(yy) if r else 0
-        order = (kf + 1 if degree == 1 else kf + kf * (kf + 1) // 2 + 1) + r
-        if on_dev:
-            import torch
-            g = torch.empty((order, order), dtype=torch.float64, device=a.device)
-            means = torch.empty((1, kf), dtype=torch.float64, device=a.device) if normalize else None
-            scales = torch.empty((1, kf), dtype=torch.float64, device=a.device) if normalize else None
-            _sync_stream(a)
-        else:
-            g = np.empty((order, order), dtype=np.float64)
-            means = np.empty((1, kf), dtype=np.float64) if normalize else None
-            scales = np.empty((1, kf), dtype=np.float64) if normalize else None
-        L.check(self._entry("corrla_polyfit_gram_", on_dev, a.dtype)(self._h, _ptr(a), m, kf, self._row_stride(a),
-                                                                    None if yy is None else _ptr(yy), r, ldy, degree, int(normalize),
-                                                                    _ptr(g), order, None if means is None else _ptr(means),
-                                                                    None if scales is None else _ptr(scales)))
-        self._call_done(on_dev, "corrla_ctx_last_polyfit", _polyfit_route=L.POLYFIT_ROUTES)
+            yy = _rowmajor(yy) if r else None
+            ldy = _row_stride(yy) if r else 0
+        order = _poly_terms(kf, degree) + r
+        g = _empty(a, (order, order), np.float64)
+        means = _empty(a, (1, kf), np.float64) if normalize else None
+        scales = _empty(a, (1, kf), np.float64) if normalize else None
+        self._call("corrla_polyfit_gram_", a.dtype, (_ptr(a), m, kf, _row_stride(a), _opt_ptr(yy), r, ldy, degree, int(normalize), _ptr(g), order,
+                   _opt_ptr(means), _opt_ptr(scales)), on_dev, a, "polyfit")
         return g, means, scales
 
     def poly_eval(self, x, coeffs, degree=2, *, jac=False):
@@ -1081,34 +1028,21 @@ class Context:
         jac = _check_bool("jac", jac, ValueError)
         a, on_dev = self._poly_x(x, "poly_eval")
         m, kf = (int(v) for v in a.shape)
-        _reject_bf16(coeffs, "poly_eval")
-        if _is_sparse(coeffs):
-            raise ValueError("poly_eval takes dense coefficients")
-        if on_dev:
-            import torch
-            c = self._model_array(coeffs, torch.empty(0, dtype=torch.float64, device=a.device), True)
-        else:
-            c = self._model_array(coeffs, np.empty(0, dtype=np.float64), False)
+        _reject(coeffs, "poly_eval", "poly_eval takes dense coefficients")
+        c = self._model_array(coeffs, _empty(a, 0, np.float64), on_dev)
         if c.ndim == 1:
             c = c.reshape(-1, 1)
-        p = kf + 1 if degree == 1 else kf + kf * (kf + 1) // 2 + 1
+        p = _poly_terms(kf, degree)
         if c.ndim != 2 or c.shape[0] != p or c.shape[1] == 0:
             raise ValueError(f"coeffs must have p = {p} rows for {kf} features at degree {degree}, got shape {tuple(c.shape)}")
         r = int(c.shape[1])
         if r > 64:
             raise ValueError(f"poly_eval: coeffs has {r} columns, the kernels take at most 64")
-        c = self._rbf_rowmajor(c, on_dev)
-        if on_dev:
-            out = torch.empty((m, r), dtype=a.dtype, device=a.device)
-            grad = torch.empty((r, m, kf), dtype=a.dtype, device=a.device) if jac else None
-            _sync_stream(a)
-        else:
-            out = np.empty((m, r), dtype=a.dtype)
-            grad = np.empty((r, m, kf), dtype=a.dtype) if jac else None
-        L.check(self._entry("corrla_poly_eval_", on_dev, a.dtype)(self._h, _ptr(a), m, kf, self._row_stride(a), _ptr(c),
-                                                                 self._row_stride(c), r, degree, _ptr(out), r,
-                                                                 None if grad is None else _ptr(grad), kf))
-        self._call_done(on_dev, "corrla_ctx_last_polyfit", _polyfit_route=L.POLYFIT_ROUTES)
+        c = _rowmajor(c)
+        out = _empty(a, (m, r))
+        grad = _empty(a, (r, m, kf)) if jac else None
+        self._call("corrla_poly_eval_", a.dtype, (_ptr(a), m, kf, _row_stride(a), _ptr(c), _row_stride(c), r, degree, _ptr(out), r, _opt_ptr(grad),
+                   kf), on_dev, a, "polyfit")
         if not jac:
             return out
         return out, (grad[0] if r == 1 else grad)
@@ -1117,15 +1051,13 @@ class Context:
         """The route of this context's last ``polyfit_gram`` / ``poly_eval`` call: "inplace" (x read where it lies with 16-byte
         loads) or "inplace_checked" (element loads: the base or the row stride of x not 16-byte aligned); None before the
         first call.  y, the narrow operand, is read by its own alignment and does not change the route."""
-        return getattr(self, "_polyfit_route", None)
+        return self._last.get("polyfit_route")
 
     # ---- Gaussian kernel density estimates (univariate_rv.rs:165-170, 423-444) ----------------------
     def _kde_vector(self, v, name, what):
         """-> (array as the entries read it, on_device, n, element stride, its shape): a vector, or an n x 1 column as the
         reference's column matrices, read in place at its stride; float32 stays float32, anything else becomes float64."""
-        _reject_bf16(v, what)
-        if _is_sparse(v):
-            raise ValueError(f"{what} takes dense vectors")
+        _reject(v, what, f"{what} takes dense vectors")
         if _is_torch(v) and v.is_cuda:
             import torch
             self._on_my_device(v)
@@ -1174,15 +1106,8 @@ class Context:
         h = float(bandwidth)
         if not (np.isfinite(h) and h > 0.0):
             raise ValueError(f"bandwidth must be finite and > 0, got {bandwidth!r}")
-        if on_dev:
-            import torch
-            out = torch.empty(shape, dtype=xa.dtype, device=xa.device)
-            _sync_stream(xa)
-        else:
-            out = np.empty(shape, dtype=xa.dtype)
-        L.check(self._entry("corrla_kde_eval_", on_dev, xa.dtype)(self._h, _ptr(xa), n_q, incx, _ptr(sa), n_s, incs, h, L.KDE_WHAT[what],
-                                                                 _ptr(out), 1))
-        self._call_done(on_dev, "corrla_ctx_last_kde", _kde_route=L.KDE_ROUTES)
+        out = _empty(xa, shape)
+        self._call("corrla_kde_eval_", xa.dtype, (_ptr(xa), n_q, incx, _ptr(sa), n_s, incs, h, L.KDE_WHAT[what], _ptr(out), 1), on_dev, xa, "kde")
         return out
 
     def kde_nll(self, x_test, supports, bandwidths):
@@ -1201,22 +1126,16 @@ class Context:
         if not (np.all(np.isfinite(hb)) and np.all(hb > 0.0)):
             raise ValueError("every bandwidth must be finite and > 0")
         n_h = int(hb.shape[0])
-        if on_dev:
-            import torch
-            nll, dnll = (torch.empty(n_h, dtype=torch.float64, device=xa.device) for _ in range(2))
-            _sync_stream(xa)
-        else:
-            nll, dnll = np.empty(n_h, dtype=np.float64), np.empty(n_h, dtype=np.float64)
-        L.check(self._entry("corrla_kde_nll_", on_dev, xa.dtype)(self._h, _ptr(xa), n_t, incx, _ptr(sa), n_s, incs, hb.ctypes.data, n_h,
-                                                                _ptr(nll), _ptr(dnll)))
-        self._call_done(on_dev, "corrla_ctx_last_kde", _kde_route=L.KDE_ROUTES)
+        nll, dnll = (_empty(xa, n_h, np.float64) for _ in range(2))
+        self._call("corrla_kde_nll_", xa.dtype, (_ptr(xa), n_t, incx, _ptr(sa), n_s, incs, hb.ctypes.data, n_h, _ptr(nll), _ptr(dnll)), on_dev, xa,
+                   "kde")
         return nll, dnll
 
     def last_kde_route(self):
         """The route of this context's last ``kde_eval`` / ``kde_nll`` call: "single" (every workgroup swept all supports) or
         "split" (few points: the supports were split over workgroups and the partial sums added in index order); None before
         the first call."""
-        return getattr(self, "_kde_route", None)
+        return self._last.get("kde_route")
 
     # ---- constrained Dirichlet sampling (space_samplers.rs:14-126) ------------------------------------
     @staticmethod
@@ -1245,20 +1164,6 @@ class Context:
             raise ValueError(f"seed must be in [0, 2^64), got {seed}")
         return np.ascontiguousarray(al), c, seed
 
-    def _dirichlet_out(self, n, d, device):
-        if device:
-            import torch
-            return torch.empty((n, d), dtype=torch.float64, device=f"cuda:{self.device}")
-        return np.empty((n, d), dtype=np.float64)
-
-    def _dirichlet_done(self, device):
-        if device:  # the draws entry only enqueues: torch's streams see the rows after this
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
-        route = C.c_int(0)
-        L.check(self._lib.corrla_ctx_last_dirichlet(self._h, C.byref(route)))
-        self._dirichlet_route = L.DIRICHLET_ROUTES.get(route.value & 0xFF)
-        self._dirichlet_readbacks = route.value >> 8
-
     def dirichlet_draws(self, n, alphas, *, c_scale=1.0, seed=0, first=0, device=False):
         """Rows [first, first + n) of the Dirichlet stream of (seed, alphas, c_scale) (corrla_dirichlet_draws_*): row t is
         x_j = c_scale g_j / sum_i g_i with g_j ~ Gamma(alphas[j], 1), a pure function of (seed, alphas, c_scale, t) -- the
@@ -1273,10 +1178,8 @@ class Context:
         if first < 0 or first + n > L.DIRICHLET_MAX_DRAWS:
             raise ValueError(f"first must be >= 0 and first + n <= 2^62, got first = {first}, n = {n}")
         d = int(al.shape[0])
-        out = self._dirichlet_out(n, d, device)
-        fn = self._lib.corrla_dirichlet_draws_dev_f64 if device else self._lib.corrla_dirichlet_draws_f64
-        L.check(fn(self._h, al.ctypes.data, d, c, seed, first, n, _ptr(out), d))
-        self._dirichlet_done(device)
+        out = _empty(self.device if device else None, (n, d), np.float64)
+        self._call("corrla_dirichlet_draws_", np.float64, (al.ctypes.data, d, c, seed, first, n, _ptr(out), d), device, last="dirichlet")
         return out
 
     def dirichlet_sample(self, bounds, n_samples, alphas=None, *, c_scale=1.0, seed=0, max_zshots=500, chunk_size=1_000_000,
@@ -1311,32 +1214,28 @@ class Context:
         slack = 8.0 * np.finfo(np.float64).eps * d * c
         if sum(b[:, 0].tolist()) > c + slack or sum(b[:, 1].tolist()) < c - slack:
             raise ValueError("bounds leave no point with sum c_scale (infeasible box)")
-        out = self._dirichlet_out(n_samples, d, device)
+        out = _empty(self.device if device else None, (n_samples, d), np.float64)
         n_found, n_drawn = C.c_int64(0), C.c_int64(0)
-        fn = self._lib.corrla_dirichlet_sample_dev_f64 if device else self._lib.corrla_dirichlet_sample_f64
-        L.check(fn(self._h, b.ctypes.data, al.ctypes.data, d, c, seed, n_samples, max_zshots, chunk_size, _ptr(out), d,
-                   C.byref(n_found), C.byref(n_drawn)))
-        self._dirichlet_done(device)
+        self._call("corrla_dirichlet_sample_", np.float64, (b.ctypes.data, al.ctypes.data, d, c, seed, n_samples, max_zshots, chunk_size, _ptr(out),
+                   d, C.byref(n_found), C.byref(n_drawn)), device, last="dirichlet")
         return out, int(n_found.value), int(n_drawn.value)
 
     def last_dirichlet_route(self):
         """The route of this context's last ``dirichlet_draws`` / ``dirichlet_sample`` call: "registers/..." (d <= 16: the
         gammas of a row stay in registers) or "regenerate/..." (wider rows: one sweep forms the sum, a second draws each gamma
         again from its counter), then ".../exponential" (every alpha is 1) or ".../general"; None before the first call."""
-        return getattr(self, "_dirichlet_route", None)
+        return self._last.get("dirichlet_route")
 
     def last_dirichlet_readbacks(self):
         """How many times the last ``dirichlet_sample`` call read the device's running count back (0 for ``dirichlet_draws``)."""
-        return getattr(self, "_dirichlet_readbacks", None)
+        return self._last.get("dirichlet_readbacks")
 
     # ---- multivariate normal rows and sandwich variances (stats_corr.rs:46-68) -----------------------------
     def _mvn_small(self, v, name, on_device, dtype_of=None):
         """A dense float32 / float64 argument (factor, mean, cov, jac) as a numpy array (host call) or a tensor on this
         context's device (device call); bfloat16, sparse and other dtypes raise ValueError.  dtype_of: the array whose type
         it has to share."""
-        _reject_bf16(v, name)
-        if _is_sparse(v):
-            raise ValueError(f"{name} must be dense")
+        _reject(v, name, f"{name} must be dense")
         if _is_torch(v) and v.is_cuda:
             self._on_my_device(v)
             a = v.detach()
@@ -1390,7 +1289,7 @@ class Context:
             raise ValueError(f"first must be >= 0 and (first + n) * r < 2^63, got first = {first}, n = {n}, r = {r}")
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"seed must be in [0, 2^64), got {seed}")
-        f = self._rbf_rowmajor(f, on_dev)
+        f = _rowmajor(f)
         mu = None
         if mean is not None:
             mu = self._mvn_small(mean, "mean", on_dev, f).reshape(-1)
@@ -1398,11 +1297,7 @@ class Context:
                 raise ValueError(f"mean must have d = {d} entries, got {mu.shape[0]}")
             mu = mu.contiguous() if on_dev else np.ascontiguousarray(mu)
         if out is None:
-            if on_dev:
-                import torch
-                out = torch.empty((n, d), dtype=f.dtype, device=f.device)
-            else:
-                out = np.empty((n, d), dtype=f.dtype)
+            out = _empty(f, (n, d))
         else:
             _reject_bf16(out, "out")
             if (_is_torch(out) and out.is_cuda) != on_dev or not (_is_torch(out) or isinstance(out, np.ndarray)):
@@ -1415,22 +1310,17 @@ class Context:
             if on_dev:
                 self._on_my_device(out)
         if n == 0:
-            self._mvn_route = "empty"
+            self._last["mvn_route"] = "empty"
             return out
-        if on_dev:
-            _sync_stream(f)
-        ldo = int(_strides(out)[0]) if n > 1 else d
-        L.check(self._entry("corrla_mvn_sample_", on_dev, f.dtype)(self._h, n, d, r, _ptr(f), self._row_stride(f),
-                                                                  None if mu is None else _ptr(mu), seed, first, int(lower),
-                                                                  _ptr(out), ldo))
-        self._call_done(on_dev, "corrla_ctx_last_mvn", _mvn_route=L.MVN_ROUTES)
+        self._call("corrla_mvn_sample_", f.dtype, (n, d, r, _ptr(f), _row_stride(f), _opt_ptr(mu), seed, first, int(lower), _ptr(out),
+                   _row_stride(out)), on_dev, f, "mvn")
         return out
 
     def last_mvn_route(self):
         """The route of this context's last ``mvn_sample`` call: "fused" (the normals of a row tile are generated once into
         LDS and multiplied there), "staged" (r > 288 in float32 / 144 in float64: ``fill_normal`` into a bounded workspace, then the
         back-projection kernel, a row chunk at a time) or "empty" (n = 0: nothing launched); None before the first call."""
-        return getattr(self, "_mvn_route", None)
+        return self._last.get("mvn_route")
 
     def sandwich_diag(self, jac, cov):
         """The first-order output variances v_i = jac[i] @ cov @ jac[i] -> (m,), on the device (corrla_sandwich_diag_*; the
@@ -1450,17 +1340,9 @@ class Context:
         c = self._mvn_small(cov, "cov", on_dev, j)
         if c.ndim != 2 or tuple(c.shape) != (d, d):
             raise ValueError(f"cov must be ({d}, {d}), got shape {tuple(c.shape)}")
-        j, c = self._rbf_rowmajor(j, on_dev), self._rbf_rowmajor(c, on_dev)
-        if on_dev:
-            import torch
-            v = torch.empty((m,), dtype=j.dtype, device=j.device)
-            _sync_stream(j)
-        else:
-            v = np.empty((m,), dtype=j.dtype)
-        L.check(self._entry("corrla_sandwich_diag_", on_dev, j.dtype)(self._h, _ptr(j), m, d, self._row_stride(j), _ptr(c),
-                                                                     self._row_stride(c), _ptr(v)))
-        if on_dev:  # the device entry only enqueues: torch's streams see the result after this
-            L.check(self._lib.corrla_ctx_synchronize(self._h))
+        j, c = _rowmajor(j), _rowmajor(c)
+        v = _empty(j, (m,))
+        self._call("corrla_sandwich_diag_", j.dtype, (_ptr(j), m, d, _row_stride(j), _ptr(c), _row_stride(c), _ptr(v)), on_dev, j)
         return v
 
     # ---- op(A) @ X hooks used by tests / bench ----------------------------------------------

@@ -34,7 +34,7 @@ Every product with an n_x- or N-sized dimension goes through the library's HIP G
 snapshot-count- and n_modes-sized matrices are touched by numpy."""
 import numpy as np
 
-from .api import _is_torch, default_context, rsvd
+from .api import _is_torch, _poly_terms, default_context, rsvd
 
 __all__ = ["pod_modes", "active_ss_fit_svd", "DMDc", "PodI", "RbfInterp", "PolyGradientEstimator", "ActiveSsRsvd",
            "FittedActiveSsRsvd", "mat_cov_centered", "pearson_corr", "rsquared_sens", "rbf_matrix", "rbf_apply",
@@ -126,7 +126,7 @@ def polyfit_solve(g, k, degree, means=None, scales=None):
       4. the coefficients of the normalised samples z = (x - means) / scales are mapped back to x by the congruence
          C_x = M^T C_z M, M = [[diag(1 / scales), -means / scales], [0, 1]], on the symmetric form of every column."""
     g = np.asarray(g, dtype=np.float64)
-    p = k + 1 if degree < 2 else k + k * (k + 1) // 2 + 1
+    p = _poly_terms(k, degree)
     a, b = g[:p, :p], g[:p, p:]
     d = np.sqrt(np.diag(a))
     d = np.where(d > 0.0, d, 1.0)

@@ -13,6 +13,7 @@ import pytest
 
 from corrla_rs_amd import _lib as L
 from corrla_rs_amd import api, callers
+from tests.api_stub import make_stub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "corrla_rsvd.h")).read()
@@ -48,30 +49,9 @@ def test_prototypes_are_declared_bound_and_in_the_rust_shim():
     assert "pub const CORRLA_COV_CORRELATION: u64 = 0x1;" in rs and "pub const CORRLA_COV_NO_CENTER: u64 = 0x2;" in rs
 
 
-class _Recorder:
-    """stands where a corrla_cov_* entry would be: keeps its arguments, reports a route and success"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __call__(self, *args):
-        self.calls.append(args)
-        args[-1]._obj.value = L.COV_ROUTE_INPLACE_CHECKED
-        return L.OK
-
-
 @pytest.fixture
 def stub():
-    c = api.Context.__new__(api.Context)   # no device, no library
-    c._lib, c._h, c.device = None, None, 0
-    rec = _Recorder()
-    names = []
-
-    def entry(stem, on_device, dtype):
-        names.append(stem + ("dev_" if on_device else "") + api._suffix(dtype))
-        return rec
-    c._entry = entry
-    return c, rec, names
+    return make_stub(route_out=L.COV_ROUTE_INPLACE_CHECKED)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

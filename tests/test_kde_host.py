@@ -14,6 +14,7 @@ import pytest
 
 from corrla_rs_amd import _lib as L
 from corrla_rs_amd import api
+from tests.api_stub import make_stub
 from tests.test_gpu_kde import assert_brackets_the_minimum, known, known_eval_bounds, nll_bounds, seeded_case
 from tests.test_kde_plan import BASE
 
@@ -48,41 +49,9 @@ def test_prototypes_are_declared_bound_and_in_the_rust_shim():
     assert "1 <= n_h <= 64" in HDR and "Stabilised form" in HDR and "deliberate difference" in HDR and "-inf" in HDR
 
 
-class _Recorder:
-    """stands where an entry would be: keeps its arguments and reports success"""
-
-    def __init__(self):
-        self.calls = []
-        self.peek = {}     # argument index -> (ctypes type, count): arrays to copy while the call's temporaries are alive
-        self.seen = {}
-
-    def __call__(self, *args):
-        self.calls.append(args)
-        self.seen = {i: np.ctypeslib.as_array(C.cast(args[i], C.POINTER(ct)), shape=(cnt,)).copy() for i, (ct, cnt) in self.peek.items()}
-        return L.OK
-
-
-class _FakeLib:
-    def corrla_ctx_synchronize(self, h):
-        return L.OK
-
-    def corrla_ctx_last_kde(self, h, route):
-        route._obj.value = 2
-        return L.OK
-
-
 @pytest.fixture
 def stub():
-    c = api.Context.__new__(api.Context)   # no device, no library
-    c._lib, c._h, c.device = _FakeLib(), None, 0
-    rec = _Recorder()
-    names = []
-
-    def entry(stem, on_device, dtype):
-        names.append(stem + ("dev_" if on_device else "") + api._suffix(dtype))
-        return rec
-    c._entry = entry
-    return c, rec, names
+    return make_stub(last={"corrla_ctx_last_kde": (2,)})
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

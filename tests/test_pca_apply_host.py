@@ -13,6 +13,7 @@ import pytest
 
 from corrla_rs_amd import _lib as L
 from corrla_rs_amd import api
+from tests.api_stub import make_stub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "corrla_rsvd.h")).read()
@@ -68,43 +69,9 @@ def test_prototypes_are_declared_bound_and_in_the_rust_shim():
     assert "pca_rsvd.rs:43-46" in HDR and "pca_rsvd.rs:49-52" in HDR
 
 
-class _Recorder:
-    """stands where an entry would be: keeps its arguments and reports success"""
-
-    def __init__(self):
-        self.calls = []
-        self.peek = {}     # argument index -> (ctypes type, count): arrays to copy while the call's temporaries are alive
-        self.seen = {}
-
-    def __call__(self, *args):
-        self.calls.append(args)
-        self.seen = {i: np.ctypeslib.as_array(C.cast(args[i], C.POINTER(ct)), shape=(cnt,)).copy() for i, (ct, cnt) in self.peek.items()}
-        return L.OK
-
-
-class _FakeLib:
-    """what _pca_apply_done asks the library after a call"""
-
-    def corrla_ctx_synchronize(self, h):
-        return L.OK
-
-    def corrla_ctx_last_pca_apply(self, h, centring, route):
-        centring._obj.value, route._obj.value = 2, L.PCA_APPLY_ROUTE_INPLACE_CHECKED
-        return L.OK
-
-
 @pytest.fixture
 def stub():
-    c = api.Context.__new__(api.Context)   # no device, no library
-    c._lib, c._h, c.device = _FakeLib(), None, 0
-    rec = _Recorder()
-    names = []
-
-    def entry(stem, on_device, dtype):
-        names.append(stem + ("dev_" if on_device else "") + api._suffix(dtype))
-        return rec
-    c._entry = entry
-    return c, rec, names
+    return make_stub(last={"corrla_ctx_last_pca_apply": (2, L.PCA_APPLY_ROUTE_INPLACE_CHECKED)})
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

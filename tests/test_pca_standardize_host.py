@@ -10,6 +10,7 @@ import pytest
 
 from corrla_rs_amd import _lib as L
 from corrla_rs_amd import api
+from tests.api_stub import make_stub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -30,29 +31,9 @@ def test_opts_ends_in_scales_out_behind_the_first_layout():
     assert C.sizeof(L.Opts) == 40
 
 
-class _Recorder:
-    """stands where a corrla_pca_* entry would be: keeps its arguments, reports success"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __call__(self, *args):
-        self.calls.append(args)
-        return L.OK
-
-
 @pytest.fixture
 def stub():
-    c = api.Context.__new__(api.Context)   # no device, no library
-    c._lib, c._h, c.device = None, None, 0
-    rec = _Recorder()
-    names = []
-
-    def entry(stem, on_device, dtype):
-        names.append(stem + ("dev_" if on_device else "") + api._suffix(dtype))
-        return rec
-    c._entry = entry
-    return c, rec, names
+    return make_stub()
 
 
 def _opts_of(call):
