@@ -3,7 +3,9 @@ wgurecky/CORRLA_RS.  The compute path is libcorrla_rsvd.so (hand-written HIP ker
 is the thin host-side mirror of the reference's Python/Rust surfaces.  No CPU fallback.
 Dense solves: ``Context.solve`` (LU, or Cholesky with assume="pos"), ``Context.cholesky`` / ``cholesky`` (the factor of a
 symmetric positive definite matrix, log det in ``Context.last_chol_info``), ``mvn_factor(device=True)``,
-``sample_mv_normal(factor="device")`` and ``RbfInterp(solver="chol")`` on top of them."""
+``sample_mv_normal(factor="device")`` and ``RbfInterp(solver="chol")`` on top of them.
+Symmetric eigendecomposition: ``Context.eigh`` and the pseudo-inverse solve ``Context.eigh_solve``, with
+``quad_fit(solve="device")``, ``mvn_factor(device=True, eig="device")`` and ``RbfInterp(solver="eigh")`` on top of them."""
 from .api import (Context, PcaRsvd, algorithmic_flops, default_context, power_iter, random_svd, rpca,  # noqa: F401
                   rsvd)
 

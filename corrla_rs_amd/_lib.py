@@ -57,6 +57,12 @@ CHOL_ROUTES = {1: "small", 2: "blocked"}
 CHOL_SMALL_N = 128
 CHOL_NB = 64
 CHOL_MAX_N = 1 << 17
+# corrla_eigh_*: what corrla_ctx_last_eigh reports, and the limits
+EIGH_ROUTES = {1: "small", 2: "blocked"}
+EIGH_SMALL_N = 64
+EIGH_B = 32
+EIGH_MAX_N = 1 << 15
+EIGH_MAX_SWEEPS = 40
 UNIQUE_ID_BYTES = 128
 
 
@@ -111,6 +117,9 @@ def _sigs():
     s["corrla_chol_solve_f64"] = (C.c_int, [vp, vp, i64, i64, vp, i64, i64, vp, i64])
     s["corrla_chol_solve_dev_f64"] = (C.c_int, [vp, vp, i64, i64, vp, i64, i64])
     s["corrla_ctx_last_chol"] = (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)])
+    # symmetric eigendecomposition, f64 only, row-major, lower triangle: a, n, lda, w, v, ldv (host and device alike)
+    s["corrla_eigh_f64"] = s["corrla_eigh_dev_f64"] = (C.c_int, [vp, vp, i64, i64, vp, vp, i64])
+    s["corrla_ctx_last_eigh"] = (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(i64)])
     for suf, sc in (("f32", flt), ("f64", dbl)):
         rsvd = [vp, vp, i64, i64, i64, i64, i64, i64, i64, C.POINTER(Opts), vp, i64, vp, vp, i64]
         s["corrla_rsvd_" + suf] = (C.c_int, rsvd)

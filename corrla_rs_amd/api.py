@@ -267,10 +267,13 @@ _RECORDS = {
     "chol": lambda route, info, min_diag, max_diag, logdet: {
         "chol_route": L.CHOL_ROUTES.get(route),
         "chol_info": {"info": info, "min_diag": min_diag, "max_diag": max_diag, "logdet": logdet}},
+    "eigh": lambda route, sweeps, off, shift, info: {
+        "eigh_route": L.EIGH_ROUTES.get(route),
+        "eigh_info": {"info": info, "sweeps": sweeps, "off": off, "shift": shift, "dropped": None}},
 }
 # The status records: they are valid after a numeric failure too (CORRLA_ENUMERIC), and the device entries that write them
-# (LU, Cholesky, RBF fit) synchronise themselves.
-_STATUS_RECORDS = ("solve", "chol")
+# (LU, Cholesky, RBF fit, eigensolver) synchronise themselves.
+_STATUS_RECORDS = ("solve", "chol", "eigh")
 
 
 def _sync_stream(t):
@@ -912,6 +915,87 @@ class Context:
         columns factored, "logdet": log det a (0.0 when info != 0)} of this context's last ``cholesky`` /
         ``solve(assume="pos")``; None before the first."""
         return self._last.get("chol_info")
+
+    # ---- symmetric eigendecomposition (corrla_eigh_*) ------------------------------------------------------------------
+    def eigh(self, a):
+        """(w, v) with a = v diag(w) v^T for a symmetric a, on the device (corrla_eigh_*): w (n,) ascending as
+        ``numpy.linalg.eigh`` returns it, v (n, n) row-major with the eigenvectors in its columns, each with its component of
+        largest magnitude positive.  Only the LOWER triangle of a is read (nobody checks the symmetry) and a is left
+        untouched.  float64 only: anything else is converted.  numpy in -> numpy out; a CUDA tensor in -> tensors on its
+        device, and nothing visits the host.
+        The route is a shift to a positive definite matrix, its Cholesky factor and one-sided block Jacobi on that factor
+        (DESIGN 7l).  It is normwise backward stable: the absolute errors of w are of order n u |a|, like LAPACK's for an
+        indefinite matrix; it is NOT relatively accurate for eigenvalues much smaller than |a|.  No atomics: a fixed input
+        gives bitwise fixed output, the same from numpy and from a tensor.  A non-finite entry in the lower triangle, or an
+        iteration beyond 40 sweeps, raises RuntimeError (``CorrlaError``, code ENUMERIC).  ``last_eigh_route`` ("small":
+        n <= 64, one workgroup; "blocked") and ``last_eigh_info`` describe the call.  ValueError: a not square, empty,
+        sparse or bfloat16, a tensor on another device, n above 32768."""
+        am, on_dev = self._f64_matrix(a, "a", "eigh")
+        n = int(am.shape[0])
+        if n == 0 or am.shape[1] != n:
+            raise ValueError(f"a must be square and non-empty, got {tuple(am.shape)}")
+        w, v = _empty(am, (n,)), _empty(am, (n, n))
+        self._call("corrla_eigh_", np.float64, (_ptr(am), n, _row_stride(am), _ptr(w), _ptr(v), n), on_dev, am if on_dev else None, "eigh")
+        return w, v
+
+    def eigh_solve(self, a, b, *, rcond=None, reg=None):
+        """x = V f(L) V^T b with (L, V) = ``eigh(a)``: the pseudo-inverse solve of a symmetric a that may be singular or
+        indefinite.  a is (n, n), b is (n,) or (n, n_rhs); x has the shape of b; numpy `a` -> numpy out, a CUDA tensor -> a
+        tensor.  The decomposition, the two products (``matmul``) and the scaling between them run on the device.
+        Default rule: f(l) = 1 / l where |l| > rcond max|l|, else 0, with rcond = n 2^-52 (the rule of ``polyfit_solve``).
+        reg=eps: f(l) = sign(l) / (|l| + eps) with sign(0) = + (the rule of ``mat_pinv`` on a symmetric matrix).  rcond and
+        reg exclude each other.  ``last_eigh_info["dropped"]`` holds the number of directions the default rule set to zero (0
+        with reg).  The accuracy is that of ``eigh``: absolute in the eigenvalues, so the cut is meaningful only as an
+        absolute one, which rcond max|l| is."""
+        import torch
+        if rcond is not None and reg is not None:
+            raise ValueError("eigh_solve takes rcond or reg, not both")
+        if reg is not None and not (np.isfinite(reg) and reg >= 0.0):
+            raise ValueError("reg must be finite and >= 0")
+        if rcond is not None and not (np.isfinite(rcond) and rcond >= 0.0):
+            raise ValueError("rcond must be finite and >= 0")
+        am, on_dev = self._f64_matrix(a, "a", "eigh_solve")
+        n = int(am.shape[0])
+        if n == 0 or am.shape[1] != n:
+            raise ValueError(f"a must be square and non-empty, got {tuple(am.shape)}")
+        vec = (b.dim() if _is_torch(b) else np.ndim(b)) == 1
+        b2 = b.reshape(-1, 1) if vec else b
+        bm, _ = self._f64_matrix(b2, "b", "eigh_solve", like=am)
+        if bm.shape[0] != n or bm.shape[1] == 0:
+            raise ValueError(f"b must have n = {n} rows and at least one column, got {tuple(bm.shape)}")
+        dev = torch.device(f"cuda:{self.device}")
+        at = am if on_dev else torch.from_numpy(am).to(dev)
+        bt = bm if on_dev else torch.from_numpy(bm).to(dev)
+        w, v = self.eigh(at)
+        if reg is not None:
+            f = torch.where(w < 0, -1.0, 1.0) / (w.abs() + float(reg))
+            dropped = 0
+        else:
+            keep = w.abs() > (n * 2.0 ** -52 if rcond is None else float(rcond)) * w.abs().max()
+            f = torch.where(keep, 1.0 / torch.where(keep, w, torch.ones_like(w)), torch.zeros_like(w))
+            dropped = n - int(keep.sum().item())
+        t = self.matmul(v, bt.contiguous(), trans=True)          # V^T b
+        L.check(self._lib.corrla_ctx_synchronize(self._h))
+        t = (t * f[:, None]).contiguous()
+        x = self.matmul(v, t).contiguous()                       # V (f(L) V^T b)
+        L.check(self._lib.corrla_ctx_synchronize(self._h))
+        self._last["eigh_info"] = dict(self._last["eigh_info"], dropped=dropped)
+        if not on_dev:
+            x = x.cpu().numpy()
+        return x.reshape(-1) if vec else x
+
+    @property
+    def last_eigh_route(self):
+        """"small" or "blocked": the route of this context's last ``eigh`` / ``eigh_solve``; None before the first."""
+        return self._last.get("eigh_route")
+
+    @property
+    def last_eigh_info(self):
+        """{"info": 0, or 1 non-finite entry / 2 Cholesky pivot / 3 sweep cap, "sweeps": the sweeps that rotated, "off": the
+        largest measure max |g_ij| / sqrt(g_ii g_jj) of the last sweep, "shift": sigma, "dropped": the directions the last
+        ``eigh_solve`` set to zero (None after a plain ``eigh``)} of this context's last ``eigh`` / ``eigh_solve``; None
+        before the first."""
+        return self._last.get("eigh_info")
 
     @property
     def last_solve_route(self):

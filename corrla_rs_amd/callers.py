@@ -114,7 +114,7 @@ def _poly_unsym(cm, k, degree):
     return np.vstack(rows)
 
 
-def polyfit_solve(g, k, degree, means=None, scales=None):
+def polyfit_solve(g, k, degree, means=None, scales=None, *, device=False, ctx=None):
     """Coefficients (p, r) of the least-squares polynomial from the Gram matrix G of ``Context.polyfit_gram`` (order p + r),
     in the coordinates of the raw x.  p-sized host work:
       1. V^T V = G[:p, :p] is equilibrated by its diagonal (D^-1/2 A D^-1/2, unit diagonal);
@@ -124,20 +124,36 @@ def polyfit_solve(g, k, degree, means=None, scales=None):
          which turns an exactly rank-deficient V into coefficients of order 1e14 times rounding noise; here the null
          directions are dropped;
       4. the coefficients of the normalised samples z = (x - means) / scales are mapped back to x by the congruence
-         C_x = M^T C_z M, M = [[diag(1 / scales), -means / scales], [0, 1]], on the symmetric form of every column."""
-    g = np.asarray(g, dtype=np.float64)
+         C_x = M^T C_z M, M = [[diag(1 / scales), -means / scales], [0, 1]], on the symmetric form of every column.
+    device=True: steps 1 to 3 run on the device -- g (a numpy array, which is uploaded, or the CUDA tensor of ``polyfit_gram``,
+    which then never visits the host) is equilibrated elementwise and solved by ``Context.eigh_solve`` of `ctx` or the default context, whose default rule
+    is the cut of step 3 on |lambda|; only the (p, r) coefficients come back for step 4, which stays as it is.  The device
+    eigenvalues carry absolute errors of order p u |A| (``Context.eigh``), which is the scale of the cut, so a direction at the
+    cut may fall on either side: compare predictions with the host solve, not coefficients."""
     p = _poly_terms(k, degree)
-    a, b = g[:p, :p], g[:p, p:]
-    d = np.sqrt(np.diag(a))
-    d = np.where(d > 0.0, d, 1.0)
-    w, q = np.linalg.eigh(a / np.outer(d, d))
-    keep = w > p * 2.0 ** -52 * w[-1]
-    qk = q[:, keep]
-    cz = (qk @ ((qk.T @ (b / d[:, None])) / w[keep][:, None])) / d[:, None]
+    if device:
+        import torch
+        c = ctx or default_context()
+        gt = g.detach().to(torch.float64) if _on_gpu(g) else torch.as_tensor(
+            np.asarray(g.detach().numpy() if _is_torch(g) else g, dtype=np.float64), device=f"cuda:{c.device}")
+        at, bt = gt[:p, :p], gt[:p, p:]
+        dt = torch.sqrt(torch.diagonal(at))
+        dt = torch.where(dt > 0.0, dt, torch.ones_like(dt))
+        cz = (c.eigh_solve((at / torch.outer(dt, dt)).contiguous(), (bt / dt[:, None]).contiguous()) / dt[:, None]).cpu().numpy()
+    else:
+        g = np.asarray(g, dtype=np.float64)
+        a, b = g[:p, :p], g[:p, p:]
+        d = np.sqrt(np.diag(a))
+        d = np.where(d > 0.0, d, 1.0)
+        w, q = np.linalg.eigh(a / np.outer(d, d))
+        keep = w > p * 2.0 ** -52 * w[-1]
+        qk = q[:, keep]
+        cz = (qk @ ((qk.T @ (b / d[:, None])) / w[keep][:, None])) / d[:, None]
     if means is None and scales is None:
         return cz
-    mu = np.zeros(k) if means is None else np.asarray(means, dtype=np.float64).reshape(-1)
-    sg = np.ones(k) if scales is None else np.asarray(scales, dtype=np.float64).reshape(-1)
+    host = lambda v: v.detach().cpu().numpy() if _is_torch(v) else v  # noqa: E731
+    mu = np.zeros(k) if means is None else np.asarray(host(means), dtype=np.float64).reshape(-1)
+    sg = np.ones(k) if scales is None else np.asarray(host(scales), dtype=np.float64).reshape(-1)
     # In extended precision, rounded once: for data far from the origin the intercept of the raw coordinates is a sum of
     # terms (mean / scale)^2 times larger than itself, and (k + 1)^2 numbers per column cost nothing.
     mm = np.zeros((k + 1, k + 1), dtype=np.longdouble)
@@ -148,33 +164,42 @@ def polyfit_solve(g, k, degree, means=None, scales=None):
     return _poly_unsym(mm.T @ _poly_sym(cz, k, degree).astype(np.longdouble) @ mm, k, degree).astype(np.float64)
 
 
-def _poly_fit(x, y, degree, normalize, ctx):
+def _poly_fit(x, y, degree, normalize, ctx, solve="host"):
+    if solve not in ("host", "device"):
+        raise ValueError("solve must be 'host' or 'device'")
     c = ctx or default_context()
     g, means, scales = c.polyfit_gram(x, y, degree, normalize=normalize)
     k = int(x.shape[1])
     on_gpu = _is_torch(g)
     host = (lambda v: None if v is None else v.cpu().numpy()) if on_gpu else (lambda v: v)
-    coeffs = polyfit_solve(host(g), k, degree, host(means), host(scales))
+    if solve == "device":
+        coeffs = polyfit_solve(g, k, degree, means, scales, device=True, ctx=c)  # a CUDA Gram matrix stays on the device
+    else:
+        coeffs = polyfit_solve(host(g), k, degree, host(means), host(scales))
     if on_gpu:
         import torch
         return torch.from_numpy(coeffs).to(g.device)
     return coeffs
 
 
-def linear_fit(x, y, *, normalize=True, ctx=None):
+def linear_fit(x, y, *, normalize=True, ctx=None, solve="host"):
     """``linear_fit(x, y)`` (stats_corr.rs:146-160): least-squares coefficients (k + 1, r) of y = [x, 1] c -- slopes, then
     the intercept -- from the fused normal-equation kernel (``Context.polyfit_gram``) and the host solve of
     ``polyfit_solve``; the (m, k + 1) Vandermonde matrix is never stored.  The coefficients are in the coordinates of the
-    raw x whether or not the kernel normalises.  numpy in -> numpy out, CUDA tensors in -> a tensor on their device."""
-    return _poly_fit(x, y, 1, normalize, ctx)
+    raw x whether or not the kernel normalises.  numpy in -> numpy out, CUDA tensors in -> a tensor on their device.
+    solve="device": the p-sized solve runs on the device too (``polyfit_solve(device=True)``)."""
+    return _poly_fit(x, y, 1, normalize, ctx, solve)
 
 
-def quad_fit(x, y, *, normalize=True, ctx=None):
+def quad_fit(x, y, *, normalize=True, ctx=None, solve="host"):
     """``quad_fit(x, y)`` (stats_corr.rs:213-219): least-squares coefficients (p, r), p = k + k (k + 1) / 2 + 1, of
     y = [x, x_a x_b (a <= b, a outer), 1] c, as ``linear_fit``.  Where V is rank-deficient the reference's
     ``pinv`` with 1 / (s + 1e-14) returns noise along the null directions; this returns the minimum-norm solution of the
-    equilibrated system (``polyfit_solve``), so compare predictions there, not coefficients."""
-    return _poly_fit(x, y, 2, normalize, ctx)
+    equilibrated system (``polyfit_solve``), so compare predictions there, not coefficients.  solve="device": the p-sized
+    solve runs on the device too (``polyfit_solve(device=True)``: ``Context.eigh_solve``).  With CUDA tensors the Gram matrix
+    never visits the host; with numpy inputs ``polyfit_gram`` returns it as a numpy array and it is uploaded again for the
+    solve.  Compare it with the host solve on predictions as well."""
+    return _poly_fit(x, y, 2, normalize, ctx, solve)
 
 
 def quad_eval(x, coeffs, *, ctx=None):
@@ -507,11 +532,17 @@ class RbfInterp:
     ``fit`` is ``Context.rbf_system`` followed by ``Context.solve(..., assume="pos", overwrite=True)`` on the device: a
     Cholesky factorisation of the lower triangle, half the work of "lu" and no pivot search.  A kernel matrix that is
     numerically not positive definite (supports too close together for the kernel parameter) raises the ``CorrlaError``
-    naming the column of the failed pivot: "lu" and "pinv" remain for that case."""
+    naming the column of the failed pivot: "lu" and "pinv" remain for that case.
+
+    solver="eigh" is opt-in and always runs on the device: ``fit`` is ``Context.rbf_system`` followed by
+    ``Context.eigh_solve(..., reg=1e-14)``.  The block system is symmetric, and for a symmetric matrix the SVD pseudo-inverse
+    with 1 / (s + 1e-14) is V diag(sign(l) / (|l| + 1e-14)) V^T: this is the reference's pseudo-inverse rule on the device, and
+    unlike "lu" it returns the minimum-norm answer on a singular system (coincident supports) where "lu" raises.  Its
+    coefficients agree with "pinv" within the conditioning of the system, not bit for bit: compare predictions."""
 
     def __init__(self, kernel_type, kernel_param, dim, poly_degree, *, device=False, ctx=None, solver="pinv"):
-        if solver not in ("pinv", "lu", "chol"):
-            raise ValueError("solver must be 'pinv', 'lu' or 'chol'")
+        if solver not in ("pinv", "lu", "chol", "eigh"):
+            raise ValueError("solver must be 'pinv', 'lu', 'chol' or 'eigh'")
         if solver == "chol":
             if int(kernel_type) in (1, 2, 3) or poly_degree is not None:
                 raise ValueError("solver='chol' takes a positive-definite system: the Gaussian kernel with poly_degree=None")
@@ -545,6 +576,8 @@ class RbfInterp:
             return self._fit_lu(x_in, y_in)
         if self.solver == "chol":
             return self._fit_chol(x_in, y_in)
+        if self.solver == "eigh":
+            return self._fit_eigh(x_in, y_in)
         if self.device or _on_gpu(x_in) or _on_gpu(y_in):
             return self._fit_device(x_in, y_in)
         x = np.asarray(x_in, np.float64)
@@ -603,8 +636,26 @@ class RbfInterp:
         coeffs = ctx.solve(m, yd, assume="pos", overwrite=True)
         self.x_known, self.coeffs = (x.clone(), coeffs) if on_gpu else (x.copy(), coeffs.cpu().numpy())
 
+    def _fit_eigh(self, x_in, y_in):
+        """Context.rbf_system, then the regularised pseudo-inverse solve through the symmetric eigendecomposition, in float64
+        on the device; the model stays where the supports were given"""
+        import torch
+        ctx = self._context()
+        on_gpu = _on_gpu(x_in)
+        x = x_in.detach().double() if on_gpu else np.asarray(x_in.detach().cpu().numpy() if _is_torch(x_in) else x_in, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError("x_in must have `dim` columns")
+        xd = x if on_gpu else torch.tensor(x, device=f"cuda:{ctx.device}")  # (copies: the arrays may be read-only)
+        y = y_in.detach() if _is_torch(y_in) else torch.tensor(np.asarray(y_in, np.float64))
+        yd = y.to(device=xd.device, dtype=torch.float64).reshape(x.shape[0], -1)
+        m = ctx.rbf_system(xd, self.kernel_type, self.eps, poly_degree=self.poly_degree)
+        rhs = torch.zeros((m.shape[0], yd.shape[1]), dtype=torch.float64, device=xd.device)
+        rhs[:x.shape[0]] = yd
+        coeffs = ctx.eigh_solve(m, rhs, reg=1e-14)
+        self.x_known, self.coeffs = (x.clone(), coeffs) if on_gpu else (x.copy(), coeffs.cpu().numpy())
+
     def predict(self, x_query):
-        if self.device or self.solver in ("lu", "chol") or _on_gpu(x_query) or _on_gpu(self.x_known):
+        if self.device or self.solver in ("lu", "chol", "eigh") or _on_gpu(x_query) or _on_gpu(self.x_known):
             return self._predict_device(x_query)
         xq = np.asarray(x_query, np.float64)
         if xq.shape[1] != self.dim:
@@ -1059,8 +1110,23 @@ def _mvn_eig_factor(c, d, big):
     return v[:, keep] * np.sqrt(w[keep])[None, :], False
 
 
-def _mvn_factor_device(cov, ctx):
-    """``mvn_factor`` with steps 1 and 2 on the device; -> (F tensor, lower)"""
+def _mvn_eig_factor_device(c, d, big, ctx):
+    """step 3 of ``mvn_factor`` on the device: ``Context.eigh`` of the symmetrised (d, d) tensor c, the test and the cut of
+    ``_mvn_eig_factor``; two eigenvalues are read back, the matrix is not"""
+    import torch
+    w, v = ctx.eigh(c)
+    w0, w1 = float(w[0]), float(w[-1])
+    cut = d * 2.0 ** -52 * max(w1, 0.0)
+    if w0 < -cut or w1 <= 0.0 and big > 0.0:
+        raise ValueError(f"cov is not positive semi-definite: smallest eigenvalue {w0:.3e}")
+    keep = w > cut
+    if not bool(keep.any()):  # the zero matrix: one column of zeros, so that r >= 1
+        return torch.zeros((d, 1), dtype=torch.float64, device=c.device), False
+    return v[:, keep] * torch.sqrt(w[keep])[None, :], False
+
+
+def _mvn_factor_device(cov, ctx, eig="host"):
+    """``mvn_factor`` with steps 1 and 2 -- and with eig="device" step 3 -- on the device; -> (F tensor, lower)"""
     import torch
     from ._lib import ENUMERIC, CorrlaError
     ctx = ctx or default_context()
@@ -1085,11 +1151,13 @@ def _mvn_factor_device(cov, ctx):
     except CorrlaError as e:
         if e.code != ENUMERIC:
             raise
+    if eig == "device":
+        return _mvn_eig_factor_device(c, d, big, ctx)
     f, lower = _mvn_eig_factor(c.cpu().numpy(), d, big)  # the one route that reads the matrix back
     return torch.as_tensor(f, device=c.device), lower
 
 
-def mvn_factor(cov, *, device=False, ctx=None):
+def mvn_factor(cov, *, device=False, ctx=None, eig="host"):
     """A factor F of a covariance matrix, F F^T = cov -> (F, lower), on the host in float64 (d-sized work).
       1. cov must be square and symmetric to 8 * 2^-52 * max|cov|, else ValueError;
       2. the Cholesky factor of the diagonally equilibrated matrix D^-1/2 cov D^-1/2 is tried: (D^1/2 L, True);
@@ -1100,9 +1168,15 @@ def mvn_factor(cov, *, device=False, ctx=None):
     device=True: steps 1 and 2 -- the symmetry check, the equilibration, the Cholesky factorisation (``Context.cholesky`` of
     `ctx` or the default context) and the rescaling -- run on the device in float64 and F is a CUDA tensor; a CUDA `cov`
     never visits the host.  Only when the factorisation reports a pivot that is not positive does the matrix come back for
-    step 3, whose F is uploaded again.  The device factor agrees with the host's within rounding, not bit for bit."""
+    step 3, whose F is uploaded again.  The device factor agrees with the host's within rounding, not bit for bit.
+    eig="device" (with device=True): step 3 runs on the device as well -- ``Context.eigh``, the same test and the same cut --
+    and a CUDA `cov` never visits the host on any branch.  Its eigenvalues carry absolute errors of order d u |cov|_F."""
+    if eig not in ("host", "device"):
+        raise ValueError("eig must be 'host' or 'device'")
+    if eig == "device" and not device:
+        raise ValueError("eig='device' needs device=True")
     if device:
-        return _mvn_factor_device(cov, ctx)
+        return _mvn_factor_device(cov, ctx, eig)
     c = np.asarray(cov.detach().cpu().numpy() if _is_torch(cov) else cov, dtype=np.float64)
     if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] == 0:
         raise ValueError(f"cov must be a non-empty square matrix, got shape {tuple(c.shape)}")
@@ -1129,19 +1203,22 @@ def mvn_factor(cov, *, device=False, ctx=None):
     return v[:, keep] * np.sqrt(w[keep])[None, :], False
 
 
-def sample_mv_normal(cov, n, *, mean=None, seed=None, device=False, ctx=None, factor="host"):
+def sample_mv_normal(cov, n, *, mean=None, seed=None, device=False, ctx=None, factor="host", eig="host"):
     """``sample_mv_normal(cov, n)`` (stats_corr.rs:46-58): n rows of N(mean, cov), (n, d) float64.  The covariance is factored
     on the host (``mvn_factor``), the rows come from ``Context.mvn_sample``.  numpy in -> numpy out; a CUDA cov or device=True
     gives a tensor.  seed=None takes a fresh one from ``numpy.random.SeedSequence``.
     The one deliberate difference from the reference: it multiplies z by cov itself, so its samples have covariance cov^2;
     these have covariance cov.  ``Context.mvn_sample(n, cov)`` (factor = cov) reproduces the reference's law.
     factor="device" factors the covariance on the device instead (``mvn_factor(cov, device=True)``): nothing d x d is computed
-    on the host; the rows are ``Context.mvn_sample(n, F, lower=True)`` of that F, in the kind the default returns."""
+    on the host; the rows are ``Context.mvn_sample(n, F, lower=True)`` of that F, in the kind the default returns.
+    eig="device" (with factor="device") factors a singular covariance on the device too (``mvn_factor(eig="device")``)."""
     if factor not in ("host", "device"):
         raise ValueError("factor must be 'host' or 'device'")
+    if eig not in ("host", "device") or (eig == "device" and factor != "device"):
+        raise ValueError("eig must be 'host' or 'device', and 'device' needs factor='device'")
     if factor == "device":
         c = ctx or default_context()
-        f, lower = mvn_factor(cov, device=True, ctx=c)
+        f, lower = mvn_factor(cov, device=True, ctx=c, eig=eig)
         mu = None if mean is None else np.asarray(mean.detach().cpu().numpy() if _is_torch(mean) else mean, dtype=np.float64).reshape(-1)
         out = c.mvn_sample(n, f, mu, seed=_fresh_seed() if seed is None else seed, lower=lower, device=True)
         return out if bool(device) or _on_gpu(cov) else out.cpu().numpy()

@@ -17,6 +17,7 @@
 #include "dirichlet_plan.hpp"  // dir_plan: the limits of the Dirichlet entries
 #include "mvn_plan.hpp"  // mvn_plan, sandwich_plan: the limits of the multivariate normal entries
 #include "chol_plan.hpp"  // chol_plan: the limits of the Cholesky entries
+#include "eigh_plan.hpp"  // eigh_plan: the limits of the eigensolver entries
 #include "lu_plan.hpp"  // lu_plan: the limits of the dense-solve entries
 
 namespace corrla {
@@ -1244,6 +1245,39 @@ inline void chol_solve_entry(Dev&, bool host_ptrs, const LuSolveCall& c, Run&& r
     no_overlap(who, nullptr, 0, out, 2);
   }
   on_backend_with<dev_has_chol<Dev>>(run, "Cholesky kernels", "corrla_chol_solve_*");
+}
+
+// ---- symmetric eigendecomposition (corrla_eigh_*) ---------------------------------------------------------------------------------
+// Argument checks of both entries -- the limits of n are the plan's (eigh_plan names the argument it rejects) -- then `run`, on
+// a backend that carries the kernels (dev_has_eigh).  f64 only.  a is read in both kinds of call, w and v are written.
+struct EighCall {
+  const double* a;
+  int64_t n, lda;
+  double* w;
+  double* v;
+  int64_t ldv;
+  Span a_span() const { return Span(a, n, n, lda, "a"); }
+  Span w_span() const { return Span(w, 1, n, n, "w"); }
+  Span v_span() const { return Span(v, n, n, ldv, "v"); }
+};
+
+template <class Dev, class Run>
+inline void eigh_entry(Dev&, const EighCall& c, Run&& run) {
+  const char* who = "eigh";
+  auto bad = [&](const char* what) { throw Error(ST_EINVAL, std::string(who) + ": " + what); };
+  if (!c.a) bad("a is NULL");
+  if (!c.w) bad("w is NULL");
+  if (!c.v) bad("v is NULL");
+  EighShape s;
+  s.n = c.n;
+  const EighPlan p = eigh_plan(s);
+  if (!p.ok) throw Error(ST_EINVAL, p.error);
+  if (c.lda < c.n) bad("lda < n");
+  if (c.ldv < c.n) bad("ldv < n");
+  const Span in[1] = {c.a_span()};
+  const Span out[2] = {c.w_span(), c.v_span()};
+  no_overlap(who, in, 1, out, 2);
+  on_backend_with<dev_has_eigh<Dev>>(run, "symmetric eigensolver kernels", "corrla_eigh_*");
 }
 
 // ---- constrained Dirichlet sampling (corrla_dirichlet_draws_* / corrla_dirichlet_sample_*, space_samplers.rs:14-126) ---------

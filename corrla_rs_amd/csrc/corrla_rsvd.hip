@@ -8,6 +8,7 @@
 #include "core_svd_stage.hpp"
 #include "cov_stage.hpp"
 #include "dirichlet_stage.hpp"
+#include "eigh_stage.hpp"
 #include "grad_stage.hpp"
 #include "hip_backend.hpp"
 #include "kde_stage.hpp"
@@ -34,6 +35,7 @@ struct corrla_ctx {
   mvn_stage::Ran mvn;              // how the last corrla_mvn_sample_* call ran
   lu_stage::Ran lu;                // how the last corrla_lu_solve_* / corrla_rbffit_* call ran
   chol_stage::Ran chol;            // how the last corrla_chol_factor_* / corrla_chol_solve_* call ran
+  eigh_stage::Ran eigh;            // how the last corrla_eigh_* call ran
   explicit corrla_ctx(int ordinal) : dev(ordinal), profile(env_int("CORRLA_PROFILE_PHASES", 0) != 0) {}
 };
 
@@ -612,6 +614,39 @@ CORRLA_API corrla_status corrla_ctx_last_chol(corrla_ctx* ctx, int* route, int64
     if (min_diag) *min_diag = c->chol.min_diag;
     if (max_diag) *max_diag = c->chol.max_diag;
     if (logdet) *logdet = c->chol.logdet;
+  });
+}
+
+// ---- symmetric eigendecomposition (A = V diag(w) V^T over the lower triangle) -----------------------------------------------------
+CORRLA_API corrla_status corrla_eigh_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, double* w, double* v, int64_t ldv) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const EighCall c{a, n, lda, w, v, ldv};
+    eigh_entry<HipDev>(cx.dev, c, [&] {
+      cx.eigh = eigh_stage::Ran();
+      eigh_stage::run(cx.dev, true, c, &cx.eigh);
+    });
+  });
+}
+CORRLA_API corrla_status corrla_eigh_dev_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, double* w, double* v, int64_t ldv) {
+  return ctx_call(ctx, [&](corrla_ctx& cx) {
+    const EighCall c{a, n, lda, w, v, ldv};
+    eigh_entry<HipDev>(cx.dev, c, [&] {
+      cx.eigh = eigh_stage::Ran();
+      eigh_stage::run(cx.dev, false, c, &cx.eigh);
+    });
+  });
+}
+// route: 1 small, 2 blocked, 0 before the first call; sweeps, off, shift, info: the record of that call.  A call rejected for its
+// arguments leaves them as they were; one that ended with CORRLA_ENUMERIC has set them.
+CORRLA_API corrla_status corrla_ctx_last_eigh(corrla_ctx* ctx, int* route, int* sweeps, double* off, double* shift, int64_t* info) {
+  return guarded([&] {
+    corrla_ctx* c = need(ctx);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (route) *route = c->eigh.route;
+    if (sweeps) *sweeps = c->eigh.sweeps;
+    if (off) *off = c->eigh.off;
+    if (shift) *shift = c->eigh.shift;
+    if (info) *info = c->eigh.info;
   });
 }
 

@@ -156,6 +156,11 @@ template <class D, class = void>
 struct dev_has_chol : std::false_type {};
 template <class D>
 struct dev_has_chol<D, std::void_t<decltype(D::kHasChol)>> : std::true_type {};
+// ... and those that carry the symmetric eigensolver kernels of corrla_eigh_* (eigh_kernels.hpp) with kHasEigh.
+template <class D, class = void>
+struct dev_has_eigh : std::false_type {};
+template <class D>
+struct dev_has_eigh<D, std::void_t<decltype(D::kHasEigh)>> : std::true_type {};
 
 // The TALL matrix A (mt x nt, mt >= nt unless the caller insists otherwise) as it sits in
 // memory: either row-major (mem = A) or column-major (mem = A^T as a row-major nt x mt).

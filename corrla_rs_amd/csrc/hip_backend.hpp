@@ -140,6 +140,9 @@ inline void set_lds_limits();  // lu_stage.hpp: the LU kernels
 namespace chol_stage {
 inline void set_lds_limits();  // chol_stage.hpp: the Cholesky kernels
 }
+namespace eigh_stage {
+inline void set_lds_limits();  // eigh_stage.hpp: the symmetric eigensolver's kernels
+}
 
 class HipDev {
  public:
@@ -848,6 +851,8 @@ class HipDev {
   static constexpr bool kHasLu = true;  // driver.hpp: dev_has_lu
   // ---- dense Cholesky factor and SPD solve: chol_plan.hpp plans, chol_stage.hpp launches chol_kernels.hpp ---------------------
   static constexpr bool kHasChol = true;  // driver.hpp: dev_has_chol
+  // ---- symmetric eigensolver: eigh_plan.hpp plans, eigh_stage.hpp launches eigh_kernels.hpp ------------------------------------
+  static constexpr bool kHasEigh = true;  // driver.hpp: dev_has_eigh
   const PolyKnobs& poly_knobs() const { return poly_knobs_; }
   // The plan's pair table on the device.  It depends on (k, r, degree) alone, so it is uploaded when those change and kept
   // between calls: a repeated fit enqueues without a synchronising copy.
@@ -1045,6 +1050,7 @@ class HipDev {
     tall_stage::set_lds_limits();
     lu_stage::set_lds_limits();
     chol_stage::set_lds_limits();
+    eigh_stage::set_lds_limits();
     // nearest neighbours and local fits of the gradient stage (grad_stage.hpp)
     lds_limit((const void*)k::knn_kernel, kMax);
     lds_limit((const void*)k::knn_mfma_kernel<4, 4>, kMax);

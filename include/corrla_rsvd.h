@@ -727,6 +727,37 @@ CORRLA_API corrla_status corrla_chol_solve_f64(corrla_ctx* ctx, const double* a,
 CORRLA_API corrla_status corrla_chol_solve_dev_f64(corrla_ctx* ctx, double* a, int64_t n, int64_t lda, double* b, int64_t n_rhs, int64_t ldb);
 CORRLA_API corrla_status corrla_ctx_last_chol(corrla_ctx* ctx, int* route, int64_t* info, double* min_diag, double* max_diag, double* logdet);
 
+/* ---- symmetric eigendecomposition A = V diag(w) V^T on the device, f64 -------------------------------------
+ * Replaces  numpy.linalg.eigh in the provided callers (polyfit_solve, mvn_factor) and the symmetric pseudo-inverse of mat_pinv.
+ * a is n x n row-major with row stride lda >= n; only its LOWER triangle (i >= j) is read, the strict upper triangle may hold
+ * anything, and a is never written.  w (n) receives the eigenvalues in ascending order, as numpy.linalg.eigh returns them
+ * (eigenvalues that are equal as doubles are ranked by the index of their column of the rotated factor); v (n x n, row stride ldv >= n, row-major) receives the eigenvectors in its columns,
+ * each with its component of largest magnitude positive (the lowest index wins a tie).  The padding columns of v are not written.
+ * Algorithm: sigma = 1.5 min(|A|_F, |A|_inf) makes B = A + sigma I positive definite with a condition number of at most 5;
+ * B = L L^T by the blocked Cholesky of corrla_chol_factor_*; one-sided block Jacobi with right rotations on W = L -- column
+ * blocks of 32, a round-robin tournament of disjoint block pairs, per pair the 64 x 64 Gram matrix on v_mfma_f64_16x16x4_f64,
+ * one sweep of a cyclic threshold Jacobi in LDS and the rotation of both panels on the same MFMA -- until every pair's measure
+ * max |g_ij| / sqrt(g_ii g_jj) is <= 2 sqrt(n) 2^-53.  The columns of W are then orthogonal: v_i is column i divided by its
+ * norm, and the eigenvalue is its Rayleigh quotient v_i^T A v_i / v_i^T v_i over the caller's matrix -- not |column|^2 - sigma,
+ * which carries the rounding of every rotation the column went through.  The norms and quotients are summed in two doubles.
+ * Accuracy: normwise backward stable; absolute errors of order n u (sigma + |A|_2) in w, like LAPACK's for an indefinite
+ * matrix.  It is NOT relatively accurate for eigenvalues much smaller than |A|.
+ * No atomics: a fixed input gives bitwise fixed output, and the host entry gives the bits of the device entry.
+ * Routes (corrla_ctx_last_eigh): 1 small, n <= 64, one workgroup and one launch: the same algorithm with one pair that holds
+ * every column -- B, its Cholesky factor W, and per sweep W^T W, the LDS Jacobi and W <- W R, all in LDS; 2 blocked.
+ *   corrla_eigh_f64    : host pointers; nothing is written when the call fails.
+ *   corrla_eigh_dev_f64: device pointers; the working copy lives in workspace (about 16 n^2 bytes).  The entry synchronises.
+ * CORRLA_ENUMERIC: a non-finite entry in the lower triangle (info 1), a pivot reported by the Cholesky factorisation (info 2,
+ * cannot happen on a finite matrix), more than 40 sweeps (info 3).  The zero matrix returns w = 0, V = I without a sweep.
+ * corrla_ctx_last_eigh returns the route, the sweeps that rotated, the largest measure of the last sweep, sigma and info of the
+ * context's last call (any pointer may be NULL).
+ * Limits: 1 <= n <= 32768.  CORRLA_ENOMEM: the workspace could not be allocated; nothing was launched.
+ * CORRLA_EINVAL (the message names the argument): a NULL array, n outside the limits, lda / ldv < n, an output overlapping the
+ * input or the other output. */
+CORRLA_API corrla_status corrla_eigh_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, double* w, double* v, int64_t ldv);
+CORRLA_API corrla_status corrla_eigh_dev_f64(corrla_ctx* ctx, const double* a, int64_t n, int64_t lda, double* w, double* v, int64_t ldv);
+CORRLA_API corrla_status corrla_ctx_last_eigh(corrla_ctx* ctx, int* route, int* sweeps, double* off, double* shift, int64_t* info);
+
 /* ---- constrained Dirichlet sampling: draws on the simplex, rejection against a box ---------------------
  * Replaces  dirichlet_shot_sample / constr_dirichlet_sample       src/lib_math_utils/space_samplers.rs:14-126
  * THE STREAM.  Draw t (0 <= t < 2^62) of (seed, alphas[0..d), c_scale) is the row x[0..d), all in IEEE double:
